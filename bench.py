@@ -2,6 +2,7 @@
 """bench.py — rays/s of the MI355X trace hot path on BASELINE.json's workloads.
 
   python bench.py --gpus N --steps K --warmup W [--config 1|2|4|4d|4p|ref:<name>] [--repeats R] [--scaling weak|strong]
+                  [--dump-outputs DIR] [--full]
 N > 1: the driver launches `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (one rank per GPU, RCCL);
 started WITHOUT a launcher (`python bench.py --gpus N`, WORLD_SIZE unset) the file launches those N ranks itself (self_launch).  One "step" = one pass of the hot path over one batch of the selected configuration:
 
@@ -23,17 +24,28 @@ started WITHOUT a launcher (`python bench.py --gpus N`, WORLD_SIZE unset) the fi
              ref:config_example, examples/config_example.json as shipped (README quick start: 9 wavelengths x 50 M rays, renderer 4;
              fixture tests/golden/ref_example_configs.json)
 
-With the default configuration on one GPU the JSON line also carries `other_configs`: short runs (3 warm-up steps, then 3 repeats of 3 timed
-steps: median + CoV) of configs 2, 4, 4d, 4p and of the five reference documents — metric, ms/step, route and roofline of each — so that the
-driver's record holds them; the headline fields are those of configs[1] alone.
+A plain run does only what the headline needs: set up, untimed settle steps (as many as trace --settle-rays rays, 30 for configs[1]),
+W warm-up steps, ONE timed region of exactly K steps, the outputs if --dump-outputs is given, the JSON line.  Everything else the benchmark measures or checks runs only with --full:
+  * the timed region is run R = 5 times (median + CoV, the reference's protocol below; --repeats R overrides either default),
+  * `cpu_baseline`: the CPU oracle on the same workload shape (--no-cpu-baseline leaves it out),
+  * `other_configs` (default configuration on one GPU; --no-others leaves them out): short runs (3 warm-up steps, then 3 repeats of 3
+    timed steps: median + CoV) of configs 2, 4, 4d, 4p and of the five reference documents — metric, ms/step, route and roofline of
+    each — so that the record holds them; the headline fields are those of configs[1] alone,
+  * `multi_gpu` (N > 1): the check pass of certify_multi_gpu.
+
+--dump-outputs DIR: after the timed steps, DIR/image.npy holds what the timed path computed in its LAST step — the H x W x 3 float32 XYZ
+image a caller of the path reads back (rank 0: the image reduced over the ranks).  The accumulator is cleared, stream-ordered, right before
+that step, so the file holds that step alone.  Rays are drawn from monotone counters and the steps before it are counted from the
+arguments alone, so the same arguments give the same inputs; an image above 64 MB is written as a fixed seeded sample (image_sample.npy, image_sample_index.npy:
+flat indices as float64).
 
 Rays shard by index range (disjoint RNG counter ranges per rank, no data-path collective); every step ends with ONE RCCL
 sum-reduce of the W*H*3(+4) fp32 accumulator to rank 0 (the reference's drain point, simulator.cpp:1409-1477).  Per-GPU work
 is fixed -> "scaling": "weak" (the default); --scaling strong fixes the TOTAL instead (configs[3]'s "400 M rays sharded across 8"
 read as a fixed job: rays per rank = rays / N).
 
-Timing follows the reference's protocol (doc/performance-testing.md:109-131: >= 5 repeats, median + CoV): after W warm-up
-steps the timed region — EXACTLY K steps between barrier + synchronize — is run R times (default 5); `value` and
+Timing: after W warm-up steps the timed region — EXACTLY K steps between barrier + synchronize — is run R times (1 in a plain
+run; 5 with --full, the reference's protocol, doc/performance-testing.md:109-131: >= 5 repeats, median + CoV); `value` and
 `ms_per_step` are the MEDIAN repeat, `repeats` carries every repeat and the coefficient of variation.
 
 Rank 0 prints ONE JSON line.  `roofline` prices the dominant kernel of the configuration against HBM (no dense contraction
@@ -456,9 +468,10 @@ def pmc_valu(cfg, rays_per_launch):
     return out
 
 
-def measure(cfg, args, ctx, steps, warmup, repeats, with_cpu):
+def measure(cfg, args, ctx, steps, warmup, repeats, with_cpu, full=False, dump=None):
     """One configuration on this rank's GPU: `warmup` untimed steps, then `repeats` timed regions of exactly `steps` steps each (barrier +
-    synchronize on both sides, MAX over ranks).  Returns the JSON object of the configuration on rank 0, None elsewhere."""
+    synchronize on both sides, MAX over ranks).  Returns the JSON object of the configuration on rank 0, None elsewhere.
+    full: also run the multi-GPU check pass (N > 1).  dump: a dict that receives {"image": the last timed step's image} on rank 0."""
     torch, dist = ctx["torch"], ctx["dist"]
     world, rank, local_rank = ctx["world"], ctx["rank"], ctx["local_rank"]
     from ice_halo_sim_amd.dist import ShardedTracer
@@ -509,6 +522,11 @@ def measure(cfg, args, ctx, steps, warmup, repeats, with_cpu):
         else:
             tracer.reduce_to_root()                          # N > 1: queued on the side stream, the next step traces into the other tensor (dist.ShardedTracer)
 
+    # Settle: a few warm-up steps do not bring the path to its steady rate (configs[1], W = 5: the first region of 20 steps read 18.4 ms per
+    # step, the four after it 17.68; after ~30 uninterrupted untimed steps the first region reads 17.64 like the rest).  A fixed number of
+    # untimed steps, from the rays of a step alone, so that every run with the same arguments draws the same rays in its timed steps.
+    for _ in range(settle_steps(args.settle_rays, len(wls) * n)):
+        step()
     for _ in range(warmup):
         step()
     if args.warm_seconds > 0.0:
@@ -536,10 +554,20 @@ def measure(cfg, args, ctx, steps, warmup, repeats, with_cpu):
     reduce_events.clear()
     del tracer.reduce_spans[:]
 
-    def timed_region():
+    def clear_before_last_step():
+        """--dump-outputs: the image of the last timed step alone.  Stream-ordered (no host wait under RCCL): the queued reduces are joined,
+        then every accumulator is cleared on the trace stream."""
+        if world > 1:
+            tracer._join()
+        for a in tracer.accs:
+            a.zero_()
+
+    def timed_region(last=False):
         barrier()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for i in range(steps):
+            if last and dump is not None and i == steps - 1:
+                clear_before_last_step()
             step()                                           # dispatches are queued; nothing waits on the host per launch
         if world > 1:
             tracer._join()                                   # the last drains' collectives are part of the steps that queued them
@@ -568,7 +596,8 @@ def measure(cfg, args, ctx, steps, warmup, repeats, with_cpu):
             first_layer[k] = 0
         reduce_events.clear()
         del tracer.reduce_spans[:]
-    times = [timed_region() for _ in range(max(repeats, 1))]
+    reps = max(repeats, 1)
+    times = [timed_region(last=(r == reps - 1)) for r in range(reps)]
     drain_switched = False
     if drain_probe is not None and tracer.two and statistics.median(times) > 1.25 * drain_probe[False]:
         # Safety net.  The probe's two short regions per mode do not always show what the side-stream drain does once the queues are deep: in the
@@ -583,7 +612,7 @@ def measure(cfg, args, ctx, steps, warmup, repeats, with_cpu):
             first_layer[k] = 0
         reduce_events.clear()
         del tracer.reduce_spans[:]
-        times = [timed_region() for _ in range(max(repeats, 1))]
+        times = [timed_region(last=(r == reps - 1)) for r in range(reps)]
         drain_switched = True
     trace_ms, post_ms, timed_launches = tracer.backend.collect_timing()   # HIP events of the LAST layer's launches: the trace kernels' own spans / their accumulation passes'
     st = tracer.backend.collect_stats()                      # HIP-event kernel times + device tallies of every timed repeat
@@ -608,7 +637,9 @@ def measure(cfg, args, ctx, steps, warmup, repeats, with_cpu):
     assert int(st.root_count) == rays_per_rank + first_layer["cont"], (int(st.root_count), rays_per_rank, first_layer["cont"])
 
     img, landed = tracer.readback()                          # collective: landed-weight scalars are summed here, once
-    multi = certify_multi_gpu(ctx, tracer, wls[0], min(n, 4_000_000), reduce_events, dist_backend=ctx.get("dist_backend", "nccl")) if world > 1 else None
+    if dump is not None and rank == 0:
+        dump["image"] = img
+    multi = certify_multi_gpu(ctx, tracer, wls[0], min(n, 4_000_000), reduce_events, dist_backend=ctx.get("dist_backend", "nccl")) if world > 1 and full else None
     if multi is not None and overlap_ab is not None:
         multi["reduce_overlap"] = overlap_ab
     tracer.backend.close()
@@ -666,7 +697,7 @@ def measure(cfg, args, ctx, steps, warmup, repeats, with_cpu):
                    "route": {"mode_mask": route.mode_mask, "geom_mask": route.geom_mask, "accum_mask": route.accum_mask,
                              "source_mask": route.source_mask, "planes": route.plane_cnt, "plane_copies": route.plane_copies,
                              "spec_mask": route.spec_mask, "generic_launches": route.generic_launches}},
-        "repeats": {"n": reps, "protocol": "reference doc/performance-testing.md:109-131 (>= 5 repeats, median + CoV); each repeat times exactly --steps steps",
+        "repeats": {"n": reps, "protocol": "each repeat times exactly --steps steps; a plain run times one, --full five (reference doc/performance-testing.md:109-131: >= 5 repeats, median + CoV)",
                     "median_ms_per_step": dt * 1e3 / steps, "cov": cov,
                     "ms_per_step_all": [x * 1e3 / steps for x in times]},
         "roofline": {"bound": "valu_issue", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -770,6 +801,32 @@ def certify_multi_gpu(ctx, tracer, wl, n_check, reduce_events, dist_backend):
 
 OTHER_CONFIGS = ("2", "4", "4d", "4p") + tuple("ref:" + n for n in REF_SCENES) + ("ref:config_example",)
 
+DUMP_LIMIT_BYTES = 64 << 20
+SETTLE_RAYS = 1.35e10       # 30 steps of configs[1], about half a second on one MI355X
+SETTLE_MAX_STEPS = 200
+
+
+def settle_steps(settle_rays, rays_per_step):
+    """untimed steps before the warm-up: enough to trace settle_rays, at most SETTLE_MAX_STEPS (a function of the arguments alone)"""
+    if settle_rays <= 0:
+        return 0
+    return int(min(SETTLE_MAX_STEPS, -(-settle_rays // max(rays_per_step, 1))))
+
+
+def write_outputs(path, dump):
+    """--dump-outputs: DIR/image.npy (H x W x 3 float32); above DUMP_LIMIT_BYTES a fixed seeded sample of its elements instead
+    (image_sample.npy float32 and image_sample_index.npy, the flat indices as float64)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    img = np.ascontiguousarray(dump["image"], dtype=np.float32)
+    if img.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(path, "image.npy"), img)
+        return
+    k = DUMP_LIMIT_BYTES // 2 // 8                           # (4 + 8) bytes per sampled element: half the limit leaves room to spare
+    idx = np.sort(np.random.default_rng(1234).choice(img.size, size=k, replace=False))
+    np.save(os.path.join(path, "image_sample.npy"), img.reshape(-1)[idx])
+    np.save(os.path.join(path, "image_sample_index.npy"), idx.astype(np.float64))
+
 
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: re-run this command line as N ranks (`python -m torch.distributed.run --nnodes=1
@@ -797,16 +854,23 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="1", help="1 | 2 | 4 | 4d | 4p | ref:<document> (see the module docstring)")
-    ap.add_argument("--repeats", type=int, default=5, help="how many times the timed region of --steps steps is run (median reported)")
+    ap.add_argument("--repeats", type=int, default=None, help="how many times the timed region of --steps steps is run (median reported; default 1, 5 with --full)")
     ap.add_argument("--rays-per-wl", type=int, default=0, help="root rays per session per GPU per step (0 = the configuration's own)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"], help="weak: per-GPU work fixed; strong: the configuration's rays are the whole job")
     ap.add_argument("--warm-seconds", type=float, default=0.0, help="extra untimed warm-up after the --warmup steps: chunks of --steps steps until two consecutive chunks agree within 5 %% (at least this long, at most 3 s; the short runs of the other configurations use 0.3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-others", action="store_true", help="default configuration on one GPU: skip the short runs of the other configurations")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: 5 repeats, the CPU baseline, the other configurations, the multi-GPU check pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's image to DIR/image.npy (float32; a seeded sample above 64 MB)")
+    ap.add_argument("--settle-rays", type=float, default=SETTLE_RAYS, help="untimed steps before the --warmup steps: as many as trace this many rays per GPU (at most %d; 0 = none)" % SETTLE_MAX_STEPS)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
+    ap.add_argument("--no-others", action="store_true", help="--full, default configuration on one GPU: skip the short runs of the other configurations")
     ap.add_argument("--blocks-per-cu", type=int, default=0)
     ap.add_argument("--aggregate", type=int, default=-1)
     ap.add_argument("--opt", action="append", default=[], help="backend option key=value (repeatable)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.dump_outputs and args.warm_seconds > 0.0:
+        raise SystemExit("--dump-outputs needs a fixed number of steps before the dumped one: --warm-seconds varies it")
 
     import torch
     import torch.distributed as dist
@@ -835,8 +899,11 @@ def main():
             dist.init_process_group(backend=dist_backend)
     ctx = {"torch": torch, "dist": dist, "world": world, "rank": rank, "local_rank": local_rank, "dist_backend": dist_backend}
 
-    out = measure(args.config, args, ctx, args.steps, args.warmup, args.repeats, with_cpu=not args.no_cpu_baseline)
-    if args.config == "1" and world == 1 and not args.no_others and not args.rays_per_wl:
+    dump = {} if args.dump_outputs else None
+    out = measure(args.config, args, ctx, args.steps, args.warmup, args.repeats, with_cpu=args.full and not args.no_cpu_baseline, full=args.full, dump=dump)
+    if dump is not None and rank == 0:
+        write_outputs(args.dump_outputs, dump)
+    if args.full and args.config == "1" and world == 1 and not args.no_others and not args.rays_per_wl:
         others = {}
         args.warm_seconds = max(args.warm_seconds, 0.3)
         for cfg in OTHER_CONFIGS:

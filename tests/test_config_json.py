@@ -145,16 +145,18 @@ def test_filters_map_onto_the_filter_table():
     assert f2.is_complex == 0 and f2.symmetry == 7 and list(f2.terms[0].raypath)[:5] == [3, 1, 5, 7, 4] and f2.terms[0].raypath_len == 5
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/examples"), reason="reference examples only exist in the build container")
-def test_reference_example_files_parse():
-    for name in ("bench_config.json", "bench_config_stoch.json", "lens_orthographic.json"):
-        path = os.path.join("/root/reference/examples", name)
-        if os.path.exists(path):
-            job = config.load_config(path)
-            assert job.scene.layer_count >= 1 and job.renders
-    if os.path.exists("/root/reference/examples/config_example.json"):
-        job = config.load_config("/root/reference/examples/config_example.json")
-        assert job.ray_num == 450_000_000 and len(job.wavelengths) == 9 and sorted(job.renders) == [1, 2, 3, 4]
+def test_reference_example_files_parse(tmp_path):
+    """The reference's example documents (kept as tests/golden/ref_example_configs.json, make_e2e_config_bundle.py), each read back
+    from a file of its own name like the CLI reads them."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_example_configs.json")) as f:
+        docs = json.load(f)
+    for name in ("bench_config", "bench_config_stoch", "lens_orthographic", "config_example"):
+        path = tmp_path / (name + ".json")
+        path.write_text(json.dumps(docs[name]))
+        job = config.load_config(str(path))
+        assert job.scene.layer_count >= 1 and job.renders
+    job = config.load_config(str(tmp_path / "config_example.json"))
+    assert job.ray_num == 450_000_000 and len(job.wavelengths) == 9 and sorted(job.renders) == [1, 2, 3, 4]
 
 
 with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_e2e_configs.json")) as _f:

@@ -194,7 +194,7 @@ def test_bench_launches_its_own_ranks_when_started_plainly():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["HALO_BENCH_BACKEND"] = "gloo"            # two ranks on this box's one device; the driver's 8-GPU run is the same code over RCCL
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--repeats", "1",
-                        "--rays-per-wl", "3000000", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+                        "--rays-per-wl", "3000000", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

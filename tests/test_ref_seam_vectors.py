@@ -22,7 +22,6 @@ from tests._oracle_backend import OracleBackend
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 V = json.load(open(os.path.join(HERE, "golden", "ref_test_vectors.json")))
-needs_ref = pytest.mark.skipif(not _libs.have_ref(), reason="oracle/_ref/libref_shared.so is built only where /root/reference exists (build container; .gpurunignore keeps it there)")
 
 
 # ---- ray_num semantics --------------------------------------------------------------------------------------------------------------------
@@ -212,34 +211,76 @@ def _expected_bytes_gray_tint(xyz_raw, scale, ray_color, background):
     return out
 
 
+def _exposure_scale(rd, landed):
+    return np.float32(np.float32(1.0) * np.float32(0.08) * np.float32(rd.width * rd.height) / np.float32(landed))   # ExposureScale render.cpp:96-102
+
+
+def _live_post_snapshot():
+    """what the reference's pieces give on the post_snapshot_fusion inputs: the image of four rays straight up, and each case's bytes"""
+    spec = V["post_snapshot_fusion"]
+    rd = _render_of(spec["render"])
+    img, landed = _scatter_with_ref(rd, [[0.0, 0.0, -1.0]] * len(spec["weights"]), spec["weights"], spec["wavelength"])
+    out = {"image": img, "landed": np.float64(landed)}
+    scale = _exposure_scale(rd, landed)
+    for case in spec["cases"]:
+        if case["ray_color"][0] < 0:
+            out[case["name"] + "_bytes"], clamps = _expected_bytes_from_ref(img, scale, case["ray_color"], case["background"])
+            out[case["name"] + "_clamps"] = np.int64(clamps)
+        else:
+            out[case["name"] + "_bytes"] = _expected_bytes_gray_tint(img, scale, case["ray_color"], case["background"])
+    return out
+
+
+def _live_scatter():
+    """the reference's ScatterOutgoingToXyz of the twelve scatter_outgoing rays"""
+    spec = V["scatter_outgoing"]
+    img, landed = _scatter_with_ref(_render_of(spec["render"]), spec["directions"], [spec["weight"]] * len(spec["directions"]), spec["wavelength"])
+    return {"image": img, "landed": np.float64(landed)}
+
+
+LIVE_REF_OUTPUTS = {"post_snapshot": _live_post_snapshot, "scatter": _live_scatter}
+
+
+def _ref_outputs(key):
+    """The reference's outputs on a group's inputs, as stored in tests/golden/ref_seam_outputs.npz (make_ref_seam_outputs.py); where the
+    reference build exists (oracle/_ref) they are recomputed live and must equal the stored arrays bit for bit."""
+    with np.load(os.path.join(HERE, "golden", "ref_seam_outputs.npz")) as z:
+        stored = {k[len(key) + 1:]: z[k] for k in z.files if k.startswith(key + "_")}
+    if _libs.have_ref():
+        live = {k: np.asarray(v) for k, v in LIVE_REF_OUTPUTS[key]().items()}
+        assert sorted(live) == sorted(stored), (sorted(live), sorted(stored))
+        for k, v in live.items():
+            assert v.dtype == stored[k].dtype and v.shape == stored[k].shape and v.tobytes() == stored[k].tobytes(), k
+    return stored
+
+
 def _snapshot_case(b, case, img, landed):
     b.Consume(img, landed)
     rgb, xyz, total = b.Snapshot(intensity_factor=1.0, ray_color=tuple(case["ray_color"]), background=tuple(case["background"]))
     return rgb, xyz, total
 
 
-@needs_ref
 def test_post_snapshot_chain_byte_for_byte_on_the_oracle():
     """The three cases on the oracle's consumer: the image ScatterOutgoingToXyz makes of four rays straight up (one lit pixel), consumed as a
     drained image, snapshot, and compared BYTE FOR BYTE — never a tolerance — with the chain rebuilt from the reference's primitives."""
     spec = V["post_snapshot_fusion"]
     rd = _render_of(spec["render"])
-    img, landed = _scatter_with_ref(rd, [[0.0, 0.0, -1.0]] * len(spec["weights"]), spec["weights"], spec["wavelength"])
+    ref = _ref_outputs("post_snapshot")
+    img, landed = ref["image"], float(ref["landed"])
     assert (img.reshape(-1, 3).sum(1) > 0).sum() == 1 and landed == pytest.approx(sum(spec["weights"]), rel=1e-6)
     for case in spec["cases"]:
         ob = OracleBackend(seed=1, threads=1)
         rgb, xyz, total = _snapshot_case(ob, case, img, landed)
         ob.close()
         assert np.array_equal(xyz, img) and total == pytest.approx(landed, rel=1e-7)
-        scale = np.float32(np.float32(1.0) * np.float32(0.08) * np.float32(rd.width * rd.height) / np.float32(landed))   # ExposureScale render.cpp:96-102
         assert (rgb != 0).any()
         if case["ray_color"][0] < 0:
-            want, clamps = _expected_bytes_from_ref(img, scale, case["ray_color"], case["background"])
+            want, clamps = ref[case["name"] + "_bytes"], int(ref[case["name"] + "_clamps"])
             assert np.array_equal(rgb, want), case["name"]
             if case.get("expect_clamp"):
                 assert clamps > 0 and (rgb.reshape(-1, 3) == rgb.reshape(-1, 3)[0]).all(1).sum() >= 255     # the background lifts every empty pixel
         else:   # gray + tint: Y times the D65 white point through the matrix, times ray_color
-            assert np.array_equal(rgb, _expected_bytes_gray_tint(img, scale, case["ray_color"], case["background"])), case["name"]
+            assert np.array_equal(rgb, ref[case["name"] + "_bytes"]), case["name"]
 
 
 @pytest.mark.gpu
@@ -272,14 +313,14 @@ def test_post_snapshot_chain_byte_for_byte_on_the_device():
 
 
 # ---- ScatterOutgoingMatchesReferenceScatter -----------------------------------------------------------------------------------------------
-@needs_ref
 def test_scatter_of_twelve_outgoing_rays_equals_the_references_scatter():
     """Twelve outgoing directions, weight 0.7, 550 nm, on the 64x64 zenith fisheye: the oracle's projection + CMF accumulate gives the image
     the reference's own ProjectExitToPixel + SpectrumToXyz give, bit for bit; the horizon ray (sky z = 0) falls outside the upper-only render."""
     spec = V["scatter_outgoing"]
     rd = _render_of(spec["render"])
-    dirs, w = spec["directions"], [spec["weight"]] * len(spec["directions"])
-    want, landed = _scatter_with_ref(rd, dirs, w, spec["wavelength"])
+    dirs = spec["directions"]
+    ref = _ref_outputs("scatter")
+    want, landed = ref["image"], float(ref["landed"])
     O = _libs.oracle()
     pp = abi.ProjParams()
     O.ho_build_proj_params(C.byref(rd), C.byref(pp))

@@ -5,7 +5,7 @@ export HALO_BENCH_BACKEND=gloo
 for spec in "2 weak" "2 strong" "4 strong" "8 strong"; do
   set -- $spec
   echo "## --gpus $1 --scaling $2"
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node $1 --master-addr 127.0.0.1 --master-port $((29500 + $1)) bench.py --gpus $1 --steps 2 --warmup 1 --repeats 2 --scaling $2 --no-cpu-baseline 2>/dev/null | python -c "
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node $1 --master-addr 127.0.0.1 --master-port $((29500 + $1)) bench.py --gpus $1 --steps 2 --warmup 1 --repeats 2 --scaling $2 --no-cpu-baseline --full 2>/dev/null | python -c "
 import json,sys
 lines=[l for l in sys.stdin.read().strip().splitlines() if l.startswith('{')]
 d=json.loads(lines[-1]); m=d['multi_gpu']

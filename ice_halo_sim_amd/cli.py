@@ -20,14 +20,17 @@ DISPATCH_RAYS_MULTI = 1 << 24  # ... for scenes with more than one scattering la
                                # and a one-shot CLI run pays for their allocation (64 Mi roots x 8 hits: two pools of 10 GB, 0.5 s of hipMalloc)
 
 
-def run_job(job, render_id=None, seed=42, device=0, max_rays=None, progress=None):
-    """Trace `job` (config.TraceJob) on one GPU. Returns dict(rays, setup_sec, active_sec, backend, render)."""
+def run_job(job, render_id=None, seed=42, device=0, max_rays=None, progress=None, canonical_order=False):
+    """Trace `job` (config.TraceJob) on one GPU. Returns dict(rays, setup_sec, active_sec, backend, render).  canonical_order: option
+    cont_order = 1 (the continuation pool of every layer but the last in (root, interaction) order)."""
     if not job.renders:
         raise config.ConfigError("config has no render entry")
     rid = render_id if render_id is not None else sorted(job.renders)[0]  # the seam supports ONE renderer (simulator.cpp:937-944)
     render = job.renders[rid]
     t0 = time.perf_counter()
     be = HipTraceBackend(device=device, seed=seed)
+    if canonical_order:
+        be.set_option("cont_order", 1)
     if job.geom_clock:
         be.set_option("geom_clock", job.geom_clock)
     be.set_filters(job.filters)
@@ -95,7 +98,7 @@ def save_all_renders(job, args):
     rc = 0
     for rid in sorted(job.renders):
         try:
-            res = run_job(job, rid, args.seed, args.device, args.max_rays)
+            res = run_job(job, rid, args.seed, args.device, args.max_rays, canonical_order=args.canonical_order)
         except BackendUnavailableError as e:
             print("backend unavailable: %s" % e, file=sys.stderr)
             return 3
@@ -130,6 +133,11 @@ def main(argv=None):
     ap.add_argument("--out-lanes", default=None, help="raypath_color configs: write the per-class Y lanes (classes, H, W) as .npy")
     ap.add_argument("--out-composite", default=None, help="raypath_color configs: write the class composite (the config's mode: dominant | additive | "
                     "painter; component_compositor.cpp) as binary PPM, composited on the device")
+    ap.add_argument("--canonical-order", action="store_true",
+                    help="multi-scattering configs: hand every layer's continuing rays to the next layer in canonical (root ray, interaction) "
+                    "order, so a fixed --seed traces the same second- and third-layer rays on every run (option cont_order = 1; costs a sort of the "
+                    "continuation pool per layer).  It does not make the image bit-identical: pixel sums are fp32 atomics in whatever order the GPU "
+                    "adds them; a multi-GPU run is canonical per rank")
     ap.add_argument("--display-ev", type=float, default=0.0, help="display-time EV of the composite (display_exposure_scale = 2^EV)")
     args = ap.parse_args(argv)
     if not 1 <= args.quality <= 100:
@@ -146,7 +154,7 @@ def main(argv=None):
         if args.output_dir is not None:
             print("[warning] -o / --output-dir is ignored with --render / --benchmark (nothing is saved)", file=sys.stderr)
         wall0 = time.perf_counter()
-        res = run_job(job, args.render, args.seed, args.device, args.max_rays)
+        res = run_job(job, args.render, args.seed, args.device, args.max_rays, canonical_order=args.canonical_order)
     except BackendUnavailableError as e:
         print("backend unavailable: %s" % e, file=sys.stderr)
         return 3

@@ -49,6 +49,8 @@ hipError_t launch_lanes_drain(double* lanes, float* dst, uint64_t n, int blocks,
 hipError_t launch_lanes_add(const float* src, double* lanes, uint64_t n, int blocks, hipStream_t stream);
 hipError_t launch_post_snapshot(const float* sum, const float* comp, uint8_t* rgb_out, float* xyz_out, uint32_t n_pix, float scale,
                                 const float ray_color[3], const float background[3], int blocks, hipStream_t stream);
+hipError_t launch_cont_reorder(const float* in, uint32_t in_stride, uint32_t region, const uint32_t* cnt, uint32_t max_fill, const uint32_t* mask, uint32_t n_roots,
+                               uint32_t* tile_sum, uint32_t* base, float* out, uint32_t out_stride, uint32_t n_cont, uint32_t planes, uint32_t* err, hipStream_t stream);
 }
 
 using namespace halo;
@@ -264,6 +266,13 @@ struct HaloBackend {
   int cont_out_slot = 0;
   uint64_t cont_in_n = 0;
   int cont_shuffle = 1;
+  int cont_order = 0;                        // option: 0 [default] continuations in append order; 1 canonical (root, interaction) order (Recombine sorts the pool)
+  DevBuf<uint32_t> cont_mask;                // cont_order = 1: per root of the layer being traced, the 128-bit mask of its continued exit seqs
+  DevBuf<uint32_t> cont_err;                 // ... the session's error word (kContErr*: appends, scan and scatter), read at the end of every layer
+  DevBuf<uint32_t> cont_base;                // ... each root's first canonical slot, and the scan's tile sums
+  DevBuf<uint32_t> cont_tiles;
+  uint32_t cont_fill_max = 0;                // fullest shard region of the last non-final layer (the scatter's grid)
+  uint64_t cont_roots = 0;                   // roots of the last non-final layer
   DevBuf<HaloExitRecord> exits;
   uint64_t exits_pending = 0;
   DevBuf<float> host_f;        // injected rays: d | p | w
@@ -588,6 +597,10 @@ int halo_destroy(halo_handle_t b) {
   b->shapes_s[0].release();
   b->shapes_s[1].release();
   b->cont_cnt.release();
+  b->cont_mask.release();
+  b->cont_err.release();
+  b->cont_base.release();
+  b->cont_tiles.release();
   b->lanes.release();
   for (int k = 0; k < 2; k++) {
     b->bin_list_s[k].release();
@@ -676,6 +689,11 @@ int halo_set_option(halo_handle_t b, const char* key, int64_t v) {
   else if (k == "rehit_strategy") {
     if (b->in_session) return fail(b, HALO_FATAL, "rehit_strategy cannot change inside a session");
     b->rehit_strategy = v ? 1 : 0;
+  }
+  else if (k == "cont_order") {
+    if (b->in_session) return fail(b, HALO_FATAL, "cont_order cannot change inside a session");
+    if (v != 0 && v != 1) return fail(b, HALO_FATAL, "cont_order must be 0 (append order) or 1 (canonical order)");
+    b->cont_order = static_cast<int>(v);
   }
   else if (k == "log_tiles_log2") b->log_tiles_log2 = static_cast<int>(std::min<int64_t>(std::max<int64_t>(v, 0), 8));
   else if (k == "alt_log2") b->alt_log2 = static_cast<int>(std::min<int64_t>(std::max<int64_t>(v, 10), 28));
@@ -981,6 +999,12 @@ int halo_end(halo_handle_t b) {
   return rc;
 }
 
+// the canonical order's error word (kContErr*) as a session failure
+static int cont_order_fail(HaloBackend* b, uint32_t err) {
+  return fail(b, HALO_FATAL, (err & kContErrSum) ? "cont_order = 1: the roots' masks do not add up to the continuation pool (an exit seq continued twice, or a record lost)"
+                                                 : "cont_order = 1: a continuation record's key lies outside its layer or pool");
+}
+
 int halo_trace_layer(halo_handle_t b, uint64_t count, const HaloHostRays* rays, HaloLayerStats* stats) {
   if (!b) return HALO_FATAL;
   if (!b->in_session) return fail(b, HALO_FATAL, "TraceLayer outside a session");
@@ -1059,14 +1083,28 @@ int halo_trace_layer(halo_handle_t b, uint64_t count, const HaloHostRays* rays, 
     region = (region + 63) & ~63ull;
     const uint64_t stride = region * kContShards;
     if (stride > 0xFFFFFFF0ull) return fail(b, HALO_FATAL, "continuation pool would exceed 2^32 rays; split the batch");
-    if (int rc = reserve_idle(b, b->cont[out_slot], stride * (b->color_classes.empty() ? 5 : 7))) return rc;  // + mask lo/hi planes with raypath colour
+    // + mask lo/hi planes with raypath colour; canonical order: + root and interaction planes (kContPlaneRoot, kContPlaneBit)
+    const uint64_t planes = b->cont_order ? kContPlanesCanonical : (b->color_classes.empty() ? 5 : 7);
+    if (b->cont_order && stride * planes > 0xFFFFFFFFull) return fail(b, HALO_FATAL, "canonical continuation pool planes would exceed 2^32 floats; split the batch");
+    if (int rc = reserve_idle(b, b->cont[out_slot], stride * planes)) return rc;
     b->cont_stride[out_slot] = static_cast<uint32_t>(stride);
     b->cont_region[out_slot] = static_cast<uint32_t>(region);
     out_cap = static_cast<uint32_t>(region);
     HIPCHK(b, b->cont_cnt.reserve(kContShards * kContCntStride));
     HIPCHK(b, hipMemsetAsync(b->cont_cnt.ptr, 0, kContShards * kContCntStride * sizeof(uint32_t), b->stream));
+    if (b->cont_order) {   // the roots' masks start empty: queued on the stream, behind the scatter that read the previous layer's
+      if (b->rehit_strategy == 0) return fail(b, HALO_FATAL, "cont_order = 1 needs rehit_strategy = 1 (the legacy strategy can emit twice at one interaction)");
+      if (int rc = reserve_idle(b, b->cont_mask, kContMaskWords * std::max<uint64_t>(n, 1))) return rc;
+      HIPCHK(b, hipMemsetAsync(b->cont_mask.ptr, 0, kContMaskWords * n * sizeof(uint32_t), b->stream));
+      if (layer == 0) {   // a session starts with a clean error word (a session that set one was refused)
+        if (int rc = reserve_idle(b, b->cont_err, 16)) return rc;
+        HIPCHK(b, hipMemsetAsync(b->cont_err.ptr, 0, sizeof(uint32_t), b->stream));
+      }
+    }
   }
-  const bool defer = b->async && final_layer && !b->capture;  // nothing the caller needs before the next call
+  // canonical order over several layers: every layer ends with the error-word check (the appends of this layer, the reorder in front of it)
+  const bool canon_check = b->cont_order && b->scene.layer_count > 1;
+  const bool defer = b->async && final_layer && !b->capture && !canon_check;  // nothing the caller needs before the next call
   if (!defer) {  // earlier queued dispatches go to `pending`, so layer_acc ends up holding this layer alone
     harvest_all(b);
     if (int rc = pull_tally(b)) return rc;   // (a copy + sync only when something was queued and never collected)
@@ -1152,6 +1190,8 @@ int halo_trace_layer(halo_handle_t b, uint64_t count, const HaloHostRays* rays, 
     P.cont_out_cap = out_cap;
     P.cont_in_region = b->cont_region[out_slot ^ 1];
     P.cont_cnt = b->cont_cnt.ptr;
+    P.cont_mask = (b->cont_order && !final_layer) ? b->cont_mask.ptr : nullptr;
+    P.cont_err = canon_check ? b->cont_err.ptr : nullptr;
     P.counters = b->counters.ptr;
     P.mono = planes_of(b);
     P.mono_s_log2 = b->mono_s_log2;
@@ -1372,7 +1412,9 @@ int halo_trace_layer(halo_handle_t b, uint64_t count, const HaloHostRays* rays, 
       const uint32_t wl_t_log2 = b->mono_s_log2 >= 4u ? b->mono_s_log2 - 4u : 0u;
       const bool log_planes_ok = b->mono_by_wl && (static_cast<uint64_t>(b->plane_cnt) << wl_t_log2) <= 512ull &&
                                  (static_cast<uint64_t>(b->plane_cnt) << (b->mono_s_log2 + 10u)) <= (1ull << 31) && b->hit_log != 0 && b->bin <= 0;
-      const bool use_bin = b->mono_session && b->aggregate == 1 && !b->capture && bin_shape_ok && bin_slots <= (1ull << 31) &&
+      // (a layer before the last under canonical continuation order takes direct accumulation: only those kernels have CANON twins)
+      const bool canon = b->cont_order && !final_layer;
+      const bool use_bin = !canon && b->mono_session && b->aggregate == 1 && !b->capture && bin_shape_ok && bin_slots <= (1ull << 31) &&
                            // own choice: only where the hit log cannot go (one plane per pool entry on a larger image) — the log beats the binned route
                            // on every launch measured (tools/bin_vs_log_probe.py: dual fisheye 50 M rays 5.13 -> 4.42 ms)
                            (b->bin < 0 ? (b->mono_by_wl && !log_planes_ok && bin_geom_ok && b->render.visible == HALO_VISIBLE_FULL && m >= (2ull << 20)) : b->bin != 0);
@@ -1389,7 +1431,7 @@ int halo_trace_layer(halo_handle_t b, uint64_t count, const HaloHostRays* rays, 
       const uint32_t log_planes = log_planes_ok ? b->plane_cnt : 1u;
       const uint32_t log_tiles = log_planes << log_t_log2;   // lists the split pass feeds
       const bool log_layout_ok = b->xyz_log ? (b->mono_s_log2 <= 11u) : (b->mono_session && (log_planes_ok || (!b->mono_by_wl && b->mono_s_log2 <= 12u)));
-      bool use_log = !use_bin && log_layout_ok && b->aggregate == 1 && fast_mode &&
+      bool use_log = !canon && !use_bin && log_layout_ok && b->aggregate == 1 && fast_mode &&
                            (P.prob < 1.0f || P.final_layer) &&   // a layer whose every exit continues puts nothing on the image
                            (b->hit_log < 0 ? m >= ((b->mono_session && !b->mono_by_wl) ? log_min_rays(b->render.visible) : (2ull << 20)) : b->hit_log != 0);
       bool use_log_xyz = use_log && b->xyz_log;
@@ -1655,21 +1697,29 @@ int halo_trace_layer(halo_handle_t b, uint64_t count, const HaloHostRays* rays, 
   std::vector<uint32_t> fill(final_layer ? 0 : kContShards * kContCntStride);
   HIPCHK(b, hipMemcpyAsync(cnt, b->counters.ptr, sizeof(cnt), hipMemcpyDeviceToHost, b->stream));
   if (!final_layer) HIPCHK(b, hipMemcpyAsync(fill.data(), b->cont_cnt.ptr, fill.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+  uint32_t cont_err = 0;
+  if (canon_check) HIPCHK(b, hipMemcpyAsync(&cont_err, b->cont_err.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
   if (b->tally_unread) {
     if (int rc = pull_tally(b)) return rc;   // (one more small copy and THE stream sync of this call: the two copies above are complete behind it)
   } else {
     HIPCHK(b, hipStreamSynchronize(b->stream));
   }
   harvest_all(b);
+  if (cont_err != 0u)   // never a pool handed on (or traced) out of canonical order in silence
+    return cont_order_fail(b, cont_err);
   uint64_t n_cont = 0;
   if (!final_layer) {  // the next layer addresses the pool through the prefix of the shard fill counts
+    b->cont_fill_max = 0;
     for (int sI = 0; sI < kContShards; sI++) {
       const uint32_t c = fill[static_cast<size_t>(sI) * kContCntStride];
-      if (c > out_cap) return fail(b, HALO_FATAL, "continuation pool overflow");
+      // (canonical order included: a pool that lost records would be handed on with holes in its order — never, the session fails)
+      if (c > out_cap) return fail(b, HALO_FATAL, b->cont_order ? "continuation pool overflow (cont_order = 1: the canonical pool would be incomplete)" : "continuation pool overflow");
       b->cont_seg[sI] = static_cast<uint32_t>(n_cont);
       n_cont += c;
+      b->cont_fill_max = std::max(b->cont_fill_max, c);
     }
     b->cont_seg[kContShards] = static_cast<uint32_t>(n_cont);
+    b->cont_roots = n;
   }
   b->exits_pending = std::min<uint64_t>(cnt[kCntExit], b->exits.cap);
   b->layer_acc.root_count = n;
@@ -1830,6 +1880,40 @@ int halo_recombine(halo_handle_t b, int shuffle, uint64_t* continuation_count) {
   if (!b->in_session) return fail(b, HALO_FATAL, "Recombine outside a session");
   // No data moves: the pools swap roles and the Feistel permutation (shuffle_cont_kernel, cu:1633-1657) is
   // applied as a gather index by the next layer's kernel.
+  if (b->cont_order) {
+    // Canonical order: the sharded pool is sorted by (root, interaction) into the pool the layer just traced has read (free now: its kernels were
+    // joined and waited for at the end of TraceLayer), as ONE region; the next layer appends to the sharded pool again.  Queued on the session's
+    // stream behind every launch of the layer, no host wait; the next layer's mask clear and counter reset queue behind it.
+    const int src = b->cont_out_slot, dst = src ^ 1;
+    const uint64_t n_cont = b->cont_in_n;
+    const uint64_t planes = b->color_classes.empty() ? 5 : 7;
+    const uint64_t stride = std::max<uint64_t>((n_cont + 63) & ~63ull, 64);
+    HIPCHK(b, hipSetDevice(b->device));
+    if (int rc = reserve_idle(b, b->cont[dst], stride * planes)) return rc;
+    if (n_cont > 0) {
+      const uint64_t tiles = (b->cont_roots + 2047) / 2048;   // (halo_kernels.hip kScanTile)
+      if (int rc = reserve_idle(b, b->cont_base, std::max<uint64_t>(b->cont_roots, 1))) return rc;
+      if (int rc = reserve_idle(b, b->cont_tiles, std::max<uint64_t>(tiles, 1))) return rc;
+      const hipError_t e = launch_cont_reorder(b->cont[src].ptr, b->cont_stride[src], b->cont_region[src], b->cont_cnt.ptr, b->cont_fill_max, b->cont_mask.ptr,
+                                               static_cast<uint32_t>(b->cont_roots), b->cont_tiles.ptr, b->cont_base.ptr, b->cont[dst].ptr, static_cast<uint32_t>(stride),
+                                               static_cast<uint32_t>(n_cont), static_cast<uint32_t>(planes), b->cont_err.ptr, b->stream);
+      if (e != hipSuccess) return hip_fail(b, e, "halo_cont_scatter_kernel launch");
+      // the reorder's invariants, checked before any layer reads the pool: one 4-byte read behind the scatter (which the next layer's kernels
+      // wait for in any case)
+      uint32_t err = 0;
+      HIPCHK(b, hipMemcpyAsync(&err, b->cont_err.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+      HIPCHK(b, hipStreamSynchronize(b->stream));
+      if (err != 0u) return cont_order_fail(b, err);
+    }
+    b->cont_stride[dst] = static_cast<uint32_t>(stride);
+    b->cont_region[dst] = static_cast<uint32_t>(stride);
+    b->cont_seg[0] = 0;   // one region: every logical index lies in shard 0
+    for (int sI = 1; sI <= kContShards; sI++) b->cont_seg[sI] = static_cast<uint32_t>(n_cont);
+    b->cont_shuffle = shuffle ? 1 : 0;
+    b->layer_idx++;
+    if (continuation_count) *continuation_count = b->cont_in_n;
+    return HALO_OK;
+  }
   b->cont_out_slot ^= 1;
   b->cont_shuffle = shuffle ? 1 : 0;
   b->layer_idx++;

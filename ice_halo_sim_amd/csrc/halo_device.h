@@ -212,6 +212,13 @@ struct FastTables {
 constexpr int kContShards = 256;
 constexpr uint32_t kLogWlShift = 23u;   // DispatchParams::log_xyz records: slot in bits 0..22, CMF code above: a wavelength-pool entry, or pool size + c for a weight that is already channel c of X, Y, Z
 constexpr int kContCntStride = 16;
+// canonical continuation order (option cont_order = 1): the two extra planes of an output pool record — layer-global root index, exit seq — and the
+// per-root mask: a root emits each seq at most once (outward child 2i+1 and a stray inward child 2i of interaction i; 0 / 1 at i = 0), seq < 2 * HALO_MAX_HITS
+constexpr uint32_t kContPlaneRoot = 7u, kContPlaneSeq = 8u, kContPlanesCanonical = 9u;
+constexpr uint32_t kContMaskWords = 4u;   // 128 bits per root
+// error word bits: a record with a key outside the layer or a slot outside the pool (append, scatter); the masks' popcounts do not sum to the
+// pool's fill — a seq continued twice, or a record lost (scan)
+constexpr uint32_t kContErrKey = 2u, kContErrSum = 4u;
 
 struct HitRec {  // one staged pixel hit of the binned accumulation: slot inside plane 0 and the weight's bits
   uint32_t slot, w_bits;
@@ -277,6 +284,10 @@ struct DispatchParams {
   uint32_t cont_out_stride;
   uint32_t cont_out_cap;       // slots per shard region of the output pool
   uint32_t* cont_cnt;          // [kContShards * kContCntStride] fill count of each shard region
+  uint32_t* cont_mask;         // canonical continuation order (option cont_order = 1; else nullptr): per root of the layer, a 128-bit mask of the
+                               // exit seqs that continued (kContMaskWords words, bit seq); each appended record also carries its root and seq in
+                               // pool planes kContPlaneRoot / kContPlaneSeq, and halo_cont_scatter_kernel sorts the pool by them
+  uint32_t* cont_err;          // ... and its error word (kContErr* bits), which the host turns into HALO_FATAL at Recombine / the end of the layer
   uint32_t* counters;          // [0] continuation count, [1] captured exits, [2] exit count lo.. see kCnt*
   // --- host-injected rays (crystal-local) -------------------------------------------------------
   const float* host_d;

@@ -845,6 +845,147 @@ hipError_t launch_fold(float* xyz, float* planes, uint32_t n_pix, uint32_t s_log
   return hipGetLastError();
 }
 
+// ---- canonical continuation order (option cont_order = 1) ----------------------------------------------------------------------------
+// A layer before the last appends its continuations wherever its waves' atomics land (sharded pool, see kContShards); with the option on each
+// record also carries (root, seq) and every root a 128-bit mask of the seqs that continued.  Recombine then sorts the pool into (root, seq)
+// order — the order a one-thread run of the oracle builds — in O(roots + records): an exclusive scan of the masks' popcounts over the roots
+// (reduce, scan of the tile sums, downsweep) gives each root its first slot, and a record's slot is that plus the number of its root's bits
+// below its own.  Roots are in tiles of kScanTile, eight consecutive roots per thread.  Whatever breaks the invariant — a key outside the
+// layer, a slot outside the pool, popcounts that do not add up to the pool's fill (a seq continued twice loses a bit) — sets a bit of the error
+// word (kContErr*), which Recombine reads behind the scatter and turns into HALO_FATAL: a pool with holes is never traced.
+constexpr uint32_t kScanBlock = 256u, kScanItems = 8u, kScanTile = kScanBlock * kScanItems;
+
+__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v) {
+  const uint32_t lane = __lane_id();
+#pragma unroll
+  for (uint32_t d = 1u; d < 64u; d <<= 1) {
+    const uint32_t t = __shfl_up(v, d, 64);
+    if (lane >= d) v += t;
+  }
+  return v;
+}
+// exclusive prefix of v over the workgroup (kScanBlock threads); `total` is the workgroup's sum
+__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t& total) {
+  __shared__ uint32_t s_wave[kScanBlock / 64u];
+  const uint32_t inc = wave_inclusive_scan(v);
+  const uint32_t w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63u) == 63u) s_wave[w] = inc;
+  __syncthreads();
+  uint32_t before = 0u;
+  total = 0u;
+#pragma unroll
+  for (uint32_t k = 0; k < kScanBlock / 64u; k++) {
+    const uint32_t s = s_wave[k];
+    before += (k < w) ? s : 0u;
+    total += s;
+  }
+  __syncthreads();   // (s_wave is reused by the next call)
+  return before + inc - v;
+}
+// a root's 128-bit mask as two 64-bit halves (kContMaskWords = 4 words)
+struct Mask128 {
+  unsigned long long lo, hi;
+};
+__device__ __forceinline__ Mask128 load_mask(const unsigned long long* __restrict__ mask, uint64_t r) { return Mask128{mask[2u * r], mask[2u * r + 1u]}; }
+__device__ __forceinline__ uint32_t mask_count(Mask128 m) { return static_cast<uint32_t>(__popcll(m.lo) + __popcll(m.hi)); }
+__device__ __forceinline__ uint32_t mask_below(Mask128 m, uint32_t seq) {   // bits of m below bit `seq` (< 128)
+  return seq < 64u ? static_cast<uint32_t>(__popcll(m.lo & ((1ull << seq) - 1ull)))
+                   : static_cast<uint32_t>(__popcll(m.lo) + __popcll(m.hi & ((1ull << (seq - 64u)) - 1ull)));
+}
+// the popcounts of one thread's eight masks (roots past n count 0)
+__device__ __forceinline__ void tile_counts(const unsigned long long* __restrict__ mask, uint32_t n, uint32_t c[kScanItems]) {
+  const uint64_t r0 = static_cast<uint64_t>(blockIdx.x) * kScanTile + static_cast<uint64_t>(threadIdx.x) * kScanItems;
+#pragma unroll
+  for (uint32_t k = 0; k < kScanItems; k++) c[k] = (r0 + k < n) ? mask_count(load_mask(mask, r0 + k)) : 0u;
+}
+
+__global__ void __launch_bounds__(kScanBlock) halo_cont_count_kernel(const unsigned long long* __restrict__ mask, uint32_t n, uint32_t* __restrict__ tile_sum) {
+  uint32_t c[kScanItems];
+  tile_counts(mask, n, c);
+  uint32_t v = 0u;
+#pragma unroll
+  for (uint32_t k = 0; k < kScanItems; k++) v += c[k];
+  uint32_t total;
+  (void)block_exclusive_scan(v, total);
+  if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
+}
+
+// one workgroup: the tile sums, exclusively scanned in place (kScanTile of them per pass, a carry between passes); the grand total must be the
+// pool's fill, n_cont
+__global__ void __launch_bounds__(kScanBlock) halo_cont_tiles_scan_kernel(uint32_t* __restrict__ tile_sum, uint32_t tiles, uint32_t n_cont, uint32_t* __restrict__ err) {
+  uint64_t carry = 0u;
+  for (uint32_t t0 = 0u; t0 < tiles; t0 += kScanTile) {
+    const uint32_t i0 = t0 + threadIdx.x * kScanItems;
+    uint32_t c[kScanItems], v = 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < kScanItems; k++) {
+      c[k] = (i0 + k < tiles) ? tile_sum[i0 + k] : 0u;
+      v += c[k];
+    }
+    uint32_t total;
+    uint32_t run = static_cast<uint32_t>(carry) + block_exclusive_scan(v, total);
+#pragma unroll
+    for (uint32_t k = 0; k < kScanItems; k++) {
+      if (i0 + k < tiles) tile_sum[i0 + k] = run;
+      run += c[k];
+    }
+    carry += total;
+  }
+  if (threadIdx.x == 0 && carry != n_cont) atomicOr(err, kContErrSum);
+}
+
+__global__ void __launch_bounds__(kScanBlock) halo_cont_base_kernel(const unsigned long long* __restrict__ mask, uint32_t n, const uint32_t* __restrict__ tile_off,
+                                                                    uint32_t* __restrict__ base) {
+  uint32_t c[kScanItems];
+  tile_counts(mask, n, c);
+  uint32_t v = 0u;
+#pragma unroll
+  for (uint32_t k = 0; k < kScanItems; k++) v += c[k];
+  uint32_t total;
+  uint32_t run = tile_off[blockIdx.x] + block_exclusive_scan(v, total);
+  const uint64_t r0 = static_cast<uint64_t>(blockIdx.x) * kScanTile + static_cast<uint64_t>(threadIdx.x) * kScanItems;
+#pragma unroll
+  for (uint32_t k = 0; k < kScanItems; k++) {
+    if (r0 + k < n) base[r0 + k] = run;
+    run += c[k];
+  }
+}
+
+// every record of the sharded pool (shard blockIdx.y, its fill count from the trace kernels' own counter) to its canonical slot, all planes
+__global__ void __launch_bounds__(kBlock) halo_cont_scatter_kernel(const uint32_t* __restrict__ in, uint32_t in_stride, uint32_t region, const uint32_t* __restrict__ cnt,
+                                                                   const unsigned long long* __restrict__ mask, const uint32_t* __restrict__ base, uint32_t n_roots,
+                                                                   uint32_t* __restrict__ out, uint32_t out_stride, uint32_t n_cont, uint32_t planes,
+                                                                   uint32_t* __restrict__ err) {
+  const uint32_t shard = blockIdx.y;
+  const uint32_t fill = min(cnt[shard * kContCntStride], region);
+  for (uint32_t off = blockIdx.x * kBlock + threadIdx.x; off < fill; off += gridDim.x * kBlock) {
+    const uint32_t src = shard * region + off;
+    const uint32_t root = in[kContPlaneRoot * in_stride + src], seq = in[kContPlaneSeq * in_stride + src];
+    const Mask128 m = (root < n_roots) ? load_mask(mask, root) : Mask128{0ull, 0ull};
+    const bool known = root < n_roots && seq < 32u * kContMaskWords && ((seq < 64u ? (m.lo >> seq) : (m.hi >> (seq - 64u))) & 1ull) != 0ull;
+    const uint32_t dst = known ? base[root] + mask_below(m, seq) : n_cont;
+    if (dst >= n_cont) {   // (cannot happen while the append and the scan hold their invariants — and if it does, the layer is refused)
+      atomicOr(err, kContErrKey);
+      continue;
+    }
+    for (uint32_t p = 0; p < planes; p++) out[p * out_stride + dst] = in[p * in_stride + src];
+  }
+}
+
+hipError_t launch_cont_reorder(const float* in, uint32_t in_stride, uint32_t region, const uint32_t* cnt, uint32_t max_fill, const uint32_t* mask, uint32_t n_roots,
+                               uint32_t* tile_sum, uint32_t* base, float* out, uint32_t out_stride, uint32_t n_cont, uint32_t planes, uint32_t* err, hipStream_t stream) {
+  if (n_cont == 0u || n_roots == 0u) return hipSuccess;
+  const uint32_t tiles = static_cast<uint32_t>((static_cast<uint64_t>(n_roots) + kScanTile - 1u) / kScanTile);
+  const unsigned long long* m = reinterpret_cast<const unsigned long long*>(mask);
+  hipLaunchKernelGGL(halo_cont_count_kernel, dim3(tiles), dim3(kScanBlock), 0, stream, m, n_roots, tile_sum);
+  hipLaunchKernelGGL(halo_cont_tiles_scan_kernel, dim3(1), dim3(kScanBlock), 0, stream, tile_sum, tiles, n_cont, err);
+  hipLaunchKernelGGL(halo_cont_base_kernel, dim3(tiles), dim3(kScanBlock), 0, stream, m, n_roots, tile_sum, base);
+  const uint32_t gx = std::max<uint32_t>(1u, std::min<uint32_t>(static_cast<uint32_t>((static_cast<uint64_t>(max_fill) + kBlock - 1u) / kBlock), 64u));
+  hipLaunchKernelGGL(halo_cont_scatter_kernel, dim3(gx, kContShards), dim3(kBlock), 0, stream, reinterpret_cast<const uint32_t*>(in), in_stride, region, cnt, m, base,
+                     n_roots, reinterpret_cast<uint32_t*>(out), out_stride, n_cont, planes, err);
+  return hipGetLastError();
+}
+
 hipError_t launch_trace_m0(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);
 hipError_t launch_trace_m1(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);
 hipError_t launch_trace_m2(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);

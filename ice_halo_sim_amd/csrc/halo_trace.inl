@@ -589,6 +589,7 @@ struct AccCtx {
   int lens, vis;     // >= 0: instantiated for this lens / visible range (the projection's dispatch folds away)
   bool nogate;       // instantiated for prob <= 0: no candidate ever passes the gate, the gate stream and its code fold away
   bool last;         // kAccLogFinal kernels: the scene's last layer — no candidate continues, the append code is compiled out
+  bool canon;        // canonical-order kernels (option cont_order = 1, layers before the last): appends carry their (root, interaction) key
   bool none;         // kAccNone kernels: every outgoing candidate continues (prob >= 1, not the last layer), nothing is projected
   ExitQueue* q;      // this wave's exit queue; nullptr = project and accumulate at the emit site
   ExitQueueMask* qm; // ... its colour-mask planes (kModeColor)
@@ -1463,6 +1464,20 @@ HD void emit_gate(const DispatchParams& P, const AccCtx<MONO, SMALLC>& cache, co
         if (MODE == kModeColor || (ModeTraits<MODE>::kTables && color != nullptr)) {  // the mask rides with the continuation (cu:922,1129)
           reinterpret_cast<uint32_t*>(P.cont_out)[5u * st + slot] = static_cast<uint32_t>(cmask);
           reinterpret_cast<uint32_t*>(P.cont_out)[6u * st + slot] = static_cast<uint32_t>(cmask >> 32);
+        }
+        // Canonical order (option cont_order = 1): the record takes its key — layer-global root, exit seq — and the root's 128-bit mask the seq's
+        // bit; Recombine sorts the pool by them (halo_cont_scatter_kernel).  Under rehit_strategy 1 (the host refuses the option with 0) a root emits
+        // each seq at most once: interaction i may emit its outward child (seq 2i+1, or 0 when entering) AND, when the inward child finds no face
+        // ahead, that one too (the stray emit below, seq 2i, or 1) — two exits of one interaction, two different seqs, in the oracle's order
+        // (child 0 before child 1).  A seq set twice would lose a bit: the masks' popcounts would then fall short of the pool's fill, which the
+        // reorder checks (kContErrSum) before anything reads the pool — a returning atomic here to catch it at once cost configs[2]'s first layer
+        // 1.9 ms per 50 M roots.  Only the CANON instantiations carry this (a run-time test here cost the no-accumulation kernel of configs[2]'s
+        // first layer 2 VGPRs and a wave per SIMD of occupancy).
+        if (cache.canon) {
+          reinterpret_cast<uint32_t*>(P.cont_out)[kContPlaneRoot * st + slot] = root;
+          reinterpret_cast<uint32_t*>(P.cont_out)[kContPlaneSeq * st + slot] = seq;
+          if (seq < 32u * kContMaskWords) atomicOr(P.cont_mask + static_cast<uint64_t>(kContMaskWords) * root + (seq >> 5), 1u << (seq & 31u));
+          else atomicOr(P.cont_err, kContErrKey);
         }
       }
     }
@@ -2509,7 +2524,8 @@ constexpr int min_waves() {
 // LENS / VIS >= 0, NOGATE: instantiated for that lens, that visible range and prob <= 0 — the projection's dispatch over 11 lens
 // types (uniform branches, and the SGPRs their parameters hold), the visibility tests and the gate stream fold away: configs[1]
 // 2.96 -> 2.73 (lens) -> 2.60 ms per launch.  Done for the last-layer one-shape scalar kernels and the lenses of the shipped examples.
-template <int MODE, int GEOM, bool MONO, int ACC, int LENS = -1, int VIS = -1, bool NOGATE = false>   // ACC: kAccDirect, kAccBin (staged + binned hit lists), kAccLog (per-workgroup hit log), ...
+// CANON: a layer before the last under canonical continuation order (option cont_order = 1) — its appends carry their (root, interaction) key.
+template <int MODE, int GEOM, bool MONO, int ACC, int LENS = -1, int VIS = -1, bool NOGATE = false, bool CANON = false>   // ACC: kAccDirect, kAccBin (staged + binned hit lists), kAccLog (per-workgroup hit log), ...
 __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) halo_trace_kernel(const DispatchParams P) {
   constexpr bool BIN = ACC == kAccBin, LOG = ACC == kAccLog || ACC == kAccLogFinal, NONE = ACC == kAccNone, LAST = ACC == kAccLogFinal;
   static_assert(!LOG || ModeTraits<MODE>::kFast, "the hit log is a production-mode route");
@@ -2549,6 +2565,7 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
   }
   acc.none = NONE;
   acc.last = LAST;
+  acc.canon = CANON;
   acc.lens = LENS;
   acc.vis = VIS;
   acc.nogate = NOGATE;
@@ -2867,8 +2884,26 @@ static void launch_lens(const DispatchParams& P, dim3 grid, dim3 block, hipStrea
   }
 }
 
+// Canonical continuation order (P.cont_mask set: option cont_order = 1, a layer before the last): the CANON twins of the direct-accumulation and
+// no-accumulation kernels — the host gives such a layer neither the hit log nor binned lists, so no other instantiation needs a twin.
+template <int MODE, int GEOM>
+static void launch_canon(const DispatchParams& P, dim3 grid, dim3 block, hipStream_t stream, bool mono) {
+  if constexpr (ModeTraits<MODE>::kFast && (GEOM == kGeomOne || GEOM == kGeomOneHex)) {
+    if (P.no_land != 0u) {
+      hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, true, kAccNone, -1, -1, false, true>), grid, block, 0, stream, P);
+      return;
+    }
+  }
+  if (mono) hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, true, kAccDirect, -1, -1, false, true>), grid, block, 0, stream, P);
+  else hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, false, kAccDirect, -1, -1, false, true>), grid, block, 0, stream, P);
+}
+
 template <int MODE, int GEOM>
 static void launch_mono(const DispatchParams& P, dim3 grid, dim3 block, hipStream_t stream, bool mono) {
+  if (P.cont_mask != nullptr) {
+    launch_canon<MODE, GEOM>(P, grid, block, stream, mono);
+    return;
+  }
   if constexpr (ModeTraits<MODE>::kFast && (GEOM == kGeomOne || GEOM == kGeomOneHex)) {
     if (P.no_land != 0u) {   // every exit of this layer continues: no cache, no queue, no accumulation code
       hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, true, kAccNone>), grid, block, 0, stream, P);

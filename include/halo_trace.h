@@ -301,6 +301,13 @@ const char* halo_last_error(halo_handle_t h);
  * several times slower) — for a caller that needs SURVEY's stated ground truth ray for ray; not inside a session),
  * "shuffle_chunk" (Recombine's shuffle permutes chunks of this many consecutive continuation-pool entries; power of two in
  * [1, 64], default 32 = one 128-byte line per plane read; 1 = the reference's per-ray permutation, cu:1633-1657),
+ * "cont_order" (additive in ABI 6, no struct changed: 0 [default] = the continuation pool in append order, which wave scheduling decides;
+ * 1 = canonical order — after every layer but the last, halo_recombine sorts the pool by (layer-global root index, exit seq) — the index
+ * HaloExitRecord::root reports, on the device and in stream order; shuffle, shuffle_chunk and the transit streams keep their meaning, so a
+ * fixed seed traces the same rays on every layer of every run (the image is still a float sum in scheduling order).  Layers before the last
+ * then accumulate with direct atomics, and every layer of a multi-layer session returns synchronously (option async does not defer the last
+ * one: the layer ends with the check of the order's invariants — a broken one, like a pool overflow, is HALO_FATAL); needs rehit_strategy = 1;
+ * not inside a session),
  * scheduling (ABI 6; none of them changes a result): "overlap" (1 [default]: launches of <= 2 Mi rays alternate between two
  * trace streams, closing folds run on an auxiliary stream; 0 = everything on the one stream), "table_cache" (1 [default]: equal
  * sessions reuse their device tables), "small_blocks_per_cu" (default 5: workgroups per CU a small launch spreads over before a

@@ -76,6 +76,17 @@ struct DevBuf {
     cap = 0;
   }
 };
+template <typename... B>
+void release_all(B&... bufs) { (bufs.release(), ...); }
+
+// "The last work of kind X": an event recorded behind that work, and whether anything has been recorded on it yet (nothing: nobody need wait).
+struct Marker {
+  hipEvent_t ev = nullptr;
+  bool set = false;
+  hipError_t mark(hipStream_t s) { const hipError_t e = hipEventRecord(ev, s); set = set || e == hipSuccess; return e; }
+  hipError_t wait_on(hipStream_t s) const { return set ? hipStreamWaitEvent(s, ev, 0) : hipSuccess; }
+  void clear() { set = false; }
+};
 
 }  // namespace
 
@@ -101,13 +112,12 @@ struct HaloBackend {
   DevBuf<HitRec> bin_list_s[2], bin_list2_s[2];   // one-level tile lists / coarse lists / log regions; tile lists of the two-level and log routes
   DevBuf<uint32_t> bin_cnt_s[2], bin_cnt2_s[2];
   int log_set = 0;                      // the set the next logged launch writes
-  bool set_used[2] = {false, false};    // ev_set_free[s] has been recorded: the set's last passes may still be running
-  hipEvent_t ev_set_free[2] = {};
+  Marker set_free[2];                   // the passes that last read log set s (they may still be running)
   // Auxiliary stream (round 5): the closing folds are queued here, behind everything the other streams hold, and nobody waits for them until
   // somebody reads the image or adds to the planes again — a session's fold (20 us) runs under the next session's first kernels instead of
   // in front of them.  (Two engines side by side on one GPU had measured +10 .. 15 % over one, tools/two_engines_probe.py; what that was,
   // looked at inside one engine, is the small things between kernels — folds, resets, uploads, the tails — not the trace kernels or their
-  // passes, which gain nothing from running under each other: see the passes in halo_trace_layer.)
+  // passes, which gain nothing from running under each other: see queue_passes.)
   hipStream_t aux = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   bool aux_pending = false;             // work has been queued on `aux` that the main stream has not waited for
@@ -182,8 +192,7 @@ struct HaloBackend {
   bool mono_two = false;
   int mono_set = 0;
   size_t mono_half = 0;                                   // floats per set
-  hipEvent_t ev_set_folded[2] = {nullptr, nullptr};      // behind the fold that last zeroed the set
-  bool set_folded_pending[2] = {false, false};
+  Marker set_folded[2];                                   // the fold that last zeroed the set
   uint32_t plane_cnt = 1, plane_copies = 8;
   std::vector<std::array<float, 3>> plane_coef;  // fold coefficients of the pending planes
   // consumer (RenderConsumer state, server/render.hpp): Neumaier running image + total landed intensity
@@ -241,16 +250,15 @@ struct HaloBackend {
   struct LutKey { int32_t type; float center, spread; host::LatLut lut; };
   std::vector<LutKey> lut_cache;
   DevBuf<ShapeDev> shapes_s[2];   // sampled-crystal pools: launch k+1's generator must not overwrite what launch k still traces
-  hipEvent_t ev_shapes_free[2] = {nullptr, nullptr};   // recorded behind the trace kernel that read the pool
+  Marker shapes_free[2];                               // the trace kernel that last read the pool
   hipEvent_t ev_gen = nullptr;                         // the generator of a chip-filling launch, queued on trace stream 1 (see gen_ahead)
-  bool shapes_used[2] = {false, false};
   int shapes_next = 0;
   // Plane ownership between the two trace streams.  The per-tile sums of a logged (or two-level binned) launch end in PLAIN read-modify-writes of
   // the planes; everything else that adds to them uses atomics.  So (1) a launch's sums wait for what the OTHER trace stream held when the launch
-  // was queued (ev_gate), and (2) a later launch on the other stream whose trace kernel adds to the planes itself waits for those sums (ev_rmw).
+  // was queued (ev_gate), and (2) a later launch on the other stream whose trace kernel adds to the planes itself waits for those sums (rmw).
   // Logged trace kernels touch no plane (their overflow goes to the fp64 twin), so they run beside a neighbour's passes freely.
-  hipEvent_t ev_gate = nullptr, ev_rmw[2] = {nullptr, nullptr};
-  bool rmw_pending[2] = {false, false};
+  hipEvent_t ev_gate = nullptr;
+  Marker rmw[2];                  // the per-tile sums last queued on trace stream i
   int log_tiles_log2 = 7;         // option (experiment knob): the scalar hit-log route cuts a plane into up to 2^this tiles (<= 8)
   int alt_log2 = 25;              // option (experiment knob): launches of up to 2^alt_log2 rays alternate between the two trace streams
   int rehit_strategy = 1;         // option: 1 [default] the reference's CUDA next-face strategy (the child that leaves through the face it stands on is emitted where it is);
@@ -278,6 +286,11 @@ struct HaloBackend {
   DevBuf<float> host_f;        // injected rays: d | p | w
   DevBuf<uint32_t> host_u;
   uint64_t sess_crystal_samples = 0, sess_orient_samples = 0;  // this session's stochastic draws (halo_last_sample_counts)
+  // every event made without timing: the one-shot ones, the joins' and the markers' (created in halo_create, destroyed in halo_destroy)
+  std::vector<hipEvent_t*> untimed_events() {
+    return {&ev_cs[0], &ev_cs[1], &ev_main, &ev_aux, &ev_fork, &ev_join, &ev_gen, &ev_gate, &set_free[0].ev, &set_free[1].ev, &shapes_free[0].ev,
+            &shapes_free[1].ev, &rmw[0].ev, &rmw[1].ev, &set_folded[0].ev, &set_folded[1].ev};
+  }
 };
 
 namespace {
@@ -326,7 +339,7 @@ int join_aux(HaloBackend* b) {
       HIPCHK(b, hipEventRecord(b->ev_cs[k], b->cs[k]));
       HIPCHK(b, hipStreamWaitEvent(b->stream, b->ev_cs[k], 0));
       b->cs_pending[k] = false;
-      b->rmw_pending[k] = false;   // (every later launch waits for the main stream, which now waits for these sums)
+      b->rmw[k].clear();   // (every later launch waits for the main stream, which now waits for these sums)
     }
   return HALO_OK;
 }
@@ -532,14 +545,8 @@ int halo_create(int device_ordinal, uint32_t seed, halo_handle_t* out) {
     return HALO_UNAVAILABLE;
   }
   bool aux_ok = hipStreamCreateWithFlags(&b->aux, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&b->cs[0], hipStreamNonBlocking) == hipSuccess &&
-                hipStreamCreateWithFlags(&b->cs[1], hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&b->ev_cs[0], hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&b->ev_cs[1], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&b->ev_main, hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&b->ev_aux, hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&b->ev_set_free[0], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&b->ev_set_free[1], hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&b->ev_shapes_free[0], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&b->ev_shapes_free[1], hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&b->ev_gen, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&b->ev_gate, hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&b->ev_rmw[0], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&b->ev_rmw[1], hipEventDisableTiming) == hipSuccess;
+                hipStreamCreateWithFlags(&b->cs[1], hipStreamNonBlocking) == hipSuccess;
+  for (hipEvent_t* ev : b->untimed_events()) aux_ok = aux_ok && hipEventCreateWithFlags(ev, hipEventDisableTiming) == hipSuccess;
   bool ring_ok = aux_ok && b->ring_dev.reserve(HaloBackend::kRing) == hipSuccess &&
                  hipHostMalloc(reinterpret_cast<void**>(&b->ring_host), HaloBackend::kRing * sizeof(DispatchSlot), hipHostMallocDefault) == hipSuccess &&
                  hipHostMalloc(reinterpret_cast<void**>(&b->tally_host), kTallyLines * kTallyStride * sizeof(double), hipHostMallocDefault) == hipSuccess;
@@ -568,67 +575,20 @@ int halo_destroy(halo_handle_t b) {
   if (b->aux) (void)hipStreamSynchronize(b->aux);
   for (int k = 0; k < 2; k++)
     if (b->cs[k]) (void)hipStreamSynchronize(b->cs[k]);
-  b->acc_own.release();
-  b->tally.release();
-  b->mono.release();
-  b->ovf.release();
-  b->ovf_flag.release();
-  b->filter_dev.release();
-  b->cons_sum.release();
-  b->cons_comp.release();
-  b->cons_xyz_out.release();
-  b->cons_stage.release();
-  b->cons_rgb.release();
-  b->comp_rgb.release();
-  b->lanes_stage.release();
-  b->comp_hist.release();
-  b->counters.release();
-  b->ring_dev.release();
-  b->tcache_dev.release();
+  release_all(b->acc_own, b->tally, b->mono, b->ovf, b->ovf_flag, b->filter_dev, b->cons_sum, b->cons_comp, b->cons_xyz_out, b->cons_stage, b->cons_rgb, b->comp_rgb,
+              b->lanes_stage, b->comp_hist, b->counters, b->ring_dev, b->tcache_dev, b->shapes_s[0], b->shapes_s[1], b->cont_cnt, b->cont_mask, b->cont_err, b->cont_base,
+              b->cont_tiles, b->lanes, b->cont[0], b->cont[1], b->exits, b->host_f, b->host_u);
+  for (int k = 0; k < 2; k++) release_all(b->bin_list_s[k], b->bin_cnt_s[k], b->bin_list2_s[k], b->bin_cnt2_s[k]);
   if (b->ring_host) (void)hipHostFree(b->ring_host);
   if (b->tally_host) (void)hipHostFree(b->tally_host);
-  for (int k = 0; k < HaloBackend::kRing; k++) {
-    if (b->ring_ev0[k]) (void)hipEventDestroy(b->ring_ev0[k]);
-    if (b->ring_ev1[k]) (void)hipEventDestroy(b->ring_ev1[k]);
-    if (b->ring_ev2[k]) (void)hipEventDestroy(b->ring_ev2[k]);
-    if (b->ring_ev3[k]) (void)hipEventDestroy(b->ring_ev3[k]);
-    if (b->ring_done[k]) (void)hipEventDestroy(b->ring_done[k]);
-  }
-  b->shapes_s[0].release();
-  b->shapes_s[1].release();
-  b->cont_cnt.release();
-  b->cont_mask.release();
-  b->cont_err.release();
-  b->cont_base.release();
-  b->cont_tiles.release();
-  b->lanes.release();
-  for (int k = 0; k < 2; k++) {
-    b->bin_list_s[k].release();
-    b->bin_cnt_s[k].release();
-    b->bin_list2_s[k].release();
-    b->bin_cnt2_s[k].release();
-    if (b->ev_set_free[k]) (void)hipEventDestroy(b->ev_set_free[k]);
-    if (b->ev_shapes_free[k]) (void)hipEventDestroy(b->ev_shapes_free[k]);
-    if (b->ev_rmw[k]) (void)hipEventDestroy(b->ev_rmw[k]);
-  }
-  for (hipEvent_t ev : b->ev_set_folded)
-    if (ev) (void)hipEventDestroy(ev);
-  if (b->ev_gen) (void)hipEventDestroy(b->ev_gen);
-  if (b->ev_gate) (void)hipEventDestroy(b->ev_gate);
-  if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
-  if (b->ev_join) (void)hipEventDestroy(b->ev_join);
+  for (int k = 0; k < HaloBackend::kRing; k++)
+    for (hipEvent_t ev : {b->ring_ev0[k], b->ring_ev1[k], b->ring_ev2[k], b->ring_ev3[k], b->ring_done[k]})
+      if (ev) (void)hipEventDestroy(ev);
+  for (hipEvent_t* ev : b->untimed_events())
+    if (*ev) (void)hipEventDestroy(*ev);
   if (b->aux) (void)hipStreamDestroy(b->aux);
-  for (int k = 0; k < 2; k++) {
-    if (b->ev_cs[k]) (void)hipEventDestroy(b->ev_cs[k]);
+  for (int k = 0; k < 2; k++)
     if (b->cs[k]) (void)hipStreamDestroy(b->cs[k]);
-  }
-  if (b->ev_main) (void)hipEventDestroy(b->ev_main);
-  if (b->ev_aux) (void)hipEventDestroy(b->ev_aux);
-  b->cont[0].release();
-  b->cont[1].release();
-  b->exits.release();
-  b->host_f.release();
-  b->host_u.release();
   if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
   delete b;
   return HALO_OK;
@@ -826,7 +786,7 @@ int halo_begin(halo_handle_t b, const HaloScene* scene, const HaloRender* render
   //    slow kind on gfx950 — per hit where a scalar plane pays one: the reference's 512x256 D65 scene runs 2.8 vs 8.0 G rays/s)
   uint32_t s_log2 = 6;  // columns per plane row: at least one fold tile
   while ((static_cast<size_t>(kMonoRows) << s_log2) < npix) s_log2++;
-  // the log's tile layout has limits (halo_trace_layer: log_layout_ok): X/Y/Z records keep the slot in 23 bits of which the per-tile pass
+  // the log's tile layout has limits (plan_route: log_layout_ok): X/Y/Z records keep the slot in 23 bits of which the per-tile pass
   // takes <= 4 Ki-slot tiles x 512, scalar planes 16 Ki-slot tiles x 256.  A session the log cannot serve keeps the routes it had before
   // (one plane per pool entry + binned lists; privatised copies for the direct atomics).
   const bool log_xyz_fits = s_log2 <= 11u, log_mono_fits = s_log2 <= 12u;
@@ -862,9 +822,9 @@ int halo_begin(halo_handle_t b, const HaloScene* scene, const HaloRender* render
                              b->acc_h == render->height && b->mono_s_log2 == s_log2 && b->plane_cnt == plane_cnt_n && b->plane_copies == plane_copies_n &&
                              b->mono_two == two_sets_n && b->plane_coef == coef_n;
     if (!same_planes) {
-      // (queued on the auxiliary stream; the HOST does not wait.  This session's trace kernels are queued behind it all the same
-      // (next_trace_stream is always told the launch touches the planes): letting a logged kernel start under the fold was measured — the step
-      // did not shrink, DESIGN.md 3.6 — so the simpler order stays, and the twin's two halves only keep a LATE fold and the open session apart)
+      // (queued on the auxiliary stream; the HOST does not wait.  This session's launches whose trace kernel adds to the planes, and its logged
+      // launches that fill the chip, are queued behind it (next_trace_stream); a SMALL logged launch starts under it and only its passes wait — for
+      // this fold, or with two plane sets for the one that last zeroed theirs (LaunchPlan::under_fold).  The twin's two halves keep the fold and the open session apart)
       int rc = fold_queue(b);  // also: a session that was never ended still owes its plane to the accumulator (old layout)
       if (rc != HALO_OK) return rc;
       const bool caller_reads = b->acc != nullptr && b->acc != b->acc_own.ptr && !b->defer_fold;   // the caller's memory, read in stream order: the fold must be in that order too
@@ -972,10 +932,8 @@ static int fold_queue(HaloBackend* b) {
   }
   if (flag) HIPCHK(b, hipMemsetAsync(flag, 0, sizeof(uint32_t), ps));   // every group has seen it; the fold zeroed what it took
   b->twin_set ^= 1;   // what traces from here on overflows into the other half
-  if (b->mono_two) {    // ... and adds to the other plane set, once the fold that last zeroed THAT one is through (ev_set_folded)
-    if (!b->ev_set_folded[b->mono_set]) HIPCHK(b, hipEventCreateWithFlags(&b->ev_set_folded[b->mono_set], hipEventDisableTiming));
-    HIPCHK(b, hipEventRecord(b->ev_set_folded[b->mono_set], ps));
-    b->set_folded_pending[b->mono_set] = true;
+  if (b->mono_two) {    // ... and adds to the other plane set, once the fold that last zeroed THAT one is through (set_folded)
+    HIPCHK(b, b->set_folded[b->mono_set].mark(ps));
     b->mono_set ^= 1;
   }
   b->mono_dirty = false;
@@ -1004,16 +962,697 @@ static int cont_order_fail(HaloBackend* b, uint32_t err) {
   return fail(b, HALO_FATAL, (err & kContErrSum) ? "cont_order = 1: the roots' masks do not add up to the continuation pool (an exit seq continued twice, or a record lost)"
                                                  : "cont_order = 1: a continuation record's key lies outside its layer or pool");
 }
+}  // extern "C"
 
+// ---- The steps of halo_trace_layer: plan (no HIP call) -> entry tables -> parameters -> route buffers -> launch + passes -> route record -> close ----
+namespace {
+
+// What the launches of one halo_trace_layer call share.
+struct LayerCtx {
+  int layer = 0, out_slot = 0;
+  uint32_t source = kSrcGen, out_cap = 0;
+  uint64_t n = 0;
+  const HaloHostRays* rays = nullptr;
+  // host_crystal — HostRayBatch::crystal (trace_backend.hpp:230-239): injected rays may bring the crystal they were sampled on; it is traced as it
+  // is — one shape for the whole batch, no draw from the shape stream, no stochastic sample counted (test_cpu_trace_backend.cpp:737-777)
+  bool final_layer = false, canon_check = false, host_crystal = false;
+};
+// Everything that is DECIDED about one launch before any HIP call is made: plan_launch fills the chunking part for the whole layer up front (the
+// continuation pool is sized from the same plans the launch loop walks), plan_route the accumulation route once the entry's kernel mode is known.
+struct LaunchPlan {
+  int ci = 0;
+  uint64_t m = 0, off = 0, first = 0;   // rays; offset within the entry's share; index of the first ray within the layer
+  bool deterministic = false, host_pool = false, alternate = false;
+  int geom = 0, blocks = 0;             // geom: 0 = one shape per dispatch, 1 = pool of ShapeDev records, 2 = pool of ShapePrism records (device-generated prisms)
+  uint32_t shape_cnt = 1;
+  bool use_bin = false, two_level = false, use_log = false, use_log_xyz = false, canon = false, no_land = false;
+  uint32_t fan_log2 = 0, lists1 = 0, bin_tiles = 0, log_t_log2 = 0, log_planes = 1, log_tiles = 0;
+  uint64_t cap1 = 0, cap2 = 0;          // records per region / coarse list and per tile list, as REQUESTED: reserve_log_buffers clamps the log's against free memory
+  // (Round 6: a LOGGED trace kernel writes records, its region counts and the twin's other half — nothing the closing fold of the session
+  //  before reads or zeroes — so on a SMALL launch it starts under that fold, and only its passes, which add to the planes, wait for it.  A
+  //  discrete spectrum of many short sessions (bench.py --config 4d: 31 x 0.8 M rays) was one serial chain of generator, trace, split, sums
+  //  and fold, 325 us per session; the trace kernel and generator of session k + 1 now run beside the passes and the fold of session k.
+  //  Launches that fill the chip keep the old order: measured in round 5, nothing to gain there and the kernel's own span stretches.)
+  bool under_fold() const { return use_log && alternate; }
+};
+// What a launch was given when it was queued: its dispatch-ring slot, log buffer set, shape pool and the first index of its shape stream.
+struct LaunchSlots { int k = 0, ls = 0, shape_set = 0; uint64_t first_shape = 0; };
+// The dispatch-constant tables of one crystal entry (prepare_entry_tables) and where a launch finds them (upload_tables).
+struct EntryTables {
+  int mode = 0;
+  bool fast_mode = true;    // production-shaped kernels: exit queue, hit log, regular-prism search
+  bool use_filter = false, use_color = false, cached = false;
+  bool entry_fast = false, hex_regular = false, has_fast = false;   // what the slot the launch reads holds
+  FilterDev fd{};
+  ColorDev cd{};
+  FastTables* fast_host = nullptr;
+  HaloBackend::TableCacheEntry* ce = nullptr;
+  DispatchSlot* ce_dev = nullptr;   // the entry's two slots
+};
+// launch plan: chunking bounds the host-built shape pool for stochastic geometry and keeps n_rays < 2^32
+uint64_t chunk_of(const HaloBackend& b, uint64_t left, const HaloCrystal& crystal, bool host_crystal) {
+  uint64_t m = std::min<uint64_t>(left, b.chunk);
+  // stochastic geometry: one pool record per geom_clock rays.  Device-generated prisms are 1360 B records (2.9 GB per
+  // 64 Mi rays), other device-generated shapes 4.1 KB (2 GB per 16 Mi rays); host-built pools (pageable staging + H2D)
+  // stay at 4 Mi rays
+  if (!host::IsDeterministic(crystal) && !host_crystal) {
+    const uint64_t dev = b.stoch_chunk ? b.stoch_chunk : (1ull << 26);   // records: 2.9 GB (prism) / 8.6 GB (general) per 64 Mi rays
+    m = std::min<uint64_t>(m, b.host_shapes ? (1ull << 22) : dev);
+  }
+  return m;
+}
+int blocks_of(const HaloBackend& b, uint64_t m, bool pool) {
+  // per-workgroup fixed costs (table staging, pixel-cache zero + flush) are paid per launch, a long tail is paid per
+  // round of resident workgroups: aim at >= 32 passes of the ray loop per workgroup, between 4 and blocks_per_cu per CU
+  // (measured: 1 M rays 0.27 -> 0.20 ms at 4/CU; 50 M rays 4.02 -> 3.67 ms at 24/CU instead of 8/CU)
+  // Small launches — a Lumice server that keeps a GPU route's small dispatch (2^15 .. 2^18 rays per session, server.cpp:140-151) sends nothing
+  // else — are latency: one pass of the ray loop is ~11 us on a wave that has its SIMD to itself, so they spread over as many workgroups as
+  // a CU holds (five) before a workgroup takes a second pass.  (Round 4 had found the opposite — one per CU best — while every WAVE ended
+  // with four same-line fp64 atomics; with those gone, tools/dispatch_probe.cpp, us per session at 1 / 2 / 3 / 4 / 5 / 8 per CU:
+  // 2^18 rays 67 / 50 / 45 / 44 / 43 / 44, 2^20 188 / 133 / 122 / 115 / 110 / 111, 2^22 326 / 326 / 276 / 261 / 250 / 259.)
+  const uint64_t want = m / (static_cast<uint64_t>(kBlock) * 32u);
+  // (shape-pool kernels hold four workgroups a CU, not six, and every workgroup of a logged launch is a region for the split pass: three per CU
+  //  there — bench.py --config 4d, 0.8 M rays per session, ms per step at 1 / 2 / 3 / 4 / 5 / 6 / 8 per CU: 7.26 / 5.99 / 5.73 / 5.77 / 5.86 / 6.14 / 6.39)
+  const int small_k = b.small_blocks_per_cu > 0 ? b.small_blocks_per_cu : pool ? 3 : 5;
+  const uint64_t lo_cap = static_cast<uint64_t>(b.cu_count) * static_cast<uint64_t>(std::min(b.blocks_per_cu, small_k));
+  const uint64_t cap = std::min<uint64_t>(static_cast<uint64_t>(b.cu_count * b.blocks_per_cu), std::max<uint64_t>(lo_cap, want));
+  uint64_t nb = std::min<uint64_t>((m + kBlock - 1) / kBlock, cap);
+  if (b.blocks_cap > 0) nb = std::min<uint64_t>(nb, static_cast<uint64_t>(b.blocks_cap));
+  return static_cast<int>(nb);
+}
+// The chunking part of a launch's plan: the next launch of entry `ci`, `left` of whose rays are still to be traced (`first_ci` = the entry's first ray).
+LaunchPlan plan_launch(const HaloBackend& b, const LayerCtx& c, int ci, uint64_t first_ci, uint64_t off, uint64_t left) {
+  const HaloCrystal& crystal = b.scene.layers[c.layer].entries[ci].crystal;
+  LaunchPlan p;
+  p.ci = ci, p.off = off, p.first = first_ci + off;
+  p.m = chunk_of(b, left, crystal, c.host_crystal);
+  p.deterministic = c.host_crystal || host::IsDeterministic(crystal);
+  p.shape_cnt = p.deterministic ? 1u : static_cast<uint32_t>((p.m + b.geom_clock - 1) / b.geom_clock);
+  p.host_pool = !p.deterministic && b.host_shapes;
+  p.geom = p.deterministic ? 0 : ((crystal.kind == HALO_CRYSTAL_PRISM && !p.host_pool) ? 2 : 1);
+  p.blocks = blocks_of(b, p.m, !p.deterministic);
+  // Launches of <= 2^21 rays alternate between the two trace streams (next_trace_stream); only those can meet a neighbour that still reads
+  // or writes a buffer set, so only those take the sets in turn — a launch that fills the chip keeps stream 0 and set 0 (a second set
+  // allocated in the middle of a run is a host sync and a multi-gigabyte hipMalloc: 1.2 s in configs[4]'s first timed step)
+  p.alternate = p.m <= (1ull << b.alt_log2);
+  return p;
+}
+// The accumulation route of a planned launch (direct / binned one- or two-level / hit log scalar / hit log X/Y/Z / none) and the buffer sizes it asks for.
+void plan_route(const HaloBackend& b, const LayerCtx& c, bool fast_mode, LaunchPlan& p) {
+  const HaloLayer& L = b.scene.layers[c.layer];
+  const uint64_t m = p.m, blocks = static_cast<uint64_t>(p.blocks);
+  const uint32_t s_log2 = b.mono_s_log2;
+  const bool full_sky = b.render.visible == HALO_VISIBLE_FULL;
+  // binned accumulation for big one-plane launches (see halo_trace.inl: HitBuffer)
+  // 16384-slot tiles over the session's planes taken as one array (1 plane, or the per-entry planes of a small image)
+  const uint64_t bin_slots = (static_cast<uint64_t>(kMonoRows) << s_log2) * (b.mono_by_wl ? b.plane_cnt : 1u);
+  p.bin_tiles = static_cast<uint32_t>(bin_slots >> 14);
+  const bool bin_geom_ok = p.deterministic || L.entries[p.ci].crystal.kind == HALO_CRYSTAL_PRISM;
+  // up to 512 tiles: one level (interleaved tiles).  More (per-wavelength planes of a large image): two levels — the
+  // trace kernel fills coarse lists of `fan` consecutive tiles each, a split pass deals them out to the tiles.
+  p.fan_log2 = 0u;
+  while (((p.bin_tiles + (1u << p.fan_log2) - 1u) >> p.fan_log2) > b.bin_l1) p.fan_log2++;
+  p.two_level = p.bin_tiles > 512u;
+  const bool bin_shape_ok = p.two_level ? (p.fan_log2 <= 8u && (bin_slots & 16383ull) == 0ull)
+                                        : (p.bin_tiles >= 8u && (p.bin_tiles & (p.bin_tiles - 1u)) == 0u);
+  // The hit log over the scalar planes of a per-entry-plane session (small images: the reference's 512x256 D65 scenes): every plane gets
+  // 2^t interleaved tiles of <= 16 Ki slots, and the split pass feeds at most 512 lists — 64 planes up to 128 Ki pixels, 32 up to 256 Ki.
+  const uint32_t wl_t_log2 = s_log2 >= 4u ? s_log2 - 4u : 0u;
+  const bool log_planes_ok = b.mono_by_wl && (static_cast<uint64_t>(b.plane_cnt) << wl_t_log2) <= 512ull &&
+                             (static_cast<uint64_t>(b.plane_cnt) << (s_log2 + 10u)) <= (1ull << 31) && b.hit_log != 0 && b.bin <= 0;
+  // (a layer before the last under canonical continuation order takes direct accumulation: only those kernels have CANON twins)
+  p.canon = b.cont_order && !c.final_layer;
+  p.use_bin = !p.canon && b.mono_session && b.aggregate == 1 && !b.capture && bin_shape_ok && bin_slots <= (1ull << 31) &&
+              // own choice: only where the hit log cannot go (one plane per pool entry on a larger image) — the log beats the binned route
+              // on every launch measured (tools/bin_vs_log_probe.py: dual fisheye 50 M rays 5.13 -> 4.42 ms)
+              (b.bin < 0 ? (b.mono_by_wl && !log_planes_ok && bin_geom_ok && full_sky && m >= (2ull << 20)) : b.bin != 0);
+  p.lists1 = p.two_level ? ((p.bin_tiles + (1u << p.fan_log2) - 1u) >> p.fan_log2) : p.bin_tiles;
+  // Hit log (halo_trace.inl log_hit): global fp32 atomics retire memory-side at 21 G/s on this part, which bounded every big
+  // launch once its trace was fast enough (configs[1]: 2.4 ms of trace, 2.8 ms of atomics).  A production-mode launch on one
+  // scalar plane, or on the X/Y/Z planes of an illuminant session, appends its cache misses to one log region per workgroup
+  // instead; a split pass and a per-tile pass add them to the plane(s) afterwards.
+  // Tiles: as many as the split pass feeds whatever the image size — the per-tile pass has one workgroup per tile — of at least
+  // 256 and at most 16 Ki slots (X/Y/Z: 4 Ki) of ONE plane: 512 for X/Y/Z; for a scalar plane 128 where that keeps them within
+  // 16 Ki slots (longer runs in the split pass: 0.23 vs 0.25 ms at configs[1]).
+  // (a small launch takes 256 tiles: its per-tile pass is one workgroup per tile, and 128 of them leave half the chip idle — config 4d 2.85 -> 3.18 G rays/s; big launches keep 128 for the split's longer runs)
+  const uint32_t asked_t_log2 = static_cast<uint32_t>(m < (4ull << 20) ? std::max(b.log_tiles_log2, 8) : b.log_tiles_log2);
+  const uint32_t scalar_t_log2 = std::max<uint32_t>(wl_t_log2, std::min<uint32_t>(asked_t_log2, s_log2 + 2u));   // tiles of 256 .. 16 Ki slots
+  p.log_t_log2 = log_planes_ok ? wl_t_log2 : b.xyz_log ? std::min<uint32_t>(9u, s_log2 + 2u) : scalar_t_log2;
+  p.log_planes = log_planes_ok ? b.plane_cnt : 1u;
+  p.log_tiles = p.log_planes << p.log_t_log2;   // lists the split pass feeds
+  const bool log_layout_ok = b.xyz_log ? (s_log2 <= 11u) : (b.mono_session && (log_planes_ok || (!b.mono_by_wl && s_log2 <= 12u)));
+  p.use_log = !p.canon && !p.use_bin && log_layout_ok && b.aggregate == 1 && fast_mode &&
+              (L.prob < 1.0f || c.final_layer) &&   // a layer whose every exit continues puts nothing on the image
+              (b.hit_log < 0 ? m >= ((b.mono_session && !b.mono_by_wl) ? log_min_rays(b.render.visible) : (2ull << 20)) : b.hit_log != 0);
+  p.use_log_xyz = p.use_log && b.xyz_log;
+  p.no_land = L.prob >= 1.0f && !c.final_layer && fast_mode && b.aggregate == 1;
+  if (p.use_log) {
+    // a region takes 4 records per ray of its workgroup (configs[1]: 1.2 logged per ray), 8 for full-sky renders (5-6 per ray),
+    // and a tile list twice its even share of that; what runs over falls back to direct atomics
+    const uint64_t per_wg = (m + blocks - 1u) / blocks;
+    p.cap1 = std::min<uint64_t>(std::max<uint64_t>(4ull * per_wg, 4096ull), (6ull << 30) / (8ull * blocks));
+    if (p.use_log_xyz || full_sky) p.cap1 = std::min<uint64_t>(std::max<uint64_t>(8ull * per_wg, 4096ull), (8ull << 30) / (8ull * blocks));
+    // (per-launch cost of the slack, measured: configs[1] split 234 / 238 / 241 us at 2x / 4x / 8x; configs[4]'s 512 X/Y/Z lists 554 / 574 / 635 us —
+    // so 8x for scalar planes, where a hot pixel meets near-constant addends, 4x for X/Y/Z, whose addends vary with the wavelength)
+    const uint64_t kListSlack = p.use_log_xyz ? 4ull : 8ull;
+    // (8x the even share, within the 8 GB below: what runs over a tile list is added with fp32 atomics, and on a pixel that holds 4e5 the
+    // rounding of a near-constant addend is a bias, not noise — tools/route_fuzz.py seed 969: the sun's tile of a 1024 x 512 render took five
+    // even shares and its pixel read 5.6e-4 high with 2x)
+    p.cap2 = std::max<uint64_t>(kListSlack * ((p.use_log_xyz || full_sky) ? 8ull : 4ull) * m / p.log_tiles, 1ull << 14);
+    p.cap2 = std::min<uint64_t>(p.cap2, (8ull << 30) / (8ull * p.log_tiles));
+    if (b.hit_log_cap) {   // tests: run both overflow fallbacks
+      p.cap1 = b.hit_log_cap;
+      p.cap2 = std::max<uint64_t>(p.cap1 * blocks / (2ull * p.log_tiles), 64ull);
+    }
+  } else if (p.use_bin) {
+    // lists sized for ~6 hits per ray spread 4x unevenly; an overflowing list falls back to direct atomics
+    // (the coarse and tile lists of the two-level route are slot ranges interleaved over the image — rows p % 1024 — and
+    // stay balanced whatever the image shows: 2x there)
+    const uint64_t slack = p.two_level ? 2ull : 4ull;
+    p.cap1 = std::min<uint64_t>(std::max<uint64_t>(slack * 6ull * m / p.lists1, 1ull << 16), (8ull << 30) / (8ull * p.lists1));
+    if (p.two_level) p.cap2 = std::min<uint64_t>(std::max<uint64_t>(slack * 6ull * m / p.bin_tiles, 1ull << 12), (8ull << 30) / (8ull * p.bin_tiles));
+  }
+}
+// The second stage of a logged launch's plan, the one that asks the device: the caps give way to free memory and both log sets are reserved.
+// p.cap1 / p.cap2 leave as what the buffers hold; a reserve that fails takes the launch off the log (p.use_log).
+int reserve_log_buffers(HaloBackend* b, LaunchPlan& p, int ls) {
+  const uint64_t blocks = static_cast<uint64_t>(p.blocks);
+  // The log's capacity is a speed matter only (what runs over is added directly), so it gives way to the memory there is: the
+  // regions and lists still to be allocated take at most half of what is free (the continuation and shape pools of later layers
+  // want theirs), and a reserve that fails all the same sends this launch down the direct route instead of failing the trace.
+  size_t free_b = 0, total_b = 0;
+  const uint64_t have = (b->bin_list_s[ls].cap + b->bin_list2_s[ls].cap) * sizeof(HitRec);
+  const uint64_t need = (p.cap1 * blocks + p.cap2 * p.log_tiles) * sizeof(HitRec);
+  if (need > have && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need - have > free_b / 2u) {
+    const double shrink = static_cast<double>(have + free_b / 2u) / static_cast<double>(need);
+    p.cap1 = std::max<uint64_t>(static_cast<uint64_t>(static_cast<double>(p.cap1) * shrink), 1024ull);
+    p.cap2 = std::max<uint64_t>(static_cast<uint64_t>(static_cast<double>(p.cap2) * shrink), 1024ull);
+  }
+  hipError_t e1 = hipSuccess, e2 = hipSuccess;
+  if (int rc = reserve_idle(b, b->bin_list_s[ls], p.cap1 * blocks, &e1)) return rc;
+  if (e1 == hipSuccess)
+    if (int rc = reserve_idle(b, b->bin_list2_s[ls], p.cap2 * p.log_tiles, &e2)) return rc;
+  if (b->overlap && p.alternate && e1 == hipSuccess && e2 == hipSuccess) {
+    // the other set with it: the next launch would otherwise stop the queue (a host sync and a multi-gigabyte hipMalloc) for it.  A speed
+    // matter only — if there is no room, the launch that finds the set short shrinks its log as above.
+    hipError_t e3 = hipSuccess, e4 = hipSuccess;
+    if (int rc = reserve_idle(b, b->bin_list_s[ls ^ 1], p.cap1 * blocks, &e3)) return rc;
+    if (e3 == hipSuccess)
+      if (int rc = reserve_idle(b, b->bin_list2_s[ls ^ 1], p.cap2 * p.log_tiles, &e4)) return rc;
+    if (e3 != hipSuccess || e4 != hipSuccess) (void)hipGetLastError();
+  }
+  if (e1 != hipSuccess || e2 != hipSuccess) {
+    (void)hipGetLastError();   // out of memory: not this launch's route
+    p.use_log = p.use_log_xyz = false;
+  }
+  return HALO_OK;
+}
+// The filter / colour / fast tables of entry `ci`, the kernel mode they ask for, and the entry's table-cache slot if it has one.
+void prepare_entry_tables(HaloBackend* b, const LayerCtx& c, int ci, EntryTables& T) {
+  const HaloEntry& E = b->scene.layers[c.layer].entries[ci];
+  const bool deterministic = c.host_crystal || host::IsDeterministic(E.crystal);
+  T = EntryTables{};
+  // the entry's tables may still be on the device from an earlier dispatch (table cache, see HaloBackend::TableCacheEntry)
+  T.ce = (b->table_cache && deterministic && !c.host_crystal && c.source != kSrcTransit) ? &b->tcache[c.layer][ci] : nullptr;
+  if (T.ce && !b->tcache_dev.ptr) {
+    if (b->tcache_dev.reserve(static_cast<size_t>(HALO_MAX_LAYERS) * HALO_MAX_ENTRIES * 2u) != hipSuccess) {
+      (void)hipGetLastError();
+      T.ce = nullptr;   // no room for the cache: every dispatch uploads its tables
+    }
+  }
+  T.ce_dev = T.ce ? b->tcache_dev.ptr + (static_cast<size_t>(c.layer) * HALO_MAX_ENTRIES + static_cast<size_t>(ci)) * 2u : nullptr;
+  T.cached = T.ce && T.ce->valid;
+  if (T.cached) T.use_filter = T.ce->use_filter;
+  else if (E.filter_id > 0) {
+    T.fd = host::BuildFilter(b->filters[static_cast<size_t>(E.filter_id - 1)], E.axis);
+    T.use_filter = T.fd.is_complex || T.fd.terms[0].type != HALO_FILTER_NONE || T.fd.action != 0;
+  }
+
+  // raypath colour: this entry's predicates (canonicalised like filter terms, each with its own symmetry) + the classes
+  ColorDev& cd = T.cd;
+  T.use_color = !b->color_classes.empty();
+  if (T.use_color && !T.cached) {
+    cd.class_cnt = static_cast<uint32_t>(b->color_classes.size());
+    for (uint32_t k = 0; k < cd.class_cnt; k++) {
+      cd.class_bits[k] = b->color_classes[k].bits;
+      cd.class_all[k] = b->color_classes[k].combine_all ? 1 : 0;
+    }
+    if (E.color_id > 0) {
+      const HaloColorSet& cs = b->color_sets[static_cast<size_t>(E.color_id - 1)];
+      cd.term_cnt = static_cast<uint32_t>(std::min(cs.term_count, HALO_COLOR_MAX_TERMS));
+      for (uint32_t k = 0; k < cd.term_cnt; k++) {
+        HaloFilter one{};
+        one.symmetry = cs.terms[k].symmetry;
+        one.terms[0] = cs.terms[k].predicate;
+        const FilterDev f1 = host::BuildFilter(one, E.axis);
+        cd.terms[k].t = f1.terms[0];
+        cd.terms[k].symmetry = f1.symmetry;
+        cd.terms[k].d_applicable = f1.d_applicable;
+        cd.terms[k].sigma_a = f1.sigma_a;
+        cd.terms[k].bit = static_cast<uint8_t>(cs.terms[k].bit & 0xFF);
+      }
+    }
+  }
+
+  // Which kernels: capture (tests) > filter / colour in their fast form (paths <= 16 faces, tables fit) > the generic filter kernels > plain
+  if (T.cached) T.mode = T.ce->mode;
+  else if (b->capture) T.mode = 2;
+  else if (b->rehit_strategy == 0) T.mode = 3;   // the legacy next-face strategy lives in the generic kernels only
+  else if (T.use_filter || T.use_color) {
+    T.mode = 3;
+    if (b->filter_fast && b->scene.max_hits <= 16) {
+      b->fast_scratch.reset(new FastTables());
+      std::memset(b->fast_scratch.get(), 0, sizeof(FastTables));
+      const HaloColorSet* cs = (T.use_color && E.color_id > 0) ? &b->color_sets[static_cast<size_t>(E.color_id - 1)] : nullptr;
+      if (host::BuildFastTables(T.use_filter ? &b->filters[static_cast<size_t>(E.filter_id - 1)] : nullptr, cs, E.axis, static_cast<uint32_t>(E.crystal_config_id), *b->fast_scratch)) {
+        T.fast_host = b->fast_scratch.get();
+        T.fast_host->class_cnt = T.use_color ? cd.class_cnt : 0u;
+        for (uint32_t k = 0; k < T.fast_host->class_cnt; k++) {
+          T.fast_host->class_bits[k] = cd.class_bits[k];
+          T.fast_host->class_all[k] = cd.class_all[k];
+        }
+        T.mode = T.use_color ? 4 : 1;
+      }
+    }
+  }
+  T.fast_mode = T.mode == 0 || T.mode == 1 || T.mode == 4;
+  T.has_fast = T.cached ? T.ce->has_fast : T.fast_host != nullptr;
+  if (T.cached) T.entry_fast = T.ce->entry_fast, T.hex_regular = T.ce->hex_regular;
+}
+// The dispatch slot a launch reads its tables from: the entry's cache slot if it is valid, else tables + zeroed tallies go up in one copy from
+// ring slot k's pinned mirror (`shape`: the one shape of a deterministic entry).
+int upload_tables(HaloBackend* b, const LayerCtx& c, const LaunchPlan& p, const HaloEntry& E, uint32_t lat_path, const ShapeDev* shape, int k, EntryTables& T,
+                  DispatchSlot** out) {
+  HaloBackend::TableCacheEntry* ce = T.ce;
+  DispatchSlot& hs = b->ring_host[k];
+  if (ce && !T.cached) ce->cur ^= 1;   // an upload takes the entry's other slot
+  DispatchSlot* ds = *out = ce ? T.ce_dev + ce->cur : b->ring_dev.ptr + k;
+  if (T.cached) return HALO_OK;   // (T describes the slot already: from the cache entry, or from this entry's previous upload)
+  if (lat_path == kLatLut) {
+    const host::LatLut& lut = cached_lut(b, E.axis.latitude);
+    std::copy(lut.theta.begin(), lut.theta.end(), hs.lut);
+    std::copy(lut.cdf.begin(), lut.cdf.end(), hs.lut + kLutNodes);
+    std::copy(lut.flip.begin(), lut.flip.end(), hs.lut + 2 * kLutNodes);
+  }
+  std::copy(b->wl_pool_host.begin(), b->wl_pool_host.end(), hs.wl);
+  if (p.deterministic) {
+    hs.shape = *shape;
+    T.entry_fast = b->entry_fast && host::BuildEntryFast(*shape, hs.efast);
+    T.hex_regular = T.entry_fast && hs.efast.hex_regular;
+  }
+  if (T.use_filter) hs.filter = T.fd;
+  if (T.use_color) hs.color = T.cd;
+  if (T.fast_host) std::memcpy(&hs.fast, T.fast_host, sizeof(FastTables));
+  if (c.source == kSrcTransit) std::copy(b->cont_seg, b->cont_seg + kContShards + 1, hs.seg);
+  // (the fast filter tables are the slot's last member and travel only with the dispatches that use them; the pinned mirror is this
+  // ring slot's, so it stays as it is until the copy has run — harvest_slot in trace_launch)
+  // A cache slot is a fixed device address: a kernel of an earlier, queued session (async: nobody harvested it) may still be staging its
+  // tables out of it on a trace stream.  The upload goes behind the last launch that read this slot (no host wait; ring slots are
+  // protected by harvest_slot).  Without this the earlier kernel's late workgroups could pick up THIS session's wavelength pool or
+  // shape (tests/test_gpu_production_routes.py::test_async_sessions_alternating_wavelengths).
+  if (ce && ce->read_ring[ce->cur] >= 0) {
+    const int rk = ce->read_ring[ce->cur];
+    if (b->ring_busy[rk] && b->ring_use[rk] == ce->read_use[ce->cur]) HIPCHK(b, hipStreamWaitEvent(b->stream, b->ring_done[rk], 0));
+  }
+  HIPCHK(b, hipMemcpyAsync(ds, &hs, T.fast_host ? sizeof(DispatchSlot) : offsetof(DispatchSlot, fast), hipMemcpyHostToDevice, b->stream));
+  if (ce) {   // the next dispatch of this entry — the layer's next chunk, the next equal session — finds the tables in place
+    ce->valid = true, ce->mode = T.mode, ce->use_filter = T.use_filter, ce->use_color = T.use_color;
+    ce->entry_fast = T.entry_fast, ce->hex_regular = T.hex_regular, ce->has_fast = T.has_fast;
+    T.cached = true;
+  }
+  return HALO_OK;
+}
+// The fields of DispatchParams that every launch of entry `ci` shares.  The accumulation route's (bin_*, log_*, mono_copy_mask, mono_by_wl,
+// no_land) are written by bind_route alone, the tables', shapes' and counters' by trace_launch.
+DispatchParams fill_params(HaloBackend* b, const LayerCtx& c, int ci) {
+  const HaloLayer& L = b->scene.layers[c.layer];
+  const HaloEntry& E = L.entries[ci];
+  DispatchParams P{};
+  P.source = c.source;
+  P.layer = static_cast<uint32_t>(c.layer);
+  P.final_layer = c.final_layer ? 1u : 0u;
+  P.max_hits = static_cast<uint32_t>(b->scene.max_hits);
+  P.prob = L.prob;
+  P.crystal_id = static_cast<uint32_t>(E.crystal_config_id);
+  P.capture = static_cast<uint32_t>(b->capture);
+  P.gen_seed = b->seed ^ kNonceGen;
+  P.gate_seed = b->seed ^ kNonceGate;
+  P.transit_seed = b->seed ^ kNonceTransit;
+  P.shuffle = static_cast<uint32_t>(b->cont_shuffle);
+  P.shuffle_seed = (b->seed ^ kNonceShuffle) ^ static_cast<uint32_t>(c.layer);  // cuda_trace_backend.cu:4541
+  P.shuffle_chunk_log2 = b->shuffle_chunk_log2;
+  // orientation wire params (BuildTransitGpParams cuda_trace_backend.cu:342-383)
+  P.lat_path = host::SelectLatPath(E.axis);
+  P.lat_mean_rad = E.axis.latitude.center * host::kDegToRad;
+  P.lat_std_rad = E.axis.latitude.spread * host::kDegToRad;
+  P.az_type = static_cast<uint32_t>(E.axis.azimuth.type);
+  P.az_mean_rad = E.axis.azimuth.center * host::kDegToRad;
+  P.az_std_rad = E.axis.azimuth.spread * host::kDegToRad;
+  P.roll_type = static_cast<uint32_t>(E.axis.roll.type);
+  P.roll_mean_rad = E.axis.roll.center * host::kDegToRad;
+  P.roll_std_rad = E.axis.roll.spread * host::kDegToRad;
+  // BuildGenGpParams cuda_trace_backend.cu:391-399, trig evaluated once on the host
+  const float sun_lon = (b->scene.sun_azimuth + 180.0f) * host::kDegToRad;
+  const float sun_lat = -b->scene.sun_altitude * host::kDegToRad;
+  const float half = (b->scene.sun_diameter * 0.5f) * host::kDegToRad;
+  P.c_cap = std::cos(half);
+  P.c_lon = std::cos(sun_lon);
+  P.s_lon = std::sin(sun_lon);
+  P.c_lat = std::cos(sun_lat);
+  P.s_lat = std::sin(sun_lat);
+  P.wl_pool_size = b->wl_pool_size;
+  P.proj = b->proj;
+  P.proj_pre[0] = static_cast<float>(b->proj.img_w) / 2.0f, P.proj_pre[1] = static_cast<float>(b->proj.img_h) / 2.0f;   // the pixel formulas' conversions, once per dispatch
+  P.proj_pre[2] = static_cast<float>(b->proj.lens_shift_x), P.proj_pre[3] = static_cast<float>(b->proj.lens_shift_y);
+  P.cont_in = b->cont[c.out_slot ^ 1].ptr;
+  P.cont_in_n = static_cast<uint32_t>(b->cont_in_n);
+  P.cont_in_stride = b->cont_stride[c.out_slot ^ 1];
+  P.cont_out = b->cont[c.out_slot].ptr;
+  P.cont_out_stride = b->cont_stride[c.out_slot];
+  P.cont_out_cap = c.out_cap;
+  P.cont_in_region = b->cont_region[c.out_slot ^ 1];
+  P.cont_cnt = b->cont_cnt.ptr;
+  P.cont_mask = (b->cont_order && !c.final_layer) ? b->cont_mask.ptr : nullptr;
+  P.cont_err = c.canon_check ? b->cont_err.ptr : nullptr;
+  P.counters = b->counters.ptr;
+  P.mono = planes_of(b);
+  P.mono_s_log2 = b->mono_s_log2;
+  P.ovf = twin_of(b, b->twin_set);
+  P.ovf_copies_log2 = static_cast<uint32_t>(__builtin_ctz(b->plane_copies));
+  P.ovf_flag = P.ovf ? b->ovf_flag.ptr + b->twin_set : nullptr;
+  P.pool_entry_fast = b->pool_entry_fast ? 1u : 0u;
+  P.rehit_legacy = b->rehit_strategy == 0 ? 1u : 0u;
+  P.tally = b->tally.ptr;
+  P.exits = b->exits.ptr;
+  P.exit_cap = static_cast<uint32_t>(std::min<uint64_t>(b->exits.cap, 0xFFFFFFFFull));
+  P.aggregate = static_cast<uint32_t>(b->aggregate);
+  P.geom_clock = b->geom_clock;
+  P.lanes = b->lanes.ptr;
+  P.lane_stride = static_cast<uint32_t>(b->acc_w) * static_cast<uint32_t>(b->acc_h);
+  return P;
+}
+// The route branch: reserves and resets the buffers of the launch's accumulation route (log set `ls`) and writes the route's fields of P — their
+// only writer.  (A direct launch leaves the list fields as the entry's previous launch set them: the kernels read them only behind bin_list.)
+int bind_route(HaloBackend* b, LaunchPlan& p, int ls, DispatchParams& P) {
+  if (p.use_log)
+    if (int rc = reserve_log_buffers(b, p, ls)) return rc;
+  DevBuf<HitRec>&bin_list = b->bin_list_s[ls], &bin_list2 = b->bin_list2_s[ls];
+  DevBuf<uint32_t>&bin_cnt = b->bin_cnt_s[ls], &bin_cnt2 = b->bin_cnt2_s[ls];
+  if (p.use_bin)   // the staged-list route shares one buffer set and resets its counters on the main stream: one launch at a time
+    if (int rc = join_aux(b)) return rc;
+  if (p.use_log) {
+    if (int rc = reserve_idle(b, bin_cnt, std::max<size_t>(static_cast<size_t>(p.blocks), static_cast<size_t>(512) * 16u))) return rc;
+    if (int rc = reserve_idle(b, bin_cnt2, static_cast<size_t>(512) * 16u)) return rc;
+    HIPCHK(b, b->set_free[ls].wait_on(b->stream));   // the passes of the launch that last wrote this set
+  } else if (p.use_bin) {
+    if (int rc = reserve_idle(b, bin_cnt, static_cast<size_t>(512) * 16u)) return rc;
+    HIPCHK(b, hipMemsetAsync(bin_cnt.ptr, 0, static_cast<size_t>(p.two_level ? 512u : p.bin_tiles) * 16u * sizeof(uint32_t), b->stream));
+    if (int rc = reserve_idle(b, bin_list, p.cap1 * p.lists1)) return rc;
+    if (p.two_level) {
+      if (int rc = reserve_idle(b, bin_cnt2, static_cast<size_t>(p.bin_tiles) * 16u)) return rc;
+      HIPCHK(b, hipMemsetAsync(bin_cnt2.ptr, 0, static_cast<size_t>(p.bin_tiles) * 16u * sizeof(uint32_t), b->stream));
+      if (int rc = reserve_idle(b, bin_list2, p.cap2 * p.bin_tiles)) return rc;
+    }
+  }
+  const bool lists = p.use_log || p.use_bin;
+  P.bin_list = lists ? bin_list.ptr : nullptr;
+  P.bin_log = p.use_log ? 1u : 0u;
+  P.log_xyz = p.use_log_xyz ? 1u : 0u;
+  P.mono_by_wl = b->mono_by_wl ? 1u : 0u;
+  P.mono_copy_mask = lists ? 0u : b->plane_copies - 1u;   // logged / staged hits and their fallbacks address copy 0
+  if (lists) {
+    P.bin_cap = static_cast<uint32_t>(p.cap1);
+    P.bin_tiles = p.use_log ? p.log_tiles : p.two_level ? b->bin_l1 : p.bin_tiles;
+    P.bin_shift = (p.use_bin && p.two_level) ? 14u + p.fan_log2 : 0u;
+    P.bin_cnt = bin_cnt.ptr;   // (log: one fill count per region, written by the trace kernel)
+  }
+  if (p.use_log) P.log_plane_stride = static_cast<uint32_t>((static_cast<uint64_t>(kMonoRows) << b->mono_s_log2) * b->plane_copies);
+  P.no_land = p.no_land ? 1u : 0u;
+  return HALO_OK;
+}
+// HaloRouteInfo (halo_last_route: what the GPU tests assert routes with).  The masks name the instantiation that launch_mode / launch_mono /
+// launch_lens / launch_vis in halo_trace.inl pick for this launch — mirrored here — not the request: the regular-prism search exists for
+// the production-shaped kernels off the binned route, the no-accumulation kernels for their one-shape dispatches.
+void record_route(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, int mode, bool fast_mode, int launch_geom) {
+  b->route.launches++;
+  b->route.mode_mask |= 1u << mode;
+  const bool ran_hex = launch_geom == 3 && fast_mode && (P.bin_list == nullptr || P.bin_log != 0u || P.no_land != 0u);
+  const bool ran_none = P.no_land != 0u && p.geom == 0;
+  b->route.geom_mask |= 1u << (launch_geom == 3 && !ran_hex ? 0 : launch_geom);
+  b->route.accum_mask |= ran_none ? 64u : p.use_log ? (p.use_log_xyz ? 32u : 16u) : (p.use_bin ? (p.two_level ? 8u : 4u) : (b->mono_session ? 2u : 1u));
+  // specialisations (plain kernels only; launch_lens / launch_vis / launch_mono): bit 0 last-layer kernel (no continuation code), 1 lens as a
+  // constant, 2 visible range as a constant, 3 closed gate as a constant
+  const bool one = p.geom == 0, lens_known = P.proj.proj_type == HALO_LENS_LINEAR || P.proj.proj_type == HALO_LENS_FISHEYE_EQUAL_AREA ||
+                                             P.proj.proj_type == HALO_LENS_DUAL_FISHEYE_EQUAL_AREA || P.proj.proj_type == HALO_LENS_RECTANGULAR;
+  const bool vis_known = P.proj.visible_range == HALO_VISIBLE_UPPER || P.proj.visible_range == HALO_VISIBLE_FULL;
+  uint32_t spec = 0u;
+  if (fast_mode && p.use_log && one && !ran_none && b->mono_session && P.final_layer) {
+    spec |= 1u;
+    if ((mode == 0 || mode == 1) && P.prob <= 0.0f && lens_known && vis_known) spec |= 2u | 4u | 8u;
+  }
+  if (fast_mode && p.use_log && one && !ran_none && b->mono_session && !P.final_layer && (mode == 0 || mode == 1) && lens_known && vis_known)
+    spec |= 2u | 4u;   // (round 6: the logging kernels of the layers before the last know their lens and visible range too; their gate is open)
+  if (mode == 0 && p.use_log && !one && !b->mono_session && P.prob <= 0.0f && P.proj.visible_range == HALO_VISIBLE_FULL) spec |= 4u | 8u;
+  if (mode == 0 && p.use_log && !one && P.prob <= 0.0f && P.proj.visible_range == HALO_VISIBLE_FULL && P.proj.proj_type == HALO_LENS_RECTANGULAR)
+    spec |= 2u | 4u | 8u;   // (shape-pool kernels, either plane layout: bench_config_stoch.json's render as constants)
+  b->route.spec_mask |= spec;
+  if (spec == 0u) b->route.generic_launches++;
+  b->route.source_mask |= 1u << P.source;
+}
+// The accumulation passes of a launch, behind its trace kernel on trace stream `ts` (index ts_i), and the ring slot's closing events.
+int queue_passes(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, const LaunchSlots& S, hipStream_t ts, int ts_i, hipEvent_t before_sums) {
+  const int k = S.k;
+  DevBuf<HitRec>&bin_list = b->bin_list_s[S.ls], &bin_list2 = b->bin_list2_s[S.ls];
+  DevBuf<uint32_t>&bin_cnt = b->bin_cnt_s[S.ls], &bin_cnt2 = b->bin_cnt2_s[S.ls];
+  // fixed-point scale of the per-tile sums (halo_kernels.hip FixQ): no slot of this launch can sum to more than 4 x max weight x rays
+  const uint32_t frac_bits = fix_frac_bits(b->sess_max_w, p.m);
+  const uint32_t cap2 = static_cast<uint32_t>(p.cap2 & ~15ull);   // whole 128-byte lines per tile list
+  if (!p.use_log) {
+    if (p.use_bin) {
+      hipError_t be = p.two_level ? launch_bin_two_level(P.mono, bin_list.ptr, P.bin_cap, bin_cnt.ptr, p.lists1, bin_list2.ptr, cap2, bin_cnt2.ptr,
+                                                         p.bin_tiles, p.fan_log2, frac_bits, P.ovf, P.ovf_flag, ts, before_sums)
+                                  : launch_bin_accumulate(P.mono, bin_list.ptr, P.bin_cap, bin_cnt.ptr, p.bin_tiles, frac_bits, ts);
+      if (be != hipSuccess) return hip_fail(b, be, "halo_bin_accumulate_kernel launch");
+      if (b->overlap && p.two_level) HIPCHK(b, b->rmw[ts_i].mark(ts));
+    }
+    HIPCHK(b, hipEventRecord(b->ring_ev1[k], ts));
+    b->ring_posts[k] = false;
+    HIPCHK(b, hipEventRecord(b->ring_done[k], ts));
+    return HALO_OK;
+  }
+  // the accumulation passes of this launch: behind the trace kernel on its stream.  (Round 5 tried them on the auxiliary stream, under the
+  // next launch's trace kernel: configs[1] + 1.2 %, the trace kernel itself 5 % slower for the CUs the 134 KB split workgroups take, the
+  // passes' spans stretched sevenfold — profiles that no longer say what a kernel costs, for one percent.  Not kept.)
+  HIPCHK(b, hipEventRecord(b->ring_ev1[k], ts));          // the trace kernel alone: ev0 .. ev1
+  hipStream_t ps = ts;
+  if (p.under_fold()) {   // the passes add to the planes: behind the fold that last touched THEIR planes
+    if (b->mono_two) {   // two plane sets: that is the fold of two sessions ago (it zeroed this set), not the one the trace kernel started under
+      HIPCHK(b, b->set_folded[b->mono_set].wait_on(ps));
+    } else if (int rc = wait_for_aux(b, ts_i)) return rc;
+  }
+  HIPCHK(b, hipEventRecord(b->ring_ev2[k], ps));
+  HIPCHK(b, hipMemsetAsync(bin_cnt2.ptr, 0, static_cast<size_t>(p.log_tiles) * 16u * sizeof(uint32_t), ps));
+  hipError_t be = p.use_log_xyz ? launch_log_route_xyz(P.mono, P.log_plane_stride, bin_list.ptr, P.bin_cap, bin_cnt.ptr, static_cast<uint32_t>(p.blocks),
+                                                       bin_list2.ptr, cap2, bin_cnt2.ptr, p.log_tiles, b->mono_s_log2, P.wl_pool, P.wl_pool_size, frac_bits, P.ovf, P.ovf_flag, P.ovf_copies_log2, ps, before_sums)
+                                : launch_log_route(P.mono, bin_list.ptr, P.bin_cap, bin_cnt.ptr, static_cast<uint32_t>(p.blocks), bin_list2.ptr, cap2,
+                                                   bin_cnt2.ptr, 1u << p.log_t_log2, p.log_planes, b->mono_s_log2, b->render.visible == HALO_VISIBLE_FULL, frac_bits,
+                                                   P.ovf, P.ovf_flag, P.ovf_copies_log2, ps, before_sums);
+  if (be != hipSuccess) return hip_fail(b, be, "halo_split_kernel launch");
+  if (b->overlap) HIPCHK(b, b->rmw[ts_i].mark(ps));
+  HIPCHK(b, hipEventRecord(b->ring_ev3[k], ps));
+  HIPCHK(b, b->set_free[S.ls].mark(ps));
+  if (b->overlap && p.alternate) b->log_set ^= 1;
+  b->ring_posts[k] = true;
+  HIPCHK(b, hipEventRecord(b->ring_done[k], ps));
+  return HALO_OK;
+}
+// Stream choice, plane gates, generator, trace kernel, route record and passes of one launch whose tables, shapes and buffers are in place.
+int queue_launch(HaloBackend* b, const LaunchPlan& p, const HaloEntry& E, EntryTables& T, const DispatchParams& P, const LaunchSlots& S) {
+  const int k = S.k;
+  // The launch's trace stream (alternating for small launches), behind whatever the auxiliary stream still does to the planes (a closing
+  // fold): the launch adds to them — from the trace kernel itself (direct atomics, staged lists) or in its passes, which follow it on
+  // the same stream.  (A small logged launch starts under that fold: LaunchPlan::under_fold.)
+  hipStream_t ts = nullptr;
+  int ts_i = 0;
+  if (int rc = next_trace_stream(b, !p.under_fold(), p.alternate, &ts, &ts_i)) return rc;
+  hipEvent_t before_sums = nullptr;   // rule (1), for the routes whose sums write the planes plainly
+#ifndef HALO_NO_PLANE_GATES   // (defined only to see tests/test_gpu_production_routes.py's two-stream test fail without the gates)
+  if (b->overlap && !p.use_log)   // this trace kernel adds to the planes itself: behind the other stream's sums
+    HIPCHK(b, b->rmw[ts_i ^ 1].wait_on(ts));
+  if (b->overlap && (p.use_log || (p.use_bin && p.two_level)) && b->cs_pending[ts_i ^ 1]) {
+    HIPCHK(b, hipEventRecord(b->ev_gate, b->cs[ts_i ^ 1]));
+    before_sums = b->ev_gate;
+  }
+#endif
+  if (!p.deterministic && !p.host_pool) {
+    // Device generator: one team per sampled crystal, in front of the trace kernel on its stream.  Option "gen_ahead" puts the one of a
+    // launch that fills the chip on trace stream 1 instead, beside the previous launch's trace kernel and passes (it needs nothing of
+    // them, only its pool back from the launch before that one).  Measured (25 M rays per launch): prism pools 4.43 -> 4.55 ms per launch,
+    // pyramid pools 7.78 -> 7.70: both kernels are VALU-bound, so sharing the chip conserves the work.  Off by default.
+    const bool ahead = b->overlap && b->gen_ahead && !p.alternate;
+    hipStream_t gs = ahead ? b->cs[1] : ts;
+    HIPCHK(b, b->shapes_free[S.shape_set].wait_on(gs));
+    hipError_t ge = launch_shapegen(const_cast<ShapeDev*>(P.shapes), p.geom == 2, p.shape_cnt, b->seed, host::MakeRecipe(E.crystal), S.first_shape, gs, b->gen_serial != 0);
+    if (ge != hipSuccess) return hip_fail(b, ge, "halo_shapegen_kernel launch");
+    if (ahead) {
+      HIPCHK(b, hipEventRecord(b->ev_gen, gs));
+      HIPCHK(b, hipStreamWaitEvent(ts, b->ev_gen, 0));
+      b->cs_pending[1] = true;
+    }
+  }
+  HIPCHK(b, hipEventRecord(b->ring_ev0[k], ts));  // HIP events on the launch stream bracket the kernel alone
+  b->ring_final[k] = P.final_layer != 0u;
+  // a one-shape dispatch of a regular hexagonal prism takes the literal-normal instantiation (kGeomOneHex = 3)
+  const int launch_geom = (p.geom == 0 && T.entry_fast && b->hex_fast && T.hex_regular) ? 3 : p.geom;
+  hipError_t le = launch_trace(P, p.blocks, ts, T.mode, launch_geom, b->mono_session);
+  if (T.ce) {   // the slot's last reader (see TableCacheEntry): this launch, whose ring_done event is recorded below
+    T.ce->read_ring[T.ce->cur] = k;
+    T.ce->read_use[T.ce->cur] = b->ring_use[k];
+  }
+  b->mono_dirty = true;
+  record_route(b, p, P, T.mode, T.fast_mode, launch_geom);
+  if (le != hipSuccess) return hip_fail(b, le, "halo_trace_kernel launch");
+  if (!p.deterministic) HIPCHK(b, b->shapes_free[S.shape_set].mark(ts));
+  if (int rc = queue_passes(b, p, P, S, ts, ts_i, before_sums)) return rc;
+  b->tally_unread = true;
+  b->ring_busy[k] = true;
+  return HALO_OK;
+}
+// One planned launch from end to end: shape pool, ring slot, tables, the per-launch fields of P, route buffers, then queue_launch.
+int trace_launch(HaloBackend* b, const LayerCtx& c, LaunchPlan& p, EntryTables& T, DispatchParams& P) {
+  const HaloEntry& E = b->scene.layers[c.layer].entries[p.ci];
+  const uint64_t m = p.m;
+  LaunchSlots S;
+  std::vector<ShapeDev> pool((p.deterministic && !T.cached) || p.host_pool ? p.shape_cnt : 0u);
+  for (uint32_t k = 0; k < static_cast<uint32_t>(pool.size()); k++) {
+    if (c.host_crystal) host::ToShapeDev(*c.rays->crystal, pool[k]);
+    else host::MakeShapeDev(b->seed, E.crystal, p.deterministic ? 0 : (b->shape_count + k), pool[k]);
+  }
+  S.first_shape = b->shape_count;
+  if (!p.deterministic) {
+    b->shape_count += p.shape_cnt;
+    b->sess_crystal_samples += p.shape_cnt;
+  }
+  if (c.rays == nullptr && (E.axis.azimuth.type != HALO_DIST_NONE || E.axis.latitude.type != HALO_DIST_NONE || E.axis.roll.type != HALO_DIST_NONE))
+    b->sess_orient_samples += m;   // AxisDistribution::IsAxisDeterministic is false: one orientation per ray
+  S.k = b->ring_next;
+  b->ring_next = (S.k + 1) % HaloBackend::kRing;
+  harvest_slot(b, S.k);  // blocks only if the ring has wrapped onto a dispatch still in flight
+  b->ring_use[S.k]++;
+  DispatchSlot* ds = nullptr;
+  if (int rc = upload_tables(b, c, p, E, P.lat_path, pool.empty() ? nullptr : pool.data(), S.k, T, &ds)) return rc;
+  P.lut = ds->lut;
+  P.wl_pool = ds->wl;
+  P.filter = T.use_filter ? &ds->filter : nullptr;
+  P.color = T.use_color ? &ds->color : nullptr;
+  P.fast = T.has_fast ? &ds->fast : nullptr;
+  P.cont_in_seg = ds->seg;
+  P.entry_fast = T.entry_fast ? &ds->efast : nullptr;
+  if (p.deterministic) {
+    P.shapes = &ds->shape;
+  } else {
+    // Two pools, taken in turn by the launches that may run beside a neighbour: the records of launch k+1 are written while launch k still
+    // traces out of the other one.
+    const bool turn = b->overlap && (p.alternate || b->gen_ahead);   // (a launch that fills the chip runs alone on stream 0: pool 0)
+    S.shape_set = turn ? b->shapes_next : 0;
+    if (turn) b->shapes_next ^= 1;
+    DevBuf<ShapeDev>& shapes = b->shapes_s[S.shape_set];
+    if (int rc = reserve_idle(b, shapes, p.shape_cnt)) return rc;   // sized for ShapeDev records; prism pools use the front third
+    if (turn)   // (its twin with it, for the same reason as the log's second buffer set)
+      if (int rc = reserve_idle(b, b->shapes_s[S.shape_set ^ 1], p.shape_cnt)) return rc;
+    if (p.host_pool) {
+      HIPCHK(b, b->shapes_free[S.shape_set].wait_on(b->stream));
+      HIPCHK(b, hipMemcpyAsync(shapes.ptr, pool.data(), pool.size() * sizeof(ShapeDev), hipMemcpyHostToDevice, b->stream));
+    }
+    // (device generator: queued by queue_launch on the launch's trace stream, in front of the trace kernel)
+    P.shapes = shapes.ptr;
+  }
+  P.shape_cnt = p.shape_cnt;
+  P.n_rays = static_cast<uint32_t>(m);
+  P.ci_start = static_cast<uint32_t>(p.first);
+  auto split = [](uint64_t v, uint32_t& lo, uint32_t& hi) { lo = static_cast<uint32_t>(v & 0xFFFFFFFFull), hi = static_cast<uint32_t>(v >> 32); };  // SplitPcgRayBase trace_backend.hpp:184-190
+  split(b->gen_count, P.gen_lo, P.gen_hi);
+  split(b->gate_count, P.gate_lo, P.gate_hi);
+  split(b->transit_count, P.transit_lo, P.transit_hi);
+  if (c.rays) {
+    P.host_d = b->host_f.ptr + p.off * 3;
+    P.host_p = b->host_f.ptr + c.n * 3 + p.off * 3;
+    P.host_w = b->host_f.ptr + c.n * 6 + p.off;
+    P.host_tf = b->host_u.ptr + p.off;
+  }
+  plan_route(*b, c, T.fast_mode, p);
+  S.ls = (b->overlap && p.alternate) ? b->log_set : 0;   // the buffer set of this launch
+  if (int rc = bind_route(b, p, S.ls, P)) return rc;
+  if (int rc = queue_launch(b, p, E, T, P, S)) return rc;
+  if (p.host_pool) HIPCHK(b, hipStreamSynchronize(b->stream));  // the pageable shape pool must outlive its copy (the copy is on the main stream)
+  if (P.source == kSrcGen) b->gen_count += m;
+  if (P.source == kSrcTransit) b->transit_count += m;
+  b->gate_count += m;
+  return HALO_OK;
+}
+// The end of a layer: counters, shard fill counts and the error word come back, the next layer's segment table and the statistics are made.
+int close_layer(HaloBackend* b, const LayerCtx& c, bool defer, HaloLayerStats* stats) {
+  const uint64_t n = c.n;
+  if (defer) {  // queued, not waited for: the tallies arrive through halo_collect_stats
+    b->layer_acc.root_count += n;
+    if (stats) {
+      std::memset(stats, 0, sizeof(*stats));
+      stats->root_count = n;
+    }
+    b->cont_in_n = 0;
+    return HALO_OK;
+  }
+  if (int rc = join_aux(b)) return rc;   // the copies below (and the caller) want this layer's kernels done: the main stream waits for the trace streams
+  uint32_t cnt[kCntNum] = {0, 0, 0, 0};
+  std::vector<uint32_t> fill(c.final_layer ? 0 : kContShards * kContCntStride);
+  HIPCHK(b, hipMemcpyAsync(cnt, b->counters.ptr, sizeof(cnt), hipMemcpyDeviceToHost, b->stream));
+  if (!c.final_layer) HIPCHK(b, hipMemcpyAsync(fill.data(), b->cont_cnt.ptr, fill.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+  uint32_t cont_err = 0;
+  if (c.canon_check) HIPCHK(b, hipMemcpyAsync(&cont_err, b->cont_err.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+  if (b->tally_unread) {
+    if (int rc = pull_tally(b)) return rc;   // (one more small copy and THE stream sync of this call: the two copies above are complete behind it)
+  } else {
+    HIPCHK(b, hipStreamSynchronize(b->stream));
+  }
+  harvest_all(b);
+  if (cont_err != 0u)   // never a pool handed on (or traced) out of canonical order in silence
+    return cont_order_fail(b, cont_err);
+  uint64_t n_cont = 0;
+  if (!c.final_layer) {  // the next layer addresses the pool through the prefix of the shard fill counts
+    b->cont_fill_max = 0;
+    for (int sI = 0; sI < kContShards; sI++) {
+      const uint32_t cs = fill[static_cast<size_t>(sI) * kContCntStride];
+      // (canonical order included: a pool that lost records would be handed on with holes in its order — never, the session fails)
+      if (cs > c.out_cap) return fail(b, HALO_FATAL, b->cont_order ? "continuation pool overflow (cont_order = 1: the canonical pool would be incomplete)" : "continuation pool overflow");
+      b->cont_seg[sI] = static_cast<uint32_t>(n_cont);
+      n_cont += cs;
+      b->cont_fill_max = std::max(b->cont_fill_max, cs);
+    }
+    b->cont_seg[kContShards] = static_cast<uint32_t>(n_cont);
+    b->cont_roots = n;
+  }
+  b->exits_pending = std::min<uint64_t>(cnt[kCntExit], b->exits.cap);
+  b->layer_acc.root_count = n;
+  b->layer_acc.continuation_count = n_cont;
+  if (stats) *stats = b->layer_acc;
+  add_stats(b->pending, b->layer_acc);
+  b->layer_acc = HaloLayerStats{};
+  b->cont_in_n = n_cont;  // becomes the next layer's input at Recombine
+  return HALO_OK;
+}
+}  // namespace
+
+extern "C" {
 int halo_trace_layer(halo_handle_t b, uint64_t count, const HaloHostRays* rays, HaloLayerStats* stats) {
   if (!b) return HALO_FATAL;
   if (!b->in_session) return fail(b, HALO_FATAL, "TraceLayer outside a session");
-  const int layer = b->layer_idx;
+  LayerCtx c;
+  const int layer = c.layer = b->layer_idx;
   if (layer >= b->scene.layer_count) return fail(b, HALO_FATAL, "TraceLayer past the last layer");
   HIPCHK(b, hipSetDevice(b->device));
   const HaloLayer& L = b->scene.layers[layer];
-  const uint64_t n = (layer == 0) ? count : b->cont_in_n;
-  const bool final_layer = (layer == b->scene.layer_count - 1);
+  const uint64_t n = c.n = (layer == 0) ? count : b->cont_in_n;
+  c.final_layer = (layer == b->scene.layer_count - 1);
   if (n > 0xFFFFFFF0ull) return fail(b, HALO_FATAL, "more than 2^32 rays in one layer dispatch; split the batch");
   if (layer > 0 && rays) return fail(b, HALO_FATAL, "host rays are first-layer only");
   if (rays && rays->crystal) {   // an injected crystal is copied into fixed-size device tables: its counts and indices are the caller's, check them
@@ -1023,7 +1662,12 @@ int halo_trace_layer(halo_handle_t b, uint64_t count, const HaloHostRays* rays, 
     for (int t = 0; t < g.tri_cnt; t++)
       if (g.tri_face[t] < 0 || g.tri_face[t] >= g.face_cnt) return fail(b, HALO_FATAL, "host crystal: tri_face refers to a face outside the table");
   }
-
+  c.rays = rays;
+  c.source = rays ? kSrcHost : (layer == 0 ? kSrcGen : kSrcTransit);
+  c.host_crystal = rays != nullptr && rays->crystal != nullptr && layer == 0;
+  c.out_slot = b->cont_out_slot;
+  // canonical order over several layers: every layer ends with the error-word check (the appends of this layer, the reorder in front of it)
+  c.canon_check = b->cont_order && b->scene.layer_count > 1;
   float props[HALO_MAX_ENTRIES];
   for (int ci = 0; ci < L.entry_count; ci++) props[ci] = L.entries[ci].proportion;
   std::vector<uint64_t> per_ci = host::Partition(props, L.entry_count, n, b->carry[layer]);
@@ -1031,54 +1675,19 @@ int halo_trace_layer(halo_handle_t b, uint64_t count, const HaloHostRays* rays, 
     std::fill(per_ci.begin(), per_ci.end(), 0);
     per_ci[0] = n;
   }
-  // launch plan: chunking bounds the host-built shape pool for stochastic geometry and keeps n_rays < 2^32
-  const int max_blocks = b->cu_count * b->blocks_per_cu;
-  auto chunk_of = [&](uint64_t left, const HaloCrystal& crystal) {
-    uint64_t m = std::min<uint64_t>(left, b->chunk);
-    // stochastic geometry: one pool record per geom_clock rays.  Device-generated prisms are 1360 B records (2.9 GB per
-    // 64 Mi rays), other device-generated shapes 4.1 KB (2 GB per 16 Mi rays); host-built pools (pageable staging + H2D)
-    // stay at 4 Mi rays
-    if (!host::IsDeterministic(crystal) && !(rays != nullptr && rays->crystal != nullptr && layer == 0)) {
-      const uint64_t dev = b->stoch_chunk ? b->stoch_chunk : (1ull << 26);   // records: 2.9 GB (prism) / 8.6 GB (general) per 64 Mi rays
-      m = std::min<uint64_t>(m, b->host_shapes ? (1ull << 22) : dev);
-    }
-    return m;
-  };
-  auto blocks_of = [&](uint64_t m, bool pool) {
-    // per-workgroup fixed costs (table staging, pixel-cache zero + flush) are paid per launch, a long tail is paid per
-    // round of resident workgroups: aim at >= 32 passes of the ray loop per workgroup, between 4 and blocks_per_cu per CU
-    // (measured: 1 M rays 0.27 -> 0.20 ms at 4/CU; 50 M rays 4.02 -> 3.67 ms at 24/CU instead of 8/CU)
-    // Small launches — a Lumice server that keeps a GPU route's small dispatch (2^15 .. 2^18 rays per session, server.cpp:140-151) sends nothing
-    // else — are latency: one pass of the ray loop is ~11 us on a wave that has its SIMD to itself, so they spread over as many workgroups as
-    // a CU holds (five) before a workgroup takes a second pass.  (Round 4 had found the opposite — one per CU best — while every WAVE ended
-    // with four same-line fp64 atomics; with those gone, tools/dispatch_probe.cpp, us per session at 1 / 2 / 3 / 4 / 5 / 8 per CU:
-    // 2^18 rays 67 / 50 / 45 / 44 / 43 / 44, 2^20 188 / 133 / 122 / 115 / 110 / 111, 2^22 326 / 326 / 276 / 261 / 250 / 259.)
-    const uint64_t want = m / (static_cast<uint64_t>(kBlock) * 32u);
-    // (shape-pool kernels hold four workgroups a CU, not six, and every workgroup of a logged launch is a region for the split pass: three per CU
-    //  there — bench.py --config 4d, 0.8 M rays per session, ms per step at 1 / 2 / 3 / 4 / 5 / 6 / 8 per CU: 7.26 / 5.99 / 5.73 / 5.77 / 5.86 / 6.14 / 6.39)
-    const int small_k = b->small_blocks_per_cu > 0 ? b->small_blocks_per_cu : pool ? 3 : 5;
-    const uint64_t lo_cap = static_cast<uint64_t>(b->cu_count) * static_cast<uint64_t>(std::min(b->blocks_per_cu, small_k));
-    const uint64_t cap = std::min<uint64_t>(static_cast<uint64_t>(max_blocks), std::max<uint64_t>(lo_cap, want));
-    uint64_t nb = std::min<uint64_t>((m + kBlock - 1) / kBlock, cap);
-    if (b->blocks_cap > 0) nb = std::min<uint64_t>(nb, static_cast<uint64_t>(b->blocks_cap));
-    return static_cast<int>(nb);
-  };
-
+  // chunked launches, planned once: the continuation pool below is sized from the plans the launch loop walks
+  std::vector<LaunchPlan> plans;
+  uint64_t ci_start = 0;
+  for (int ci = 0; ci < L.entry_count; ci_start += per_ci[ci], ci++)
+    for (uint64_t off = 0; off < per_ci[ci]; off += plans.back().m) plans.push_back(plan_launch(*b, c, ci, ci_start, off, per_ci[ci] - off));
   // continuation output pool: kContShards regions; a region must hold everything its blocks can emit over the layer's
   // dispatches (every root emits at most max_hits candidates)
-  const int out_slot = b->cont_out_slot;
-  uint32_t out_cap = 0;
-  if (!final_layer) {
+  if (!c.final_layer) {
     uint64_t region = 0;
-    for (int ci = 0; ci < L.entry_count; ci++) {
-      const bool det = (rays != nullptr && rays->crystal != nullptr && layer == 0) || host::IsDeterministic(L.entries[ci].crystal);   // (as the launch below decides it: the same workgroup count)
-      for (uint64_t off = 0; off < per_ci[ci];) {
-        const uint64_t m = chunk_of(per_ci[ci] - off, L.entries[ci].crystal);
-        const uint64_t nb = static_cast<uint64_t>(blocks_of(m, !det));
-        const uint64_t per_block = (m + nb * kBlock - 1) / (nb * kBlock) * kBlock;   // grid-stride share, rounded up
-        region += (nb + kContShards - 1) / kContShards * per_block * static_cast<uint64_t>(b->scene.max_hits);
-        off += m;
-      }
+    for (const LaunchPlan& p : plans) {
+      const uint64_t nb = static_cast<uint64_t>(p.blocks);
+      const uint64_t per_block = (p.m + nb * kBlock - 1) / (nb * kBlock) * kBlock;   // grid-stride share, rounded up
+      region += (nb + kContShards - 1) / kContShards * per_block * static_cast<uint64_t>(b->scene.max_hits);
     }
     region = (region + 63) & ~63ull;
     const uint64_t stride = region * kContShards;
@@ -1086,25 +1695,23 @@ int halo_trace_layer(halo_handle_t b, uint64_t count, const HaloHostRays* rays, 
     // + mask lo/hi planes with raypath colour; canonical order: + root and interaction planes (kContPlaneRoot, kContPlaneBit)
     const uint64_t planes = b->cont_order ? kContPlanesCanonical : (b->color_classes.empty() ? 5 : 7);
     if (b->cont_order && stride * planes > 0xFFFFFFFFull) return fail(b, HALO_FATAL, "canonical continuation pool planes would exceed 2^32 floats; split the batch");
-    if (int rc = reserve_idle(b, b->cont[out_slot], stride * planes)) return rc;
-    b->cont_stride[out_slot] = static_cast<uint32_t>(stride);
-    b->cont_region[out_slot] = static_cast<uint32_t>(region);
-    out_cap = static_cast<uint32_t>(region);
+    if (int rc = reserve_idle(b, b->cont[c.out_slot], stride * planes)) return rc;
+    b->cont_stride[c.out_slot] = static_cast<uint32_t>(stride);
+    b->cont_region[c.out_slot] = static_cast<uint32_t>(region);
+    c.out_cap = static_cast<uint32_t>(region);
     HIPCHK(b, b->cont_cnt.reserve(kContShards * kContCntStride));
     HIPCHK(b, hipMemsetAsync(b->cont_cnt.ptr, 0, kContShards * kContCntStride * sizeof(uint32_t), b->stream));
     if (b->cont_order) {   // the roots' masks start empty: queued on the stream, behind the scatter that read the previous layer's
       if (b->rehit_strategy == 0) return fail(b, HALO_FATAL, "cont_order = 1 needs rehit_strategy = 1 (the legacy strategy can emit twice at one interaction)");
-      if (int rc = reserve_idle(b, b->cont_mask, kContMaskWords * std::max<uint64_t>(n, 1))) return rc;
-      HIPCHK(b, hipMemsetAsync(b->cont_mask.ptr, 0, kContMaskWords * n * sizeof(uint32_t), b->stream));
-      if (layer == 0) {   // a session starts with a clean error word (a session that set one was refused)
+      if (int rc = reserve_idle(b, b->cont_mask, kContMaskWords * std::max<uint64_t>(c.n, 1))) return rc;
+      HIPCHK(b, hipMemsetAsync(b->cont_mask.ptr, 0, kContMaskWords * c.n * sizeof(uint32_t), b->stream));
+      if (c.layer == 0) {   // a session starts with a clean error word (a session that set one was refused)
         if (int rc = reserve_idle(b, b->cont_err, 16)) return rc;
         HIPCHK(b, hipMemsetAsync(b->cont_err.ptr, 0, sizeof(uint32_t), b->stream));
       }
     }
   }
-  // canonical order over several layers: every layer ends with the error-word check (the appends of this layer, the reorder in front of it)
-  const bool canon_check = b->cont_order && b->scene.layer_count > 1;
-  const bool defer = b->async && final_layer && !b->capture && !canon_check;  // nothing the caller needs before the next call
+  const bool defer = b->async && c.final_layer && !b->capture && !c.canon_check;  // nothing the caller needs before the next call
   if (!defer) {  // earlier queued dispatches go to `pending`, so layer_acc ends up holding this layer alone
     harvest_all(b);
     if (int rc = pull_tally(b)) return rc;   // (a copy + sync only when something was queued and never collected)
@@ -1123,10 +1730,8 @@ int halo_trace_layer(halo_handle_t b, uint64_t count, const HaloHostRays* rays, 
       b->exits = bigger;
     }
   }
-
-  if (rays && layer == 0)   // host rays bring their own weights (and hand them on to the layers behind)
+  if (rays && layer == 0) {   // host rays bring their own weights (and hand them on to the layers behind)
     for (uint64_t i = 0; i < n; i++) b->sess_max_w = std::max(b->sess_max_w, static_cast<double>(std::fabs(rays->w[i])));
-  if (rays && layer == 0) {
     // a queued session's kernel on a trace stream (async + overlap) may still be reading the previous batch out of these buffers: the copies
     // go behind everything the trace / auxiliary streams hold, and a buffer only grows with all streams idle
     if (int rc = join_aux(b)) return rc;
@@ -1138,597 +1743,19 @@ int halo_trace_layer(halo_handle_t b, uint64_t count, const HaloHostRays* rays, 
     HIPCHK(b, hipMemcpyAsync(b->host_u.ptr, rays->tf, n * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
     HIPCHK(b, hipStreamSynchronize(b->stream));
   }
-
-  uint64_t ci_start = 0;
-  for (int ci = 0; ci < L.entry_count; ci++) {
-    const uint64_t n_ci = per_ci[ci];
-    if (n_ci == 0) continue;
-    const HaloEntry& E = L.entries[ci];
-    DispatchParams P{};
-    P.source = rays ? kSrcHost : (layer == 0 ? kSrcGen : kSrcTransit);
-    P.layer = static_cast<uint32_t>(layer);
-    P.final_layer = final_layer ? 1u : 0u;
-    P.max_hits = static_cast<uint32_t>(b->scene.max_hits);
-    P.prob = L.prob;
-    P.crystal_id = static_cast<uint32_t>(E.crystal_config_id);
-    P.capture = static_cast<uint32_t>(b->capture);
-    P.gen_seed = b->seed ^ kNonceGen;
-    P.gate_seed = b->seed ^ kNonceGate;
-    P.transit_seed = b->seed ^ kNonceTransit;
-    P.shuffle = static_cast<uint32_t>(b->cont_shuffle);
-    P.shuffle_seed = (b->seed ^ kNonceShuffle) ^ static_cast<uint32_t>(layer);  // cuda_trace_backend.cu:4541
-    P.shuffle_chunk_log2 = b->shuffle_chunk_log2;
-    // orientation wire params (BuildTransitGpParams cuda_trace_backend.cu:342-383)
-    P.lat_path = host::SelectLatPath(E.axis);
-    P.lat_mean_rad = E.axis.latitude.center * host::kDegToRad;
-    P.lat_std_rad = E.axis.latitude.spread * host::kDegToRad;
-    P.az_type = static_cast<uint32_t>(E.axis.azimuth.type);
-    P.az_mean_rad = E.axis.azimuth.center * host::kDegToRad;
-    P.az_std_rad = E.axis.azimuth.spread * host::kDegToRad;
-    P.roll_type = static_cast<uint32_t>(E.axis.roll.type);
-    P.roll_mean_rad = E.axis.roll.center * host::kDegToRad;
-    P.roll_std_rad = E.axis.roll.spread * host::kDegToRad;
-    {  // BuildGenGpParams cuda_trace_backend.cu:391-399, trig evaluated once on the host
-      const float sun_lon = (b->scene.sun_azimuth + 180.0f) * host::kDegToRad;
-      const float sun_lat = -b->scene.sun_altitude * host::kDegToRad;
-      const float half = (b->scene.sun_diameter * 0.5f) * host::kDegToRad;
-      P.c_cap = std::cos(half);
-      P.c_lon = std::cos(sun_lon);
-      P.s_lon = std::sin(sun_lon);
-      P.c_lat = std::cos(sun_lat);
-      P.s_lat = std::sin(sun_lat);
+  // the launches: an entry's tables and shared parameters are made when its first launch comes up
+  EntryTables T;
+  DispatchParams P{};
+  int cur = -1;
+  for (LaunchPlan& p : plans) {
+    if (p.ci != cur) {
+      cur = p.ci;
+      prepare_entry_tables(b, c, cur, T);
+      P = fill_params(b, c, cur);
     }
-    P.wl_pool_size = b->wl_pool_size;
-    P.proj = b->proj;
-    P.proj_pre[0] = static_cast<float>(b->proj.img_w) / 2.0f, P.proj_pre[1] = static_cast<float>(b->proj.img_h) / 2.0f;   // the pixel formulas' conversions, once per dispatch
-    P.proj_pre[2] = static_cast<float>(b->proj.lens_shift_x), P.proj_pre[3] = static_cast<float>(b->proj.lens_shift_y);
-    P.cont_in = b->cont[out_slot ^ 1].ptr;
-    P.cont_in_n = static_cast<uint32_t>(b->cont_in_n);
-    P.cont_in_stride = b->cont_stride[out_slot ^ 1];
-    P.cont_out = b->cont[out_slot].ptr;
-    P.cont_out_stride = b->cont_stride[out_slot];
-    P.cont_out_cap = out_cap;
-    P.cont_in_region = b->cont_region[out_slot ^ 1];
-    P.cont_cnt = b->cont_cnt.ptr;
-    P.cont_mask = (b->cont_order && !final_layer) ? b->cont_mask.ptr : nullptr;
-    P.cont_err = canon_check ? b->cont_err.ptr : nullptr;
-    P.counters = b->counters.ptr;
-    P.mono = planes_of(b);
-    P.mono_s_log2 = b->mono_s_log2;
-    P.ovf = twin_of(b, b->twin_set);
-    P.ovf_copies_log2 = static_cast<uint32_t>(__builtin_ctz(b->plane_copies));
-    P.ovf_flag = P.ovf ? b->ovf_flag.ptr + b->twin_set : nullptr;
-    P.mono_copy_mask = b->plane_copies - 1u;
-    P.mono_by_wl = b->mono_by_wl ? 1u : 0u;
-    P.bin_list = nullptr;
-    P.bin_log = 0u;
-    P.log_xyz = 0u;
-    P.log_plane_stride = 0u;
-    P.pool_entry_fast = b->pool_entry_fast ? 1u : 0u;
-    P.rehit_legacy = b->rehit_strategy == 0 ? 1u : 0u;
-    P.bin_shift = 0u;
-    P.tally = b->tally.ptr;
-    P.exits = b->exits.ptr;
-    P.exit_cap = static_cast<uint32_t>(std::min<uint64_t>(b->exits.cap, 0xFFFFFFFFull));
-    P.aggregate = static_cast<uint32_t>(b->aggregate);
-    P.geom_clock = b->geom_clock;
-    // HostRayBatch::crystal (trace_backend.hpp:230-239): injected rays may bring the crystal they were sampled on; it is traced as it is —
-    // one shape for the whole batch, no draw from the shape stream, no stochastic sample counted (test_cpu_trace_backend.cpp:737-777)
-    const bool host_crystal = rays != nullptr && rays->crystal != nullptr && layer == 0;
-    const bool deterministic = host_crystal || host::IsDeterministic(E.crystal);
-    // the entry's tables may still be on the device from an earlier dispatch (table cache, see HaloBackend::TableCacheEntry)
-    HaloBackend::TableCacheEntry* ce = (b->table_cache && deterministic && !host_crystal && P.source != kSrcTransit) ? &b->tcache[layer][ci] : nullptr;
-    if (ce && !b->tcache_dev.ptr) {
-      if (b->tcache_dev.reserve(static_cast<size_t>(HALO_MAX_LAYERS) * HALO_MAX_ENTRIES * 2u) != hipSuccess) {
-        (void)hipGetLastError();
-        ce = nullptr;   // no room for the cache: every dispatch uploads its tables
-      }
-    }
-    DispatchSlot* const ce_dev = ce ? b->tcache_dev.ptr + (static_cast<size_t>(layer) * HALO_MAX_ENTRIES + static_cast<size_t>(ci)) * 2u : nullptr;   // the entry's two slots
-    bool cached = ce && ce->valid;
-    FilterDev fd{};
-    bool use_filter = false;
-    if (cached) use_filter = ce->use_filter;
-    else if (E.filter_id > 0) {
-      fd = host::BuildFilter(b->filters[static_cast<size_t>(E.filter_id - 1)], E.axis);
-      use_filter = fd.is_complex || fd.terms[0].type != HALO_FILTER_NONE || fd.action != 0;
-    }
-
-    // raypath colour: this entry's predicates (canonicalised like filter terms, each with its own symmetry) + the classes
-    ColorDev cd{};
-    const bool use_color = !b->color_classes.empty();
-    if (use_color && !cached) {
-      cd.class_cnt = static_cast<uint32_t>(b->color_classes.size());
-      for (uint32_t c = 0; c < cd.class_cnt; c++) {
-        cd.class_bits[c] = b->color_classes[c].bits;
-        cd.class_all[c] = b->color_classes[c].combine_all ? 1 : 0;
-      }
-      if (E.color_id > 0) {
-        const HaloColorSet& cs = b->color_sets[static_cast<size_t>(E.color_id - 1)];
-        cd.term_cnt = static_cast<uint32_t>(std::min(cs.term_count, HALO_COLOR_MAX_TERMS));
-        for (uint32_t k = 0; k < cd.term_cnt; k++) {
-          HaloFilter one{};
-          one.symmetry = cs.terms[k].symmetry;
-          one.terms[0] = cs.terms[k].predicate;
-          const FilterDev f1 = host::BuildFilter(one, E.axis);
-          cd.terms[k].t = f1.terms[0];
-          cd.terms[k].symmetry = f1.symmetry;
-          cd.terms[k].d_applicable = f1.d_applicable;
-          cd.terms[k].sigma_a = f1.sigma_a;
-          cd.terms[k].bit = static_cast<uint8_t>(cs.terms[k].bit & 0xFF);
-        }
-      }
-    }
-
-    // Which kernels: capture (tests) > filter / colour in their fast form (paths <= 16 faces, tables fit) > the generic filter kernels > plain
-    int mode = 0;
-    FastTables* fast_host = nullptr;
-    if (cached) mode = ce->mode;
-    else if (b->capture) mode = 2;
-    else if (b->rehit_strategy == 0) mode = 3;   // the legacy next-face strategy lives in the generic kernels only
-    else if (use_filter || use_color) {
-      mode = 3;
-      if (b->filter_fast && b->scene.max_hits <= 16) {
-        b->fast_scratch.reset(new FastTables());
-        std::memset(b->fast_scratch.get(), 0, sizeof(FastTables));
-        const HaloColorSet* cs = (use_color && E.color_id > 0) ? &b->color_sets[static_cast<size_t>(E.color_id - 1)] : nullptr;
-        if (host::BuildFastTables(use_filter ? &b->filters[static_cast<size_t>(E.filter_id - 1)] : nullptr, cs, E.axis, static_cast<uint32_t>(E.crystal_config_id), *b->fast_scratch)) {
-          fast_host = b->fast_scratch.get();
-          fast_host->class_cnt = use_color ? cd.class_cnt : 0u;
-          for (uint32_t c = 0; c < fast_host->class_cnt; c++) {
-            fast_host->class_bits[c] = cd.class_bits[c];
-            fast_host->class_all[c] = cd.class_all[c];
-          }
-          mode = use_color ? 4 : 1;
-        }
-      }
-    }
-    const bool fast_mode = mode == 0 || mode == 1 || mode == 4;   // production-shaped kernels: exit queue, hit log, regular-prism search
-
-    // chunked launches: bounds the host-built shape pool for stochastic geometry and keeps n_rays < 2^32
-    for (uint64_t off = 0; off < n_ci;) {
-      const uint64_t m = chunk_of(n_ci - off, E.crystal);
-      const uint32_t shape_cnt = deterministic ? 1u : static_cast<uint32_t>((m + b->geom_clock - 1) / b->geom_clock);
-      const bool host_pool = !deterministic && b->host_shapes;
-      // 0 = one shape per dispatch, 1 = pool of ShapeDev records, 2 = pool of ShapePrism records (device-generated prisms)
-      const int geom = deterministic ? 0 : ((E.crystal.kind == HALO_CRYSTAL_PRISM && !host_pool) ? 2 : 1);
-      std::vector<ShapeDev> pool((deterministic && !cached) || host_pool ? shape_cnt : 0u);
-      for (uint32_t k = 0; k < static_cast<uint32_t>(pool.size()); k++) {
-        if (host_crystal) host::ToShapeDev(*rays->crystal, pool[k]);
-        else host::MakeShapeDev(b->seed, E.crystal, deterministic ? 0 : (b->shape_count + k), pool[k]);
-      }
-      const uint64_t first_shape = b->shape_count;
-      if (!deterministic) {
-        b->shape_count += shape_cnt;
-        b->sess_crystal_samples += shape_cnt;
-      }
-      if (rays == nullptr && (E.axis.azimuth.type != HALO_DIST_NONE || E.axis.latitude.type != HALO_DIST_NONE || E.axis.roll.type != HALO_DIST_NONE))
-        b->sess_orient_samples += m;   // AxisDistribution::IsAxisDeterministic is false: one orientation per ray
-      // ---- dispatch slot: tables + zeroed tallies go up in one copy from the pinned mirror ----
-      const int k = b->ring_next;
-      b->ring_next = (k + 1) % HaloBackend::kRing;
-      harvest_slot(b, k);  // blocks only if the ring has wrapped onto a dispatch still in flight
-      b->ring_use[k]++;
-      DispatchSlot& hs = b->ring_host[k];
-      if (ce && !cached) ce->cur ^= 1;   // an upload takes the entry's other slot
-      DispatchSlot* ds = ce ? ce_dev + ce->cur : b->ring_dev.ptr + k;
-      bool entry_fast = false, hex_regular = false, has_fast = fast_host != nullptr;
-      if (cached) {
-        entry_fast = ce->entry_fast, hex_regular = ce->hex_regular, has_fast = ce->has_fast;
-      } else {
-        if (P.lat_path == kLatLut) {
-          const host::LatLut& lut = cached_lut(b, E.axis.latitude);
-          std::copy(lut.theta.begin(), lut.theta.end(), hs.lut);
-          std::copy(lut.cdf.begin(), lut.cdf.end(), hs.lut + kLutNodes);
-          std::copy(lut.flip.begin(), lut.flip.end(), hs.lut + 2 * kLutNodes);
-        }
-        std::copy(b->wl_pool_host.begin(), b->wl_pool_host.end(), hs.wl);
-        if (deterministic) {
-          hs.shape = pool[0];
-          entry_fast = b->entry_fast && host::BuildEntryFast(pool[0], hs.efast);
-          hex_regular = entry_fast && hs.efast.hex_regular;
-        }
-        if (use_filter) hs.filter = fd;
-        if (use_color) hs.color = cd;
-        if (fast_host) std::memcpy(&hs.fast, fast_host, sizeof(FastTables));
-        if (P.source == kSrcTransit) std::copy(b->cont_seg, b->cont_seg + kContShards + 1, hs.seg);
-        // (the fast filter tables are the slot's last member and travel only with the dispatches that use them; the pinned mirror is this
-        // ring slot's, so it stays as it is until the copy has run — harvest_slot above)
-        // A cache slot is a fixed device address: a kernel of an earlier, queued session (async: nobody harvested it) may still be staging its
-        // tables out of it on a trace stream.  The upload goes behind the last launch that read this slot (no host wait; ring slots are
-        // protected by harvest_slot above).  Without this the earlier kernel's late workgroups could pick up THIS session's wavelength pool or
-        // shape (tests/test_gpu_production_routes.py::test_async_sessions_alternating_wavelengths).
-        if (ce && ce->read_ring[ce->cur] >= 0) {
-          const int rk = ce->read_ring[ce->cur];
-          if (b->ring_busy[rk] && b->ring_use[rk] == ce->read_use[ce->cur]) HIPCHK(b, hipStreamWaitEvent(b->stream, b->ring_done[rk], 0));
-        }
-        HIPCHK(b, hipMemcpyAsync(ds, &hs, fast_host ? sizeof(DispatchSlot) : offsetof(DispatchSlot, fast), hipMemcpyHostToDevice, b->stream));
-        if (ce) {   // the next dispatch of this entry — the layer's next chunk, the next equal session — finds the tables in place
-          ce->valid = true, ce->mode = mode, ce->use_filter = use_filter, ce->use_color = use_color;
-          ce->entry_fast = entry_fast, ce->hex_regular = hex_regular, ce->has_fast = has_fast;
-          cached = true;
-        }
-      }
-      P.lut = ds->lut;
-      P.wl_pool = ds->wl;
-      P.filter = use_filter ? &ds->filter : nullptr;
-      P.color = use_color ? &ds->color : nullptr;
-      P.fast = has_fast ? &ds->fast : nullptr;
-      P.lanes = b->lanes.ptr;
-      P.lane_stride = static_cast<uint32_t>(b->acc_w) * static_cast<uint32_t>(b->acc_h);
-      P.cont_in_seg = ds->seg;
-      P.entry_fast = entry_fast ? &ds->efast : nullptr;
-      int shape_set = 0;
-      if (deterministic) {
-        P.shapes = &ds->shape;
-      } else {
-        // Two pools, taken in turn by the launches that may run beside a neighbour: the records of launch k+1 are written while launch k still
-        // traces out of the other one.
-        const bool turn = b->overlap && (m <= (1ull << b->alt_log2) || b->gen_ahead);   // (a launch that fills the chip runs alone on stream 0: pool 0)
-        shape_set = turn ? b->shapes_next : 0;
-        if (turn) b->shapes_next ^= 1;
-        DevBuf<ShapeDev>& shapes = b->shapes_s[shape_set];
-        if (int rc = reserve_idle(b, shapes, shape_cnt)) return rc;   // sized for ShapeDev records; prism pools use the front third
-        if (turn)   // (its twin with it, for the same reason as the log's second buffer set)
-          if (int rc = reserve_idle(b, b->shapes_s[shape_set ^ 1], shape_cnt)) return rc;
-        if (host_pool) {
-          if (b->shapes_used[shape_set]) HIPCHK(b, hipStreamWaitEvent(b->stream, b->ev_shapes_free[shape_set], 0));
-          HIPCHK(b, hipMemcpyAsync(shapes.ptr, pool.data(), pool.size() * sizeof(ShapeDev), hipMemcpyHostToDevice, b->stream));
-        }
-        // (device generator: queued below on the launch's trace stream, in front of the trace kernel)
-        P.shapes = shapes.ptr;
-      }
-      P.shape_cnt = shape_cnt;
-      P.n_rays = static_cast<uint32_t>(m);
-      P.ci_start = static_cast<uint32_t>(ci_start + off);
-      auto split = [](uint64_t v, uint32_t& lo, uint32_t& hi) {  // SplitPcgRayBase trace_backend.hpp:184-190
-        lo = static_cast<uint32_t>(v & 0xFFFFFFFFull);
-        hi = static_cast<uint32_t>(v >> 32);
-      };
-      split(b->gen_count, P.gen_lo, P.gen_hi);
-      split(b->gate_count, P.gate_lo, P.gate_hi);
-      split(b->transit_count, P.transit_lo, P.transit_hi);
-      if (rays) {
-        P.host_d = b->host_f.ptr + off * 3;
-        P.host_p = b->host_f.ptr + n * 3 + off * 3;
-        P.host_w = b->host_f.ptr + n * 6 + off;
-        P.host_tf = b->host_u.ptr + off;
-      }
-      const int blocks = blocks_of(m, !deterministic);
-      // binned accumulation for big one-plane launches (see halo_trace.inl: HitBuffer)
-      // 16384-slot tiles over the session's planes taken as one array (1 plane, or the per-entry planes of a small image)
-      const uint64_t bin_slots = (static_cast<uint64_t>(kMonoRows) << b->mono_s_log2) * (b->mono_by_wl ? b->plane_cnt : 1u);
-      const uint32_t bin_tiles = static_cast<uint32_t>(bin_slots >> 14);
-      const bool bin_geom_ok = deterministic || E.crystal.kind == HALO_CRYSTAL_PRISM;
-      // up to 512 tiles: one level (interleaved tiles).  More (per-wavelength planes of a large image): two levels — the
-      // trace kernel fills coarse lists of `fan` consecutive tiles each, a split pass deals them out to the tiles.
-      uint32_t fan_log2 = 0u;
-      while (((bin_tiles + (1u << fan_log2) - 1u) >> fan_log2) > b->bin_l1) fan_log2++;
-      const bool two_level = bin_tiles > 512u;
-      const bool bin_shape_ok = two_level ? (fan_log2 <= 8u && (bin_slots & 16383ull) == 0ull)
-                                          : (bin_tiles >= 8u && (bin_tiles & (bin_tiles - 1u)) == 0u);
-      // The hit log over the scalar planes of a per-entry-plane session (small images: the reference's 512x256 D65 scenes): every plane gets
-      // 2^t interleaved tiles of <= 16 Ki slots, and the split pass feeds at most 512 lists — 64 planes up to 128 Ki pixels, 32 up to 256 Ki.
-      const uint32_t wl_t_log2 = b->mono_s_log2 >= 4u ? b->mono_s_log2 - 4u : 0u;
-      const bool log_planes_ok = b->mono_by_wl && (static_cast<uint64_t>(b->plane_cnt) << wl_t_log2) <= 512ull &&
-                                 (static_cast<uint64_t>(b->plane_cnt) << (b->mono_s_log2 + 10u)) <= (1ull << 31) && b->hit_log != 0 && b->bin <= 0;
-      // (a layer before the last under canonical continuation order takes direct accumulation: only those kernels have CANON twins)
-      const bool canon = b->cont_order && !final_layer;
-      const bool use_bin = !canon && b->mono_session && b->aggregate == 1 && !b->capture && bin_shape_ok && bin_slots <= (1ull << 31) &&
-                           // own choice: only where the hit log cannot go (one plane per pool entry on a larger image) — the log beats the binned route
-                           // on every launch measured (tools/bin_vs_log_probe.py: dual fisheye 50 M rays 5.13 -> 4.42 ms)
-                           (b->bin < 0 ? (b->mono_by_wl && !log_planes_ok && bin_geom_ok && b->render.visible == HALO_VISIBLE_FULL && m >= (2ull << 20)) : b->bin != 0);
-      const uint32_t lists1 = two_level ? ((bin_tiles + (1u << fan_log2) - 1u) >> fan_log2) : bin_tiles;
-      uint32_t cap2 = 0u;
-      // Hit log (halo_trace.inl log_hit): global fp32 atomics retire memory-side at 21 G/s on this part, which bounded every big
-      // launch once its trace was fast enough (configs[1]: 2.4 ms of trace, 2.8 ms of atomics).  A production-mode launch on one
-      // scalar plane, or on the X/Y/Z planes of an illuminant session, appends its cache misses to one log region per workgroup
-      // instead; a split pass and a per-tile pass add them to the plane(s) afterwards.
-      // Tiles: as many as the split pass feeds whatever the image size — the per-tile pass has one workgroup per tile — of at least
-      // 256 and at most 16 Ki slots (X/Y/Z: 4 Ki) of ONE plane: 512 for X/Y/Z; for a scalar plane 128 where that keeps them within
-      // 16 Ki slots (longer runs in the split pass: 0.23 vs 0.25 ms at configs[1]).
-      const uint32_t log_t_log2 = log_planes_ok ? wl_t_log2 : b->xyz_log ? std::min<uint32_t>(9u, b->mono_s_log2 + 2u) : std::max<uint32_t>(b->mono_s_log2 >= 4u ? b->mono_s_log2 - 4u : 0u, std::min<uint32_t>(static_cast<uint32_t>(m < (4ull << 20) ? std::max(b->log_tiles_log2, 8) : b->log_tiles_log2), b->mono_s_log2 + 2u));   // (a small launch takes 256 tiles: its per-tile pass is one workgroup per tile, and 128 of them leave half the chip idle — config 4d 2.85 -> 3.18 G rays/s; big launches keep 128 for the split's longer runs)
-      const uint32_t log_planes = log_planes_ok ? b->plane_cnt : 1u;
-      const uint32_t log_tiles = log_planes << log_t_log2;   // lists the split pass feeds
-      const bool log_layout_ok = b->xyz_log ? (b->mono_s_log2 <= 11u) : (b->mono_session && (log_planes_ok || (!b->mono_by_wl && b->mono_s_log2 <= 12u)));
-      bool use_log = !canon && !use_bin && log_layout_ok && b->aggregate == 1 && fast_mode &&
-                           (P.prob < 1.0f || P.final_layer) &&   // a layer whose every exit continues puts nothing on the image
-                           (b->hit_log < 0 ? m >= ((b->mono_session && !b->mono_by_wl) ? log_min_rays(b->render.visible) : (2ull << 20)) : b->hit_log != 0);
-      bool use_log_xyz = use_log && b->xyz_log;
-      uint64_t log_cap = 0;
-      // Launches of <= 2^21 rays alternate between the two trace streams (next_trace_stream); only those can meet a neighbour that still reads
-      // or writes a buffer set, so only those take the sets in turn — a launch that fills the chip keeps stream 0 and set 0 (a second set
-      // allocated in the middle of a run is a host sync and a multi-gigabyte hipMalloc: 1.2 s in configs[4]'s first timed step)
-      const bool alternate = m <= (1ull << b->alt_log2);
-      const int ls = (b->overlap && alternate) ? b->log_set : 0;   // the buffer set of this launch
-      if (use_log) {
-        // a region takes 4 records per ray of its workgroup (configs[1]: 1.2 logged per ray), 8 for full-sky renders (5-6 per ray),
-        // and a tile list twice its even share of that; what runs over falls back to direct atomics
-        const uint64_t per_wg = (m + static_cast<uint64_t>(blocks) - 1u) / static_cast<uint64_t>(blocks);
-        uint64_t cap = std::max<uint64_t>(4ull * per_wg, 4096ull);
-        cap = std::min<uint64_t>(cap, (6ull << 30) / (8ull * static_cast<uint64_t>(blocks)));
-        if (use_log_xyz || b->render.visible == HALO_VISIBLE_FULL) cap = std::min<uint64_t>(std::max<uint64_t>(8ull * per_wg, 4096ull), (8ull << 30) / (8ull * static_cast<uint64_t>(blocks)));
-        // (per-launch cost of the slack, measured: configs[1] split 234 / 238 / 241 us at 2x / 4x / 8x; configs[4]'s 512 X/Y/Z lists 554 / 574 / 635 us —
-        // so 8x for scalar planes, where a hot pixel meets near-constant addends, 4x for X/Y/Z, whose addends vary with the wavelength)
-        const uint64_t kListSlack = use_log_xyz ? 4ull : 8ull;
-        // (8x the even share, within the 8 GB below: what runs over a tile list is added with fp32 atomics, and on a pixel that holds 4e5 the
-        // rounding of a near-constant addend is a bias, not noise — tools/route_fuzz.py seed 969: the sun's tile of a 1024 x 512 render took five
-        // even shares and its pixel read 5.6e-4 high with 2x)
-        uint64_t c2 = std::max<uint64_t>(kListSlack * ((use_log_xyz || b->render.visible == HALO_VISIBLE_FULL) ? 8ull : 4ull) * m / log_tiles, 1ull << 14);
-        c2 = std::min<uint64_t>(c2, (8ull << 30) / (8ull * log_tiles));
-        if (b->hit_log_cap) {   // tests: run both overflow fallbacks
-          cap = b->hit_log_cap;
-          c2 = std::max<uint64_t>(cap * static_cast<uint64_t>(blocks) / (2ull * log_tiles), 64ull);
-        }
-        // The log's capacity is a speed matter only (what runs over is added directly), so it gives way to the memory there is: the
-        // regions and lists still to be allocated take at most half of what is free (the continuation and shape pools of later layers
-        // want theirs), and a reserve that fails all the same sends this launch down the direct route instead of failing the trace.
-        {
-          size_t free_b = 0, total_b = 0;
-          const uint64_t have = (b->bin_list_s[ls].cap + b->bin_list2_s[ls].cap) * sizeof(HitRec);
-          uint64_t need = (cap * static_cast<uint64_t>(blocks) + c2 * log_tiles) * sizeof(HitRec);
-          if (need > have && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need - have > free_b / 2u) {
-            const double shrink = static_cast<double>(have + free_b / 2u) / static_cast<double>(need);
-            cap = std::max<uint64_t>(static_cast<uint64_t>(static_cast<double>(cap) * shrink), 1024ull);
-            c2 = std::max<uint64_t>(static_cast<uint64_t>(static_cast<double>(c2) * shrink), 1024ull);
-          }
-        }
-        cap2 = static_cast<uint32_t>(c2 & ~15ull);   // whole 128-byte lines per tile list
-        log_cap = cap;
-        hipError_t e1 = hipSuccess, e2 = hipSuccess;
-        if (int rc = reserve_idle(b, b->bin_list_s[ls], cap * static_cast<uint64_t>(blocks), &e1)) return rc;
-        if (e1 == hipSuccess)
-          if (int rc = reserve_idle(b, b->bin_list2_s[ls], c2 * log_tiles, &e2)) return rc;
-        if (b->overlap && alternate && e1 == hipSuccess && e2 == hipSuccess) {
-          // the other set with it: the next launch would otherwise stop the queue (a host sync and a multi-gigabyte hipMalloc) for it.  A speed
-          // matter only — if there is no room, the launch that finds the set short shrinks its log as above.
-          hipError_t e3 = hipSuccess, e4 = hipSuccess;
-          if (int rc = reserve_idle(b, b->bin_list_s[ls ^ 1], cap * static_cast<uint64_t>(blocks), &e3)) return rc;
-          if (e3 == hipSuccess)
-            if (int rc = reserve_idle(b, b->bin_list2_s[ls ^ 1], c2 * log_tiles, &e4)) return rc;
-          if (e3 != hipSuccess || e4 != hipSuccess) (void)hipGetLastError();
-        }
-        if (e1 != hipSuccess || e2 != hipSuccess) {
-          (void)hipGetLastError();   // out of memory: not this launch's route
-          use_log = use_log_xyz = false;
-        }
-      }
-      DevBuf<HitRec>&bin_list = b->bin_list_s[ls], &bin_list2 = b->bin_list2_s[ls];
-      DevBuf<uint32_t>&bin_cnt = b->bin_cnt_s[ls], &bin_cnt2 = b->bin_cnt2_s[ls];
-      if (use_bin)   // the staged-list route shares one buffer set and resets its counters on the main stream: one launch at a time
-        if (int rc = join_aux(b)) return rc;
-      if (use_log) {
-        const uint64_t cap = log_cap;
-        if (int rc = reserve_idle(b, bin_cnt, std::max<size_t>(static_cast<size_t>(blocks), static_cast<size_t>(512) * 16u))) return rc;
-        if (int rc = reserve_idle(b, bin_cnt2, static_cast<size_t>(512) * 16u)) return rc;
-        if (b->set_used[ls]) HIPCHK(b, hipStreamWaitEvent(b->stream, b->ev_set_free[ls], 0));   // the passes of the launch that last wrote this set
-        P.bin_list = bin_list.ptr;
-        P.bin_cap = static_cast<uint32_t>(cap);
-        P.bin_tiles = log_tiles;
-        P.bin_shift = 0u;
-        P.bin_cnt = bin_cnt.ptr;   // one fill count per region, written by the trace kernel
-        P.bin_log = 1u;
-        P.mono_copy_mask = 0u;   // logged slots and their fallbacks address copy 0
-        P.log_xyz = use_log_xyz ? 1u : 0u;
-        P.log_plane_stride = static_cast<uint32_t>((static_cast<uint64_t>(kMonoRows) << b->mono_s_log2) * b->plane_copies);
-      } else
-      if (use_bin) {
-        // lists sized for ~6 hits per ray spread 4x unevenly; an overflowing list falls back to direct atomics
-        // (the coarse and tile lists of the two-level route are slot ranges interleaved over the image — rows p % 1024 — and
-        // stay balanced whatever the image shows: 2x there)
-        const uint64_t slack = two_level ? 2ull : 4ull;
-        uint64_t cap = std::max<uint64_t>(slack * 6ull * m / lists1, 1ull << 16);
-        cap = std::min<uint64_t>(cap, (8ull << 30) / (8ull * lists1));
-        if (int rc = reserve_idle(b, bin_cnt, static_cast<size_t>(512) * 16u)) return rc;
-        HIPCHK(b, hipMemsetAsync(bin_cnt.ptr, 0, static_cast<size_t>(two_level ? 512u : bin_tiles) * 16u * sizeof(uint32_t), b->stream));
-        if (int rc = reserve_idle(b, bin_list, cap * lists1)) return rc;
-        P.bin_list = bin_list.ptr;
-        P.bin_cap = static_cast<uint32_t>(cap);
-        P.bin_tiles = two_level ? b->bin_l1 : bin_tiles;
-        P.bin_shift = two_level ? 14u + fan_log2 : 0u;
-        P.bin_cnt = bin_cnt.ptr;
-        P.bin_log = 0u;
-        P.log_xyz = 0u;
-        P.mono_by_wl = b->mono_by_wl ? 1u : 0u;
-        P.mono_copy_mask = 0u;   // staged hits and their fallbacks address copy 0
-        if (two_level) {
-          uint64_t c2 = std::max<uint64_t>(slack * 6ull * m / bin_tiles, 1ull << 12);
-          c2 = std::min<uint64_t>(c2, (8ull << 30) / (8ull * bin_tiles));
-          cap2 = static_cast<uint32_t>(c2 & ~15ull);   // whole 128-byte lines per tile list
-          if (int rc = reserve_idle(b, bin_cnt2, static_cast<size_t>(bin_tiles) * 16u)) return rc;
-          HIPCHK(b, hipMemsetAsync(bin_cnt2.ptr, 0, static_cast<size_t>(bin_tiles) * 16u * sizeof(uint32_t), b->stream));
-          if (int rc = reserve_idle(b, bin_list2, c2 * bin_tiles)) return rc;
-        }
-      } else {
-        P.bin_list = nullptr;
-        P.bin_log = 0u;
-        P.log_xyz = 0u;
-        P.mono_by_wl = b->mono_by_wl ? 1u : 0u;
-        P.mono_copy_mask = b->plane_copies - 1u;
-      }
-      P.no_land = (P.prob >= 1.0f && !P.final_layer && fast_mode && b->aggregate == 1) ? 1u : 0u;
-      // The launch's trace stream (alternating for small launches), behind whatever the auxiliary stream still does to the planes (a closing
-      // fold): the launch adds to them — from the trace kernel itself (direct atomics, staged lists) or in its passes, which follow it on
-      // the same stream.
-      hipStream_t ts = nullptr;
-      int ts_i = 0;
-      // (Round 6: a LOGGED trace kernel writes records, its region counts and the twin's other half — nothing the closing fold of the session
-      //  before reads or zeroes — so on a SMALL launch it starts under that fold, and only its passes, which add to the planes, wait for it.  A
-      //  discrete spectrum of many short sessions (bench.py --config 4d: 31 x 0.8 M rays) was one serial chain of generator, trace, split, sums
-      //  and fold, 325 us per session; the trace kernel and generator of session k + 1 now run beside the passes and the fold of session k.
-      //  Launches that fill the chip keep the old order: measured in round 5, nothing to gain there and the kernel's own span stretches.)
-      const bool under_fold = use_log && alternate;
-      if (int rc = next_trace_stream(b, !under_fold, alternate, &ts, &ts_i)) return rc;
-      hipEvent_t before_sums = nullptr;   // rule (1), for the routes whose sums write the planes plainly
-#ifndef HALO_NO_PLANE_GATES   // (defined only to see tests/test_gpu_production_routes.py's two-stream test fail without the gates)
-      if (b->overlap && !use_log && b->rmw_pending[ts_i ^ 1])   // this trace kernel adds to the planes itself: behind the other stream's sums
-        HIPCHK(b, hipStreamWaitEvent(ts, b->ev_rmw[ts_i ^ 1], 0));
-      if (b->overlap && (use_log || (use_bin && two_level)) && b->cs_pending[ts_i ^ 1]) {
-        HIPCHK(b, hipEventRecord(b->ev_gate, b->cs[ts_i ^ 1]));
-        before_sums = b->ev_gate;
-      }
-#endif
-      if (!deterministic && !host_pool) {
-        // Device generator: one team per sampled crystal, in front of the trace kernel on its stream.  Option "gen_ahead" puts the one of a
-        // launch that fills the chip on trace stream 1 instead, beside the previous launch's trace kernel and passes (it needs nothing of
-        // them, only its pool back from the launch before that one).  Measured (25 M rays per launch): prism pools 4.43 -> 4.55 ms per launch,
-        // pyramid pools 7.78 -> 7.70: both kernels are VALU-bound, so sharing the chip conserves the work.  Off by default.
-        const bool ahead = b->overlap && b->gen_ahead && !alternate;
-        hipStream_t gs = ahead ? b->cs[1] : ts;
-        if (b->shapes_used[shape_set]) HIPCHK(b, hipStreamWaitEvent(gs, b->ev_shapes_free[shape_set], 0));
-        hipError_t ge = launch_shapegen(const_cast<ShapeDev*>(P.shapes), geom == 2, shape_cnt, b->seed, host::MakeRecipe(E.crystal), first_shape, gs, b->gen_serial != 0);
-        if (ge != hipSuccess) return hip_fail(b, ge, "halo_shapegen_kernel launch");
-        if (ahead) {
-          HIPCHK(b, hipEventRecord(b->ev_gen, gs));
-          HIPCHK(b, hipStreamWaitEvent(ts, b->ev_gen, 0));
-          b->cs_pending[1] = true;
-        }
-      }
-      HIPCHK(b, hipEventRecord(b->ring_ev0[k], ts));  // HIP events on the launch stream bracket the kernel alone
-      b->ring_final[k] = P.final_layer != 0u;
-      // a one-shape dispatch of a regular hexagonal prism takes the literal-normal instantiation (kGeomOneHex = 3)
-      const int launch_geom = (geom == 0 && entry_fast && b->hex_fast && hex_regular) ? 3 : geom;
-      hipError_t le = launch_trace(P, blocks, ts, mode, launch_geom, b->mono_session);
-      if (ce) {   // the slot's last reader (see TableCacheEntry): this launch, whose ring_done event is recorded below
-        ce->read_ring[ce->cur] = k;
-        ce->read_use[ce->cur] = b->ring_use[k];
-      }
-      b->mono_dirty = true;
-      b->route.launches++;
-      b->route.mode_mask |= 1u << mode;
-      // the masks name the instantiation launch_mode / launch_mono pick (halo_trace.inl), not the request: the regular-prism search exists for
-      // the production-shaped kernels off the binned route, the no-accumulation kernels for their one-shape dispatches
-      const bool ran_hex = launch_geom == 3 && fast_mode && (P.bin_list == nullptr || P.bin_log != 0u || P.no_land != 0u);
-      const bool ran_none = P.no_land != 0u && geom == 0;
-      b->route.geom_mask |= 1u << (launch_geom == 3 && !ran_hex ? 0 : launch_geom);
-      b->route.accum_mask |= ran_none ? 64u : use_log ? (use_log_xyz ? 32u : 16u) : (use_bin ? (two_level ? 8u : 4u) : (b->mono_session ? 2u : 1u));
-      // specialisations (plain kernels only; launch_lens / launch_vis / launch_mono): bit 0 last-layer kernel (no continuation code), 1 lens as a
-      // constant, 2 visible range as a constant, 3 closed gate as a constant
-      {
-        const bool one = geom == 0, lens_known = P.proj.proj_type == HALO_LENS_LINEAR || P.proj.proj_type == HALO_LENS_FISHEYE_EQUAL_AREA ||
-                                                 P.proj.proj_type == HALO_LENS_DUAL_FISHEYE_EQUAL_AREA || P.proj.proj_type == HALO_LENS_RECTANGULAR;
-        const bool vis_known = P.proj.visible_range == HALO_VISIBLE_UPPER || P.proj.visible_range == HALO_VISIBLE_FULL;
-        uint32_t spec = 0u;
-        if (fast_mode && use_log && one && !ran_none && b->mono_session && P.final_layer) {
-          spec |= 1u;
-          if ((mode == 0 || mode == 1) && P.prob <= 0.0f && lens_known && vis_known) spec |= 2u | 4u | 8u;
-        }
-        if (fast_mode && use_log && one && !ran_none && b->mono_session && !P.final_layer && (mode == 0 || mode == 1) && lens_known && vis_known)
-          spec |= 2u | 4u;   // (round 6: the logging kernels of the layers before the last know their lens and visible range too; their gate is open)
-        if (mode == 0 && use_log && !one && !b->mono_session && P.prob <= 0.0f && P.proj.visible_range == HALO_VISIBLE_FULL) spec |= 4u | 8u;
-        if (mode == 0 && use_log && !one && P.prob <= 0.0f && P.proj.visible_range == HALO_VISIBLE_FULL && P.proj.proj_type == HALO_LENS_RECTANGULAR)
-          spec |= 2u | 4u | 8u;   // (shape-pool kernels, either plane layout: bench_config_stoch.json's render as constants)
-        b->route.spec_mask |= spec;
-        if (spec == 0u) b->route.generic_launches++;
-      }
-      b->route.source_mask |= 1u << P.source;
-      if (le != hipSuccess) return hip_fail(b, le, "halo_trace_kernel launch");
-      if (!deterministic) {
-        HIPCHK(b, hipEventRecord(b->ev_shapes_free[shape_set], ts));
-        b->shapes_used[shape_set] = true;
-      }
-      // fixed-point scale of the per-tile sums (halo_kernels.hip FixQ): no slot of this launch can sum to more than 4 x max weight x rays
-      const uint32_t frac_bits = fix_frac_bits(b->sess_max_w, m);
-      if (use_log) {
-        // the accumulation passes of this launch: behind the trace kernel on its stream.  (Round 5 tried them on the auxiliary stream, under the
-        // next launch's trace kernel: configs[1] + 1.2 %, the trace kernel itself 5 % slower for the CUs the 134 KB split workgroups take, the
-        // passes' spans stretched sevenfold — profiles that no longer say what a kernel costs, for one percent.  Not kept.)
-        HIPCHK(b, hipEventRecord(b->ring_ev1[k], ts));          // the trace kernel alone: ev0 .. ev1
-        hipStream_t ps = ts;
-        if (under_fold) {   // the passes add to the planes: behind the fold that last touched THEIR planes
-          if (b->mono_two) {   // two plane sets: that is the fold of two sessions ago (it zeroed this set), not the one the trace kernel started under
-            if (b->set_folded_pending[b->mono_set]) HIPCHK(b, hipStreamWaitEvent(ps, b->ev_set_folded[b->mono_set], 0));
-          } else if (int rc = wait_for_aux(b, ts_i)) return rc;
-        }
-        HIPCHK(b, hipEventRecord(b->ring_ev2[k], ps));
-        HIPCHK(b, hipMemsetAsync(bin_cnt2.ptr, 0, static_cast<size_t>(log_tiles) * 16u * sizeof(uint32_t), ps));
-        hipError_t be = use_log_xyz ? launch_log_route_xyz(P.mono, P.log_plane_stride, bin_list.ptr, P.bin_cap, bin_cnt.ptr, static_cast<uint32_t>(blocks),
-                                                           bin_list2.ptr, cap2, bin_cnt2.ptr, log_tiles, b->mono_s_log2, P.wl_pool, P.wl_pool_size, frac_bits, P.ovf, P.ovf_flag, P.ovf_copies_log2, ps, before_sums)
-                                    : launch_log_route(P.mono, bin_list.ptr, P.bin_cap, bin_cnt.ptr, static_cast<uint32_t>(blocks), bin_list2.ptr, cap2,
-                                                       bin_cnt2.ptr, 1u << log_t_log2, log_planes, b->mono_s_log2, b->render.visible == HALO_VISIBLE_FULL, frac_bits,
-                                                       P.ovf, P.ovf_flag, P.ovf_copies_log2, ps, before_sums);
-        if (be != hipSuccess) return hip_fail(b, be, "halo_split_kernel launch");
-        if (b->overlap) {
-          HIPCHK(b, hipEventRecord(b->ev_rmw[ts_i], ps));
-          b->rmw_pending[ts_i] = true;
-        }
-        HIPCHK(b, hipEventRecord(b->ring_ev3[k], ps));
-        HIPCHK(b, hipEventRecord(b->ev_set_free[ls], ps));
-        b->set_used[ls] = true;
-        if (b->overlap && alternate) b->log_set ^= 1;
-        b->ring_posts[k] = true;
-        HIPCHK(b, hipEventRecord(b->ring_done[k], ps));
-      } else {
-      if (use_bin) {
-        hipError_t be = two_level ? launch_bin_two_level(P.mono, bin_list.ptr, P.bin_cap, bin_cnt.ptr, lists1, bin_list2.ptr, cap2, bin_cnt2.ptr,
-                                                         bin_tiles, fan_log2, frac_bits, P.ovf, P.ovf_flag, ts, before_sums)
-                                  : launch_bin_accumulate(P.mono, bin_list.ptr, P.bin_cap, bin_cnt.ptr, bin_tiles, frac_bits, ts);
-        if (be != hipSuccess) return hip_fail(b, be, "halo_bin_accumulate_kernel launch");
-        if (b->overlap && two_level) {
-          HIPCHK(b, hipEventRecord(b->ev_rmw[ts_i], ts));
-          b->rmw_pending[ts_i] = true;
-        }
-      }
-      HIPCHK(b, hipEventRecord(b->ring_ev1[k], ts));
-      b->ring_posts[k] = false;
-      HIPCHK(b, hipEventRecord(b->ring_done[k], ts));
-      }
-      b->tally_unread = true;
-      b->ring_busy[k] = true;
-      if (host_pool) HIPCHK(b, hipStreamSynchronize(b->stream));  // the pageable shape pool must outlive its copy (the copy is on the main stream)
-      if (P.source == kSrcGen) b->gen_count += m;
-      if (P.source == kSrcTransit) b->transit_count += m;
-      b->gate_count += m;
-      off += m;
-    }
-    ci_start += n_ci;
+    if (int rc = trace_launch(b, c, p, T, P)) return rc;
   }
-  if (defer) {  // queued, not waited for: the tallies arrive through halo_collect_stats
-    b->layer_acc.root_count += n;
-    if (stats) {
-      std::memset(stats, 0, sizeof(*stats));
-      stats->root_count = n;
-    }
-    b->cont_in_n = 0;
-    return HALO_OK;
-  }
-  if (int rc = join_aux(b)) return rc;   // the copies below (and the caller) want this layer's kernels done: the main stream waits for the trace streams
-  uint32_t cnt[kCntNum] = {0, 0, 0, 0};
-  std::vector<uint32_t> fill(final_layer ? 0 : kContShards * kContCntStride);
-  HIPCHK(b, hipMemcpyAsync(cnt, b->counters.ptr, sizeof(cnt), hipMemcpyDeviceToHost, b->stream));
-  if (!final_layer) HIPCHK(b, hipMemcpyAsync(fill.data(), b->cont_cnt.ptr, fill.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
-  uint32_t cont_err = 0;
-  if (canon_check) HIPCHK(b, hipMemcpyAsync(&cont_err, b->cont_err.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
-  if (b->tally_unread) {
-    if (int rc = pull_tally(b)) return rc;   // (one more small copy and THE stream sync of this call: the two copies above are complete behind it)
-  } else {
-    HIPCHK(b, hipStreamSynchronize(b->stream));
-  }
-  harvest_all(b);
-  if (cont_err != 0u)   // never a pool handed on (or traced) out of canonical order in silence
-    return cont_order_fail(b, cont_err);
-  uint64_t n_cont = 0;
-  if (!final_layer) {  // the next layer addresses the pool through the prefix of the shard fill counts
-    b->cont_fill_max = 0;
-    for (int sI = 0; sI < kContShards; sI++) {
-      const uint32_t c = fill[static_cast<size_t>(sI) * kContCntStride];
-      // (canonical order included: a pool that lost records would be handed on with holes in its order — never, the session fails)
-      if (c > out_cap) return fail(b, HALO_FATAL, b->cont_order ? "continuation pool overflow (cont_order = 1: the canonical pool would be incomplete)" : "continuation pool overflow");
-      b->cont_seg[sI] = static_cast<uint32_t>(n_cont);
-      n_cont += c;
-      b->cont_fill_max = std::max(b->cont_fill_max, c);
-    }
-    b->cont_seg[kContShards] = static_cast<uint32_t>(n_cont);
-    b->cont_roots = n;
-  }
-  b->exits_pending = std::min<uint64_t>(cnt[kCntExit], b->exits.cap);
-  b->layer_acc.root_count = n;
-  b->layer_acc.continuation_count = n_cont;
-  if (stats) *stats = b->layer_acc;
-  add_stats(b->pending, b->layer_acc);
-  b->layer_acc = HaloLayerStats{};
-  b->cont_in_n = n_cont;  // becomes the next layer's input at Recombine
-  return HALO_OK;
+  return close_layer(b, c, defer, stats);
 }
 
 int halo_generate_shapes(halo_handle_t b, const HaloCrystal* crystal, uint64_t first_index, uint32_t n, int on_device, HaloGeomTables* out) {

@@ -220,6 +220,8 @@ constexpr uint32_t kContMaskWords = 4u;   // 128 bits per root
 // pool's fill — a seq continued twice, or a record lost (scan)
 constexpr uint32_t kContErrKey = 2u, kContErrSum = 4u;
 
+constexpr uint32_t kBinTileLog2 = 14u;   // binned accumulation: slots per tile, 64 KB of fp32 in the accumulate pass
+constexpr int kBinCntStride = 16;        // ... and its tile counters, 64 B apart
 struct HitRec {  // one staged pixel hit of the binned accumulation: slot inside plane 0 and the weight's bits
   uint32_t slot, w_bits;
 };

@@ -2,6 +2,7 @@
 // plane fold, device consumer) and the launch dispatcher.  The trace kernel itself is a template in halo_trace.inl, instantiated per MODE in
 // halo_trace_m{0,1,2}.hip.
 #include "halo_trace.inl"
+#include "halo_launch.h"
 
 namespace halo {
 

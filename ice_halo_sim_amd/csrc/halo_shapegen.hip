@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include "halo_geom.h"
+#include "halo_launch.h"
 
 namespace halo {
 

@@ -525,9 +525,8 @@ struct PixCache {
 // hotter than average) fall back to the direct atomic, so capacity is a speed matter only.
 constexpr int kAccDirect = 0, kAccBin = 1, kAccLog = 2, kAccNone = 3, kAccLogFinal = 4;   // halo_trace_kernel ACC (None: a layer whose every exit continues — nothing lands)
 constexpr int kHitBuf = 1536;                 // staged hits per workgroup (16 KB)
-constexpr uint32_t kBinTileLog2 = 14u;         // slots per tile: 64 KB of fp32 in the accumulate pass
+// (kBinTileLog2, slots per tile, and kBinCntStride, the spacing of the tile counters: halo_device.h)
 constexpr int kBinMaxTiles = 512;
-constexpr int kBinCntStride = 16;              // tile counters 64 B apart
 struct HitBuffer {
   uint2 h[kHitBuf];
   uint32_t n;

@@ -125,7 +125,10 @@ struct HaloBackend {
   int filter_fast = 1;         // 1: filtered / colour-tagged dispatches with max_hits <= 16 run the production-shaped kernels (FastTables); 0: the generic ones
   int async = 0;               // 1: final-layer dispatches are queued without a host sync; stats via halo_collect_stats
   uint32_t shuffle_chunk_log2 = 5;   // Recombine's shuffle moves chunks of 2^k pool entries (k = 0: per ray, like the reference)
+  int spec_root = 1;           // option (A/B knob): 1 = last-layer plain hit-log launches over a regular prism whose root generation matches a root profile
+                               // (halo_trace.inl kRoot*) run the instantiation that has it as constants; 0 = always the generic root generation
   HaloRouteInfo route{};       // kernels that served the current / last session (halo_last_route)
+  uint32_t route_root = 0;     // ... and the root profiles among them (halo_last_root_profile): bit kRootProfile* - 1
 
   // monotone ray counters: seeded once, never reset per session (cuda_trace_backend.cu:3724-3741)
   uint64_t gen_count = 0, gate_count = 0, transit_count = 0, shape_count = 0;
@@ -603,6 +606,7 @@ int halo_set_option(halo_handle_t b, const char* key, int64_t v) {
   else if (k == "entry_fast") b->entry_fast = v ? 1 : 0;
   else if (k == "hex_fast") b->hex_fast = v ? 1 : 0;
   else if (k == "filter_fast") b->filter_fast = v ? 1 : 0;
+  else if (k == "spec_root") b->spec_root = v ? 1 : 0;
   else if (k == "hit_log") b->hit_log = static_cast<int>(v);
   else if (k == "hit_log_cap") b->hit_log_cap = static_cast<uint32_t>(std::max<int64_t>(v, 0));
   else if (k == "gen_serial") b->gen_serial = v ? 1 : 0;
@@ -859,6 +863,7 @@ int halo_begin(halo_handle_t b, const HaloScene* scene, const HaloRender* render
   }
   b->sess_crystal_samples = b->sess_orient_samples = 0;
   b->route = HaloRouteInfo{};
+  b->route_root = 0u;
   b->route.plane_cnt = b->plane_cnt;
   b->route.plane_copies = b->plane_copies;
   b->route.shuffle_chunk = 1u << b->shuffle_chunk_log2;
@@ -1256,6 +1261,13 @@ int upload_tables(HaloBackend* b, const LayerCtx& c, const LaunchPlan& p, const 
   }
   return HALO_OK;
 }
+// The root profile a dispatch record matches exactly (halo_trace.inl kRoot*: LUT latitude, uniform azimuth and roll, generated roots or the
+// continuation pool); anything else keeps the generic root generation.  Whether an instantiation with that profile exists for the launch's
+// kernel is the launcher's business (launch_root) and record_route's.
+uint32_t root_profile_of(const DispatchParams& P) {
+  if (P.lat_path != kLatLut || P.az_type != HALO_DIST_UNIFORM || P.roll_type != HALO_DIST_UNIFORM) return kRootProfileNone;
+  return P.source == kSrcGen ? kRootProfileGen : P.source == kSrcTransit ? kRootProfileTransit : kRootProfileNone;
+}
 // The fields of DispatchParams that every launch of entry `ci` shares.  The accumulation route's (bin_*, log_*, mono_copy_mask, mono_by_wl,
 // no_land) are written by bind_route alone, the tables', shapes' and counters' by trace_launch.
 DispatchParams fill_params(HaloBackend* b, const LayerCtx& c, int ci) {
@@ -1323,6 +1335,7 @@ DispatchParams fill_params(HaloBackend* b, const LayerCtx& c, int ci) {
   P.geom_clock = b->geom_clock;
   P.lanes = b->lanes.ptr;
   P.lane_stride = static_cast<uint32_t>(b->acc_w) * static_cast<uint32_t>(b->acc_h);
+  P.root_profile = b->spec_root ? root_profile_of(P) : kRootProfileNone;
   return P;
 }
 // The route branch: reserves and resets the buffers of the launch's accumulation route (log set `ls`) and writes the route's fields of P — their
@@ -1391,6 +1404,12 @@ void record_route(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, 
     spec |= 2u | 4u | 8u;   // (shape-pool kernels, either plane layout: bench_config_stoch.json's render as constants)
   b->route.spec_mask |= spec;
   if (spec == 0u) b->route.generic_launches++;
+  // root profiles (launch_root): instantiated for the regular prism's last-layer plain kernels with lens, visible range and closed gate as constants
+  // (... except the continuation-pool profile under the linear lens over the full sky)
+  const bool no_transit = P.proj.proj_type == HALO_LENS_LINEAR && P.proj.visible_range == HALO_VISIBLE_FULL;
+  if (mode == 0 && ran_hex && P.final_layer && (spec & (2u | 4u | 8u)) == (2u | 4u | 8u) && P.root_profile != kRootProfileNone && P.root_profile == root_profile_of(P) &&
+      !(no_transit && P.root_profile == kRootProfileTransit))
+    b->route_root |= 1u << (P.root_profile - 1u);
   b->route.source_mask |= 1u << P.source;
 }
 // The accumulation passes of a launch, behind its trace kernel on trace stream `ts` (index ts_i), and the ring slot's closing events.
@@ -1821,6 +1840,12 @@ int halo_last_sample_counts(halo_handle_t b, uint64_t* crystal_samples, uint64_t
 int halo_last_route(halo_handle_t b, HaloRouteInfo* out) {
   if (!b || !out) return HALO_FATAL;
   *out = b->route;
+  return HALO_OK;
+}
+
+int halo_last_root_profile(halo_handle_t b, uint32_t* out) {
+  if (!b || !out) return HALO_FATAL;
+  *out = b->route_root;
   return HALO_OK;
 }
 

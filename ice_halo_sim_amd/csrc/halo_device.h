@@ -331,6 +331,7 @@ struct DispatchParams {
   const FastTables* fast;      // kFilter / kColor kernels: the filter and the colour predicates in their fast form (else nullptr)
   double* lanes;               // class_cnt x lane_stride Y lanes, fp64: a hot pixel's lane passes 1e7 and fp32 atomics round a near-constant addend the same way every time (3e-3 low, round 3)
   uint32_t lane_stride;        // W*H
+  uint32_t root_profile;       // host-side only (no kernel reads it): kRootProfile* — the root-generation profile the launcher may instantiate for this dispatch
 };
 
 // Pixel → slot map of the mono plane.  The plane is kMonoRows rows of S = 2^s_log2 slots; pixel p sits in row p % kMonoRows
@@ -373,6 +374,10 @@ __host__ __device__
 inline size_t TwinOffset(size_t off, uint32_t plane_log2, uint32_t copies_log2) {
   return ((off >> (plane_log2 + copies_log2)) << plane_log2) | (off & ((static_cast<size_t>(1) << plane_log2) - 1u));
 }
+
+// DispatchParams::root_profile: none (the generic root generation), or LUT latitude + uniform azimuth and roll over generated roots / over the
+// continuation pool (halo_trace.inl kRoot*)
+constexpr uint32_t kRootProfileNone = 0u, kRootProfileGen = 1u, kRootProfileTransit = 2u;
 
 enum { kCntCont = 0, kCntExit = 1, kCntNum = 4 };
 enum { kSumLanded = 0, kSumExitW = 1, kSumExitN = 2, kSumPixN = 3, kSumNum = 4 };

@@ -268,18 +268,29 @@ HD uint32_t lat_lut_bin(float theta, const float* lut) {
   return static_cast<uint32_t>(idx);
 }
 
+// Root profiles (halo_trace_kernel's ROOT): what the last-layer kernels of the regular prism know about their root generation at compile time.
+// kRootAny keeps every choice a run-time test.  The two others are the orientation the shipped column / plate examples and the BASELINE
+// configurations take — latitude by the LUT, azimuth and roll uniform — over generated roots or over the continuation pool: the tests on the
+// source, the latitude path and the five distribution kinds (three of which carry logf / cosf / sinf) fold away, and with them 60 % of the
+// kernel's code.  Same expressions, draws and stream slots.
+constexpr int kRootAny = -1, kRootGenLutUniform = 0, kRootTransitLutUniform = 1;
+
+template <int ROOT = kRootAny>
 HD void sample_lat_lon_roll(Stream& s, const DispatchParams& P, const float* lut, float& lon, float& lat, float& roll) {
   float phi = 0.0f;
   bool flip = false;
   lon = 0.0f;
-  if (P.lat_path == kLatFullSphere) {
+  const uint32_t lat_path = ROOT != kRootAny ? static_cast<uint32_t>(kLatLut) : P.lat_path;
+  const uint32_t az_type = ROOT != kRootAny ? static_cast<uint32_t>(HALO_DIST_UNIFORM) : P.az_type;
+  const uint32_t roll_type = ROOT != kRootAny ? static_cast<uint32_t>(HALO_DIST_UNIFORM) : P.roll_type;
+  if (lat_path == kLatFullSphere) {
     float u = uniform(s) * 2.0f - 1.0f;
     u = fminf(fmaxf(u, -1.0f), 1.0f);
     phi = asinf(u);
     lon = uniform(s) * 2.0f * kPiF;
-  } else if (P.lat_path == kLatNoRandom) {
+  } else if (lat_path == kLatNoRandom) {
     phi = P.lat_mean_rad;
-  } else if (P.lat_path == kLatGaussLegacy) {
+  } else if (lat_path == kLatGaussLegacy) {
     float raw = get_dist(s, HALO_DIST_GAUSS_LEGACY, P.lat_mean_rad, P.lat_std_rad);
     normalize_latitude(raw, phi, flip);
   } else {  // kLatLut
@@ -294,8 +305,8 @@ HD void sample_lat_lon_roll(Stream& s, const DispatchParams& P, const float* lut
       s.slot++;  // u < 0 is false for every u: keep the stream aligned, skip the two hashes
     }
   }
-  if (P.lat_path != kLatFullSphere) lon = get_dist(s, P.az_type, P.az_mean_rad, P.az_std_rad);
-  roll = get_dist(s, P.roll_type, P.roll_mean_rad, P.roll_std_rad);
+  if (lat_path != kLatFullSphere) lon = get_dist(s, az_type, P.az_mean_rad, P.az_std_rad);
+  roll = get_dist(s, roll_type, P.roll_mean_rad, P.roll_std_rad);
   if (flip) {
     lon += kPiF;
     roll += kPiF;
@@ -1940,7 +1951,7 @@ struct Wl0 {   // entry 0 of the wavelength pool and 1 / n, loaded once per kern
   float inv_n;
 };
 
-template <int MODE, bool MONO, bool SMALLC, bool HEX, typename ShapePtr, typename NextT = NextShape>
+template <int MODE, bool MONO, bool SMALLC, bool HEX, int ROOT, typename ShapePtr, typename NextT = NextShape>
 HD void trace_one(const DispatchParams& P, LdsTables<MONO, SMALLC>& T, const AccCtx<MONO, SMALLC>& acc, const FilterDev* filter, const ColorDev* color, ShapePtr sh,
                   const Wl0& wl0, uint32_t tid, RaySums& sums, Probe& pr, NextT* next = nullptr, const WlEntryDev* wl_lds = nullptr,
                   const SlotFast* slot_fast = nullptr) {
@@ -1958,7 +1969,9 @@ HD void trace_one(const DispatchParams& P, LdsTables<MONO, SMALLC>& T, const Acc
 #endif
   Stream gate = make_stream(G.gate_seed, G.gate_lo, G.gate_hi, tid);
 
-  const uint32_t source = G.source;
+  // (a root profile's source is a constant: the branches below fold to the one it names.  The pool size stays a run-time value: as a constant 1
+  //  it saves 300 bytes of code and costs the generated-roots profile 4 spilled VGPRs and scratch)
+  const uint32_t source = ROOT == kRootGenLutUniform ? static_cast<uint32_t>(kSrcGen) : ROOT == kRootTransitLutUniform ? static_cast<uint32_t>(kSrcTransit) : G.source;
   if (source == kSrcGen) {
     Stream s = make_stream(G.gen_seed, G.gen_lo, G.gen_hi, tid);
     // per-ray wavelength in its own seed domain (BuildWlStream pcg_shared.h:213-219)
@@ -1970,7 +1983,7 @@ HD void trace_one(const DispatchParams& P, LdsTables<MONO, SMALLC>& T, const Acc
     }
     float lon, lat, roll;
     PROBE_MARK(pr, kPhStream);
-    sample_lat_lon_roll(s, G, T.lut, lon, lat, roll);
+    sample_lat_lon_roll<ROOT>(s, G, T.lut, lon, lat, roll);
     PROBE_MARK(pr, kPhOrient);
     build_crystal_rotation(lon, lat, roll, R);
     PROBE_MARK(pr, kPhRotation);
@@ -2034,7 +2047,7 @@ HD void trace_one(const DispatchParams& P, LdsTables<MONO, SMALLC>& T, const Acc
     HALO_ARRIVED(pinned, wl_idx);
     float lon, lat, roll;
     PROBE_MARK(pr, kPhStream);
-    sample_lat_lon_roll(s, G, T.lut, lon, lat, roll);
+    sample_lat_lon_roll<ROOT>(s, G, T.lut, lon, lat, roll);
     PROBE_MARK(pr, kPhOrient);
     build_crystal_rotation(lon, lat, roll, R);
     PROBE_MARK(pr, kPhRotation);
@@ -2524,13 +2537,15 @@ constexpr int min_waves() {
 // types (uniform branches, and the SGPRs their parameters hold), the visibility tests and the gate stream fold away: configs[1]
 // 2.96 -> 2.73 (lens) -> 2.60 ms per launch.  Done for the last-layer one-shape scalar kernels and the lenses of the shipped examples.
 // CANON: a layer before the last under canonical continuation order (option cont_order = 1) — its appends carry their (root, interaction) key.
-template <int MODE, int GEOM, bool MONO, int ACC, int LENS = -1, int VIS = -1, bool NOGATE = false, bool CANON = false>   // ACC: kAccDirect, kAccBin (staged + binned hit lists), kAccLog (per-workgroup hit log), ...
+// ROOT: a root profile (kRoot*, at sample_lat_lon_roll) — the last-layer plain hit-log kernels of the regular prism, which launch_vis fans out.
+template <int MODE, int GEOM, bool MONO, int ACC, int LENS = -1, int VIS = -1, bool NOGATE = false, bool CANON = false, int ROOT = kRootAny>   // ACC: kAccDirect, kAccBin (staged + binned hit lists), kAccLog (per-workgroup hit log), ...
 __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) halo_trace_kernel(const DispatchParams P) {
   constexpr bool BIN = ACC == kAccBin, LOG = ACC == kAccLog || ACC == kAccLogFinal, NONE = ACC == kAccNone, LAST = ACC == kAccLogFinal;
   static_assert(!LOG || ModeTraits<MODE>::kFast, "the hit log is a production-mode route");
   static_assert(!NONE || (ModeTraits<MODE>::kFast && MONO), "kAccNone: production mode; nothing accumulates, so one (scalar) flavour serves every session");
   static_assert(MODE == kModePlain || MODE == kModeFilter || (LENS < 0 && VIS < 0 && !NOGATE), "lens / visible-range / closed-gate specialisations exist for the plain and the filter kernels");
   static_assert(!BIN || MONO, "binned accumulation is a one-plane mode");
+  static_assert(ROOT == kRootAny || (MODE == kModePlain && GEOM == kGeomOneHex && MONO && LAST && NOGATE), "root profiles exist for the last-layer plain hit-log kernels of the regular prism");
   Probe pr;
 #ifdef HALO_PROBE
   for (int k = 0; k < 16; k++) pr.acc[k] = 0u;
@@ -2623,14 +2638,14 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
     for (int i = threadIdx.x; i < CacheGeom<MONO, SMALLC>::kN * (MONO ? 1 : 3); i += kBlock) T.cache.val[i] = 0.0f;
   }
   // ---- stage the dispatch-constant tables into LDS ----
-  if (P.lat_path == kLatLut)
+  if (ROOT != kRootAny || P.lat_path == kLatLut)
     for (int i = threadIdx.x; i < 3 * kLutNodes; i += kBlock) T.lut[i] = P.lut[i];
   if constexpr (POOLDB) {
     static_assert(sizeof(WlEntryDev) == 32u, "copied as two float4");
     if (P.wl_pool_size <= kWlLds)
       for (uint32_t i = threadIdx.x; i < 2u * P.wl_pool_size; i += kBlock) reinterpret_cast<f4v*>(s_wl)[i] = reinterpret_cast<const f4v*>(P.wl_pool)[i];
   }
-  if (P.source == kSrcTransit)
+  if (ROOT == kRootAny ? P.source == kSrcTransit : ROOT == kRootTransitLutUniform)
     for (int i = threadIdx.x; i <= kContShards; i += kBlock) T.seg[i] = P.cont_in_seg[i];
   if (threadIdx.x == 0) T.fidx.ok = 0u;
   if (!POOL && P.entry_fast != nullptr) {
@@ -2735,7 +2750,7 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
         mirrored = nx.src != nullptr;
         PROBE_MARK(pr, kPhStage);
         // (a lane without a ray — the launch's last rays — has no next record either: next_first > tid >= n_rays)
-        if (tid < P.n_rays) trace_one<MODE, MONO, SMALLC, false>(P, T, acc, filter, color, static_cast<const PoolSlot*>(slot), wl0, tid, sums, pr, &nx, wl_lds, sfast);
+        if (tid < P.n_rays) trace_one<MODE, MONO, SMALLC, false, kRootAny>(P, T, acc, filter, color, static_cast<const PoolSlot*>(slot), wl0, tid, sums, pr, &nx, wl_lds, sfast);
         asm volatile("" : : : "memory");
         __builtin_amdgcn_wave_barrier();
         PROBE_MARK(pr, kPhSlab);
@@ -2750,7 +2765,7 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
       __builtin_amdgcn_wave_barrier();
       PROBE_MARK(pr, kPhStage);
-      if (tid < P.n_rays) trace_one<MODE, MONO, SMALLC, GEOM == kGeomOneHex>(P, T, acc, filter, color, static_cast<const PoolSlot*>(slot), wl0, tid, sums, pr);
+      if (tid < P.n_rays) trace_one<MODE, MONO, SMALLC, GEOM == kGeomOneHex, kRootAny>(P, T, acc, filter, color, static_cast<const PoolSlot*>(slot), wl0, tid, sums, pr);
       __builtin_amdgcn_wave_barrier();
       PROBE_MARK(pr, kPhSlab);
       if constexpr (BIN) {
@@ -2767,10 +2782,10 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
       if (tid < P.n_rays) {
         if constexpr (POOL) {  // shape clock not a multiple of 32: lanes of a half-wave may differ, read the pool through L1/L2
           const PoolRec* sh = reinterpret_cast<const PoolRec*>(P.shapes) + (tid / P.geom_clock);
-          trace_one<MODE, MONO, SMALLC, GEOM == kGeomOneHex>(P, T, acc, filter, color, sh, wl0, tid, sums, pr);
+          trace_one<MODE, MONO, SMALLC, GEOM == kGeomOneHex, ROOT>(P, T, acc, filter, color, sh, wl0, tid, sums, pr);
         } else {
           const OneShape* sh = &s_shape.s[0];  // LDS: ds_read_b128 broadcasts
-          trace_one<MODE, MONO, SMALLC, GEOM == kGeomOneHex>(P, T, acc, filter, color, sh, wl0, tid, sums, pr);
+          trace_one<MODE, MONO, SMALLC, GEOM == kGeomOneHex, ROOT>(P, T, acc, filter, color, sh, wl0, tid, sums, pr);
         }
       }
       if constexpr (BIN) {
@@ -2862,10 +2877,30 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
 // (NOGATE = true: the last layer with prob <= 0.  NOGATE = false, round 6: the logging kernels of the layers BEFORE the last — their gate is open, the lens
 //  and the visible range are as constant as in the last layer, and the generic-lens form of them carried every lens's code: 8723 instructions, 120
 //  spilled SGPRs, 10 spilled VGPRs and scratch against 4612 / 45 / 0 / none for the dual-fisheye instantiation, tools/isa_by_line.py.)
+// ... and, for the last-layer plain hit-log kernels of the regular prism alone, the root profile the host asks for (DispatchParams::root_profile,
+// halo_backend.cpp root_profile_of) — taken only when the record itself says what the profile assumes: a record that does not runs the generic form.
+template <int MODE, int GEOM, bool MONO, int ACC, int LENS, int VIS, bool NOGATE>
+static void launch_root(const DispatchParams& P, dim3 grid, dim3 block, hipStream_t stream) {
+  if constexpr (MODE == kModePlain && GEOM == kGeomOneHex && MONO && ACC == kAccLogFinal && NOGATE) {
+    const bool lut_uniform = P.lat_path == kLatLut && P.az_type == HALO_DIST_UNIFORM && P.roll_type == HALO_DIST_UNIFORM;
+    if (lut_uniform && P.root_profile == kRootProfileGen && P.source == kSrcGen) {
+      hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, MONO, ACC, LENS, VIS, NOGATE, false, kRootGenLutUniform>), grid, block, 0, stream, P);
+      return;
+    }
+    // (the linear lens over the full sky keeps the generic form over the continuation pool: that one instantiation's register allocation
+    //  answers the profile with 4 spilled VGPRs and scratch)
+    constexpr bool kTransit = !(LENS == HALO_LENS_LINEAR && VIS == HALO_VISIBLE_FULL);
+    if (kTransit && lut_uniform && P.root_profile == kRootProfileTransit && P.source == kSrcTransit) {
+      hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, MONO, ACC, LENS, kTransit ? VIS : HALO_VISIBLE_UPPER, NOGATE, false, kRootTransitLutUniform>), grid, block, 0, stream, P);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, MONO, ACC, LENS, VIS, NOGATE>), grid, block, 0, stream, P);
+}
 template <int MODE, int GEOM, bool MONO, int ACC, int LENS, bool NOGATE>
 static void launch_vis(const DispatchParams& P, dim3 grid, dim3 block, hipStream_t stream) {
-  if (P.proj.visible_range == HALO_VISIBLE_UPPER) hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, MONO, ACC, LENS, HALO_VISIBLE_UPPER, NOGATE>), grid, block, 0, stream, P);
-  else if (P.proj.visible_range == HALO_VISIBLE_FULL) hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, MONO, ACC, LENS, HALO_VISIBLE_FULL, NOGATE>), grid, block, 0, stream, P);
+  if (P.proj.visible_range == HALO_VISIBLE_UPPER) launch_root<MODE, GEOM, MONO, ACC, LENS, HALO_VISIBLE_UPPER, NOGATE>(P, grid, block, stream);
+  else if (P.proj.visible_range == HALO_VISIBLE_FULL) launch_root<MODE, GEOM, MONO, ACC, LENS, HALO_VISIBLE_FULL, NOGATE>(P, grid, block, stream);
   else hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, MONO, ACC>), grid, block, 0, stream, P);
 }
 template <int MODE, int GEOM, bool MONO, int ACC, bool NOGATE = true>

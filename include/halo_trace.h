@@ -291,6 +291,10 @@ const char* halo_last_error(halo_handle_t h);
  * normals as literals; 0: the table-driven search — same candidates, order and comparisons, A/B knob),
  * "entry_fast" (1 [default]: one-shape dispatches of a full 8-face prism pick the entry face slab by slab, in registers;
  * 0: the generic walk over faces — same uniform, same cumulative order, A/B knob),
+ * "spec_root" (1 [default]: a last-layer logged launch of a discrete-wavelength session over one regular hexagonal prism, whose lens, visible range
+ * and closed gate are already compile-time constants, also takes its root generation as constants when the entry's axis is "latitude by the LUT,
+ * azimuth and roll uniform" — over generated roots or over the continuation pool; same draws, same stream slots, same rays; 0: the run-time
+ * form everywhere, A/B knob; halo_last_root_profile tells which ran),
  * "pool_entry_fast" (1 [default]: logged launches over sampled PRISMS pick the entry face of every full eight-face prism slab by slab, from tables
  * its half-wave rebuilds each pass; 0: the walk over the fan triangles — same uniform, same cumulative order; the same prisms, when their slab normals are the regular prism's, search their next face with literal normals — same candidates and comparisons as the table-driven search; A/B knob),
  * "rehit_strategy" (which of the reference's two next-face strategies the trace follows where they part, src/core/shared/traversal_shared.h:23-29:
@@ -378,6 +382,11 @@ typedef struct HaloRouteInfo {
   uint32_t generic_launches; /* launches that ran an instantiation with none of those specialisations */
 } HaloRouteInfo;
 int halo_last_route(halo_handle_t h, HaloRouteInfo* out);
+/* Root-generation profiles among the kernels that served the session traced last (reset at halo_begin; additive in ABI 6, no struct changed —
+ * HaloRouteInfo keeps its size and its masks their meaning).  Bit 0: a launch ran the last-layer instantiation that has "generated roots, latitude
+ * by the LUT, azimuth and roll uniform" as compile-time constants; bit 1: the same orientation over the continuation pool (a last layer >= 1).
+ * 0: every launch generated its roots with run-time tests on source, latitude path and distribution kinds (see option "spec_root"). */
+int halo_last_root_profile(halo_handle_t h, uint32_t* profile_mask);
 /* Bring the accumulator up to date WITHOUT a host wait: the closing folds of the ended sessions are queued and the backend's stream is made
  * to wait for them, so that work queued on that stream afterwards (a collective on a bound accumulator, a copy) sees the finished image.
  * Needed with option "defer_fold" = 1 (halo_end then leaves the fold of a caller-bound accumulator pending so that the next session's trace

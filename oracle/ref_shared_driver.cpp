@@ -117,6 +117,19 @@ void ref_project_exit_to_pixel(const void* pp, float wx, float wy, float wz, int
     out7[3 + 3 * k] = (k < r.count) ? (r.hits[k].bump_landed ? 1 : 0) : 0;
   }
 }
+// the same over n directions (dirs[3n]); out5[5n] = {count, px0, py0, px1, py1}, absent hits 0
+void ref_project_exit_batch(const void* pp, const float* dirs, uint64_t n, int* out5) {
+  lm_proj::ProjParams p;
+  std::memcpy(&p, pp, sizeof(p));
+  for (uint64_t i = 0; i < n; i++) {
+    lm_proj::ProjResult r = lm_proj::ProjectExitToPixel(p, dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]);
+    out5[5 * i] = r.count;
+    for (int k = 0; k < 2; k++) {
+      out5[5 * i + 1 + 2 * k] = (k < r.count) ? r.hits[k].px : 0;
+      out5[5 * i + 2 + 2 * k] = (k < r.count) ? r.hits[k].py : 0;
+    }
+  }
+}
 void ref_accum_xyz_to_pixel(float* buf, uint32_t pix, float cx, float cy, float cz, float w) { AccumXyzToPixel(buf, pix, cx, cy, cz, w); }
 // color_util.hpp:29 SpectrumToXyz for one sample into xyz[3]
 void ref_spectrum_to_xyz(float wl, float v, float* xyz3) { lumice::SpectrumToXyz(wl, &v, nullptr, xyz3, 1); }

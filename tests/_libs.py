@@ -133,6 +133,27 @@ def oracle(fma=False):
     return L
 
 
+PROJ_BATCH_SO = os.path.join(ROOT, "tests", "cpp", "libproj_batch.so")
+_proj_batch = None
+
+
+def build_proj_batch():
+    """tests/cpp/libproj_batch.so: a loop around a projection function handed in as a pointer (the recipe is __graft_entry__.build_proj_batch)."""
+    import __graft_entry__
+    return __graft_entry__.build_proj_batch()
+
+
+def oracle_project_batch(pp, dirs, out5):
+    """ho_project_exit_to_pixel of the oracle over dirs float32[n, 3] into out5 int32[n, 5] = {count, px0, py0, px1, py1}."""
+    global _proj_batch
+    if _proj_batch is None:
+        _proj_batch = C.CDLL(build_proj_batch())
+        _proj_batch.proj_batch.restype = None
+        _proj_batch.proj_batch.argtypes = [C.c_void_p, C.c_void_p, f32p, C.c_uint64, i32p]
+    fn = C.cast(oracle().ho_project_exit_to_pixel, C.c_void_p)
+    _proj_batch.proj_batch(fn, C.addressof(pp), fptr(dirs), len(dirs), i32ptr(out5))
+
+
 _ref = None
 
 
@@ -170,6 +191,7 @@ def ref():
     L.ref_proj_params_size.restype = C.c_int
     L.ref_project_exit_to_pixel.restype = None
     L.ref_project_exit_to_pixel.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float, i32p]
+    L.ref_project_exit_batch.restype = None; L.ref_project_exit_batch.argtypes = [C.c_void_p, f32p, C.c_uint64, i32p]
     L.ref_spectrum_to_xyz.restype = None; L.ref_spectrum_to_xyz.argtypes = [C.c_float, C.c_float, f32p]
     L.ref_exact_prism.restype = None; L.ref_exact_prism.argtypes = [f32p, i32p]
     L.ref_gamut_clip_xyz.restype = None; L.ref_gamut_clip_xyz.argtypes = [f32p, f32p]

@@ -116,6 +116,7 @@ ROOT_GEN, ROOT_TRANSIT = 1, 2                                                   
 
 
 ACCUM_XYZ, ACCUM_SCALAR, ACCUM_BIN1, ACCUM_BIN2, ACCUM_LOG, ACCUM_LOG_XYZ, ACCUM_NONE = 1, 2, 4, 8, 16, 32, 64   # HaloRouteInfo.accum_mask bits
+ACCUM_FIXED = 128   # ... fixed-point planes (option "deterministic"): beside it only ACCUM_NONE may be set
 
 
 class HaloGeomTables(C.Structure):

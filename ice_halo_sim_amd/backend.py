@@ -64,6 +64,8 @@ def load_library():
         "halo_generate_shapes": (C.c_int, [H, C.POINTER(abi.HaloCrystal), C.c_uint64, C.c_uint32, C.c_int, C.POINTER(abi.HaloGeomTables)]),
         "halo_collect_stats": (C.c_int, [H, C.POINTER(abi.HaloLayerStats)]),
         "halo_take_landed": (C.c_int, [H, C.POINTER(C.c_double)]),
+        "halo_peek_fixed": (C.c_int, [H, C.c_int32, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+        "halo_host_fixed_frac_bits": (C.c_uint32, [C.c_double, C.c_uint64]),
         "halo_flush": (C.c_int, [H]),
         "halo_collect_timing": (C.c_int, [H, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
         "halo_consumer_fold": (C.c_int, [H]),
@@ -103,6 +105,7 @@ EXPORTED_SYMBOLS = [
     "halo_drain_exits", "halo_end", "halo_readback_xyz", "halo_readback_xyz64", "halo_sync", "halo_flush", "halo_collect_timing", "halo_last_sample_counts", "halo_last_route", "halo_last_root_profile", "halo_set_color", "halo_readback_class_lanes", "halo_generate_shapes", "halo_collect_stats", "halo_take_landed", "halo_consumer_fold", "halo_consumer_consume", "halo_consumer_snapshot", "halo_consumer_reset", "halo_consumer_composite", "halo_consumer_load_lanes", "halo_host_parse_composite_mode", "halo_host_prism_geometry",
     "halo_host_pyramid_geometry", "halo_host_shape_scalars", "halo_host_build_lat_lut", "halo_host_build_proj_params", "halo_host_partition",
     "halo_host_refractive_index", "halo_host_reduce_raypath", "halo_host_filter_fast_check", "halo_host_color_fast_mask", "halo_host_illuminant_spd", "halo_host_wl_pool", "halo_reduce_accumulator",
+    "halo_peek_fixed", "halo_host_fixed_frac_bits",
 ]
 
 
@@ -224,6 +227,17 @@ class HipTraceBackend:
         self._check(self._L.halo_take_landed(self._h, C.byref(v)))
         return v.value
 
+    def peek_fixed(self, plane=0):
+        """The pending fixed-point planes of deterministic sessions (option deterministic = 1, after EndSession, lazy_fold = 1, own accumulator)
+        as the integers they are: (sums uint64[H, W] of `plane` in pixel order, frac_bits, landed uint64 scalar, landed_frac_bits).  A plane
+        value is sums * 2**-frac_bits, the landed weight landed * 2**-landed_frac_bits.  Folds, zeroes and takes nothing; BackendError when
+        no fixed-point planes are pending."""
+        w, h = self._render.width, self._render.height
+        sums = np.empty((h, w), np.uint64)
+        f, fl, landed = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self._check(self._L.halo_peek_fixed(self._h, int(plane), sums.ctypes.data_as(C.POINTER(C.c_uint64)), w * h, C.byref(f), C.byref(landed), C.byref(fl)))
+        return sums, f.value, np.uint64(landed.value), fl.value
+
     # --- the seam (trace_backend.hpp:374-632) ---
     def SupportsDeviceXyzAccum(self):
         return True
@@ -336,6 +350,11 @@ class HipTraceBackend:
         self._check(self._L.halo_consumer_composite(self._h, C.byref(spec), lin.ctypes.data_as(C.POINTER(C.c_float)),
                                                     srgb.ctypes.data_as(C.POINTER(C.c_uint8)) if want_srgb else None, C.byref(p99), C.byref(produced)))
         return bool(produced.value), lin, srgb, p99.value
+
+
+def host_fixed_frac_bits(max_w, hits):
+    """halo_host_fixed_frac_bits: the scale F of a 64-bit fixed-point sum of up to `hits` addends of at most `max_w` (no device needed)."""
+    return int(load_library().halo_host_fixed_frac_bits(float(max_w), int(hits)))
 
 
 EXIT_DTYPE = np.dtype([("dir", np.float32, 3), ("weight", np.float32), ("root", np.uint32), ("seq", np.uint16),

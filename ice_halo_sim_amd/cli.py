@@ -5,6 +5,7 @@ doc/performance-testing.md:86-131: Σ root rays over wavelengths / steady second
   python -m ice_halo_sim_amd.cli -f examples/config_example.json --render 4 --benchmark
 """
 import argparse
+import hashlib
 import json
 import os
 import sys
@@ -13,24 +14,28 @@ import time
 import numpy as np
 
 from . import config
-from .backend import BackendUnavailableError, HipTraceBackend
+from .backend import BackendError, BackendUnavailableError, HipTraceBackend
 
 DISPATCH_RAYS = 1 << 26  # rays per TraceLayer call (the reference's GPU dispatch is 2^18, server.cpp:151; we batch far larger)
 DISPATCH_RAYS_MULTI = 1 << 24  # ... for scenes with more than one scattering layer: the continuation pools are sized for roots x max_hits,
                                # and a one-shot CLI run pays for their allocation (64 Mi roots x 8 hits: two pools of 10 GB, 0.5 s of hipMalloc)
 
 
-def run_job(job, render_id=None, seed=42, device=0, max_rays=None, progress=None, canonical_order=False):
+def run_job(job, render_id=None, seed=42, device=0, max_rays=None, progress=None, canonical_order=False, deterministic=False):
     """Trace `job` (config.TraceJob) on one GPU. Returns dict(rays, setup_sec, active_sec, backend, render).  canonical_order: option
-    cont_order = 1 (the continuation pool of every layer but the last in (root, interaction) order)."""
+    cont_order = 1 (the continuation pool of every layer but the last in (root, interaction) order).  deterministic: option deterministic = 1
+    (fixed-point accumulation; with it a multi-layer document takes cont_order = 1 as well) — BackendError when the document needs what that
+    route refuses."""
     if not job.renders:
         raise config.ConfigError("config has no render entry")
     rid = render_id if render_id is not None else sorted(job.renders)[0]  # the seam supports ONE renderer (simulator.cpp:937-944)
     render = job.renders[rid]
     t0 = time.perf_counter()
     be = HipTraceBackend(device=device, seed=seed)
-    if canonical_order:
+    if canonical_order or (deterministic and job.scene.layer_count > 1):
         be.set_option("cont_order", 1)
+    if deterministic:
+        be.set_option("deterministic", 1)
     if job.geom_clock:
         be.set_option("geom_clock", job.geom_clock)
     be.set_filters(job.filters)
@@ -98,14 +103,21 @@ def save_all_renders(job, args):
     rc = 0
     for rid in sorted(job.renders):
         try:
-            res = run_job(job, rid, args.seed, args.device, args.max_rays, canonical_order=args.canonical_order)
+            res = run_job(job, rid, args.seed, args.device, args.max_rays, canonical_order=args.canonical_order, deterministic=args.deterministic)
         except BackendUnavailableError as e:
             print("backend unavailable: %s" % e, file=sys.stderr)
             return 3
+        except BackendError as e:
+            if not args.deterministic:
+                raise
+            print("refused: %s" % e, file=sys.stderr)
+            return 4
         be = res["backend"]
         meta = job.render_meta.get(rid, {})
-        rgb, _, total_intensity = be.Snapshot(intensity_factor=meta.get("intensity_factor", 1.0), ray_color=meta.get("ray_color", (-1.0, -1.0, -1.0)),
-                                              background=meta.get("background", (0.0, 0.0, 0.0)), want_xyz=False)
+        rgb, xyz, total_intensity = be.Snapshot(intensity_factor=meta.get("intensity_factor", 1.0), ray_color=meta.get("ray_color", (-1.0, -1.0, -1.0)),
+                                                background=meta.get("background", (0.0, 0.0, 0.0)), want_xyz=args.deterministic)
+        if args.deterministic:
+            print("xyz sha256 (render %d): %s" % (rid, hashlib.sha256(xyz.tobytes()).hexdigest()))
         write_image(os.path.join(args.output_dir, "img_%02d.%s" % (rid, args.format)), rgb, args.format, args.quality)
         if job.color_classes:
             ok, _, srgb, p99 = be.CompositeColorClasses(job.color_meta, job.color_mode, 2.0 ** args.display_ev, meta.get("intensity_factor", 1.0))
@@ -138,6 +150,11 @@ def main(argv=None):
                     "order, so a fixed --seed traces the same second- and third-layer rays on every run (option cont_order = 1; costs a sort of the "
                     "continuation pool per layer).  It does not make the image bit-identical: pixel sums are fp32 atomics in whatever order the GPU "
                     "adds them; a multi-GPU run is canonical per rank")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="bit-reproducible image: pixel sums and the landed weight are 64-bit fixed-point integers from the first add to the fold "
+                    "(option deterministic = 1; multi-scattering configs take cont_order = 1 with it), so a fixed --seed gives the same XYZ bytes on "
+                    "every run, whose sha256 is printed.  A config that needs what the route does not cover (raypath_color, a filter outside the fast "
+                    "form) is refused with the reason and a non-zero exit; a multi-GPU run is reproducible per rank")
     ap.add_argument("--display-ev", type=float, default=0.0, help="display-time EV of the composite (display_exposure_scale = 2^EV)")
     args = ap.parse_args(argv)
     if not 1 <= args.quality <= 100:
@@ -154,18 +171,25 @@ def main(argv=None):
         if args.output_dir is not None:
             print("[warning] -o / --output-dir is ignored with --render / --benchmark (nothing is saved)", file=sys.stderr)
         wall0 = time.perf_counter()
-        res = run_job(job, args.render, args.seed, args.device, args.max_rays, canonical_order=args.canonical_order)
+        res = run_job(job, args.render, args.seed, args.device, args.max_rays, canonical_order=args.canonical_order, deterministic=args.deterministic)
     except BackendUnavailableError as e:
         print("backend unavailable: %s" % e, file=sys.stderr)
         return 3
     except config.ConfigError as e:
         print("config error: %s" % e, file=sys.stderr)
         return 2
+    except BackendError as e:
+        if not args.deterministic:
+            raise
+        print("refused: %s" % e, file=sys.stderr)
+        return 4
     be = res["backend"]
     meta = job.render_meta.get(res["render_id"], {})
     rgb, xyz, total_intensity = be.Snapshot(intensity_factor=meta.get("intensity_factor", 1.0), ray_color=meta.get("ray_color", (-1.0, -1.0, -1.0)),
                                             background=meta.get("background", (0.0, 0.0, 0.0)))
     wall = time.perf_counter() - wall0
+    if args.deterministic:
+        print("xyz sha256: %s" % hashlib.sha256(xyz.tobytes()).hexdigest())
     if args.out_rgb:
         write_ppm(args.out_rgb, rgb)
     if args.out_xyz:

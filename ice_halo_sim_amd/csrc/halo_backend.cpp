@@ -243,6 +243,17 @@ struct HaloBackend {
                                   // SURVEY's stated ground truth): every launch then takes the generic kernels, which carry the re-hit test
   int pool_entry_fast = 1;        // option (A/B knob): prism pools under the hit log pick a sampled full prism's entry face slab by slab; 0 = the walk over its fan triangles
   int gen_ahead = 0;              // option (experiment knob): 1 queues the generator of a chip-filling launch on trace stream 1, beside the previous launch's kernels
+  // Deterministic sessions (option "deterministic"): every accumulating launch runs a kAccFixed kernel — 64-bit fixed-point sums from the first add
+  // to the fold, so the plane sums depend on the set of rays alone.  The planes are a buffer of their own, [plane][slot], one copy,
+  // all-zero between folds like the float planes; F and the budget belong to the PENDING plane set (they may span sessions under lazy_fold).
+  int deterministic = 0;                     // the option (not inside a session)
+  bool det_session = false;                  // the open / last session is a deterministic one
+  bool fix_planes = false;                   // the pending planes (mono_dirty) are the fixed-point ones
+  DevBuf<unsigned long long> fix;
+  uint32_t fix_frac = 32, fix_frac_landed = 32;   // F of the pending plane set; F_L of the landed integer (tally slot kSumFixLanded)
+  uint64_t fix_hits = 0;                     // rays traced into the pending plane set since its last fold (<= kFixBudgetHits)
+  unsigned long long fix_landed_seen = 0;    // the cumulative landed integer already handed on (like tally_seen)
+  double landed_carry = 0.0;                 // landed integers converted when F_L had to change before anybody took them
   DevBuf<float> cont[2];       // SoA continuation pools, 5 planes
   uint32_t cont_stride[2] = {0, 0};
   uint32_t cont_region[2] = {0, 0};          // slots per shard region
@@ -435,9 +446,17 @@ void harvest_slot(HaloBackend* b, int k) {
   b->ring_busy[k] = false;
 }
 // Snapshot of the cumulative tallies (one 1 KB D2H copy + a stream sync): the sum over the lines, per tally.
-int read_tally(HaloBackend* b, double out[kSumNum]) {
+int read_tally(HaloBackend* b, double out[kSumNum], unsigned long long* fix_landed = nullptr) {
   HIPCHK(b, hipMemcpyAsync(b->tally_host, b->tally.ptr, kTallyLines * kTallyStride * sizeof(double), hipMemcpyDeviceToHost, b->stream));
   HIPCHK(b, hipStreamSynchronize(b->stream));
+  if (fix_landed) {   // the lines' integer slot (deterministic sessions), summed modulo 2^64
+    *fix_landed = 0ull;
+    for (uint32_t l = 0; l < kTallyLines; l++) {
+      unsigned long long v;
+      std::memcpy(&v, &b->tally_host[l * kTallyStride + kSumFixLanded], sizeof(v));
+      *fix_landed += v;
+    }
+  }
   for (int t = 0; t < kSumNum; t++) {
     double v = 0.0;
     for (uint32_t l = 0; l < kTallyLines; l++) v += b->tally_host[l * kTallyStride + static_cast<uint32_t>(t)];
@@ -461,10 +480,14 @@ int pull_tally(HaloBackend* b) {
 // The landed weight since the last taker (readback, take_landed, consumer fold).
 int take_landed_delta(HaloBackend* b, double* landed) {
   double now[kSumNum];
-  int rc = read_tally(b, now);
+  unsigned long long fix_now = 0ull;
+  int rc = read_tally(b, now, &fix_now);
   if (rc != HALO_OK) return rc;
-  *landed = now[kSumLanded] - b->tally_seen[kSumLanded];
+  // (deterministic sessions land as an integer in units of 2^-F_L: exact in the integer, one conversion here)
+  *landed = now[kSumLanded] - b->tally_seen[kSumLanded] + std::ldexp(static_cast<double>(fix_now - b->fix_landed_seen), -static_cast<int>(b->fix_frac_landed)) + b->landed_carry;
   b->tally_seen[kSumLanded] = now[kSumLanded];
+  b->fix_landed_seen = fix_now;
+  b->landed_carry = 0.0;
   return HALO_OK;
 }
 void harvest_all(HaloBackend* b) {
@@ -554,7 +577,7 @@ int halo_destroy(halo_handle_t b) {
     if (b->cs[k]) (void)hipStreamSynchronize(b->cs[k]);
   release_all(b->acc_own, b->tally, b->mono, b->ovf, b->ovf_flag, b->filter_dev, b->cons_sum, b->cons_comp, b->cons_xyz_out, b->cons_stage, b->cons_rgb, b->comp_rgb,
               b->lanes_stage, b->comp_hist, b->counters, b->ring_dev, b->tcache_dev, b->shapes_s[0], b->shapes_s[1], b->cont_cnt, b->cont_mask, b->cont_err, b->cont_base,
-              b->cont_tiles, b->lanes, b->cont[0], b->cont[1], b->exits, b->host_f, b->host_u);
+              b->cont_tiles, b->lanes, b->fix, b->cont[0], b->cont[1], b->exits, b->host_f, b->host_u);
   for (int k = 0; k < 2; k++) release_all(b->bin_list_s[k], b->bin_cnt_s[k], b->bin_list2_s[k], b->bin_cnt2_s[k]);
   if (b->ring_host) (void)hipHostFree(b->ring_host);
   if (b->tally_host) (void)hipHostFree(b->tally_host);
@@ -632,6 +655,11 @@ int halo_set_option(halo_handle_t b, const char* key, int64_t v) {
     if (b->in_session) return fail(b, HALO_FATAL, "cont_order cannot change inside a session");
     if (v != 0 && v != 1) return fail(b, HALO_FATAL, "cont_order must be 0 (append order) or 1 (canonical order)");
     b->cont_order = static_cast<int>(v);
+  }
+  else if (k == "deterministic") {
+    if (b->in_session) return fail(b, HALO_FATAL, "deterministic cannot change inside a session");
+    if (v != 0 && v != 1) return fail(b, HALO_FATAL, "deterministic must be 0 (float accumulation) or 1 (fixed-point accumulation)");
+    b->deterministic = static_cast<int>(v);
   }
   else if (k == "log_tiles_log2") b->log_tiles_log2 = static_cast<int>(std::min<int64_t>(std::max<int64_t>(v, 0), 8));
   else if (k == "alt_log2") b->alt_log2 = static_cast<int>(std::min<int64_t>(std::max<int64_t>(v, 10), 28));
@@ -733,6 +761,28 @@ int halo_begin(halo_handle_t b, const HaloScene* scene, const HaloRender* render
       if (kind != HALO_CRYSTAL_PRISM && kind != HALO_CRYSTAL_PYRAMID) return fail(b, HALO_FATAL, "unknown crystal kind");
     }
   }
+  const bool det = b->deterministic != 0;
+  if (det) {
+    // A deterministic session runs the kAccFixed kernels or nothing: what they do not cover is refused here, by name, before any state changes —
+    // never run on a float route in silence.
+    if (scene->layer_count > 1 && !b->cont_order)
+      return fail(b, HALO_FATAL, "deterministic = 1: a multi-layer session needs cont_order = 1 (the continuation pool's append order decides which rays the next layer traces)");
+    if (!b->color_classes.empty() || !b->color_sets.empty()) return fail(b, HALO_FATAL, "deterministic = 1: raypath-colour tables are set (the class lanes are fp64 atomics)");
+    if (b->capture) return fail(b, HALO_FATAL, "deterministic = 1: capture_exits = 1 is not supported (the capture kernels have no fixed-point route)");
+    if (b->rehit_strategy == 0) return fail(b, HALO_FATAL, "deterministic = 1: rehit_strategy = 0 is not supported (the legacy strategy lives in the generic kernels)");
+    for (int l = 0; l < scene->layer_count; l++)
+      for (int e = 0; e < scene->layers[l].entry_count; e++) {
+        const HaloEntry& E = scene->layers[l].entries[e];
+        if (E.filter_id <= 0) continue;
+        const FilterDev fd = host::BuildFilter(b->filters[static_cast<size_t>(E.filter_id - 1)], E.axis);
+        if (!(fd.is_complex || fd.terms[0].type != HALO_FILTER_NONE || fd.action != 0)) continue;   // a filter that passes everything: the plain kernels
+        std::unique_ptr<FastTables> ft(new FastTables());
+        std::memset(ft.get(), 0, sizeof(FastTables));
+        if (!b->filter_fast || scene->max_hits > 16 ||
+            !host::BuildFastTables(&b->filters[static_cast<size_t>(E.filter_id - 1)], nullptr, E.axis, static_cast<uint32_t>(E.crystal_config_id), *ft))
+          return fail(b, HALO_FATAL, "deterministic = 1: a filter of this scene needs the generic filter kernels (filter_fast = 0, max_hits > 16, or tables that do not fit the fast form)");
+      }
+  }
   HIPCHK(b, hipSetDevice(b->device));
   if (std::memcmp(&b->tcache_scene, scene, sizeof(HaloScene)) != 0 || std::memcmp(&b->tcache_wl, wl, sizeof(HaloWl)) != 0) {
     drop_table_cache(b);   // another scene or wavelength: the cached tables are not this session's
@@ -769,8 +819,8 @@ int halo_begin(halo_handle_t b, const HaloScene* scene, const HaloRender* render
   // (one plane per pool entry + binned lists; privatised copies for the direct atomics).
   const bool log_xyz_fits = s_log2 <= 11u, log_mono_fits = s_log2 <= 12u;
   // (the layout is worked out in locals first: whether the planes of earlier sessions must be folded before this one starts depends on it)
-  const bool xyz_log_n = b->mono_enabled && !discrete && b->lambda_planes < 0 && b->hit_log != 0 && ray_num >= (2ull << 20) && npix > HALO_XYZ_LOG_MIN_PIX && log_xyz_fits;
-  const bool mono_by_wl_n = b->mono_enabled && !discrete && !xyz_log_n && npix <= (1u << 23) && (b->lambda_planes < 0 ? ray_num >= (8ull << 20) : b->lambda_planes != 0);
+  const bool xyz_log_n = !det && b->mono_enabled && !discrete && b->lambda_planes < 0 && b->hit_log != 0 && ray_num >= (2ull << 20) && npix > HALO_XYZ_LOG_MIN_PIX && log_xyz_fits;
+  const bool mono_by_wl_n = !det && b->mono_enabled && !discrete && !xyz_log_n && npix <= (1u << 23) && (b->lambda_planes < 0 ? ray_num >= (8ull << 20) : b->lambda_planes != 0);
   const bool mono_session_n = b->mono_enabled && (discrete || mono_by_wl_n);
   const uint32_t plane_cnt_n = mono_by_wl_n ? static_cast<uint32_t>(pool.size()) : (mono_session_n ? 1u : 3u);
   // privatised copies spread the direct atomics of hot pixels; per-entry planes spread them already, and a session whose
@@ -781,9 +831,10 @@ int halo_begin(halo_handle_t b, const HaloScene* scene, const HaloRender* render
   bool one_entry_layers = true;
   for (int l = 0; l < scene->layer_count; l++) one_entry_layers = one_entry_layers && scene->layers[l].entry_count == 1;
   const bool fast_scene = b->rehit_strategy != 0 && (plain_scene || (!b->capture && b->filter_fast && scene->max_hits <= 16));   // (a dispatch whose tables do not fit the fast form still adds directly: copy 0 only, correct, slower)
-  const bool all_logged = fast_scene && one_entry_layers && b->hit_log < 0 && b->aggregate == 1 && ray_num >= (discrete ? log_min_rays(render->visible) : (2ull << 20)) &&
+  const bool all_logged = !det && fast_scene && one_entry_layers && b->hit_log < 0 && b->aggregate == 1 && ray_num >= (discrete ? log_min_rays(render->visible) : (2ull << 20)) &&
                           (discrete ? log_mono_fits : xyz_log_n) && (mono_session_n || xyz_log_n);
-  const uint32_t plane_copies_n = (mono_by_wl_n || all_logged) ? 1u : static_cast<uint32_t>(b->mono_copies);
+  // (a deterministic session: one scalar plane or X, Y, Z, one copy — integer atomics onto HaloBackend::fix; hit_log, bin, lambda_planes and mono_copies do not apply)
+  const uint32_t plane_copies_n = (mono_by_wl_n || all_logged || det) ? 1u : static_cast<uint32_t>(b->mono_copies);
   const bool two_sets_n = all_logged && discrete && mono_session_n && !mono_by_wl_n && b->overlap != 0;   // (see HaloBackend::mono_two)
   std::vector<std::array<float, 3>> coef_n;
   for (uint32_t m = 0; m < plane_cnt_n; m++) {
@@ -798,7 +849,7 @@ int halo_begin(halo_handle_t b, const HaloScene* scene, const HaloRender* render
     // now, with the members still describing the old planes.
     const bool same_planes = b->mono_dirty && b->lazy_fold && b->acc != nullptr && b->acc == b->acc_own.ptr && b->acc_w == render->width &&
                              b->acc_h == render->height && b->mono_s_log2 == s_log2 && b->plane_cnt == plane_cnt_n && b->plane_copies == plane_copies_n &&
-                             b->mono_two == two_sets_n && b->plane_coef == coef_n;
+                             b->mono_two == two_sets_n && b->plane_coef == coef_n && b->fix_planes == det;
     if (!same_planes) {
       // (queued on the auxiliary stream; the HOST does not wait.  This session's launches whose trace kernel adds to the planes, and its logged
       // launches that fill the chip, are queued behind it (next_trace_stream); a SMALL logged launch starts under it and only its passes wait — for
@@ -821,7 +872,17 @@ int halo_begin(halo_handle_t b, const HaloScene* scene, const HaloRender* render
   b->plane_cnt = plane_cnt_n;
   b->plane_copies = plane_copies_n;
   b->plane_coef = coef_n;
-  {
+  b->det_session = det;
+  if (det) {   // the fixed-point planes, made here with the session's other buffers and all-zero between folds
+    const size_t need = (static_cast<size_t>(kMonoRows) << s_log2) * b->plane_cnt;
+    b->mono_two = false;
+    b->mono_set = 0;
+    if (b->fix.cap < need) {
+      if (int rc = reserve_idle(b, b->fix, need)) return rc;
+      HIPCHK(b, hipMemsetAsync(b->fix.ptr, 0, b->fix.cap * sizeof(unsigned long long), b->stream));
+    }
+    b->mono_s_log2 = s_log2;
+  } else {
     const size_t one = (static_cast<size_t>(kMonoRows) << s_log2) * b->plane_copies * b->plane_cnt;
     b->mono_two = two_sets_n;
     b->mono_half = one;
@@ -876,12 +937,19 @@ int halo_begin(halo_handle_t b, const HaloScene* scene, const HaloRender* render
 
 // Fractional bits of the per-tile fixed-point sums for a launch of `m` rays whose weights are at most `max_w`: the largest F <= 32 with
 // 4 * max_w * m * 2^F < 2^62 (see halo_kernels.hip FixQ for the factor 4).
+// The deterministic route applies the same bound to the rays a plane set may take before it is folded (kFixBudgetHits) and to the landed integer
+// (kFixLandedHits): halo_host_fixed_frac_bits exports the rule.
 static uint32_t fix_frac_bits(double max_w, uint64_t m) {
   const double bound = 4.0 * std::max(max_w, 1e-30) * static_cast<double>(std::max<uint64_t>(m, 1));
   int e = 0;
   (void)std::frexp(bound, &e);   // bound < 2^e
   return static_cast<uint32_t>(std::min(32, std::max(0, 62 - e)));
 }
+
+// Rays one unfolded fixed-point plane set takes (F = 29 for weights up to 1: a hit is quantised to 1.9e-9): a constant, because F must not depend
+// on how a run is cut into launches or sessions.  The landed integer's scale allows for the 2^32 rays of the largest layer.
+constexpr uint64_t kFixBudgetHits = 1ull << 30, kFixLandedHits = 1ull << 32;
+uint32_t halo_host_fixed_frac_bits(double max_w, uint64_t hits) { return fix_frac_bits(max_w, hits); }
 
 // The twin half a session of the current layout uses: valid only when the buffer holds two halves of this layout.
 static double* twin_of(HaloBackend* b, int set) {
@@ -897,6 +965,17 @@ static int fold_queue(HaloBackend* b) {
   if (int rc = fork_aux(b)) return rc;
   hipStream_t ps = post_stream(b);
   const uint32_t npix = static_cast<uint32_t>(b->acc_w) * static_cast<uint32_t>(b->acc_h);
+  if (b->fix_planes) {   // a deterministic session's planes: integers in, float32(double(S) * 2^-F) out, then the same chain (no copies, no twin)
+    FoldCoef coef{};
+    for (uint32_t m = 0; m < b->plane_cnt; m++)
+      for (int a = 0; a < 3; a++) coef.c[m][a] = b->plane_coef[m][static_cast<size_t>(a)];
+    hipError_t e = launch_fold_fixed(b->acc, b->fix.ptr, npix, b->mono_s_log2, b->plane_cnt, coef, b->fix_frac, ps);
+    if (e != hipSuccess) return hip_fail(b, e, "halo_fold_fixed_kernel launch");
+    b->fix_hits = 0;
+    b->fix_planes = false;
+    b->mono_dirty = false;
+    return HALO_OK;
+  }
   const size_t plane = (static_cast<size_t>(kMonoRows) << b->mono_s_log2) * b->plane_copies;
   const size_t twin_plane = static_cast<size_t>(kMonoRows) << b->mono_s_log2;
   double* twin = twin_of(b, b->twin_set);
@@ -965,6 +1044,7 @@ struct LaunchPlan {
   int geom = 0, blocks = 0;             // geom: 0 = one shape per dispatch, 1 = pool of ShapeDev records, 2 = pool of ShapePrism records (device-generated prisms)
   uint32_t shape_cnt = 1;
   bool use_bin = false, two_level = false, use_log = false, use_log_xyz = false, canon = false, no_land = false;
+  bool fixed = false;                   // a deterministic session's launch: the kAccFixed kernels (or, where every exit continues, kAccNone)
   uint32_t fan_log2 = 0, lists1 = 0, bin_tiles = 0, log_t_log2 = 0, log_planes = 1, log_tiles = 0;
   uint64_t cap1 = 0, cap2 = 0;          // records per region / coarse list and per tile list, as REQUESTED: reserve_log_buffers clamps the log's against free memory
   // (Round 6: a LOGGED trace kernel writes records, its region counts and the twin's other half — nothing the closing fold of the session
@@ -991,6 +1071,7 @@ struct EntryTables {
 // launch plan: chunking bounds the host-built shape pool for stochastic geometry and keeps n_rays < 2^32
 uint64_t chunk_of(const HaloBackend& b, uint64_t left, const HaloCrystal& crystal, bool host_crystal) {
   uint64_t m = std::min<uint64_t>(left, b.chunk);
+  if (b.det_session) m = std::min<uint64_t>(m, kFixBudgetHits);   // a launch fits the budget of one fixed-point plane set
   // stochastic geometry: one pool record per geom_clock rays.  Device-generated prisms are 1360 B records (2.9 GB per
   // 64 Mi rays), other device-generated shapes 4.1 KB (2 GB per 16 Mi rays); host-built pools (pageable staging + H2D)
   // stay at 4 Mi rays
@@ -1061,7 +1142,8 @@ void plan_route(const HaloBackend& b, const LayerCtx& c, bool fast_mode, LaunchP
                              (static_cast<uint64_t>(b.plane_cnt) << (s_log2 + 10u)) <= (1ull << 31) && b.hit_log != 0 && b.bin <= 0;
   // (a layer before the last under canonical continuation order takes direct accumulation: only those kernels have CANON twins)
   p.canon = b.cont_order && !c.final_layer;
-  p.use_bin = !p.canon && b.mono_session && b.aggregate == 1 && !b.capture && bin_shape_ok && bin_slots <= (1ull << 31) &&
+  p.fixed = b.det_session;   // neither lists nor log: every accumulating launch of a deterministic session adds integers
+  p.use_bin = !p.fixed && !p.canon && b.mono_session && b.aggregate == 1 && !b.capture && bin_shape_ok && bin_slots <= (1ull << 31) &&
               // own choice: only where the hit log cannot go (one plane per pool entry on a larger image) — the log beats the binned route
               // on every launch measured (tools/bin_vs_log_probe.py: dual fisheye 50 M rays 5.13 -> 4.42 ms)
               (b.bin < 0 ? (b.mono_by_wl && !log_planes_ok && bin_geom_ok && full_sky && m >= (2ull << 20)) : b.bin != 0);
@@ -1080,7 +1162,7 @@ void plan_route(const HaloBackend& b, const LayerCtx& c, bool fast_mode, LaunchP
   p.log_planes = log_planes_ok ? b.plane_cnt : 1u;
   p.log_tiles = p.log_planes << p.log_t_log2;   // lists the split pass feeds
   const bool log_layout_ok = b.xyz_log ? (s_log2 <= 11u) : (b.mono_session && (log_planes_ok || (!b.mono_by_wl && s_log2 <= 12u)));
-  p.use_log = !p.canon && !p.use_bin && log_layout_ok && b.aggregate == 1 && fast_mode &&
+  p.use_log = !p.fixed && !p.canon && !p.use_bin && log_layout_ok && b.aggregate == 1 && fast_mode &&
               (L.prob < 1.0f || c.final_layer) &&   // a layer whose every exit continues puts nothing on the image
               (b.hit_log < 0 ? m >= ((b.mono_session && !b.mono_by_wl) ? log_min_rays(b.render.visible) : (2ull << 20)) : b.hit_log != 0);
   p.use_log_xyz = p.use_log && b.xyz_log;
@@ -1336,6 +1418,7 @@ DispatchParams fill_params(HaloBackend* b, const LayerCtx& c, int ci) {
   P.lanes = b->lanes.ptr;
   P.lane_stride = static_cast<uint32_t>(b->acc_w) * static_cast<uint32_t>(b->acc_h);
   P.root_profile = b->spec_root ? root_profile_of(P) : kRootProfileNone;
+  P.fix = b->det_session ? b->fix.ptr : nullptr;   // (fix_frac, fix_frac_landed: trace_launch, once fix_prepare has settled them)
   return P;
 }
 // The route branch: reserves and resets the buffers of the launch's accumulation route (log set `ls`) and writes the route's fields of P — their
@@ -1386,7 +1469,7 @@ void record_route(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, 
   const bool ran_hex = launch_geom == 3 && fast_mode && (P.bin_list == nullptr || P.bin_log != 0u || P.no_land != 0u);
   const bool ran_none = P.no_land != 0u && p.geom == 0;
   b->route.geom_mask |= 1u << (launch_geom == 3 && !ran_hex ? 0 : launch_geom);
-  b->route.accum_mask |= ran_none ? 64u : p.use_log ? (p.use_log_xyz ? 32u : 16u) : (p.use_bin ? (p.two_level ? 8u : 4u) : (b->mono_session ? 2u : 1u));
+  b->route.accum_mask |= ran_none ? 64u : p.fixed ? 128u : p.use_log ? (p.use_log_xyz ? 32u : 16u) : (p.use_bin ? (p.two_level ? 8u : 4u) : (b->mono_session ? 2u : 1u));
   // specialisations (plain kernels only; launch_lens / launch_vis / launch_mono): bit 0 last-layer kernel (no continuation code), 1 lens as a
   // constant, 2 visible range as a constant, 3 closed gate as a constant
   const bool one = p.geom == 0, lens_known = P.proj.proj_type == HALO_LENS_LINEAR || P.proj.proj_type == HALO_LENS_FISHEYE_EQUAL_AREA ||
@@ -1503,12 +1586,36 @@ int queue_launch(HaloBackend* b, const LaunchPlan& p, const HaloEntry& E, EntryT
     T.ce->read_use[T.ce->cur] = b->ring_use[k];
   }
   b->mono_dirty = true;
+  b->fix_planes = b->det_session;
   record_route(b, p, P, T.mode, T.fast_mode, launch_geom);
   if (le != hipSuccess) return hip_fail(b, le, "halo_trace_kernel launch");
   if (!p.deterministic) HIPCHK(b, b->shapes_free[S.shape_set].mark(ts));
   if (int rc = queue_passes(b, p, P, S, ts, ts_i, before_sums)) return rc;
   b->tally_unread = true;
   b->ring_busy[k] = true;
+  return HALO_OK;
+}
+// Before a deterministic launch of `m` rays: the scales it adds with.  All adds into one unfolded plane set share one F, so the pending planes are
+// folded first when F has to change (a session of other weights under lazy_fold, host rays heavier than the pool's) or the set's budget is
+// spent; the landed integer is taken to the host before ITS scale changes.
+int fix_prepare(HaloBackend* b, uint64_t m) {
+  const uint32_t f = fix_frac_bits(b->sess_max_w, kFixBudgetHits), fl = fix_frac_bits(b->sess_max_w, kFixLandedHits);
+  if (b->mono_dirty && b->fix_planes && (f != b->fix_frac || b->fix_hits + m > kFixBudgetHits))
+    if (int rc = fold_queue(b)) return rc;   // (on the auxiliary stream; the launch is queued behind it: next_trace_stream)
+  if (!(b->mono_dirty && b->fix_planes)) {
+    b->fix_frac = f;
+    b->fix_hits = 0;
+  }
+  b->fix_hits += m;
+  if (fl != b->fix_frac_landed) {
+    if (int rc = join_aux(b)) return rc;
+    double now[kSumNum];
+    unsigned long long fix_now = 0ull;
+    if (int rc = read_tally(b, now, &fix_now)) return rc;
+    b->landed_carry += std::ldexp(static_cast<double>(fix_now - b->fix_landed_seen), -static_cast<int>(b->fix_frac_landed));
+    b->fix_landed_seen = fix_now;
+    b->fix_frac_landed = fl;
+  }
   return HALO_OK;
 }
 // One planned launch from end to end: shape pool, ring slot, tables, the per-launch fields of P, route buffers, then queue_launch.
@@ -1574,6 +1681,12 @@ int trace_launch(HaloBackend* b, const LayerCtx& c, LaunchPlan& p, EntryTables& 
     P.host_tf = b->host_u.ptr + p.off;
   }
   plan_route(*b, c, T.fast_mode, p);
+  if (p.fixed) {
+    if (T.mode != 0 && T.mode != 1) return fail(b, HALO_FATAL, "deterministic = 1: this entry needs kernels without a fixed-point route");   // (halo_begin refuses these scenes: never a float route)
+    if (int rc = fix_prepare(b, m)) return rc;
+    P.fix_frac = b->fix_frac;
+    P.fix_frac_landed = b->fix_frac_landed;
+  }
   S.ls = (b->overlap && p.alternate) ? b->log_set : 0;   // the buffer set of this launch
   if (int rc = bind_route(b, p, S.ls, P)) return rc;
   if (int rc = queue_launch(b, p, E, T, P, S)) return rc;
@@ -2001,6 +2114,32 @@ int halo_take_landed(halo_handle_t b, double* landed) {
     if (rc != HALO_OK) return rc;
   }
   return take_landed_delta(b, landed);
+}
+
+int halo_peek_fixed(halo_handle_t b, int32_t plane, uint64_t* sums, uint64_t n_pix, uint32_t* frac_bits, uint64_t* landed, uint32_t* landed_frac_bits) {
+  if (!b) return HALO_FATAL;
+  if (b->in_session) return fail(b, HALO_FATAL, "halo_peek_fixed inside a session");
+  if (!b->mono_dirty || !b->fix_planes || b->acc != b->acc_own.ptr)
+    return fail(b, HALO_FATAL, "halo_peek_fixed: no fixed-point planes are pending (needs deterministic = 1, lazy_fold = 1 and the backend's own accumulator, after halo_end and before any reader)");
+  if (plane < 0 || static_cast<uint32_t>(plane) >= b->plane_cnt) return fail(b, HALO_FATAL, "halo_peek_fixed: plane outside the session's planes");
+  if (sums && n_pix != static_cast<uint64_t>(b->acc_w) * static_cast<uint64_t>(b->acc_h)) return fail(b, HALO_FATAL, "halo_peek_fixed: n_pix is not the session's width * height");
+  HIPCHK(b, hipSetDevice(b->device));
+  if (int rc = sync_all(b)) return rc;
+  if (sums) {
+    const size_t slots = static_cast<size_t>(kMonoRows) << b->mono_s_log2;
+    std::vector<unsigned long long> host(slots);
+    HIPCHK(b, hipMemcpy(host.data(), b->fix.ptr + static_cast<size_t>(plane) * slots, slots * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (uint64_t pix = 0; pix < n_pix; pix++) sums[pix] = host[MonoSlot(static_cast<uint32_t>(pix), b->mono_s_log2)];   // pixel order: the slot hash undone
+  }
+  if (frac_bits) *frac_bits = b->fix_frac;
+  if (landed) {   // what landed since the last taker, as the integer it is (nothing is taken)
+    double now[kSumNum];
+    unsigned long long fix_now = 0ull;
+    if (int rc = read_tally(b, now, &fix_now)) return rc;
+    *landed = fix_now - b->fix_landed_seen;
+  }
+  if (landed_frac_bits) *landed_frac_bits = b->fix_frac_landed;
+  return HALO_OK;
 }
 
 int halo_readback_xyz64(halo_handle_t b, float* xyz, int width, int height, double* landed) {

@@ -332,6 +332,11 @@ struct DispatchParams {
   double* lanes;               // class_cnt x lane_stride Y lanes, fp64: a hot pixel's lane passes 1e7 and fp32 atomics round a near-constant addend the same way every time (3e-3 low, round 3)
   uint32_t lane_stride;        // W*H
   uint32_t root_profile;       // host-side only (no kernel reads it): kRootProfile* — the root-generation profile the launcher may instantiate for this dispatch
+  // --- deterministic sessions (option "deterministic": the kAccFixed kernels, integer from the first add to the fold) --------------
+  unsigned long long* fix;     // fixed-point planes [plane][slot], one copy, pixel p at MonoSlot(p) (nullptr = not a deterministic launch): every hit
+                               // adds floor(double(v) * 2^fix_frac + 0.5) with an integer atomic, halo_fold_fixed_kernel reads and zeroes them
+  uint32_t fix_frac;           // F of the pending plane set (halo_host_fixed_frac_bits): the same for every add between two folds
+  uint32_t fix_frac_landed;    // F_L of the landed-weight integer (tally slot kSumFixLanded of each line)
 };
 
 // Pixel → slot map of the mono plane.  The plane is kMonoRows rows of S = 2^s_log2 slots; pixel p sits in row p % kMonoRows
@@ -382,6 +387,8 @@ constexpr uint32_t kRootProfileNone = 0u, kRootProfileGen = 1u, kRootProfileTran
 enum { kCntCont = 0, kCntExit = 1, kCntNum = 4 };
 enum { kSumLanded = 0, kSumExitW = 1, kSumExitN = 2, kSumPixN = 3, kSumNum = 4 };
 constexpr uint32_t kTallyLines = 16u, kTallyStride = 8u;   // 64-byte lines: same-line fp64 atomics serialise memory-side (~12 ns each)
+constexpr uint32_t kSumFixLanded = 4u;   // slot of each tally line that is a 64-bit INTEGER: the landed weight of deterministic sessions, in units of
+                                         // 2^-fix_frac_landed, cumulative modulo 2^64 like the doubles beside it (the host reads differences)
 
 }  // namespace halo
 

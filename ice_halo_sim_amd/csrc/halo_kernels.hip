@@ -27,15 +27,7 @@ __device__ __forceinline__ uint4 load_list_u4(const uint4* p) {
   return make_uint4(__builtin_nontemporal_load(q), __builtin_nontemporal_load(q + 1), __builtin_nontemporal_load(q + 2), __builtin_nontemporal_load(q + 3));
 }
 
-struct FixQ {
-  double to_fix, from_fix;
-  __device__ __forceinline__ explicit FixQ(uint32_t frac_bits)
-      : to_fix(__hiloint2double(static_cast<int>((1023u + frac_bits) << 20), 0)), from_fix(__hiloint2double(static_cast<int>((1023u - frac_bits) << 20), 0)) {}
-  __device__ __forceinline__ unsigned long long fix(float v) const {   // round to nearest; v <= the launch's bound by construction
-    return static_cast<unsigned long long>(static_cast<long long>(fma(static_cast<double>(fmaxf(v, 0.0f)), to_fix, 0.5)));
-  }
-  __device__ __forceinline__ float unfix(unsigned long long a) const { return static_cast<float>(static_cast<double>(a) * from_fix); }
-};
+// (struct FixQ: halo_trace.inl, beside the deterministic route's cache, which sums by the same rule)
 
 // kBinSplit workgroups per image tile: each sums its share of the tile's hit list in a 64 KB LDS tile (8 independent
 // loads in flight per thread — the loop is load-latency-bound otherwise) and adds the non-zero slots to the plane.
@@ -524,6 +516,24 @@ hipError_t launch_bin_two_level(float* plane, const HitRec* list1, uint32_t cap1
 // thread requests kFoldBatch plane values before it looks at any of them or zeroes anything.
 constexpr uint32_t kFoldTile = 64u;
 constexpr uint32_t kFoldBatch = 8u;
+// The second half of a fold: the workgroup's R-row x 64-column tile of X, Y, Z sums, walked along the rows — consecutive rows are consecutive
+// pixels — and added to the image.
+template <uint32_t R>
+__device__ __forceinline__ void fold_store_tile(const float (&tile)[3][R][kFoldTile + 1], float* __restrict__ xyz, uint32_t n_pix, uint32_t s_log2, uint32_t row0, uint32_t col0) {
+  const uint32_t s_mask = (1u << s_log2) - 1u;
+  const uint32_t wr = threadIdx.x % R;   // row of the tile = consecutive pixels
+  for (uint32_t c = threadIdx.x / R; c < kFoldTile; c += kBlock / R) {
+    const float x = tile[0][wr][c], y = tile[1][wr][c], z = tile[2][wr][c];
+    if (x == 0.0f && y == 0.0f && z == 0.0f) continue;
+    const uint32_t a = ((col0 + c) * kMonoMulInv) & s_mask;   // column hash inverted
+    const uint32_t pix = a * kMonoRows + row0 + wr;
+    if (pix < n_pix) {
+      xyz[3u * pix + 0u] += x;
+      xyz[3u * pix + 1u] += y;
+      xyz[3u * pix + 2u] += z;
+    }
+  }
+}
 template <uint32_t R>
 __global__ void __launch_bounds__(kBlock) halo_fold_kernel(float* __restrict__ xyz, float* __restrict__ planes, uint32_t n_pix,
                                                             uint32_t s_log2, uint32_t copies, uint32_t n_planes, const FoldCoef coef,
@@ -599,19 +609,43 @@ __global__ void __launch_bounds__(kBlock) halo_fold_kernel(float* __restrict__ x
     tile[2][r][lo] = z;
   }
   __syncthreads();
-  const uint32_t s_mask = (1u << s_log2) - 1u;
-  const uint32_t wr = threadIdx.x % R;   // row of the tile = consecutive pixels
-  for (uint32_t c = threadIdx.x / R; c < kFoldTile; c += kBlock / R) {
-    const float x = tile[0][wr][c], y = tile[1][wr][c], z = tile[2][wr][c];
-    if (x == 0.0f && y == 0.0f && z == 0.0f) continue;
-    const uint32_t a = ((col0 + c) * kMonoMulInv) & s_mask;   // column hash inverted
-    const uint32_t pix = a * kMonoRows + row0 + wr;
-    if (pix < n_pix) {
-      xyz[3u * pix + 0u] += x;
-      xyz[3u * pix + 1u] += y;
-      xyz[3u * pix + 2u] += z;
+  fold_store_tile<R>(tile, xyz, n_pix, s_log2, row0, col0);
+}
+
+// The same fold over the 64-bit fixed-point planes of a deterministic session (DispatchParams::fix: [plane][slot], one copy, no twin): a slot's
+// value is float(double(S) * 2^-F), exact in the integer and rounded once; coefficients, the add to XYZ and the zeroing of what was read are
+// the float fold's.  One or three planes (a discrete wavelength's scalar plane, or X, Y, Z).
+constexpr uint32_t kFixPlanesMax = 3u;
+template <uint32_t R>
+__global__ void __launch_bounds__(kBlock) halo_fold_fixed_kernel(float* __restrict__ xyz, unsigned long long* __restrict__ planes, uint32_t n_pix,
+                                                                  uint32_t s_log2, uint32_t n_planes, const FoldCoef coef, uint32_t frac_bits) {
+  __shared__ float tile[3][R][kFoldTile + 1];
+  const FixQ fq(frac_bits);
+  const uint32_t tiles_c = (1u << s_log2) / kFoldTile;
+  const uint32_t row0 = (blockIdx.x / tiles_c) * R, col0 = (blockIdx.x % tiles_c) * kFoldTile;
+  const size_t plane = static_cast<size_t>(kMonoRows) << s_log2;
+  const uint32_t lo = threadIdx.x & (kFoldTile - 1u), hi = threadIdx.x / kFoldTile;
+  for (uint32_t r = hi; r < R; r += kBlock / kFoldTile) {
+    unsigned long long* q = planes + (static_cast<size_t>(row0 + r) << s_log2) + col0 + lo;
+    float x = 0.0f, y = 0.0f, z = 0.0f;
+    unsigned long long t[kFixPlanesMax];
+#pragma unroll
+    for (uint32_t u = 0; u < kFixPlanesMax; ++u) t[u] = u < n_planes ? q[static_cast<size_t>(u) * plane] : 0ull;
+#pragma unroll
+    for (uint32_t u = 0; u < kFixPlanesMax; ++u) {
+      if (t[u] == 0ull) continue;
+      q[static_cast<size_t>(u) * plane] = 0ull;
+      const float v = fq.unfix(t[u]);
+      x += coef.c[u][0] * v;
+      y += coef.c[u][1] * v;
+      z += coef.c[u][2] * v;
     }
+    tile[0][r][lo] = x;
+    tile[1][r][lo] = y;
+    tile[2][r][lo] = z;
   }
+  __syncthreads();
+  fold_store_tile<R>(tile, xyz, n_pix, s_log2, row0, col0);
 }
 
 // Consumer fold: running image += drained accumulator, Neumaier-compensated (accum_shared.h:70-74), accumulator zeroed.
@@ -843,6 +877,19 @@ hipError_t launch_fold(float* xyz, float* planes, uint32_t n_pix, uint32_t s_log
     hipLaunchKernelGGL(halo_fold_kernel<16u>, dim3(tiles_c * (kMonoRows / 16u)), dim3(kBlock), 0, stream, xyz, planes, n_pix, s_log2, copies, n_planes, coef, ovf, ovf_flag);
   else
     hipLaunchKernelGGL(halo_fold_kernel<4u>, dim3(tiles_c * (kMonoRows / 4u)), dim3(kBlock), 0, stream, xyz, planes, n_pix, s_log2, copies, n_planes, coef, ovf, ovf_flag);
+  return hipGetLastError();
+}
+
+hipError_t launch_fold_fixed(float* xyz, unsigned long long* planes, uint32_t n_pix, uint32_t s_log2, uint32_t n_planes, const FoldCoef& coef, uint32_t frac_bits,
+                             hipStream_t stream) {
+  if (n_planes > kFixPlanesMax) return hipErrorInvalidValue;
+  const uint32_t tiles_c = (1u << s_log2) / kFoldTile;
+  if (tiles_c * (kMonoRows / 64u) >= 512u)
+    hipLaunchKernelGGL(halo_fold_fixed_kernel<64u>, dim3(tiles_c * (kMonoRows / 64u)), dim3(kBlock), 0, stream, xyz, planes, n_pix, s_log2, n_planes, coef, frac_bits);
+  else if (tiles_c * (kMonoRows / 16u) >= 512u)
+    hipLaunchKernelGGL(halo_fold_fixed_kernel<16u>, dim3(tiles_c * (kMonoRows / 16u)), dim3(kBlock), 0, stream, xyz, planes, n_pix, s_log2, n_planes, coef, frac_bits);
+  else
+    hipLaunchKernelGGL(halo_fold_fixed_kernel<4u>, dim3(tiles_c * (kMonoRows / 4u)), dim3(kBlock), 0, stream, xyz, planes, n_pix, s_log2, n_planes, coef, frac_bits);
   return hipGetLastError();
 }
 

@@ -26,6 +26,8 @@ hipError_t launch_shapegen(void* pool, bool prism_records, uint32_t n, uint32_t 
                            hipStream_t stream, bool serial_pyramid);
 hipError_t launch_fold(float* xyz, float* planes, uint32_t n_pix, uint32_t s_log2, uint32_t copies, uint32_t n_planes, const FoldCoef& coef,
                        double* ovf, const uint32_t* ovf_flag, hipStream_t stream);
+hipError_t launch_fold_fixed(float* xyz, unsigned long long* planes, uint32_t n_pix, uint32_t s_log2, uint32_t n_planes, const FoldCoef& coef, uint32_t frac_bits,
+                             hipStream_t stream);
 hipError_t launch_consumer_fold(float* acc, float* sum, float* comp, uint32_t n, int blocks, hipStream_t stream);
 hipError_t launch_lane_hist(const double* lanes, uint32_t n_pix, const CompositeDev& cd, uint32_t shift, uint32_t bits, uint32_t prefix, uint32_t* hist, int blocks,
                             hipStream_t stream);

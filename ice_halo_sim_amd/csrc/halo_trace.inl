@@ -527,6 +527,35 @@ struct PixCache {
   float val[CacheGeom<MONO, SMALLC>::kN * (MONO ? 1 : 3)];
 };
 
+// Fixed point, 64-bit: a value v enters a sum as floor(double(v) * 2^F + 0.5), a NaN or a negative value as nothing, and integer sums do not
+// depend on the order of their adds.  F comes with the launch (halo_backend.cpp fix_frac_bits: no sum it is used for can wrap).  The rule of the
+// per-tile passes (halo_kernels.hip) and of the deterministic route (kAccFixed) below.
+struct FixQ {
+  double to_fix, from_fix;
+  __device__ __forceinline__ explicit FixQ(uint32_t frac_bits)
+      : to_fix(__hiloint2double(static_cast<int>((1023u + frac_bits) << 20), 0)), from_fix(__hiloint2double(static_cast<int>((1023u - frac_bits) << 20), 0)) {}
+  __device__ __forceinline__ unsigned long long fix(float v) const {   // round to nearest; v <= the launch's bound by construction
+    return static_cast<unsigned long long>(static_cast<long long>(fma(static_cast<double>(fmaxf(v, 0.0f)), to_fix, 0.5)));
+  }
+  __device__ __forceinline__ float unfix(unsigned long long a) const { return static_cast<float>(static_cast<double>(a) * from_fix); }
+};
+
+// The pixel cache of the deterministic route (kAccFixed): the same tags, ways and claim protocol, 64-bit integer values added with ds_add_u64 —
+// the fastest LDS atomic on this part.  It is a VIEW of the PixCache<MONO, false> in the workgroup's LdsTables, which a
+// kAccFixed kernel touches in no other way: 1024 scalar slots (4 + 8 KB) or 512 X/Y/Z slots (2 + 12 KB) inside the 16 KB the direct kernels'
+// caches take, so that the integer twin of a direct kernel has that kernel's LDS and keeps the waves per SIMD its __launch_bounds__ asks for.
+template <bool MONO>
+struct FixCache {
+  static constexpr int kLog2 = MONO ? 10 : 9;
+  static constexpr int kN = 1 << kLog2;
+  typedef uint32_t tag_t __attribute__((may_alias));
+  typedef unsigned long long val_t __attribute__((may_alias));
+  __attribute__((aligned(16))) tag_t tag[kN];   // pixel + 1, 0 = free (a deterministic session has no plane per pool entry)
+  val_t val[kN * (MONO ? 1 : 3)];
+};
+static_assert(sizeof(FixCache<true>) <= sizeof(PixCache<true, false>) && sizeof(FixCache<false>) <= sizeof(PixCache<false, false>), "the fixed-point cache lies inside the float cache's LDS");
+static_assert(offsetof(FixCache<true>, val) % 8 == 0 && offsetof(FixCache<false>, val) % 8 == 0, "ds_add_u64 operands");
+
 // Binned accumulation (discrete-wavelength sessions, big launches).  A launch of n rays puts tens of hits on EVERY pixel,
 // but no workgroup sees a pixel twice — the reuse only exists chip-wide, and one global atomic per hit caps the kernel at
 // ~21 G hits/s.  So hits are exchanged through per-tile lists in HBM instead: a workgroup stages its hits {slot, w} in LDS,
@@ -535,6 +564,7 @@ struct PixCache {
 // sums each tile's list in a 64 KB LDS tile and adds it to the plane with plain stores.  Lists that run over (a tile much
 // hotter than average) fall back to the direct atomic, so capacity is a speed matter only.
 constexpr int kAccDirect = 0, kAccBin = 1, kAccLog = 2, kAccNone = 3, kAccLogFinal = 4;   // halo_trace_kernel ACC (None: a layer whose every exit continues — nothing lands)
+constexpr int kAccFixed = 5;   // the integer twin of kAccDirect (option "deterministic"): FixCache in LDS, 64-bit integer atomics onto DispatchParams::fix
 constexpr int kHitBuf = 1536;                 // staged hits per workgroup (16 KB)
 // (kBinTileLog2, slots per tile, and kBinCntStride, the spacing of the tile counters: halo_device.h)
 constexpr int kBinMaxTiles = 512;
@@ -601,6 +631,7 @@ struct AccCtx {
   bool last;         // kAccLogFinal kernels: the scene's last layer — no candidate continues, the append code is compiled out
   bool canon;        // canonical-order kernels (option cont_order = 1, layers before the last): appends carry their (root, interaction) key
   bool none;         // kAccNone kernels: every outgoing candidate continues (prob >= 1, not the last layer), nothing is projected
+  bool fixed;        // kAccFixed kernels: hits and landed weight are summed as 64-bit fixed point (accumulate_fixed)
   ExitQueue* q;      // this wave's exit queue; nullptr = project and accumulate at the emit site
   ExitQueueMask* qm; // ... its colour-mask planes (kModeColor)
   const FastTables __attribute__((address_space(4)))* fast;   // kModeFilter / kModeColor: the dispatch's filter + colour predicates (dispatch-uniform, scalar loads)
@@ -681,10 +712,79 @@ HD uint32_t log_slot(const DispatchParams& P, uint32_t pl, uint32_t pix) { retur
 // X/Y/Z kernels under the hit log: the slot in ONE plane with the CMF code above it (the per-tile pass makes X, Y, Z)
 HD uint32_t log_slot_xyz(const DispatchParams& P, uint32_t code, uint32_t pix) { return MonoSlot(pix, P.mono_s_log2) | (code << kLogWlShift); }
 
+// The deterministic route (kAccFixed kernels): the hit's value(s) — w on the scalar plane, the fp32 products cx w, cy w, cz w on X, Y, Z — are
+// quantised ONCE, here, and are integers from then on: ds_add_u64 into the workgroup's cache (same sets, ways and claim protocol as the float
+// caches), a global 64-bit integer atomic where the pixel lost the claim or the cache is off.  Nothing on this path rounds after the quantisation,
+// so a plane's sums depend on the SET of hits alone — not on which hits met the cache, in which order, or from which workgroup.
+HD unsigned long long* fix_slot(const DispatchParams& P, uint32_t pl, uint32_t pix) {
+  return P.fix + (static_cast<size_t>(pl) << (P.mono_s_log2 + 10u)) + MonoSlot(pix, P.mono_s_log2);
+}
+template <bool MONO, bool SMALLC>
+HD void accumulate_fixed(const DispatchParams& P, const AccCtx<MONO, SMALLC>& ctx, uint32_t pix, float w, float cx, float cy, float cz) {
+  static_assert(!SMALLC, "the fixed-point cache is a view of the full-size float cache");
+  if (P.aggregate == 2u) return;  // diagnostic: trace + project only
+  FixCache<MONO>& C = *reinterpret_cast<FixCache<MONO>*>(ctx.cache);
+  const FixQ fq(P.fix_frac);
+  const unsigned long long q0 = fq.fix(MONO ? w : cx * w), q1 = MONO ? 0ull : fq.fix(cy * w), q2 = MONO ? 0ull : fq.fix(cz * w);
+  if (P.aggregate == 1u || P.aggregate == 3u) {
+    const uint32_t key = pix + 1u;
+    uint32_t slot = 0xFFFFFFFFu;
+    if constexpr (!MONO && HALO_CACHE_WAYS == 4) {   // four-way sets, one 16-byte read of the set's tags (see accumulate)
+      const uint32_t set = ((key * 2654435761u) >> (32 - (FixCache<MONO>::kLog2 - 2))) << 2;
+#pragma unroll
+      for (int attempt = 0; attempt < 2; ++attempt) {
+        const uint4 t = *reinterpret_cast<const uint4*>(&C.tag[set]);
+        const uint32_t found = t.x == key ? 0u : t.y == key ? 1u : t.z == key ? 2u : t.w == key ? 3u : 4u;
+        if (found < 4u) {
+          slot = set + found;
+          break;
+        }
+        const uint32_t empty = t.x == 0u ? 0u : t.y == 0u ? 1u : t.z == 0u ? 2u : t.w == 0u ? 3u : 4u;
+        if (empty == 4u) break;
+        const uint32_t old = atomicCAS(&C.tag[set + empty], 0u, key);
+        if (old == 0u || old == key) {
+          slot = set + empty;
+          break;
+        }
+      }
+    } else {   // two-way: slot s or s ^ 1
+      uint32_t s = (key * 2654435761u) >> (32 - FixCache<MONO>::kLog2);
+      uint32_t old = atomicCAS(&C.tag[s], 0u, key);
+      if (old != 0u && old != key) {
+        s ^= 1u;
+        old = atomicCAS(&C.tag[s], 0u, key);
+      }
+      if (old == 0u || old == key) slot = s;
+    }
+    if (slot != 0xFFFFFFFFu) {
+      if (MONO) {
+        atomicAdd(&C.val[slot], q0);   // ds_add_u64
+      } else {
+        atomicAdd(&C.val[slot * 3 + 0], q0);
+        atomicAdd(&C.val[slot * 3 + 1], q1);
+        atomicAdd(&C.val[slot * 3 + 2], q2);
+      }
+      return;
+    }
+    if (P.aggregate == 3u) return;  // diagnostic: cache only, misses dropped
+  }
+  atomicAdd(fix_slot(P, 0u, pix), q0);   // global_atomic_add_x2, no return value
+  if (!MONO) {
+    atomicAdd(fix_slot(P, 1u, pix), q1);
+    atomicAdd(fix_slot(P, 2u, pix), q2);
+  }
+}
+
 // MONO: one scalar per hit into plane 0 (discrete wavelength) or plane wl_idx (illuminant session with one plane per
 // pool entry); the CMF is applied by halo_fold_kernel.  !MONO: X, Y, Z into planes 0..2.
 template <bool MONO, bool SMALLC>
 HD void accumulate(const DispatchParams& P, const AccCtx<MONO, SMALLC>& ctx, uint32_t pix, uint32_t wl_idx, float w, float cx, float cy, float cz) {
+  if constexpr (!SMALLC) {
+    if (ctx.fixed) {   // (a constant of the instantiation, like lens / vis / none: the other route folds away)
+      accumulate_fixed<MONO, SMALLC>(P, ctx, pix, w, cx, cy, cz);
+      return;
+    }
+  }
   PixCache<MONO, SMALLC>& C = *ctx.cache;
   if (P.aggregate == 2u) return;  // diagnostic: trace + project only
   const uint32_t pl = (MONO && P.mono_by_wl) ? wl_idx : 0u;
@@ -770,6 +870,7 @@ struct RaySums {
   uint32_t exit_n;
   uint32_t pix_n;
   uint32_t qn;   // exit queue fill (see ExitQueue)
+  unsigned long long landed_q;   // kAccFixed kernels: the landed weight as an integer, FixQ(fix_frac_landed) of every primary hit (`landed` is not tallied)
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -1340,6 +1441,9 @@ HD int land_exit(const DispatchParams& P, const AccCtx<MONO, SMALLC>& cache, con
     if (ModeTraits<MODE>::kTables && color != nullptr) fan_lanes(P, *color, cmask, pix, cmf_y * w);
     if constexpr (MODE == kModeColor) fan_lanes_fast(P, *cache.fast, cmask, pix, cmf_y * w);
     sums.landed += w;  // bump_landed: primary hit only (scatter_accum.hpp:96-108)
+    if constexpr (!SMALLC && (MODE == kModePlain || MODE == kModeFilter)) {   // (only these have kAccFixed twins; the test is not even compiled into the others)
+      if (cache.fixed) sums.landed_q += FixQ(P.fix_frac_landed).fix(w);     // ... which tally this integer instead
+    }
     sums.pix_n++;
     primary = static_cast<int>(pix);
   }
@@ -2493,6 +2597,11 @@ HD float wave_sum(float v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
   return v;
 }
+HD unsigned long long wave_sum(unsigned long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+  return v;
+}
 
 // waves per SIMD the register allocator must leave room for: 5 for the production kernels (96 VGPRs, measured 4.5 % faster
 // than 4); the filter / capture kernels carry the path register, the predicate tables' addressing and the colour mask on
@@ -2525,6 +2634,7 @@ template <int MODE, int GEOM, bool MONO, int ACC>
 constexpr bool small_cache_hex() { return (MODE == kModePlain || (HALO_FILTER_SIX && MODE == kModeFilter)) && GEOM == kGeomOneHex && MONO && (ACC == kAccLog || ACC == kAccLogFinal); }
 template <int MODE, int GEOM, bool MONO, int ACC>
 constexpr int min_waves() {
+  if (ACC == kAccFixed) return min_waves<MODE, GEOM, MONO, kAccDirect>();   // the integer twin keeps its float kernel's bound (and its LDS: FixCache)
   if (!ModeTraits<MODE>::kFast) return HALO_MIN_WAVES_FILTER;
   if ((ACC != kAccDirect && ACC != kAccNone) || ((GEOM == kGeomOne || GEOM == kGeomOneHex) && ACC != kAccNone)) {
     if (small_cache_hex<MODE, GEOM, MONO, ACC>()) return HALO_LOG_WAVES;
@@ -2540,7 +2650,8 @@ constexpr int min_waves() {
 // ROOT: a root profile (kRoot*, at sample_lat_lon_roll) — the last-layer plain hit-log kernels of the regular prism, which launch_vis fans out.
 template <int MODE, int GEOM, bool MONO, int ACC, int LENS = -1, int VIS = -1, bool NOGATE = false, bool CANON = false, int ROOT = kRootAny>   // ACC: kAccDirect, kAccBin (staged + binned hit lists), kAccLog (per-workgroup hit log), ...
 __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) halo_trace_kernel(const DispatchParams P) {
-  constexpr bool BIN = ACC == kAccBin, LOG = ACC == kAccLog || ACC == kAccLogFinal, NONE = ACC == kAccNone, LAST = ACC == kAccLogFinal;
+  constexpr bool BIN = ACC == kAccBin, LOG = ACC == kAccLog || ACC == kAccLogFinal, NONE = ACC == kAccNone, LAST = ACC == kAccLogFinal, FIXED = ACC == kAccFixed;
+  static_assert(!FIXED || ((MODE == kModePlain || MODE == kModeFilter) && LENS < 0 && VIS < 0 && !NOGATE && ROOT == kRootAny), "kAccFixed: the plain and the fast-filter kernels, in the generic run-time lens form");
   static_assert(!LOG || ModeTraits<MODE>::kFast, "the hit log is a production-mode route");
   static_assert(!NONE || (ModeTraits<MODE>::kFast && MONO), "kAccNone: production mode; nothing accumulates, so one (scalar) flavour serves every session");
   static_assert(MODE == kModePlain || MODE == kModeFilter || (LENS < 0 && VIS < 0 && !NOGATE), "lens / visible-range / closed-gate specialisations exist for the plain and the filter kernels");
@@ -2578,6 +2689,7 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
     for (uint32_t i = threadIdx.x; i < kFastEeLds * 32u; i += kBlock) s_fast_ee[i] = P.fast->ee[i >> 5][i & 31u];
   }
   acc.none = NONE;
+  acc.fixed = FIXED;
   acc.last = LAST;
   acc.canon = CANON;
   acc.lens = LENS;
@@ -2633,6 +2745,13 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
     for (uint32_t i = threadIdx.x; i < sizeof(FilterDev) / 4u; i += kBlock) dst[i] = src[i];
     filter = reinterpret_cast<const FilterDev*>(&s_filter);
   }
+  if constexpr (FIXED) {
+    if (P.aggregate == 1u || P.aggregate == 3u) {
+      FixCache<MONO>& C = *reinterpret_cast<FixCache<MONO>*>(&T.cache);
+      for (int i = threadIdx.x; i < FixCache<MONO>::kN; i += kBlock) C.tag[i] = 0u;
+      for (int i = threadIdx.x; i < FixCache<MONO>::kN * (MONO ? 1 : 3); i += kBlock) C.val[i] = 0ull;
+    }
+  } else
   if (!NONE && (P.aggregate == 1u || P.aggregate == 3u)) {
     for (int i = threadIdx.x; i < CacheGeom<MONO, SMALLC>::kN; i += kBlock) T.cache.tag[i] = 0u;
     for (int i = threadIdx.x; i < CacheGeom<MONO, SMALLC>::kN * (MONO ? 1 : 3); i += kBlock) T.cache.val[i] = 0.0f;
@@ -2809,6 +2928,20 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
 #ifdef HALO_PROBE
   probe_start(pr);
 #endif
+  if constexpr (FIXED) {   // ... of the fixed-point cache: one 64-bit integer atomic per claimed slot and channel
+    if (P.aggregate == 1u || P.aggregate == 3u) {
+      __syncthreads();
+      const FixCache<MONO>& C = *reinterpret_cast<const FixCache<MONO>*>(&T.cache);
+      for (int i = threadIdx.x; i < FixCache<MONO>::kN; i += kBlock) {
+        const uint32_t key = C.tag[i];
+        if (key == 0u) continue;
+        for (uint32_t c = 0; c < (MONO ? 1u : 3u); ++c) {
+          const unsigned long long v = C.val[i * (MONO ? 1 : 3) + c];
+          if (v != 0ull) atomicAdd(fix_slot(P, c, key - 1u), v);
+        }
+      }
+    }
+  } else
   if (!NONE && (P.aggregate == 1u || P.aggregate == 3u)) {
     __syncthreads();
     for (int i = threadIdx.x; i < CacheGeom<MONO, SMALLC>::kN; i += kBlock) {
@@ -2844,7 +2977,7 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
   // reads differences (halo_backend.cpp pull_tally).
   __shared__ float s_tally[kBlock / 64][4];
   {
-    const float landed = wave_sum(sums.landed);
+    const float landed = FIXED ? 0.0f : wave_sum(sums.landed);   // (kAccFixed: the landed weight leaves as an integer, below)
     const float exit_w = wave_sum(sums.exit_w);
     const float exit_n = wave_sum(static_cast<float>(sums.exit_n));
     const float pix_n = wave_sum(static_cast<float>(sums.pix_n));
@@ -2858,6 +2991,20 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
 #pragma unroll
       for (int w = 0; w < kBlock / 64; ++w) v += static_cast<double>(s_tally[w][threadIdx.x]);
       if (v != 0.0) atomicAdd(&P.tally[(blockIdx.x & (kTallyLines - 1u)) * kTallyStride + threadIdx.x], v);
+    }
+  }
+  if constexpr (FIXED) {   // the landed weight as an integer: lanes (RaySums::landed_q), the wave, the workgroup, then ONE 64-bit integer atomic onto the line's integer slot
+    // (no LDS of its own — 32 bytes more and the prism-pool kernels would lose their fifth workgroup per CU: the cache is flushed and every
+    //  thread is past the barrier above, so its first words serve)
+    typename FixCache<MONO>::val_t* const s_landed_q = reinterpret_cast<FixCache<MONO>*>(&T.cache)->val;
+    const unsigned long long lq = wave_sum(sums.landed_q);
+    if ((threadIdx.x & 63) == 0) s_landed_q[threadIdx.x >> 6] = lq;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned long long v = 0ull;
+#pragma unroll
+      for (int w = 0; w < kBlock / 64; ++w) v += s_landed_q[w];
+      if (v != 0ull) atomicAdd(reinterpret_cast<unsigned long long*>(P.tally) + (blockIdx.x & (kTallyLines - 1u)) * kTallyStride + kSumFixLanded, v);
     }
   }
 #ifdef HALO_PROBE
@@ -2990,9 +3137,39 @@ static void launch_mono(const DispatchParams& P, dim3 grid, dim3 block, hipStrea
   }
 }
 
+// The deterministic route (DispatchParams::fix set: option "deterministic"): the kAccFixed twins of the direct kernels — plain and fast-filter mode,
+// every GEOM, scalar and X/Y/Z planes, with and without the canonical order's append keys, in the generic run-time lens form.  They are
+// instantiated in translation units of their own (halo_trace_fx0.hip, halo_trace_fx1.hip), which compile beside the others.
+hipError_t launch_trace_fx0(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);   // kModePlain
+hipError_t launch_trace_fx1(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);   // kModeFilter
+template <int MODE, int GEOM>
+static void launch_fixed_geom(const DispatchParams& P, dim3 grid, dim3 block, hipStream_t stream, bool mono) {
+  const bool canon = P.cont_mask != nullptr;
+  if (mono && canon) hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, true, kAccFixed, -1, -1, false, true>), grid, block, 0, stream, P);
+  else if (mono) hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, true, kAccFixed>), grid, block, 0, stream, P);
+  else if (canon) hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, false, kAccFixed, -1, -1, false, true>), grid, block, 0, stream, P);
+  else hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, false, kAccFixed>), grid, block, 0, stream, P);
+}
+template <int MODE>
+static hipError_t launch_fixed(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono) {
+  dim3 grid(blocks), block(kBlock);
+  if (geom == kGeomOneHex) launch_fixed_geom<MODE, kGeomOneHex>(P, grid, block, stream, mono);
+  else if (geom == kGeomPoolPrism) launch_fixed_geom<MODE, kGeomPoolPrism>(P, grid, block, stream, mono);
+  else if (geom == kGeomPool) launch_fixed_geom<MODE, kGeomPool>(P, grid, block, stream, mono);
+  else launch_fixed_geom<MODE, kGeomOne>(P, grid, block, stream, mono);
+  return hipGetLastError();
+}
+
 template <int MODE>
 static hipError_t launch_mode(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono) {
   dim3 grid(blocks), block(kBlock);
+  // a deterministic launch that accumulates: its kAccFixed kernel, or an error — never a float route.  (A one-shape layer whose every exit
+  // continues accumulates nothing and keeps its kAccNone kernel below.)
+  if (P.fix != nullptr && !(P.no_land != 0u && ModeTraits<MODE>::kFast && (geom == kGeomOne || geom == kGeomOneHex))) {
+    if constexpr (MODE == kModePlain) return launch_trace_fx0(P, blocks, stream, geom, mono);
+    else if constexpr (MODE == kModeFilter) return launch_trace_fx1(P, blocks, stream, geom, mono);
+    else return hipErrorNotSupported;
+  }
   if constexpr (ModeTraits<MODE>::kFast) {
     if (geom == kGeomOneHex && (P.bin_list == nullptr || P.bin_log != 0u || P.no_land != 0u)) {
       launch_mono<MODE, kGeomOneHex>(P, grid, block, stream, mono);

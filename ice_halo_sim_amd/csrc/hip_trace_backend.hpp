@@ -48,6 +48,9 @@ class HipTraceBackend {
   HipTraceBackend& operator=(const HipTraceBackend&) = delete;
 
   void SetOption(const char* key, int64_t value) { Check(halo_set_option(h_, key, value)); }
+  // option "deterministic" (halo_trace.h): fixed-point accumulation — a fixed seed and ray_base give the same image bytes on every run; a
+  // multi-layer scene needs SetOption("cont_order", 1) beside it, and BeginSession throws for what the route does not cover.  Not inside a session.
+  void SetDeterministic(bool on) { SetOption("deterministic", on ? 1 : 0); }
 
   // --- the seam ---------------------------------------------------------------------------------------------
   void BeginSession(const HaloScene& scene, const HaloRender& render, const HaloWl& wl, size_t ray_num = 0) {

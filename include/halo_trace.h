@@ -308,10 +308,25 @@ const char* halo_last_error(halo_handle_t h);
  * "cont_order" (additive in ABI 6, no struct changed: 0 [default] = the continuation pool in append order, which wave scheduling decides;
  * 1 = canonical order — after every layer but the last, halo_recombine sorts the pool by (layer-global root index, exit seq) — the index
  * HaloExitRecord::root reports, on the device and in stream order; shuffle, shuffle_chunk and the transit streams keep their meaning, so a
- * fixed seed traces the same rays on every layer of every run (the image is still a float sum in scheduling order).  Layers before the last
+ * fixed seed traces the same rays on every layer of every run (the image is still a float sum in scheduling order — unless option "deterministic" is on).  Layers before the last
  * then accumulate with direct atomics, and every layer of a multi-layer session returns synchronously (option async does not defer the last
  * one: the layer ends with the check of the order's invariants — a broken one, like a pool overflow, is HALO_FATAL); needs rehit_strategy = 1;
  * not inside a session),
+ * "deterministic" (additive in ABI 6, no struct changed: 0 [default] = the float routes above; 1 = every accumulating launch of every layer runs the
+ * fixed-point route — a hit's value v (the weight on a scalar plane, the fp32 products cmf * weight on X, Y, Z) enters every sum as the 64-bit
+ * integer floor(double(v) * 2^F + 0.5), in the workgroup's pixel cache, in the global planes and in the landed-weight tally alike, and integer
+ * sums do not depend on the order of their adds.  A discrete session keeps one scalar plane, an illuminant session X, Y, Z planes; hit_log, bin,
+ * lambda_planes and mono_copies are ignored.  REPRODUCIBLE: the integer plane sums and the landed integer of a session depend only on the set of
+ * rays traced into them — not on chunk, blocks_per_cu, small_blocks_per_cu, overlap, async, aggregate, mono_copies, table_cache, stream
+ * assignment or wave scheduling; the XYZ image is a per-pixel function of those sums and of the order of the folds, which is the order of the
+ * caller's sessions (a plane value is float32(double(S) * 2^-F)), so a fixed seed and ray_base give the same bytes on every run.  Over several
+ * layers this holds together with cont_order = 1.  F is the largest scale <= 32 at which 2^30 rays of the session's largest weight cannot wrap a
+ * slot (halo_host_fixed_frac_bits: 29 for weights up to 1); a plane set that has taken 2^30 rays is folded before the next launch, at a launch
+ * boundary — beyond that budget the image, not the sums of each fold, depends on chunk.  NOT covered: a multi-GPU run is reproducible per rank,
+ * the collective's order is RCCL's.  REFUSED, by name, at halo_begin (nothing is ever run on
+ * a float route in silence): a multi-layer session without cont_order = 1, raypath-colour tables, capture_exits = 1, rehit_strategy = 0, a
+ * filter that needs the generic filter kernels.  Every hit outside the pixel cache is a memory-side 64-bit integer atomic, the price of the
+ * direct route: configs[1]'s step +58 %, a full-sky X/Y/Z session 4.8 x; not inside a session),
  * scheduling (ABI 6; none of them changes a result): "overlap" (1 [default]: launches of <= 2 Mi rays alternate between two
  * trace streams, closing folds run on an auxiliary stream; 0 = everything on the one stream), "table_cache" (1 [default]: equal
  * sessions reuse their device tables), "small_blocks_per_cu" (default 5: workgroups per CU a small launch spreads over before a
@@ -372,7 +387,7 @@ typedef struct HaloRouteInfo {
                             raypath colour (both for max_hits <= 16: path in a register, predicates as host-built member tables); 2 + exit capture
                             (tests); 3 the generic filter / colour kernels (paths to 64 faces, or tables that do not fit the fast form) */
   uint32_t geom_mask;    /* bit g: GEOM g (0 one shape per dispatch, 1 pool of 4.1 KB records, 2 pool of prism records, 3 one shape = regular hexagonal prism) */
-  uint32_t accum_mask;   /* bit 0 direct X/Y/Z planes, 1 direct scalar plane(s), 2 binned one level, 3 binned two levels, 4 hit log, 5 hit log of an illuminant session (X, Y, Z made in the per-tile pass), 6 none (a layer whose every exit continues) */
+  uint32_t accum_mask;   /* bit 0 direct X/Y/Z planes, 1 direct scalar plane(s), 2 binned one level, 3 binned two levels, 4 hit log, 5 hit log of an illuminant session (X, Y, Z made in the per-tile pass), 6 none (a layer whose every exit continues), 7 fixed-point planes (option "deterministic": no other accumulating bit is set beside it) */
   uint32_t source_mask;  /* bit 0 generated roots, 1 continuation pool (layer >= 1), 2 host-injected rays */
   uint32_t plane_cnt;    /* accumulation planes of the session (1 discrete, 3 X/Y/Z, M per-entry) */
   uint32_t plane_copies; /* privatised copies of each plane */
@@ -405,6 +420,13 @@ int halo_collect_stats(halo_handle_t h, HaloLayerStats* out);
 /* Read AND zero the device landed-weight tally (fp64) without touching the image: used when the image lives in a
  * bound external accumulator that is reduced across ranks in place. */
 int halo_take_landed(halo_handle_t h, double* landed_weight);
+/* The pending fixed-point planes of deterministic sessions, as the integers they are (additive in ABI 6).  Valid after halo_end, with option
+ * "lazy_fold" = 1 and the backend's OWN accumulator, until a reader of the image or a session with other planes folds them: waits for the device and
+ * copies plane `plane` (0 for a discrete session; 0, 1, 2 = X, Y, Z for an illuminant one) in PIXEL order — sums[py * width + px], the planes' slot
+ * hash undone — n_pix = width * height; *frac_bits = F of those sums (a plane value is sums[p] * 2^-F); *landed = the landed weight of the ended
+ * deterministic sessions nobody has taken yet, in units of 2^-*landed_frac_bits.  Every out pointer may be NULL.  Folds, zeroes and takes
+ * nothing.  HALO_FATAL when no fixed-point planes are pending. */
+int halo_peek_fixed(halo_handle_t h, int32_t plane, uint64_t* sums, uint64_t n_pix, uint32_t* frac_bits, uint64_t* landed, uint32_t* landed_frac_bits);
 
 /* Multi-GPU drain for a C/C++ host (one process — or one thread — per GPU, one backend per GPU): sum-reduce this rank's XYZ
  * accumulator (width*height*3+4 floats, owned or bound) onto rank `root` with ONE ncclReduce over RCCL/xGMI, queued on the
@@ -521,6 +543,11 @@ int halo_host_filter_fast_check(const HaloFilter* f, const HaloAxis* axis, const
  * Same member tables as halo_host_filter_fast_check (n <= 16).  A host-side test hook for the reference's component-gate vectors. */
 int halo_host_color_fast_mask(const HaloColorSet* colors, const HaloAxis* axis, const uint8_t* path, int32_t n, const float dir[3], int32_t crystal_id,
                               uint64_t carried, uint64_t* mask);
+/* The scale of a 64-bit fixed-point sum that takes up to `hits` addends of at most `max_w` each: the largest F <= 32 with
+ * 4 * max(max_w, 1e-30) * max(hits, 1) * 2^F < 2^62 (the factor 4: a ray's exits never outweigh the ray; x 2 for the second hit of a dual lens, x 2
+ * for the CMF rows).  The per-tile passes of the hit log use it with the rays of one launch, option "deterministic" with 2^30 for the planes
+ * and 2^32 for the landed integer. */
+uint32_t halo_host_fixed_frac_bits(double max_w, uint64_t hits);
 /* IceRefractiveIndex::Get — optics.cpp:180-197. */
 double halo_host_refractive_index(double wavelength_nm);
 /* GetIlluminantSpd(type, wavelength) — util/illuminant.cpp:113-134 (HALO_ILLUM_*; 0 outside the tabulated range). */

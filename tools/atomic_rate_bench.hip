@@ -15,7 +15,8 @@ __device__ __forceinline__ uint32_t pcg(uint32_t x) {
 }
 
 // MODE 0: non-returning fp32 atomic; 1: plain 4-byte store to the slot; 2: 8-byte store to a per-wave contiguous log;
-// 3: returning u32 atomic on a per-workgroup counter + 8-byte store (the shard-log scheme); 4: nothing (ALU only)
+// 3: returning u32 atomic on a per-workgroup counter + 8-byte store (the shard-log scheme); 4: nothing (ALU only);
+// 5: non-returning 64-bit INTEGER atomic on 8-byte slots (the deterministic route's fixed-point planes: same slot counts, twice the bytes)
 template <int MODE>
 __global__ void __launch_bounds__(256, 5) k(float* plane, uint32_t slot_mask, uint32_t copy_shift, uint32_t iters, uint32_t lane_keep, uint32_t alu, uint2* log,
                                             uint32_t* cnt, float* sink) {
@@ -35,6 +36,8 @@ __global__ void __launch_bounds__(256, 5) k(float* plane, uint32_t slot_mask, ui
       const uint32_t slot = (s & slot_mask) + copy;
       if (MODE == 0) {
         unsafeAtomicAdd(plane + slot, v);
+      } else if (MODE == 5) {
+        atomicAdd(reinterpret_cast<unsigned long long*>(plane) + slot, static_cast<unsigned long long>(v * 4294967296.0f));
       } else if (MODE == 1) {
         plane[slot] = v;
       } else if (MODE == 2) {
@@ -59,7 +62,7 @@ __global__ void __launch_bounds__(256, 5) k(float* plane, uint32_t slot_mask, ui
 template <int MODE>
 static void run(const char* name, uint32_t foot_mb, uint32_t copies, uint32_t lane_keep, uint32_t alu, float* plane, uint2* log, uint32_t* cnt, float* sink) {
   const uint32_t blocks = 6104, iters = 512;
-  const uint32_t slots = (foot_mb << 20) / 4u / copies;
+  const uint32_t slots = (foot_mb << 20) / (MODE == 5 ? 8u : 4u) / copies;   // (foot_mb <= 1024: inside the 1 GB plane either way)
   uint32_t shift = 0;
   while ((1u << shift) < slots) shift++;
   hipMemset(cnt, 0, 256 * 64);
@@ -96,6 +99,11 @@ int main() {
       run<0>("atomic_add_f32", 64, 1, lanes, alu, plane, log, cnt, sink);
       run<0>("atomic_add_f32", 1024, 1, lanes, alu, plane, log, cnt, sink);
       run<0>("atomic_add_f32", 1, 1, lanes, alu, plane, log, cnt, sink);
+      run<5>("atomic_add_u64", 16, 1, lanes, alu, plane, log, cnt, sink);
+      run<5>("atomic_add_u64", 128, 8, lanes, alu, plane, log, cnt, sink);
+      run<5>("atomic_add_u64", 128, 1, lanes, alu, plane, log, cnt, sink);
+      run<5>("atomic_add_u64", 1024, 1, lanes, alu, plane, log, cnt, sink);
+      run<5>("atomic_add_u64", 2, 1, lanes, alu, plane, log, cnt, sink);
       run<1>("plain store", 64, 8, lanes, alu, plane, log, cnt, sink);
       run<2>("per-wave log store", 64, 8, lanes, alu, plane, log, cnt, sink);
       run<3>("shard log (ret. atomic)", 64, 8, lanes, alu, plane, log, cnt, sink);

@@ -116,7 +116,8 @@ ROOT_GEN, ROOT_TRANSIT = 1, 2                                                   
 
 
 ACCUM_XYZ, ACCUM_SCALAR, ACCUM_BIN1, ACCUM_BIN2, ACCUM_LOG, ACCUM_LOG_XYZ, ACCUM_NONE = 1, 2, 4, 8, 16, 32, 64   # HaloRouteInfo.accum_mask bits
-ACCUM_FIXED = 128   # ... fixed-point planes (option "deterministic"): beside it only ACCUM_NONE may be set
+ACCUM_FIXED = 128   # ... fixed-point planes (option "deterministic"): beside it ACCUM_NONE, and ACCUM_LOG or ACCUM_LOG_XYZ for launches that took the hit log's integer twins
+ACCUM_FIXED_LOG, ACCUM_FIXED_LOG_XYZ = ACCUM_FIXED | ACCUM_LOG, ACCUM_FIXED | ACCUM_LOG_XYZ   # a deterministic session whose launches were logged (scalar plane; X, Y, Z planes)
 
 
 class HaloGeomTables(C.Structure):

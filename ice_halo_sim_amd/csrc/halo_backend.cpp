@@ -1044,7 +1044,7 @@ struct LaunchPlan {
   int geom = 0, blocks = 0;             // geom: 0 = one shape per dispatch, 1 = pool of ShapeDev records, 2 = pool of ShapePrism records (device-generated prisms)
   uint32_t shape_cnt = 1;
   bool use_bin = false, two_level = false, use_log = false, use_log_xyz = false, canon = false, no_land = false;
-  bool fixed = false;                   // a deterministic session's launch: the kAccFixed kernels (or, where every exit continues, kAccNone)
+  bool fixed = false;                   // a deterministic session's launch: the kAccFixed kernels, with use_log their logging twins (or, where every exit continues, kAccNone)
   uint32_t fan_log2 = 0, lists1 = 0, bin_tiles = 0, log_t_log2 = 0, log_planes = 1, log_tiles = 0;
   uint64_t cap1 = 0, cap2 = 0;          // records per region / coarse list and per tile list, as REQUESTED: reserve_log_buffers clamps the log's against free memory
   // (Round 6: a LOGGED trace kernel writes records, its region counts and the twin's other half — nothing the closing fold of the session
@@ -1052,7 +1052,8 @@ struct LaunchPlan {
   //  discrete spectrum of many short sessions (bench.py --config 4d: 31 x 0.8 M rays) was one serial chain of generator, trace, split, sums
   //  and fold, 325 us per session; the trace kernel and generator of session k + 1 now run beside the passes and the fold of session k.
   //  Launches that fill the chip keep the old order: measured in round 5, nothing to gain there and the kernel's own span stretches.)
-  bool under_fold() const { return use_log && alternate; }
+  // (A deterministic logged launch flushes its integer cache onto the planes from the trace kernel itself: it waits for the fold, as a direct one does.)
+  bool under_fold() const { return use_log && alternate && !fixed; }
 };
 // What a launch was given when it was queued: its dispatch-ring slot, log buffer set, shape pool and the first index of its shape stream.
 struct LaunchSlots { int k = 0, ls = 0, shape_set = 0; uint64_t first_shape = 0; };
@@ -1142,7 +1143,8 @@ void plan_route(const HaloBackend& b, const LayerCtx& c, bool fast_mode, LaunchP
                              (static_cast<uint64_t>(b.plane_cnt) << (s_log2 + 10u)) <= (1ull << 31) && b.hit_log != 0 && b.bin <= 0;
   // (a layer before the last under canonical continuation order takes direct accumulation: only those kernels have CANON twins)
   p.canon = b.cont_order && !c.final_layer;
-  p.fixed = b.det_session;   // neither lists nor log: every accumulating launch of a deterministic session adds integers
+  p.fixed = b.det_session;   // every accumulating launch of a deterministic session adds integers: directly, or through the hit log's integer twins — never lists
+  const bool fixed_xyz = p.fixed && !b.mono_session;   // ... on X, Y, Z planes (a deterministic session has no plane per pool entry)
   p.use_bin = !p.fixed && !p.canon && b.mono_session && b.aggregate == 1 && !b.capture && bin_shape_ok && bin_slots <= (1ull << 31) &&
               // own choice: only where the hit log cannot go (one plane per pool entry on a larger image) — the log beats the binned route
               // on every launch measured (tools/bin_vs_log_probe.py: dual fisheye 50 M rays 5.13 -> 4.42 ms)
@@ -1158,14 +1160,19 @@ void plan_route(const HaloBackend& b, const LayerCtx& c, bool fast_mode, LaunchP
   // (a small launch takes 256 tiles: its per-tile pass is one workgroup per tile, and 128 of them leave half the chip idle — config 4d 2.85 -> 3.18 G rays/s; big launches keep 128 for the split's longer runs)
   const uint32_t asked_t_log2 = static_cast<uint32_t>(m < (4ull << 20) ? std::max(b.log_tiles_log2, 8) : b.log_tiles_log2);
   const uint32_t scalar_t_log2 = std::max<uint32_t>(wl_t_log2, std::min<uint32_t>(asked_t_log2, s_log2 + 2u));   // tiles of 256 .. 16 Ki slots
-  p.log_t_log2 = log_planes_ok ? wl_t_log2 : b.xyz_log ? std::min<uint32_t>(9u, s_log2 + 2u) : scalar_t_log2;
+  p.log_t_log2 = log_planes_ok ? wl_t_log2 : (b.xyz_log || fixed_xyz) ? std::min<uint32_t>(9u, s_log2 + 2u) : scalar_t_log2;
   p.log_planes = log_planes_ok ? b.plane_cnt : 1u;
   p.log_tiles = p.log_planes << p.log_t_log2;   // lists the split pass feeds
-  const bool log_layout_ok = b.xyz_log ? (s_log2 <= 11u) : (b.mono_session && (log_planes_ok || (!b.mono_by_wl && s_log2 <= 12u)));
-  p.use_log = !p.fixed && !p.canon && !p.use_bin && log_layout_ok && b.aggregate == 1 && fast_mode &&
+  const bool log_layout_ok = (b.xyz_log || fixed_xyz) ? (s_log2 <= 11u) : (b.mono_session && (log_planes_ok || (!b.mono_by_wl && s_log2 <= 12u)));
+  // (aggregate = 0 under a forced log — every hit a record — exists in deterministic sessions only, where the cache is a run-time branch of accumulate_fixed)
+  const bool log_agg_ok = b.aggregate == 1 || (p.fixed && b.aggregate == 0 && b.hit_log > 0);
+  p.use_log = !p.canon && !p.use_bin && log_layout_ok && log_agg_ok && fast_mode &&
               (L.prob < 1.0f || c.final_layer) &&   // a layer whose every exit continues puts nothing on the image
-              (b.hit_log < 0 ? m >= ((b.mono_session && !b.mono_by_wl) ? log_min_rays(b.render.visible) : (2ull << 20)) : b.hit_log != 0);
-  p.use_log_xyz = p.use_log && b.xyz_log;
+              // (own choice in a deterministic session: from 2 Mi rays on either plane layout and whatever the visible range — the float route's
+              //  512 Ki for full-sky scalar sessions buys nothing there: the integer log neither starts under the previous fold nor has two plane
+              //  sets, and bench.py --config 4d measured 10.96 ms per step logged against 10.79 direct)
+              (b.hit_log < 0 ? m >= (p.fixed ? (2ull << 20) : (b.mono_session && !b.mono_by_wl) ? log_min_rays(b.render.visible) : (2ull << 20)) : b.hit_log != 0);
+  p.use_log_xyz = p.use_log && (b.xyz_log || fixed_xyz);
   p.no_land = L.prob >= 1.0f && !c.final_layer && fast_mode && b.aggregate == 1;
   if (p.use_log) {
     // a region takes 4 records per ray of its workgroup (configs[1]: 1.2 logged per ray), 8 for full-sky renders (5-6 per ray),
@@ -1469,21 +1476,22 @@ void record_route(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, 
   const bool ran_hex = launch_geom == 3 && fast_mode && (P.bin_list == nullptr || P.bin_log != 0u || P.no_land != 0u);
   const bool ran_none = P.no_land != 0u && p.geom == 0;
   b->route.geom_mask |= 1u << (launch_geom == 3 && !ran_hex ? 0 : launch_geom);
-  b->route.accum_mask |= ran_none ? 64u : p.fixed ? 128u : p.use_log ? (p.use_log_xyz ? 32u : 16u) : (p.use_bin ? (p.two_level ? 8u : 4u) : (b->mono_session ? 2u : 1u));
+  b->route.accum_mask |= ran_none ? 64u : p.fixed ? (128u | (p.use_log ? (p.use_log_xyz ? 32u : 16u) : 0u)) : p.use_log ? (p.use_log_xyz ? 32u : 16u) : (p.use_bin ? (p.two_level ? 8u : 4u) : (b->mono_session ? 2u : 1u));
   // specialisations (plain kernels only; launch_lens / launch_vis / launch_mono): bit 0 last-layer kernel (no continuation code), 1 lens as a
   // constant, 2 visible range as a constant, 3 closed gate as a constant
   const bool one = p.geom == 0, lens_known = P.proj.proj_type == HALO_LENS_LINEAR || P.proj.proj_type == HALO_LENS_FISHEYE_EQUAL_AREA ||
                                              P.proj.proj_type == HALO_LENS_DUAL_FISHEYE_EQUAL_AREA || P.proj.proj_type == HALO_LENS_RECTANGULAR;
   const bool vis_known = P.proj.visible_range == HALO_VISIBLE_UPPER || P.proj.visible_range == HALO_VISIBLE_FULL;
   uint32_t spec = 0u;
-  if (fast_mode && p.use_log && one && !ran_none && b->mono_session && P.final_layer) {
+  const bool logged = p.use_log && !p.fixed;   // (the fixed-point kernels, logging or not, exist in the generic run-time lens form only)
+  if (fast_mode && logged && one && !ran_none && b->mono_session && P.final_layer) {
     spec |= 1u;
     if ((mode == 0 || mode == 1) && P.prob <= 0.0f && lens_known && vis_known) spec |= 2u | 4u | 8u;
   }
-  if (fast_mode && p.use_log && one && !ran_none && b->mono_session && !P.final_layer && (mode == 0 || mode == 1) && lens_known && vis_known)
+  if (fast_mode && logged && one && !ran_none && b->mono_session && !P.final_layer && (mode == 0 || mode == 1) && lens_known && vis_known)
     spec |= 2u | 4u;   // (round 6: the logging kernels of the layers before the last know their lens and visible range too; their gate is open)
-  if (mode == 0 && p.use_log && !one && !b->mono_session && P.prob <= 0.0f && P.proj.visible_range == HALO_VISIBLE_FULL) spec |= 4u | 8u;
-  if (mode == 0 && p.use_log && !one && P.prob <= 0.0f && P.proj.visible_range == HALO_VISIBLE_FULL && P.proj.proj_type == HALO_LENS_RECTANGULAR)
+  if (mode == 0 && logged && !one && !b->mono_session && P.prob <= 0.0f && P.proj.visible_range == HALO_VISIBLE_FULL) spec |= 4u | 8u;
+  if (mode == 0 && logged && !one && P.prob <= 0.0f && P.proj.visible_range == HALO_VISIBLE_FULL && P.proj.proj_type == HALO_LENS_RECTANGULAR)
     spec |= 2u | 4u | 8u;   // (shape-pool kernels, either plane layout: bench_config_stoch.json's render as constants)
   b->route.spec_mask |= spec;
   if (spec == 0u) b->route.generic_launches++;
@@ -1528,13 +1536,19 @@ int queue_passes(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, c
   }
   HIPCHK(b, hipEventRecord(b->ring_ev2[k], ps));
   HIPCHK(b, hipMemsetAsync(bin_cnt2.ptr, 0, static_cast<size_t>(p.log_tiles) * 16u * sizeof(uint32_t), ps));
-  hipError_t be = p.use_log_xyz ? launch_log_route_xyz(P.mono, P.log_plane_stride, bin_list.ptr, P.bin_cap, bin_cnt.ptr, static_cast<uint32_t>(p.blocks),
+  // (a deterministic launch: the integer twins of the passes, onto the integer planes with the pending plane set's F.  Every writer of those planes
+  //  adds with an integer atomic, so the passes take no `before_sums` and leave no rmw marker: nothing has to be ordered against them but the fold.)
+  hipError_t be = p.fixed ? (p.use_log_xyz ? launch_log_route_xyz_fixed(P.fix, P.log_plane_stride, bin_list.ptr, P.bin_cap, bin_cnt.ptr, static_cast<uint32_t>(p.blocks), bin_list2.ptr, cap2,
+                                                                        bin_cnt2.ptr, p.log_tiles, b->mono_s_log2, P.wl_pool, P.wl_pool_size, b->fix_frac, ps)
+                                           : launch_log_route_fixed(P.fix, bin_list.ptr, P.bin_cap, bin_cnt.ptr, static_cast<uint32_t>(p.blocks), bin_list2.ptr, cap2, bin_cnt2.ptr,
+                                                                    1u << p.log_t_log2, b->mono_s_log2, b->render.visible == HALO_VISIBLE_FULL, b->fix_frac, ps))
+                  : p.use_log_xyz ? launch_log_route_xyz(P.mono, P.log_plane_stride, bin_list.ptr, P.bin_cap, bin_cnt.ptr, static_cast<uint32_t>(p.blocks),
                                                        bin_list2.ptr, cap2, bin_cnt2.ptr, p.log_tiles, b->mono_s_log2, P.wl_pool, P.wl_pool_size, frac_bits, P.ovf, P.ovf_flag, P.ovf_copies_log2, ps, before_sums)
                                 : launch_log_route(P.mono, bin_list.ptr, P.bin_cap, bin_cnt.ptr, static_cast<uint32_t>(p.blocks), bin_list2.ptr, cap2,
                                                    bin_cnt2.ptr, 1u << p.log_t_log2, p.log_planes, b->mono_s_log2, b->render.visible == HALO_VISIBLE_FULL, frac_bits,
                                                    P.ovf, P.ovf_flag, P.ovf_copies_log2, ps, before_sums);
   if (be != hipSuccess) return hip_fail(b, be, "halo_split_kernel launch");
-  if (b->overlap) HIPCHK(b, b->rmw[ts_i].mark(ps));
+  if (b->overlap && !p.fixed) HIPCHK(b, b->rmw[ts_i].mark(ps));
   HIPCHK(b, hipEventRecord(b->ring_ev3[k], ps));
   HIPCHK(b, b->set_free[S.ls].mark(ps));
   if (b->overlap && p.alternate) b->log_set ^= 1;
@@ -1555,7 +1569,7 @@ int queue_launch(HaloBackend* b, const LaunchPlan& p, const HaloEntry& E, EntryT
 #ifndef HALO_NO_PLANE_GATES   // (defined only to see tests/test_gpu_production_routes.py's two-stream test fail without the gates)
   if (b->overlap && !p.use_log)   // this trace kernel adds to the planes itself: behind the other stream's sums
     HIPCHK(b, b->rmw[ts_i ^ 1].wait_on(ts));
-  if (b->overlap && (p.use_log || (p.use_bin && p.two_level)) && b->cs_pending[ts_i ^ 1]) {
+  if (b->overlap && ((p.use_log && !p.fixed) || (p.use_bin && p.two_level)) && b->cs_pending[ts_i ^ 1]) {
     HIPCHK(b, hipEventRecord(b->ev_gate, b->cs[ts_i ^ 1]));
     before_sums = b->ev_gate;
   }

@@ -151,11 +151,17 @@ __device__ __forceinline__ void split_overflow(float* plane, const SplitXyz& x, 
     atomic_add_f32(plane + off, v);
   }
 }
-template <uint32_t kSplitBlock, uint32_t kSplitPer, uint32_t kSplitFanMax, bool kXyz, bool kMix>
-__global__ void __launch_bounds__(kSplitBlock) halo_split_kernel(float* __restrict__ plane, const uint2* __restrict__ list1, uint32_t cap1,
-                                                                 const uint32_t* __restrict__ cnt1, uint32_t cnt1_stride, uint32_t parts,
-                                                                 uint2* __restrict__ list2, uint32_t cap2, uint32_t* __restrict__ cnt2, uint32_t fan_log2,
-                                                                 uint32_t coarse, uint32_t slot_mask, uint32_t tile_log2, uint32_t mix_log2, SplitXyz xyz) {
+// The deterministic route's log (kFix instantiations: halo_split_fixed_kernel) differs in the fallback alone: a record that finds its tile list
+// full is quantised with the session's F — X/Y/Z: the three fp32 products first — and added to the integer planes with integer atomics.
+struct SplitFix {
+  unsigned long long* planes;  // DispatchParams::fix
+  uint32_t frac_bits;          // the session's F
+};
+template <uint32_t kSplitBlock, uint32_t kSplitPer, uint32_t kSplitFanMax, bool kXyz, bool kMix, bool kFix>
+__device__ __forceinline__ void split_body(float* __restrict__ plane, const uint2* __restrict__ list1, uint32_t cap1,
+                                           const uint32_t* __restrict__ cnt1, uint32_t cnt1_stride, uint32_t parts,
+                                           uint2* __restrict__ list2, uint32_t cap2, uint32_t* __restrict__ cnt2, uint32_t fan_log2,
+                                           uint32_t coarse, uint32_t slot_mask, uint32_t tile_log2, uint32_t mix_log2, const SplitXyz& xyz, const SplitFix& fix) {
   __shared__ __attribute__((aligned(16))) uint32_t s_cnt[kSplitFanMax];
   __shared__ __attribute__((aligned(16))) uint32_t s_off[kSplitFanMax];
   __shared__ uint32_t s_base[kSplitFanMax];
@@ -236,6 +242,21 @@ __global__ void __launch_bounds__(kSplitBlock) halo_split_kernel(float* __restri
       const uint32_t pos = s_base[t] + (i - s_off[t]);
       if (pos < cap2) {
         list2[static_cast<size_t>(tile0 + t) * cap2 + pos] = r;
+      } else if constexpr (kFix) {
+        const FixQ fq(fix.frac_bits);
+        const float w = __uint_as_float(r.y);
+        if constexpr (kXyz) {
+          const uint32_t code = r.x >> kLogWlShift;
+          if (code < xyz.pool_size) {   // (a deterministic launch logs pool entries only: no unit rows)
+            const WlEntryDev e = xyz.pool[code];
+            unsigned long long* at = fix.planes + (r.x & slot_mask);
+            atomicAdd(at, fq.fix(e.cmf_x * w));
+            atomicAdd(at + xyz.plane_stride, fq.fix(e.cmf_y * w));
+            atomicAdd(at + 2u * static_cast<size_t>(xyz.plane_stride), fq.fix(e.cmf_z * w));
+          }
+        } else {
+          atomicAdd(fix.planes + r.x, fq.fix(w));
+        }
       } else if (kXyz) {
         const uint32_t code = r.x >> kLogWlShift;
         float c[3];
@@ -255,11 +276,31 @@ __global__ void __launch_bounds__(kSplitBlock) halo_split_kernel(float* __restri
     __syncthreads();
   }
 }
+template <uint32_t kSplitBlock, uint32_t kSplitPer, uint32_t kSplitFanMax, bool kXyz, bool kMix>
+__global__ void __launch_bounds__(kSplitBlock) halo_split_kernel(float* __restrict__ plane, const uint2* __restrict__ list1, uint32_t cap1,
+                                                                 const uint32_t* __restrict__ cnt1, uint32_t cnt1_stride, uint32_t parts,
+                                                                 uint2* __restrict__ list2, uint32_t cap2, uint32_t* __restrict__ cnt2, uint32_t fan_log2,
+                                                                 uint32_t coarse, uint32_t slot_mask, uint32_t tile_log2, uint32_t mix_log2, SplitXyz xyz) {
+  split_body<kSplitBlock, kSplitPer, kSplitFanMax, kXyz, kMix, false>(plane, list1, cap1, cnt1, cnt1_stride, parts, list2, cap2, cnt2, fan_log2, coarse, slot_mask, tile_log2,
+                                                                      mix_log2, xyz, SplitFix{nullptr, 0u});
+}
+template <uint32_t kSplitBlock, uint32_t kSplitPer, uint32_t kSplitFanMax, bool kXyz, bool kMix>
+__global__ void __launch_bounds__(kSplitBlock) halo_split_fixed_kernel(const uint2* __restrict__ list1, uint32_t cap1, const uint32_t* __restrict__ cnt1,
+                                                                       uint2* __restrict__ list2, uint32_t cap2, uint32_t* __restrict__ cnt2, uint32_t fan_log2,
+                                                                       uint32_t slot_mask, uint32_t tile_log2, uint32_t mix_log2, SplitXyz xyz, SplitFix fix) {
+  split_body<kSplitBlock, kSplitPer, kSplitFanMax, kXyz, kMix, true>(nullptr, list1, cap1, cnt1, 1u, 1u, list2, cap2, cnt2, fan_log2, 0u, slot_mask, tile_log2, mix_log2, xyz, fix);
+}
 
 // One workgroup per tile of 16 Ki CONSECUTIVE slots: sums the tile's list in LDS and adds the tile to the plane with plain
 // coalesced float4 read-modify-writes — the workgroup is the only writer of those slots while this kernel runs (direct
 // atomics of the trace / split kernels are ordered before it on the stream).
-__global__ void __launch_bounds__(kBinBlock) halo_bin_accumulate_range_kernel(float* __restrict__ plane, const uint2* __restrict__ list, uint32_t cap,
+// (kFix, the deterministic route's integer twin: `plane` is the integer plane, frac_bits the session's F, and the write-out ADDS the LDS integers
+// to it — no-return 64-bit atomics for the non-zero slots, so it needs no ordering against any other writer.  The float instantiation's code is
+// what it was.)
+template <bool kFix>
+using PlaneOf = typename std::conditional<kFix, unsigned long long, float>::type;
+template <bool kFix = false>
+__global__ void __launch_bounds__(kBinBlock) halo_bin_accumulate_range_kernel(PlaneOf<kFix>* __restrict__ plane, const uint2* __restrict__ list, uint32_t cap,
                                                                                const uint32_t* __restrict__ cnt, uint32_t tile_log2, uint32_t frac_bits) {
   __shared__ __attribute__((aligned(16))) unsigned long long acc[1u << kBinTileLog2];   // fixed point (FixQ); tile_log2 <= kBinTileLog2
   const FixQ fq(frac_bits);
@@ -315,6 +356,13 @@ __global__ void __launch_bounds__(kBinBlock) halo_bin_accumulate_range_kernel(fl
     atomicAdd(&acc[h.x & mask], fq.fix(__uint_as_float(h.y)));
   }
   __syncthreads();
+  if constexpr (kFix) {
+    unsigned long long* dst = plane + (static_cast<size_t>(tile) << tile_log2);
+    for (uint32_t j = threadIdx.x; j < slots; j += kBinBlock) {
+      const unsigned long long v = acc[j];
+      if (v != 0ull) atomicAdd(&dst[j], v);
+    }
+  } else {
   float4* dst = reinterpret_cast<float4*>(plane + (static_cast<size_t>(tile) << tile_log2));
   for (uint32_t j = threadIdx.x; j < slots / 4u; j += kBinBlock) {
     const float4 v = make_float4(fq.unfix(acc[4u * j]), fq.unfix(acc[4u * j + 1u]), fq.unfix(acc[4u * j + 2u]), fq.unfix(acc[4u * j + 3u]));
@@ -327,6 +375,7 @@ __global__ void __launch_bounds__(kBinBlock) halo_bin_accumulate_range_kernel(fl
       dst[j] = q;
     }
   }
+  }
 }
 
 // The hit log's per-tile pass.  CH = 1: one scalar plane (discrete wavelength), records {slot, w}, tiles of 16 Ki slots.
@@ -338,8 +387,9 @@ __global__ void __launch_bounds__(kBinBlock) halo_bin_accumulate_range_kernel(fl
 // the pass has one workgroup per tile, and a 512 x 256 image cut into 16 Ki-slot tiles would leave it 8 workgroups.  A tile's
 // slots are scattered, so its write-out is plain 4-byte read-modify-writes (the workgroup is the only writer of its slots
 // while this kernel runs).
-template <uint32_t CH>
-__global__ void __launch_bounds__(kBinBlock) halo_log_accumulate_kernel(float* __restrict__ planes, uint32_t plane_stride, const uint2* __restrict__ list, uint32_t cap,
+// (kFix, the deterministic route's integer twins: as in halo_bin_accumulate_range_kernel.)
+template <uint32_t CH, bool kFix = false>
+__global__ void __launch_bounds__(kBinBlock) halo_log_accumulate_kernel(PlaneOf<kFix>* __restrict__ planes, uint32_t plane_stride, const uint2* __restrict__ list, uint32_t cap,
                                                                         const uint32_t* __restrict__ cnt, const WlEntryDev* __restrict__ pool, uint32_t pool_size,
                                                                         uint32_t tiles_log2, uint32_t s_log2, uint32_t frac_bits) {
   constexpr uint32_t kTileLog2 = CH == 3u ? 12u : 14u;
@@ -430,10 +480,15 @@ __global__ void __launch_bounds__(kBinBlock) halo_log_accumulate_kernel(float* _
   }
   __syncthreads();
   for (uint32_t c = 0; c < CH; ++c) {
-    float* dst = planes + static_cast<size_t>(c) * plane_stride + (static_cast<size_t>(plane_of_tile) << (s_log2 + 10u));
+    PlaneOf<kFix>* dst = planes + static_cast<size_t>(c) * plane_stride + (static_cast<size_t>(plane_of_tile) << (s_log2 + 10u));
     for (uint32_t j = threadIdx.x; j < slots; j += kBinBlock) {
+      if constexpr (kFix) {
+        const unsigned long long v = acc[c][j];
+        if (v != 0ull) atomicAdd(&dst[map.slot_of(tile_in, j)], v);
+      } else {
       const float v = fq.unfix(acc[c][j]);
       if (v != 0.0f) dst[map.slot_of(tile_in, j)] += v;
+      }
     }
   }
 }
@@ -472,7 +527,7 @@ hipError_t launch_log_route(float* plane, const HitRec* log, uint32_t cap1, cons
   if (interleaved)
     hipLaunchKernelGGL((halo_log_accumulate_kernel<1u>), dim3(tiles), dim3(kBinBlock), 0, stream, plane, 0u, reinterpret_cast<const uint2*>(list2), cap2, cnt2,
                        static_cast<const WlEntryDev*>(nullptr), 0u, tiles_log2, s_log2, frac_bits);
-  else hipLaunchKernelGGL(halo_bin_accumulate_range_kernel, dim3(tiles), dim3(kBinBlock), 0, stream, plane, reinterpret_cast<const uint2*>(list2), cap2, cnt2, tile_log2, frac_bits);
+  else hipLaunchKernelGGL((halo_bin_accumulate_range_kernel<false>), dim3(tiles), dim3(kBinBlock), 0, stream, plane, reinterpret_cast<const uint2*>(list2), cap2, cnt2, tile_log2, frac_bits);
   return hipGetLastError();
 }
 
@@ -491,6 +546,53 @@ hipError_t launch_log_route_xyz(float* planes, uint32_t plane_stride, const HitR
   return hipGetLastError();
 }
 
+// The deterministic route's log (halo_backend.cpp: a kAccFixedLog trace kernel wrote the regions): the same split — only its full-list fallback
+// differs — and the integer twins of the per-tile sums, with the SESSION's F.  Every write to the integer planes is an atomic add of integers, so the
+// passes need no ordering against another stream's cache flushes, overflow adds or sums (no `before_sums`), and the planes hold the same integers
+// whatever ran when.  One scalar plane, `tiles` (a power of two <= 512) tiles: contiguous ones unless `interleaved`.
+hipError_t launch_log_route_fixed(unsigned long long* fix, const HitRec* log, uint32_t cap1, const uint32_t* cnt1, uint32_t regions, HitRec* list2, uint32_t cap2,
+                                  uint32_t* cnt2, uint32_t tiles, uint32_t s_log2, bool interleaved, uint32_t frac_bits, hipStream_t stream) {
+  const uint32_t tiles_log2 = static_cast<uint32_t>(__builtin_ctz(tiles)), tile_log2 = s_log2 + 10u - tiles_log2;   // slots per tile <= 16 Ki
+  if (tiles > 512u || tile_log2 > kBinTileLog2) return hipErrorInvalidValue;
+  const uint2* l1 = reinterpret_cast<const uint2*>(log);
+  uint2* l2 = reinterpret_cast<uint2*>(list2);
+  const SplitXyz none{nullptr, 0u, 0u, nullptr, nullptr, 0u, 0u};
+  const SplitFix sf{fix, frac_bits};
+  const bool mix = interleaved || tiles > 256u;
+  if (tiles > 256u)
+    hipLaunchKernelGGL((halo_split_fixed_kernel<kLogSplitThreads, kLogSplitPer, 512u, false, true>), dim3(regions), dim3(kLogSplitThreads), 0, stream, l1, cap1, cnt1, l2, cap2, cnt2,
+                       tiles_log2, 0xFFFFFFFFu, 0u, s_log2, none, sf);
+  else if (mix)
+    hipLaunchKernelGGL((halo_split_fixed_kernel<kLogSplitThreads, kLogSplitPer, 256u, false, true>), dim3(regions), dim3(kLogSplitThreads), 0, stream, l1, cap1, cnt1, l2, cap2, cnt2,
+                       tiles_log2, 0xFFFFFFFFu, 0u, s_log2, none, sf);
+  else
+    hipLaunchKernelGGL((halo_split_fixed_kernel<kLogSplitThreads, kLogSplitPer, 256u, false, false>), dim3(regions), dim3(kLogSplitThreads), 0, stream, l1, cap1, cnt1, l2, cap2, cnt2,
+                       tiles_log2, 0xFFFFFFFFu, tile_log2, 0u, none, sf);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (mix)
+    hipLaunchKernelGGL((halo_log_accumulate_kernel<1u, true>), dim3(tiles), dim3(kBinBlock), 0, stream, fix, 0u, reinterpret_cast<const uint2*>(list2), cap2, cnt2,
+                       static_cast<const WlEntryDev*>(nullptr), 0u, tiles_log2, s_log2, frac_bits);
+  else hipLaunchKernelGGL((halo_bin_accumulate_range_kernel<true>), dim3(tiles), dim3(kBinBlock), 0, stream, fix, reinterpret_cast<const uint2*>(list2), cap2, cnt2, tile_log2, frac_bits);
+  return hipGetLastError();
+}
+
+// ... and for X, Y, Z planes: `tiles` (a power of two <= 512) interleaved tiles of <= 4 Ki slots of one plane
+hipError_t launch_log_route_xyz_fixed(unsigned long long* fix, uint32_t plane_stride, const HitRec* log, uint32_t cap1, const uint32_t* cnt1, uint32_t regions, HitRec* list2,
+                                      uint32_t cap2, uint32_t* cnt2, uint32_t tiles, uint32_t s_log2, const WlEntryDev* pool, uint32_t pool_size, uint32_t frac_bits,
+                                      hipStream_t stream) {
+  const uint32_t tiles_log2 = static_cast<uint32_t>(__builtin_ctz(tiles));
+  if (tiles > 512u || s_log2 + 10u - tiles_log2 > 12u || pool_size > HALO_WL_POOL_MAX) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((halo_split_fixed_kernel<kLogSplitThreads, kLogSplitPer, 512u, true, true>), dim3(regions), dim3(kLogSplitThreads), 0, stream, reinterpret_cast<const uint2*>(log), cap1, cnt1,
+                     reinterpret_cast<uint2*>(list2), cap2, cnt2, tiles_log2, (1u << kLogWlShift) - 1u, 0u, s_log2, SplitXyz{pool, pool_size, plane_stride, nullptr, nullptr, 0u, 0u},
+                     SplitFix{fix, frac_bits});
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((halo_log_accumulate_kernel<3u, true>), dim3(tiles), dim3(kBinBlock), 0, stream, fix, plane_stride, reinterpret_cast<const uint2*>(list2), cap2, cnt2,
+                     pool, pool_size, tiles_log2, s_log2, frac_bits);
+  return hipGetLastError();
+}
+
 hipError_t launch_bin_two_level(float* plane, const HitRec* list1, uint32_t cap1, uint32_t* cnt1, uint32_t lists1, HitRec* list2, uint32_t cap2,
                                 uint32_t* cnt2, uint32_t tiles, uint32_t fan_log2, uint32_t frac_bits, double* ovf, uint32_t* ovf_flag, hipStream_t stream, hipEvent_t before_sums) {
   hipLaunchKernelGGL((halo_split_kernel<256u, 16u, 256u, false, false>), dim3(lists1 * kSplitParts), dim3(256u), 0, stream, plane, reinterpret_cast<const uint2*>(list1), cap1,
@@ -499,7 +601,7 @@ hipError_t launch_bin_two_level(float* plane, const HitRec* list1, uint32_t cap1
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (before_sums && (e = hipStreamWaitEvent(stream, before_sums, 0)) != hipSuccess) return e;
-  hipLaunchKernelGGL(halo_bin_accumulate_range_kernel, dim3(tiles), dim3(kBinBlock), 0, stream, plane, reinterpret_cast<const uint2*>(list2), cap2, cnt2,
+  hipLaunchKernelGGL((halo_bin_accumulate_range_kernel<false>), dim3(tiles), dim3(kBinBlock), 0, stream, plane, reinterpret_cast<const uint2*>(list2), cap2, cnt2,
                      static_cast<uint32_t>(kBinTileLog2), frac_bits);
   return hipGetLastError();
 }

@@ -565,6 +565,7 @@ static_assert(offsetof(FixCache<true>, val) % 8 == 0 && offsetof(FixCache<false>
 // hotter than average) fall back to the direct atomic, so capacity is a speed matter only.
 constexpr int kAccDirect = 0, kAccBin = 1, kAccLog = 2, kAccNone = 3, kAccLogFinal = 4;   // halo_trace_kernel ACC (None: a layer whose every exit continues — nothing lands)
 constexpr int kAccFixed = 5;   // the integer twin of kAccDirect (option "deterministic"): FixCache in LDS, 64-bit integer atomics onto DispatchParams::fix
+constexpr int kAccFixedLog = 6;   // ... and of the logging kernels: the same cache, but a hit that loses the claim leaves as a raw {slot, weight} record (log_hit_fixed)
 constexpr int kHitBuf = 1536;                 // staged hits per workgroup (16 KB)
 // (kBinTileLog2, slots per tile, and kBinCntStride, the spacing of the tile counters: halo_device.h)
 constexpr int kBinMaxTiles = 512;
@@ -624,7 +625,7 @@ struct ProjLds {
 };
 static_assert(offsetof(ProjLds, half_w) == sizeof(ProjDev) && offsetof(DispatchParams, proj_pre) == offsetof(DispatchParams, proj) + sizeof(ProjDev),
               "the four floats lie directly behind the ProjDev, in LDS and in the dispatch record");
-template <bool MONO, bool SMALLC>
+template <bool MONO, bool SMALLC, bool FIXLOG = false>   // FIXLOG: the context of a kAccFixedLog kernel (a type, so that no other kernel compiles its branch)
 struct AccCtx {
   int lens, vis;     // >= 0: instantiated for this lens / visible range (the projection's dispatch folds away)
   bool nogate;       // instantiated for prob <= 0: no candidate ever passes the gate, the gate stream and its code fold away
@@ -719,8 +720,31 @@ HD uint32_t log_slot_xyz(const DispatchParams& P, uint32_t code, uint32_t pix) {
 HD unsigned long long* fix_slot(const DispatchParams& P, uint32_t pl, uint32_t pix) {
   return P.fix + (static_cast<size_t>(pl) << (P.mono_s_log2 + 10u)) + MonoSlot(pix, P.mono_s_log2);
 }
-template <bool MONO, bool SMALLC>
-HD void accumulate_fixed(const DispatchParams& P, const AccCtx<MONO, SMALLC>& ctx, uint32_t pix, float w, float cx, float cy, float cz) {
+// The hit log of the deterministic route (kAccFixedLog kernels): log_hit's mechanism — cursor in LDS, one ds_add_rtn per wave and call, no global
+// atomic — with the RAW fp32 weight in the record: the per-tile passes quantise it with the session's F by the rule used here (X/Y/Z: of the same
+// fp32 products cmf * w), so the planes end up holding the integers the direct route adds.  A record that finds its region full is added here, as
+// the integers q0 (, q1, q2) the caller has made of it: never to the fp64 twin, never to a float plane.
+template <bool MONO>
+HD void log_hit_fixed(const DispatchParams& P, uint32_t* log_n, uint32_t pix, uint32_t wl_idx, float w, unsigned long long q0, unsigned long long q1, unsigned long long q2) {
+  const uint64_t mask = __ballot(1);
+  const uint32_t before = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
+  uint32_t base = 0u;
+  if (before == 0u) base = atomicAdd(log_n, static_cast<uint32_t>(__popcll(mask)));
+  const uint32_t idx = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(base))) + before;
+  if (idx < P.bin_cap) {
+    reinterpret_cast<uint2*>(P.bin_list)[static_cast<size_t>(blockIdx.x) * P.bin_cap + idx] =
+        make_uint2(MONO ? log_slot(P, 0u, pix) : log_slot_xyz(P, wl_idx, pix), __float_as_uint(w));
+    return;
+  }
+  atomicAdd(fix_slot(P, 0u, pix), q0);
+  if (!MONO) {
+    atomicAdd(fix_slot(P, 1u, pix), q1);
+    atomicAdd(fix_slot(P, 2u, pix), q2);
+  }
+}
+
+template <bool MONO, bool SMALLC, bool FL>
+HD void accumulate_fixed(const DispatchParams& P, const AccCtx<MONO, SMALLC, FL>& ctx, uint32_t pix, uint32_t wl_idx, float w, float cx, float cy, float cz) {
   static_assert(!SMALLC, "the fixed-point cache is a view of the full-size float cache");
   if (P.aggregate == 2u) return;  // diagnostic: trace + project only
   FixCache<MONO>& C = *reinterpret_cast<FixCache<MONO>*>(ctx.cache);
@@ -768,20 +792,24 @@ HD void accumulate_fixed(const DispatchParams& P, const AccCtx<MONO, SMALLC>& ct
     }
     if (P.aggregate == 3u) return;  // diagnostic: cache only, misses dropped
   }
+  if constexpr (FL) {   // kAccFixedLog kernels: the raw record (aggregate = 0: every hit is one)
+    log_hit_fixed<MONO>(P, ctx.log_n, pix, wl_idx, w, q0, q1, q2);
+  } else {
   atomicAdd(fix_slot(P, 0u, pix), q0);   // global_atomic_add_x2, no return value
   if (!MONO) {
     atomicAdd(fix_slot(P, 1u, pix), q1);
     atomicAdd(fix_slot(P, 2u, pix), q2);
   }
+  }
 }
 
 // MONO: one scalar per hit into plane 0 (discrete wavelength) or plane wl_idx (illuminant session with one plane per
 // pool entry); the CMF is applied by halo_fold_kernel.  !MONO: X, Y, Z into planes 0..2.
-template <bool MONO, bool SMALLC>
-HD void accumulate(const DispatchParams& P, const AccCtx<MONO, SMALLC>& ctx, uint32_t pix, uint32_t wl_idx, float w, float cx, float cy, float cz) {
+template <bool MONO, bool SMALLC, bool FL>
+HD void accumulate(const DispatchParams& P, const AccCtx<MONO, SMALLC, FL>& ctx, uint32_t pix, uint32_t wl_idx, float w, float cx, float cy, float cz) {
   if constexpr (!SMALLC) {
     if (ctx.fixed) {   // (a constant of the instantiation, like lens / vis / none: the other route folds away)
-      accumulate_fixed<MONO, SMALLC>(P, ctx, pix, w, cx, cy, cz);
+      accumulate_fixed<MONO, SMALLC, FL>(P, ctx, pix, wl_idx, w, cx, cy, cz);
       return;
     }
   }
@@ -1413,8 +1441,8 @@ HD void stage_shape(SlotT* slot, const RecT* g, uint32_t l32) {
                            // around it) and the projection's FMAs take VGPR operands (an SGPR operand makes a VALU instruction 1.56x dearer on this part).  0 = off
 #endif
 // One exit that goes to the image: project, accumulate, tally (the tail of CollectData, simulator.cpp:719-760).
-template <int MODE, bool MONO, bool SMALLC>
-HD int land_exit(const DispatchParams& P, const AccCtx<MONO, SMALLC>& cache, const ColorDev* color, uint64_t cmask, float wx, float wy, float wz, float w,
+template <int MODE, bool MONO, bool SMALLC, bool FL>
+HD int land_exit(const DispatchParams& P, const AccCtx<MONO, SMALLC, FL>& cache, const ColorDev* color, uint64_t cmask, float wx, float wy, float wz, float w,
                  float cmf_x, float cmf_y, float cmf_z, uint32_t wl_idx, RaySums& sums, Probe& pr) {
 #if HALO_PROJ_LDS
   const ProjDev& pj = cache.proj != nullptr ? cache.proj->p : P.proj;
@@ -1493,8 +1521,8 @@ HD DispatchParams reload_params() {
 
 // Pop exits off the wave's queue, one per active lane and round, until fewer than 64 are left (`all`: until it is empty).
 // Called where every lane that took part in the pushes is active (their counts agree).
-template <int MODE, bool MONO, bool SMALLC>
-HD void drain_exits(const DispatchParams& P_kernel, const AccCtx<MONO, SMALLC>& cache, RaySums& sums, bool all, Probe& pr) {
+template <int MODE, bool MONO, bool SMALLC, bool FL>
+HD void drain_exits(const DispatchParams& P_kernel, const AccCtx<MONO, SMALLC, FL>& cache, RaySums& sums, bool all, Probe& pr) {
 #if HALO_RELOAD & 1
   const DispatchParams P = reload_params();
 #else
@@ -1525,8 +1553,8 @@ HD void drain_exits(const DispatchParams& P_kernel, const AccCtx<MONO, SMALLC>& 
 
 
 
-template <int MODE, bool MONO, bool SMALLC>
-HD void emit_gate(const DispatchParams& P, const AccCtx<MONO, SMALLC>& cache, const FilterDev* filter, const ColorDev* color, uint64_t carried, Stream& gate, const float* R, bool live,
+template <int MODE, bool MONO, bool SMALLC, bool FL>
+HD void emit_gate(const DispatchParams& P, const AccCtx<MONO, SMALLC, FL>& cache, const FilterDev* filter, const ColorDev* color, uint64_t carried, Stream& gate, const float* R, bool live,
                   float lx, float ly, float lz, float w, float cmf_x, float cmf_y, float cmf_z, uint32_t wl_idx, uint32_t root, uint32_t seq,
                   const PathView& pv, uint32_t uni_len, RaySums& sums, Probe& pr) {
   // `live`: this lane has an outgoing candidate.  Kernels with an exit queue call this with every lane of the interaction loop
@@ -2055,8 +2083,8 @@ struct Wl0 {   // entry 0 of the wavelength pool and 1 / n, loaded once per kern
   float inv_n;
 };
 
-template <int MODE, bool MONO, bool SMALLC, bool HEX, int ROOT, typename ShapePtr, typename NextT = NextShape>
-HD void trace_one(const DispatchParams& P, LdsTables<MONO, SMALLC>& T, const AccCtx<MONO, SMALLC>& acc, const FilterDev* filter, const ColorDev* color, ShapePtr sh,
+template <int MODE, bool MONO, bool SMALLC, bool HEX, int ROOT, bool FL, typename ShapePtr, typename NextT = NextShape>
+HD void trace_one(const DispatchParams& P, LdsTables<MONO, SMALLC>& T, const AccCtx<MONO, SMALLC, FL>& acc, const FilterDev* filter, const ColorDev* color, ShapePtr sh,
                   const Wl0& wl0, uint32_t tid, RaySums& sums, Probe& pr, NextT* next = nullptr, const WlEntryDev* wl_lds = nullptr,
                   const SlotFast* slot_fast = nullptr) {
   const bool pinned = next != nullptr;   // (a compile-time constant after inlining: see HALO_ARRIVED)
@@ -2497,7 +2525,7 @@ walk_path:
     // projection and accumulation at the site, no queue), with the path it has recorded so far.
     const bool stray = !done && (none_ahead || t_best <= -kSlabEps);
     if (__ballot(stray) != 0ull) {
-      AccCtx<MONO, SMALLC> direct = acc;
+      AccCtx<MONO, SMALLC, FL> direct = acc;
       direct.q = nullptr;
       emit_gate<MODE, MONO, SMALLC>(P, direct, filter, color, carried, gate, R, stray, d[0], d[1], d[2], w, cmf_x, cmf_y, cmf_z, wl_idx, P.ci_start + tid, inward_seq, pv, i + 1u,
                                     sums, pr);
@@ -2634,7 +2662,7 @@ template <int MODE, int GEOM, bool MONO, int ACC>
 constexpr bool small_cache_hex() { return (MODE == kModePlain || (HALO_FILTER_SIX && MODE == kModeFilter)) && GEOM == kGeomOneHex && MONO && (ACC == kAccLog || ACC == kAccLogFinal); }
 template <int MODE, int GEOM, bool MONO, int ACC>
 constexpr int min_waves() {
-  if (ACC == kAccFixed) return min_waves<MODE, GEOM, MONO, kAccDirect>();   // the integer twin keeps its float kernel's bound (and its LDS: FixCache)
+  if (ACC == kAccFixed || ACC == kAccFixedLog) return min_waves<MODE, GEOM, MONO, kAccDirect>();   // the integer twins keep the direct float kernel's bound (and its LDS: FixCache)
   if (!ModeTraits<MODE>::kFast) return HALO_MIN_WAVES_FILTER;
   if ((ACC != kAccDirect && ACC != kAccNone) || ((GEOM == kGeomOne || GEOM == kGeomOneHex) && ACC != kAccNone)) {
     if (small_cache_hex<MODE, GEOM, MONO, ACC>()) return HALO_LOG_WAVES;
@@ -2650,7 +2678,8 @@ constexpr int min_waves() {
 // ROOT: a root profile (kRoot*, at sample_lat_lon_roll) — the last-layer plain hit-log kernels of the regular prism, which launch_vis fans out.
 template <int MODE, int GEOM, bool MONO, int ACC, int LENS = -1, int VIS = -1, bool NOGATE = false, bool CANON = false, int ROOT = kRootAny>   // ACC: kAccDirect, kAccBin (staged + binned hit lists), kAccLog (per-workgroup hit log), ...
 __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) halo_trace_kernel(const DispatchParams P) {
-  constexpr bool BIN = ACC == kAccBin, LOG = ACC == kAccLog || ACC == kAccLogFinal, NONE = ACC == kAccNone, LAST = ACC == kAccLogFinal, FIXED = ACC == kAccFixed;
+  constexpr bool BIN = ACC == kAccBin, LOG = ACC == kAccLog || ACC == kAccLogFinal, NONE = ACC == kAccNone, LAST = ACC == kAccLogFinal, FIXLOG = ACC == kAccFixedLog, FIXED = ACC == kAccFixed || FIXLOG;
+  static_assert(!FIXLOG || !CANON, "a canonical layer before the last never logs");
   static_assert(!FIXED || ((MODE == kModePlain || MODE == kModeFilter) && LENS < 0 && VIS < 0 && !NOGATE && ROOT == kRootAny), "kAccFixed: the plain and the fast-filter kernels, in the generic run-time lens form");
   static_assert(!LOG || ModeTraits<MODE>::kFast, "the hit log is a production-mode route");
   static_assert(!NONE || (ModeTraits<MODE>::kFast && MONO), "kAccNone: production mode; nothing accumulates, so one (scalar) flavour serves every session");
@@ -2673,7 +2702,7 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
   __shared__ __attribute__((aligned(16))) ExitQueues<QUEUE> s_queue;
   __shared__ __attribute__((aligned(16))) ExitQueueMasks<QUEUE && MODE == kModeColor> s_queue_mask;
   __shared__ uint32_t s_fast_ee[ModeTraits<MODE>::kFastPath ? kFastEeLds * 32u : 1u];
-  AccCtx<MONO, SMALLC> acc;
+  AccCtx<MONO, SMALLC, ACC == kAccFixedLog> acc;
   acc.q = nullptr;
   acc.qm = nullptr;
   acc.fast = nullptr;
@@ -2713,6 +2742,13 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
   if constexpr (LOG) {
     acc.log_n = &s_log_n;
     if (threadIdx.x == 0) s_log_n = 0u;
+  }
+  if constexpr (FIXLOG) {
+    // (the cursor of a kAccFixedLog kernel: the word behind the FixCache, inside the float cache's 16 KB that the kernel owns anyway — a word of
+    //  its own would cost the prism-pool kernels their fifth workgroup per CU, like the landed reduction's below)
+    static_assert(sizeof(FixCache<MONO>) + sizeof(uint32_t) <= sizeof(PixCache<MONO, false>) && sizeof(FixCache<MONO>) % 4 == 0, "the log cursor lies behind the fixed-point cache, inside the float cache's LDS");
+    acc.log_n = reinterpret_cast<typename FixCache<MONO>::tag_t*>(reinterpret_cast<char*>(&T.cache) + sizeof(FixCache<MONO>));
+    if (threadIdx.x == 0) *acc.log_n = 0u;
   }
   if constexpr (BIN) {
     acc.hits = &s_hits.b;
@@ -2970,6 +3006,10 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
     __syncthreads();
     if (threadIdx.x == 0) P.bin_cnt[blockIdx.x] = min(s_log_n, P.bin_cap);
   }
+  if constexpr (FIXLOG) {
+    __syncthreads();
+    if (threadIdx.x == 0) P.bin_cnt[blockIdx.x] = min(*acc.log_n, P.bin_cap);
+  }
   // ---- the scalar tallies: per-wave reduction, the four waves' sums joined in LDS, then ONE set of fp64 atomics per workgroup onto
   // one of kTallyLines cache lines.  (Round 5: four atomics per WAVE onto one line were 4 x 1024 same-line atomics for a 256-workgroup
   // launch — they serialise memory-side at ~12 ns each, 37 us behind a kernel whose waves were gone after 18: the fixed cost of every
@@ -3150,6 +3190,25 @@ static void launch_fixed_geom(const DispatchParams& P, dim3 grid, dim3 block, hi
   else if (canon) hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, false, kAccFixed, -1, -1, false, true>), grid, block, 0, stream, P);
   else hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, false, kAccFixed>), grid, block, 0, stream, P);
 }
+// ... and the kAccFixedLog twins of the logging kernels (DispatchParams::bin_log beside ::fix: halo_trace_fxl0.hip, halo_trace_fxl1.hip) — no
+// CANON twins, a canonical layer before the last never logs.
+hipError_t launch_trace_fxl0(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);   // kModePlain
+hipError_t launch_trace_fxl1(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);   // kModeFilter
+template <int MODE, int GEOM>
+static void launch_fixed_log_geom(const DispatchParams& P, dim3 grid, dim3 block, hipStream_t stream, bool mono) {
+  if (mono) hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, true, kAccFixedLog>), grid, block, 0, stream, P);
+  else hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, false, kAccFixedLog>), grid, block, 0, stream, P);
+}
+template <int MODE>
+static hipError_t launch_fixed_log(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono) {
+  dim3 grid(blocks), block(kBlock);
+  if (P.cont_mask != nullptr) return hipErrorNotSupported;
+  if (geom == kGeomOneHex) launch_fixed_log_geom<MODE, kGeomOneHex>(P, grid, block, stream, mono);
+  else if (geom == kGeomPoolPrism) launch_fixed_log_geom<MODE, kGeomPoolPrism>(P, grid, block, stream, mono);
+  else if (geom == kGeomPool) launch_fixed_log_geom<MODE, kGeomPool>(P, grid, block, stream, mono);
+  else launch_fixed_log_geom<MODE, kGeomOne>(P, grid, block, stream, mono);
+  return hipGetLastError();
+}
 template <int MODE>
 static hipError_t launch_fixed(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono) {
   dim3 grid(blocks), block(kBlock);
@@ -3166,8 +3225,8 @@ static hipError_t launch_mode(const DispatchParams& P, int blocks, hipStream_t s
   // a deterministic launch that accumulates: its kAccFixed kernel, or an error — never a float route.  (A one-shape layer whose every exit
   // continues accumulates nothing and keeps its kAccNone kernel below.)
   if (P.fix != nullptr && !(P.no_land != 0u && ModeTraits<MODE>::kFast && (geom == kGeomOne || geom == kGeomOneHex))) {
-    if constexpr (MODE == kModePlain) return launch_trace_fx0(P, blocks, stream, geom, mono);
-    else if constexpr (MODE == kModeFilter) return launch_trace_fx1(P, blocks, stream, geom, mono);
+    if constexpr (MODE == kModePlain) return P.bin_log != 0u ? launch_trace_fxl0(P, blocks, stream, geom, mono) : launch_trace_fx0(P, blocks, stream, geom, mono);
+    else if constexpr (MODE == kModeFilter) return P.bin_log != 0u ? launch_trace_fxl1(P, blocks, stream, geom, mono) : launch_trace_fx1(P, blocks, stream, geom, mono);
     else return hipErrorNotSupported;
   }
   if constexpr (ModeTraits<MODE>::kFast) {

@@ -285,7 +285,12 @@ const char* halo_last_error(halo_handle_t h);
  * FULL: every exit of a full-sky render lands, and that many direct atomics cost more than the log's passes), or on the X/Y/Z planes of an illuminant
  * session (>= 2 Mi rays, image above 512 Ki pixels), append the hits that miss the pixel cache to a log region per workgroup — plain stores instead of
  * memory-side fp32 atomics — which a split pass and a per-tile LDS pass then add to the plane(s); 0 = never (direct atomics),
- * 1 = whenever applicable), "hit_log_cap" (test knob: records per log region, 0 [default] = sized from the launch; what runs
+ * 1 = whenever applicable.  In a DETERMINISTIC session (option "deterministic" below) the log has integer twins: the trace kernel keeps its
+ * integer pixel cache and flushes it onto the integer planes itself, a hit that loses the cache claim leaves as a raw {slot, fp32 weight} record,
+ * and the split and per-tile passes quantise the records with the session's F and add integers — the planes end up holding, bit for bit, the
+ * integers of the direct deterministic route.  There -1 takes the log from 2 Mi rays per launch on either plane layout (whatever the
+ * visible range; any image the log's tiles fit: up to 4 Mi slots on a scalar plane, 2 Mi on X, Y, Z), 0 = every miss an integer atomic, 1 = whenever applicable —
+ * and only there also with "aggregate" = 0, where every hit is a record), "hit_log_cap" (test knob: records per log region, 0 [default] = sized from the launch; what runs
  * over a region or a tile list is added directly),
  * "hex_fast" (1 [default]: one-shape dispatches of a REGULAR hexagonal prism run the instantiation whose next-face search has the
  * normals as literals; 0: the table-driven search — same candidates, order and comparisons, A/B knob),
@@ -315,9 +320,9 @@ const char* halo_last_error(halo_handle_t h);
  * "deterministic" (additive in ABI 6, no struct changed: 0 [default] = the float routes above; 1 = every accumulating launch of every layer runs the
  * fixed-point route — a hit's value v (the weight on a scalar plane, the fp32 products cmf * weight on X, Y, Z) enters every sum as the 64-bit
  * integer floor(double(v) * 2^F + 0.5), in the workgroup's pixel cache, in the global planes and in the landed-weight tally alike, and integer
- * sums do not depend on the order of their adds.  A discrete session keeps one scalar plane, an illuminant session X, Y, Z planes; hit_log, bin,
- * lambda_planes and mono_copies are ignored.  REPRODUCIBLE: the integer plane sums and the landed integer of a session depend only on the set of
- * rays traced into them — not on chunk, blocks_per_cu, small_blocks_per_cu, overlap, async, aggregate, mono_copies, table_cache, stream
+ * sums do not depend on the order of their adds.  A discrete session keeps one scalar plane, an illuminant session X, Y, Z planes; bin,
+ * lambda_planes and mono_copies are ignored, hit_log chooses between the direct route and the hit log's integer twins (same integers either way).  REPRODUCIBLE: the integer plane sums and the landed integer of a session depend only on the set of
+ * rays traced into them — not on chunk, blocks_per_cu, small_blocks_per_cu, overlap, async, aggregate, hit_log, hit_log_cap, mono_copies, table_cache, stream
  * assignment or wave scheduling; the XYZ image is a per-pixel function of those sums and of the order of the folds, which is the order of the
  * caller's sessions (a plane value is float32(double(S) * 2^-F)), so a fixed seed and ray_base give the same bytes on every run.  Over several
  * layers this holds together with cont_order = 1.  F is the largest scale <= 32 at which 2^30 rays of the session's largest weight cannot wrap a
@@ -325,8 +330,9 @@ const char* halo_last_error(halo_handle_t h);
  * boundary — beyond that budget the image, not the sums of each fold, depends on chunk.  NOT covered: a multi-GPU run is reproducible per rank,
  * the collective's order is RCCL's.  REFUSED, by name, at halo_begin (nothing is ever run on
  * a float route in silence): a multi-layer session without cont_order = 1, raypath-colour tables, capture_exits = 1, rehit_strategy = 0, a
- * filter that needs the generic filter kernels.  Every hit outside the pixel cache is a memory-side 64-bit integer atomic, the price of the
- * direct route: configs[1]'s step +58 %, a full-sky X/Y/Z session 4.8 x; not inside a session),
+ * filter that needs the generic filter kernels.  On the direct route every hit outside the pixel cache is a memory-side 64-bit integer atomic
+ * (configs[1]'s step +62 %, a full-sky X/Y/Z session 5 x); launches of 2 Mi rays and more take the hit log's integer twins instead (see "hit_log":
+ * +33 % and 1.43 x); not inside a session),
  * scheduling (ABI 6; none of them changes a result): "overlap" (1 [default]: launches of <= 2 Mi rays alternate between two
  * trace streams, closing folds run on an auxiliary stream; 0 = everything on the one stream), "table_cache" (1 [default]: equal
  * sessions reuse their device tables), "small_blocks_per_cu" (default 5: workgroups per CU a small launch spreads over before a
@@ -387,7 +393,7 @@ typedef struct HaloRouteInfo {
                             raypath colour (both for max_hits <= 16: path in a register, predicates as host-built member tables); 2 + exit capture
                             (tests); 3 the generic filter / colour kernels (paths to 64 faces, or tables that do not fit the fast form) */
   uint32_t geom_mask;    /* bit g: GEOM g (0 one shape per dispatch, 1 pool of 4.1 KB records, 2 pool of prism records, 3 one shape = regular hexagonal prism) */
-  uint32_t accum_mask;   /* bit 0 direct X/Y/Z planes, 1 direct scalar plane(s), 2 binned one level, 3 binned two levels, 4 hit log, 5 hit log of an illuminant session (X, Y, Z made in the per-tile pass), 6 none (a layer whose every exit continues), 7 fixed-point planes (option "deterministic": no other accumulating bit is set beside it) */
+  uint32_t accum_mask;   /* bit 0 direct X/Y/Z planes, 1 direct scalar plane(s), 2 binned one level, 3 binned two levels, 4 hit log, 5 hit log of an illuminant session (X, Y, Z made in the per-tile pass), 6 none (a layer whose every exit continues), 7 fixed-point planes (option "deterministic": beside it only bit 4 or 5 — launches that went through the hit log's integer twins, scalar plane or X, Y, Z — and bit 6) */
   uint32_t source_mask;  /* bit 0 generated roots, 1 continuation pool (layer >= 1), 2 host-injected rays */
   uint32_t plane_cnt;    /* accumulation planes of the session (1 discrete, 3 X/Y/Z, M per-entry) */
   uint32_t plane_copies; /* privatised copies of each plane */

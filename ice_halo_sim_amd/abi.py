@@ -113,6 +113,7 @@ class HaloRouteInfo(C.Structure):
 MODE_PLAIN, MODE_FILTER, MODE_CAPTURE, MODE_GENERIC, MODE_COLOR = 1, 2, 4, 8, 16   # HaloRouteInfo.mode_mask bits
 SPEC_LAST, SPEC_LENS, SPEC_VIS, SPEC_NOGATE = 1, 2, 4, 8                           # HaloRouteInfo.spec_mask bits
 ROOT_GEN, ROOT_TRANSIT = 1, 2                                                      # halo_last_root_profile bits
+CLOSE_AUTO, CLOSE_NEVER, CLOSE_ALWAYS = -1, 0, 1                                          # option "close_direct" (halo_direct_closes counts the launches it took)
 
 
 ACCUM_XYZ, ACCUM_SCALAR, ACCUM_BIN1, ACCUM_BIN2, ACCUM_LOG, ACCUM_LOG_XYZ, ACCUM_NONE = 1, 2, 4, 8, 16, 32, 64   # HaloRouteInfo.accum_mask bits

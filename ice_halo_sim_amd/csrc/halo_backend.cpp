@@ -127,6 +127,15 @@ struct HaloBackend {
   uint32_t shuffle_chunk_log2 = 5;   // Recombine's shuffle moves chunks of 2^k pool entries (k = 0: per ray, like the reference)
   int spec_root = 1;           // option (A/B knob): 1 = last-layer plain hit-log launches over a regular prism whose root generation matches a root profile
                                // (halo_trace.inl kRoot*) run the instantiation that has it as constants; 0 = always the generic root generation
+  // Direct close: a logged launch that is its whole session — one plane, one copy, nothing pending in the planes — has its per-tile
+  // pass add coef x sum to the XYZ image itself (launch_log_route_close): no plane write, no fold on the auxiliary stream, no stream hop in front of
+  // the next session's trace kernel.  The pass is a PLAIN read-modify-write of the image and of the twin's half, on the launch's trace stream: a later
+  // launch on the other trace stream waits for it (close_done), readers and folds join the trace streams as they always do.
+  int close_direct = -1;       // option: -1 auto (launches that fill the chip), 0 never, 1 wherever eligible
+  uint64_t direct_closes = 0;  // launches that closed their session directly, ever (halo_direct_closes)
+  Marker close_done;           // the direct close queued last, on trace stream close_ts
+  int close_ts = 0;
+  bool cnt2_clean[2] = {false, false};   // log set s: the tile-list counters are known to be zero (the closing pass zeroes what it consumed)
   HaloRouteInfo route{};       // kernels that served the current / last session (halo_last_route)
   uint32_t route_root = 0;     // ... and the root profiles among them (halo_last_root_profile): bit kRootProfile* - 1
 
@@ -277,7 +286,7 @@ struct HaloBackend {
   // every event made without timing: the one-shot ones, the joins' and the markers' (created in halo_create, destroyed in halo_destroy)
   std::vector<hipEvent_t*> untimed_events() {
     return {&ev_cs[0], &ev_cs[1], &ev_main, &ev_aux, &ev_fork, &ev_join, &ev_gen, &ev_gate, &set_free[0].ev, &set_free[1].ev, &shapes_free[0].ev,
-            &shapes_free[1].ev, &rmw[0].ev, &rmw[1].ev, &set_folded[0].ev, &set_folded[1].ev};
+            &shapes_free[1].ev, &rmw[0].ev, &rmw[1].ev, &set_folded[0].ev, &set_folded[1].ev, &close_done.ev};
   }
 };
 
@@ -328,6 +337,7 @@ int join_aux(HaloBackend* b) {
       HIPCHK(b, hipStreamWaitEvent(b->stream, b->ev_cs[k], 0));
       b->cs_pending[k] = false;
       b->rmw[k].clear();   // (every later launch waits for the main stream, which now waits for these sums)
+      if (b->close_ts == k) b->close_done.clear();   // ... and for this direct close
     }
   return HALO_OK;
 }
@@ -646,6 +656,7 @@ int halo_set_option(halo_handle_t b, const char* key, int64_t v) {
   }
   else if (k == "defer_fold") b->defer_fold = v ? 1 : 0;
   else if (k == "gen_ahead") b->gen_ahead = v ? 1 : 0;
+  else if (k == "close_direct") b->close_direct = v < 0 ? -1 : (v ? 1 : 0);
   else if (k == "pool_entry_fast") b->pool_entry_fast = v ? 1 : 0;
   else if (k == "rehit_strategy") {
     if (b->in_session) return fail(b, HALO_FATAL, "rehit_strategy cannot change inside a session");
@@ -1044,6 +1055,8 @@ struct LaunchPlan {
   int geom = 0, blocks = 0;             // geom: 0 = one shape per dispatch, 1 = pool of ShapeDev records, 2 = pool of ShapePrism records (device-generated prisms)
   uint32_t shape_cnt = 1;
   bool use_bin = false, two_level = false, use_log = false, use_log_xyz = false, canon = false, no_land = false;
+  bool only = false;                    // the layer's only launch, on the session's last layer (halo_trace_layer)
+  bool close = false;                   // ... that closes its session in its per-tile pass (close_direct_ok): nothing is left in the planes
   bool fixed = false;                   // a deterministic session's launch: the kAccFixed kernels, with use_log their logging twins (or, where every exit continues, kAccNone)
   uint32_t fan_log2 = 0, lists1 = 0, bin_tiles = 0, log_t_log2 = 0, log_planes = 1, log_tiles = 0;
   uint64_t cap1 = 0, cap2 = 0;          // records per region / coarse list and per tile list, as REQUESTED: reserve_log_buffers clamps the log's against free memory
@@ -1053,7 +1066,8 @@ struct LaunchPlan {
   //  and fold, 325 us per session; the trace kernel and generator of session k + 1 now run beside the passes and the fold of session k.
   //  Launches that fill the chip keep the old order: measured in round 5, nothing to gain there and the kernel's own span stretches.)
   // (A deterministic logged launch flushes its integer cache onto the planes from the trace kernel itself: it waits for the fold, as a direct one does.)
-  bool under_fold() const { return use_log && alternate && !fixed; }
+  // (A directly closing launch writes the image and the twin's half in its passes: it is queued behind the auxiliary stream like a launch that fills the chip.)
+  bool under_fold() const { return use_log && alternate && !fixed && !close; }
 };
 // What a launch was given when it was queued: its dispatch-ring slot, log buffer set, shape pool and the first index of its shape stream.
 struct LaunchSlots { int k = 0, ls = 0, shape_set = 0; uint64_t first_shape = 0; };
@@ -1448,6 +1462,7 @@ int bind_route(HaloBackend* b, LaunchPlan& p, int ls, DispatchParams& P) {
     if (p.two_level) {
       if (int rc = reserve_idle(b, bin_cnt2, static_cast<size_t>(p.bin_tiles) * 16u)) return rc;
       HIPCHK(b, hipMemsetAsync(bin_cnt2.ptr, 0, static_cast<size_t>(p.bin_tiles) * 16u * sizeof(uint32_t), b->stream));
+      b->cnt2_clean[ls] = false;
       if (int rc = reserve_idle(b, bin_list2, p.cap2 * p.bin_tiles)) return rc;
     }
   }
@@ -1466,6 +1481,18 @@ int bind_route(HaloBackend* b, LaunchPlan& p, int ls, DispatchParams& P) {
   if (p.use_log) P.log_plane_stride = static_cast<uint32_t>((static_cast<uint64_t>(kMonoRows) << b->mono_s_log2) * b->plane_copies);
   P.no_land = p.no_land ? 1u : 0u;
   return HALO_OK;
+}
+// Whether a planned, bound launch closes its session in its per-tile pass (HaloBackend::close_direct).  What is checked: it is the only launch of
+// its halo_trace_layer call (one crystal entry, one chunk), on the last layer, with nothing pending in the planes — an earlier layer that put light
+// on them, or an unfolded session under lazy_fold, has left mono_dirty set — on the float hit log's contiguous-tile scalar route, one plane in one
+// copy, with the twin to overflow to.  (halo_begin's ray count is not consulted: a caller that traces a last layer in several calls gets a direct
+// close per call, each adding its own sums to the image — the planes stay clean in between, so that is the same image.)
+bool close_direct_ok(const HaloBackend& b, const LaunchPlan& p, const DispatchParams& P) {
+  if (b.close_direct == 0 || !p.only || p.fixed || !p.use_log || p.use_log_xyz || p.log_planes != 1u || b.mono_by_wl) return false;
+  if (b.plane_cnt != 1u || b.plane_copies != 1u || b.render.visible == HALO_VISIBLE_FULL) return false;   // (full sky: interleaved tiles)
+  if ((1u << p.log_t_log2) > 256u || b.mono_s_log2 + 10u - p.log_t_log2 > kBinTileLog2) return false;
+  if (P.ovf == nullptr || P.ovf_flag == nullptr || b.mono_dirty || b.acc == nullptr) return false;
+  return b.close_direct > 0 || !p.alternate;   // auto: the hit log's own threshold chose the log; launches that fill the chip only
 }
 // HaloRouteInfo (halo_last_route: what the GPU tests assert routes with).  The masks name the instantiation that launch_mode / launch_mono /
 // launch_lens / launch_vis in halo_trace.inl pick for this launch — mirrored here — not the request: the regular-prism search exists for
@@ -1535,7 +1562,28 @@ int queue_passes(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, c
     } else if (int rc = wait_for_aux(b, ts_i)) return rc;
   }
   HIPCHK(b, hipEventRecord(b->ring_ev2[k], ps));
+  if (p.close) {
+    // the split and the closing per-tile pass, which leaves nothing behind: counters zeroed by the workgroups that consumed them (the memset in front
+    // of the split goes: 4-7 us per launch, profiles/direct_close_ab.txt), the twin's flag cleared behind the pass, the planes untouched (mono_dirty stays false: no fold follows)
+    if (!b->cnt2_clean[S.ls]) HIPCHK(b, hipMemsetAsync(bin_cnt2.ptr, 0, static_cast<size_t>(p.log_tiles) * 16u * sizeof(uint32_t), ps));
+    const float coef[3] = {b->plane_coef[0][0], b->plane_coef[0][1], b->plane_coef[0][2]};
+    hipError_t ce = launch_log_route_close(b->acc, static_cast<uint32_t>(b->acc_w) * static_cast<uint32_t>(b->acc_h), coef, bin_list.ptr, P.bin_cap, bin_cnt.ptr,
+                                           static_cast<uint32_t>(p.blocks), bin_list2.ptr, cap2, bin_cnt2.ptr, 1u << p.log_t_log2, b->mono_s_log2, frac_bits, P.ovf, P.ovf_flag,
+                                           ps, before_sums);
+    if (ce != hipSuccess) return hip_fail(b, ce, "halo_split_kernel launch (direct close)");
+    b->cnt2_clean[S.ls] = true;
+    b->direct_closes++;
+    HIPCHK(b, b->close_done.mark(ps));
+    b->close_ts = ts_i;
+    HIPCHK(b, hipEventRecord(b->ring_ev3[k], ps));
+    HIPCHK(b, b->set_free[S.ls].mark(ps));
+    if (b->overlap && p.alternate) b->log_set ^= 1;
+    b->ring_posts[k] = true;
+    HIPCHK(b, hipEventRecord(b->ring_done[k], ps));
+    return HALO_OK;
+  }
   HIPCHK(b, hipMemsetAsync(bin_cnt2.ptr, 0, static_cast<size_t>(p.log_tiles) * 16u * sizeof(uint32_t), ps));
+  b->cnt2_clean[S.ls] = false;
   // (a deterministic launch: the integer twins of the passes, onto the integer planes with the pending plane set's F.  Every writer of those planes
   //  adds with an integer atomic, so the passes take no `before_sums` and leave no rmw marker: nothing has to be ordered against them but the fold.)
   hipError_t be = p.fixed ? (p.use_log_xyz ? launch_log_route_xyz_fixed(P.fix, P.log_plane_stride, bin_list.ptr, P.bin_cap, bin_cnt.ptr, static_cast<uint32_t>(p.blocks), bin_list2.ptr, cap2,
@@ -1565,6 +1613,8 @@ int queue_launch(HaloBackend* b, const LaunchPlan& p, const HaloEntry& E, EntryT
   hipStream_t ts = nullptr;
   int ts_i = 0;
   if (int rc = next_trace_stream(b, !p.under_fold(), p.alternate, &ts, &ts_i)) return rc;
+  if (b->close_done.set && b->close_ts != ts_i)   // a direct close on the other trace stream: it writes the image and the twin's half plainly
+    HIPCHK(b, b->close_done.wait_on(ts));
   hipEvent_t before_sums = nullptr;   // rule (1), for the routes whose sums write the planes plainly
 #ifndef HALO_NO_PLANE_GATES   // (defined only to see tests/test_gpu_production_routes.py's two-stream test fail without the gates)
   if (b->overlap && !p.use_log)   // this trace kernel adds to the planes itself: behind the other stream's sums
@@ -1599,7 +1649,10 @@ int queue_launch(HaloBackend* b, const LaunchPlan& p, const HaloEntry& E, EntryT
     T.ce->read_ring[T.ce->cur] = k;
     T.ce->read_use[T.ce->cur] = b->ring_use[k];
   }
-  b->mono_dirty = true;
+  // (a launch that closes its session itself leaves the planes as it found them; so does one of the no-accumulation kernels — no_land on one shape,
+  // launch_mono / launch_canon: kAccNone has no cache, no exit queue and no code that touches a plane, the log or the twin.  The latter holds for
+  // EVERY such launch, eligible for a direct close or not: a session of such launches alone queues no fold of planes nobody wrote.)
+  if (!p.close && !(p.no_land && p.geom == 0)) b->mono_dirty = true;
   b->fix_planes = b->det_session;
   record_route(b, p, P, T.mode, T.fast_mode, launch_geom);
   if (le != hipSuccess) return hip_fail(b, le, "halo_trace_kernel launch");
@@ -1703,6 +1756,7 @@ int trace_launch(HaloBackend* b, const LayerCtx& c, LaunchPlan& p, EntryTables& 
   }
   S.ls = (b->overlap && p.alternate) ? b->log_set : 0;   // the buffer set of this launch
   if (int rc = bind_route(b, p, S.ls, P)) return rc;
+  p.close = close_direct_ok(*b, p, P);
   if (int rc = queue_launch(b, p, E, T, P, S)) return rc;
   if (p.host_pool) HIPCHK(b, hipStreamSynchronize(b->stream));  // the pageable shape pool must outlive its copy (the copy is on the main stream)
   if (P.source == kSrcGen) b->gen_count += m;
@@ -1867,6 +1921,7 @@ int halo_trace_layer(halo_handle_t b, uint64_t count, const HaloHostRays* rays, 
   EntryTables T;
   DispatchParams P{};
   int cur = -1;
+  if (plans.size() == 1u) plans[0].only = c.final_layer;
   for (LaunchPlan& p : plans) {
     if (p.ci != cur) {
       cur = p.ci;
@@ -1967,6 +2022,12 @@ int halo_last_sample_counts(halo_handle_t b, uint64_t* crystal_samples, uint64_t
 int halo_last_route(halo_handle_t b, HaloRouteInfo* out) {
   if (!b || !out) return HALO_FATAL;
   *out = b->route;
+  return HALO_OK;
+}
+
+int halo_direct_closes(halo_handle_t b, uint64_t* out) {
+  if (!b || !out) return HALO_FATAL;
+  *out = b->direct_closes;
   return HALO_OK;
 }
 

@@ -297,16 +297,60 @@ __global__ void __launch_bounds__(kSplitBlock) halo_split_fixed_kernel(const uin
 // (kFix, the deterministic route's integer twin: `plane` is the integer plane, frac_bits the session's F, and the write-out ADDS the LDS integers
 // to it — no-return 64-bit atomics for the non-zero slots, so it needs no ordering against any other writer.  The float instantiation's code is
 // what it was.)
+// (kClose, the float route's closing form, for a launch that is its whole session — DESIGN.md 3.2: the plane is zero before this pass, so the tile's
+// sums ARE the plane, and the workgroup, the only writer of its tile, adds coef x sum to the XYZ image itself — what the closing fold would do
+// with the plane it read back, value for value: the twin taken in and zeroed when its flag is up, the slot mapped back to its pixel, the product
+// and the add rounded separately.  `plane` and `cnt` are not used (null): the plane is neither read nor written, and the tile's count is read and
+// ZEROED through CloseArgs::cnt — the next split pass on this list set, later on the same stream, finds its counters clear.  The twin's flag is
+// read by every workgroup, so no workgroup may clear it: a 4-byte memset follows the kernel on its stream (an end-of-grid ticket — the last
+// workgroup to finish clears the flag — measured no better than the memset, profiles/direct_close_ab.txt, and is not kept).)
+template <bool kClose>
+struct CloseArgsOf {};
+template <>
+struct CloseArgsOf<true> {
+  float* xyz;         // the image: 3 floats per pixel
+  uint32_t n_pix;
+  uint32_t s_log2;    // columns per plane row (MonoSlot)
+  float coef[3];      // the session's CMF
+  uint32_t* cnt;      // the tile lists' counters (read, then zeroed)
+  double* twin;       // the plane's fp64 twin and its flag (DispatchParams::ovf, ovf_flag)
+  const uint32_t* flag;
+};
+// image += coef x sum as the fold makes it: the product rounded, then the add (the fold's product goes through LDS before it meets the image;
+// written as one expression here, the two would contract into one fma and round once)
+__device__ __forceinline__ float close_add(float q, float c, float v) {
+#pragma clang fp contract(off)
+  const float p = c * v;
+  return q + p;
+}
+// a workgroup's last step in the closing form: its counter cleared
+__device__ __forceinline__ void close_done(const CloseArgsOf<true>& cl, uint32_t tile) {
+  __syncthreads();   // every thread has the count it loaded
+  if (threadIdx.x == 0u) cl.cnt[static_cast<size_t>(tile) * kBinCntStride] = 0u;
+}
 template <bool kFix>
 using PlaneOf = typename std::conditional<kFix, unsigned long long, float>::type;
-template <bool kFix = false>
+template <bool kFix = false, bool kClose = false>
 __global__ void __launch_bounds__(kBinBlock) halo_bin_accumulate_range_kernel(PlaneOf<kFix>* __restrict__ plane, const uint2* __restrict__ list, uint32_t cap,
-                                                                               const uint32_t* __restrict__ cnt, uint32_t tile_log2, uint32_t frac_bits) {
+                                                                               const uint32_t* __restrict__ cnt, uint32_t tile_log2, uint32_t frac_bits,
+                                                                               const CloseArgsOf<kClose> cl) {
+  static_assert(!(kFix && kClose), "the closing form exists on the float route only");
   __shared__ __attribute__((aligned(16))) unsigned long long acc[1u << kBinTileLog2];   // fixed point (FixQ); tile_log2 <= kBinTileLog2
   const FixQ fq(frac_bits);
   const uint32_t tile = blockIdx.x;
-  const uint32_t n = min(cnt[static_cast<size_t>(tile) * kBinCntStride], cap);
-  if (n == 0u) return;
+  uint32_t n;
+  bool take_twin = false;   // workgroup-uniform, like n
+  if constexpr (kClose) {
+    n = min(cl.cnt[static_cast<size_t>(tile) * kBinCntStride], cap);
+    take_twin = *cl.flag != 0u;
+    if (n == 0u && !take_twin) {
+      close_done(cl, tile);
+      return;
+    }
+  } else {
+    n = min(cnt[static_cast<size_t>(tile) * kBinCntStride], cap);
+    if (n == 0u) return;
+  }
   const uint32_t slots = 1u << tile_log2, mask = slots - 1u;
   for (uint32_t j = threadIdx.x; j < slots; j += kBinBlock) acc[j] = 0ull;
   __syncthreads();
@@ -356,7 +400,33 @@ __global__ void __launch_bounds__(kBinBlock) halo_bin_accumulate_range_kernel(Pl
     atomicAdd(&acc[h.x & mask], fq.fix(__uint_as_float(h.y)));
   }
   __syncthreads();
-  if constexpr (kFix) {
+  if constexpr (kClose) {
+    // Consecutive lanes take consecutive ROWS of one column — consecutive pixels — in runs of up to eight (96 bytes of XYZ; the fold's own runs are
+    // 48 bytes and more), then the next column.  A tile-local slot is row bits above `cb` column bits.
+    const uint32_t s_mask = (1u << cl.s_log2) - 1u;
+    const uint32_t cb = min(cl.s_log2, tile_log2), rl = min(tile_log2 - cb, 3u);
+    const uint32_t base = tile << tile_log2;
+    for (uint32_t i = threadIdx.x; i < slots; i += kBinBlock) {
+      const uint32_t rest = i >> rl;
+      const uint32_t j = (((((rest >> cb) << rl) | (i & ((1u << rl) - 1u))) << cb) | (rest & ((1u << cb) - 1u)));
+      const uint32_t slot = base | j;
+      float v = fq.unfix(acc[j]);
+      if (take_twin) {
+        const double o = cl.twin[slot];
+        if (o != 0.0) {
+          cl.twin[slot] = 0.0;
+          v = static_cast<float>(static_cast<double>(v) + o);
+        }
+      }
+      if (v == 0.0f) continue;
+      const uint32_t pix = (((slot & s_mask) * kMonoMulInv) & s_mask) * kMonoRows + (slot >> cl.s_log2);   // MonoSlot inverted, as the fold does
+      if (pix >= cl.n_pix) continue;
+      float* q = cl.xyz + 3u * static_cast<size_t>(pix);
+#pragma unroll
+      for (uint32_t c = 0; c < 3u; ++c) q[c] = close_add(q[c], cl.coef[c], v);
+    }
+    close_done(cl, tile);
+  } else if constexpr (kFix) {
     unsigned long long* dst = plane + (static_cast<size_t>(tile) << tile_log2);
     for (uint32_t j = threadIdx.x; j < slots; j += kBinBlock) {
       const unsigned long long v = acc[j];
@@ -527,8 +597,31 @@ hipError_t launch_log_route(float* plane, const HitRec* log, uint32_t cap1, cons
   if (interleaved)
     hipLaunchKernelGGL((halo_log_accumulate_kernel<1u>), dim3(tiles), dim3(kBinBlock), 0, stream, plane, 0u, reinterpret_cast<const uint2*>(list2), cap2, cnt2,
                        static_cast<const WlEntryDev*>(nullptr), 0u, tiles_log2, s_log2, frac_bits);
-  else hipLaunchKernelGGL((halo_bin_accumulate_range_kernel<false>), dim3(tiles), dim3(kBinBlock), 0, stream, plane, reinterpret_cast<const uint2*>(list2), cap2, cnt2, tile_log2, frac_bits);
+  else hipLaunchKernelGGL((halo_bin_accumulate_range_kernel<false>), dim3(tiles), dim3(kBinBlock), 0, stream, plane, reinterpret_cast<const uint2*>(list2), cap2, cnt2, tile_log2, frac_bits, CloseArgsOf<false>{});
   return hipGetLastError();
+}
+
+// The scalar route's closing form (halo_bin_accumulate_range_kernel<false, true>): regions -> `tiles` CONTIGUOUS tiles -> coef x sum added to the
+// XYZ image, for a launch that is its whole session.  The plane is not touched; what the lists cannot hold goes to the twin, which must be there.
+// The pass leaves cnt2 zeroed; a 4-byte memset behind it clears the twin's flag.
+hipError_t launch_log_route_close(float* xyz, uint32_t n_pix, const float* coef, const HitRec* log, uint32_t cap1, const uint32_t* cnt1, uint32_t regions, HitRec* list2,
+                                  uint32_t cap2, uint32_t* cnt2, uint32_t tiles, uint32_t s_log2, uint32_t frac_bits, double* ovf, uint32_t* ovf_flag,
+                                  hipStream_t stream, hipEvent_t before_sums) {
+  if (tiles == 0u || (tiles & (tiles - 1u)) != 0u || tiles > 256u || xyz == nullptr || coef == nullptr || ovf == nullptr || ovf_flag == nullptr) return hipErrorInvalidValue;
+  const uint32_t tiles_log2 = static_cast<uint32_t>(__builtin_ctz(tiles));
+  if (s_log2 + 10u < tiles_log2 || s_log2 + 10u - tiles_log2 > kBinTileLog2) return hipErrorInvalidValue;
+  const uint32_t tile_log2 = s_log2 + 10u - tiles_log2;
+  hipLaunchKernelGGL((halo_split_kernel<kLogSplitThreads, kLogSplitPer, 256u, false, false>), dim3(regions), dim3(kLogSplitThreads), 0, stream, static_cast<float*>(nullptr),
+                     reinterpret_cast<const uint2*>(log), cap1, cnt1, 1u, 1u, reinterpret_cast<uint2*>(list2), cap2, cnt2, tiles_log2, 0u, 0xFFFFFFFFu, tile_log2, 0u,
+                     SplitXyz{nullptr, 0u, 0u, ovf, ovf_flag, s_log2 + 10u, 0u});
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (before_sums && (e = hipStreamWaitEvent(stream, before_sums, 0)) != hipSuccess) return e;
+  const CloseArgsOf<true> cl{xyz, n_pix, s_log2, {coef[0], coef[1], coef[2]}, cnt2, ovf, ovf_flag};
+  hipLaunchKernelGGL((halo_bin_accumulate_range_kernel<false, true>), dim3(tiles), dim3(kBinBlock), 0, stream, static_cast<float*>(nullptr), reinterpret_cast<const uint2*>(list2), cap2,
+                     static_cast<const uint32_t*>(nullptr), tile_log2, frac_bits, cl);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  return hipMemsetAsync(ovf_flag, 0, sizeof(uint32_t), stream);   // every workgroup has seen it; the pass zeroed what it took
 }
 
 // the same for an illuminant session on X, Y, Z planes: `tiles` (a power of two <= 512) interleaved tiles of <= 4 Ki slots of one plane
@@ -573,7 +666,7 @@ hipError_t launch_log_route_fixed(unsigned long long* fix, const HitRec* log, ui
   if (mix)
     hipLaunchKernelGGL((halo_log_accumulate_kernel<1u, true>), dim3(tiles), dim3(kBinBlock), 0, stream, fix, 0u, reinterpret_cast<const uint2*>(list2), cap2, cnt2,
                        static_cast<const WlEntryDev*>(nullptr), 0u, tiles_log2, s_log2, frac_bits);
-  else hipLaunchKernelGGL((halo_bin_accumulate_range_kernel<true>), dim3(tiles), dim3(kBinBlock), 0, stream, fix, reinterpret_cast<const uint2*>(list2), cap2, cnt2, tile_log2, frac_bits);
+  else hipLaunchKernelGGL((halo_bin_accumulate_range_kernel<true>), dim3(tiles), dim3(kBinBlock), 0, stream, fix, reinterpret_cast<const uint2*>(list2), cap2, cnt2, tile_log2, frac_bits, CloseArgsOf<false>{});
   return hipGetLastError();
 }
 
@@ -602,7 +695,7 @@ hipError_t launch_bin_two_level(float* plane, const HitRec* list1, uint32_t cap1
   if (e != hipSuccess) return e;
   if (before_sums && (e = hipStreamWaitEvent(stream, before_sums, 0)) != hipSuccess) return e;
   hipLaunchKernelGGL((halo_bin_accumulate_range_kernel<false>), dim3(tiles), dim3(kBinBlock), 0, stream, plane, reinterpret_cast<const uint2*>(list2), cap2, cnt2,
-                     static_cast<uint32_t>(kBinTileLog2), frac_bits);
+                     static_cast<uint32_t>(kBinTileLog2), frac_bits, CloseArgsOf<false>{});
   return hipGetLastError();
 }
 

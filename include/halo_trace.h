@@ -337,7 +337,11 @@ const char* halo_last_error(halo_handle_t h);
  * trace streams, closing folds run on an auxiliary stream; 0 = everything on the one stream), "table_cache" (1 [default]: equal
  * sessions reuse their device tables), "small_blocks_per_cu" (default 5: workgroups per CU a small launch spreads over before a
  * workgroup takes a second pass), "defer_fold" (see halo_flush), "gen_ahead" (experiment knob, 0 [default]; 1: the crystal generator of a
- * launch that fills the chip is queued beside the previous launch's trace kernel — measured, gains nothing: both are VALU-bound). */
+ * launch that fills the chip is queued beside the previous launch's trace kernel — measured, gains nothing: both are VALU-bound),
+ * "close_direct" (-1 [default]: a hit-log launch that is its whole session — last layer, one crystal entry, one chunk, nothing pending in the
+ * planes — on the float route's contiguous-tile scalar path (one plane, one copy, twin present, not a full-sky render) and large enough to fill
+ * the chip has its per-tile pass add CMF x sum to the XYZ image itself: bit-equal to plane-then-fold, no closing fold; 0: never; 1: wherever
+ * eligible, whatever the launch size; halo_direct_closes counts them). */
 int halo_set_option(halo_handle_t h, const char* key, int64_t value);
 /* Use an external HIP stream (e.g. torch's current stream) for all launches. NULL = own stream. */
 int halo_set_stream(halo_handle_t h, void* hip_stream);
@@ -408,6 +412,9 @@ int halo_last_route(halo_handle_t h, HaloRouteInfo* out);
  * by the LUT, azimuth and roll uniform" as compile-time constants; bit 1: the same orientation over the continuation pool (a last layer >= 1).
  * 0: every launch generated its roots with run-time tests on source, latitude path and distribution kinds (see option "spec_root"). */
 int halo_last_root_profile(halo_handle_t h, uint32_t* profile_mask);
+/* Launches, since halo_create, that closed their session in their own per-tile pass (option "close_direct"; additive in ABI 6, no struct changed —
+ * such a launch still reports accum_mask bit 4).  A cumulative count: take the difference around the sessions of interest. */
+int halo_direct_closes(halo_handle_t h, uint64_t* count);
 /* Bring the accumulator up to date WITHOUT a host wait: the closing folds of the ended sessions are queued and the backend's stream is made
  * to wait for them, so that work queued on that stream afterwards (a collective on a bound accumulator, a copy) sees the finished image.
  * Needed with option "defer_fold" = 1 (halo_end then leaves the fold of a caller-bound accumulator pending so that the next session's trace

@@ -60,6 +60,7 @@ def load_library():
         "halo_last_route": (C.c_int, [H, C.POINTER(abi.HaloRouteInfo)]),
         "halo_last_root_profile": (C.c_int, [H, C.POINTER(C.c_uint32)]),
         "halo_direct_closes": (C.c_int, [H, C.POINTER(C.c_uint64)]),
+        "halo_tile_appends": (C.c_int, [H, C.POINTER(C.c_uint64)]),
         "halo_set_color": (C.c_int, [H, C.POINTER(abi.HaloColorSet), C.c_int, C.POINTER(abi.HaloColorClass), C.c_int]),
         "halo_readback_class_lanes": (C.c_int, [H, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int]),
         "halo_generate_shapes": (C.c_int, [H, C.POINTER(abi.HaloCrystal), C.c_uint64, C.c_uint32, C.c_int, C.POINTER(abi.HaloGeomTables)]),
@@ -103,7 +104,7 @@ def load_library():
 EXPORTED_SYMBOLS = [
     "halo_abi_version", "halo_abi_sizeof", "halo_device_count", "halo_create", "halo_destroy", "halo_last_error",
     "halo_set_option", "halo_set_stream", "halo_bind_accumulator", "halo_set_filters", "halo_begin", "halo_trace_layer", "halo_recombine",
-    "halo_drain_exits", "halo_end", "halo_readback_xyz", "halo_readback_xyz64", "halo_sync", "halo_flush", "halo_collect_timing", "halo_last_sample_counts", "halo_last_route", "halo_last_root_profile", "halo_direct_closes", "halo_set_color", "halo_readback_class_lanes", "halo_generate_shapes", "halo_collect_stats", "halo_take_landed", "halo_consumer_fold", "halo_consumer_consume", "halo_consumer_snapshot", "halo_consumer_reset", "halo_consumer_composite", "halo_consumer_load_lanes", "halo_host_parse_composite_mode", "halo_host_prism_geometry",
+    "halo_drain_exits", "halo_end", "halo_readback_xyz", "halo_readback_xyz64", "halo_sync", "halo_flush", "halo_collect_timing", "halo_last_sample_counts", "halo_last_route", "halo_last_root_profile", "halo_direct_closes", "halo_tile_appends", "halo_set_color", "halo_readback_class_lanes", "halo_generate_shapes", "halo_collect_stats", "halo_take_landed", "halo_consumer_fold", "halo_consumer_consume", "halo_consumer_snapshot", "halo_consumer_reset", "halo_consumer_composite", "halo_consumer_load_lanes", "halo_host_parse_composite_mode", "halo_host_prism_geometry",
     "halo_host_pyramid_geometry", "halo_host_shape_scalars", "halo_host_build_lat_lut", "halo_host_build_proj_params", "halo_host_partition",
     "halo_host_refractive_index", "halo_host_reduce_raypath", "halo_host_filter_fast_check", "halo_host_color_fast_mask", "halo_host_illuminant_spd", "halo_host_wl_pool", "halo_reduce_accumulator",
     "halo_peek_fixed", "halo_host_fixed_frac_bits",
@@ -220,6 +221,12 @@ class HipTraceBackend:
         """Launches of this backend, ever, that closed their session in their own per-tile pass (option close_direct): a cumulative count."""
         n = C.c_uint64()
         self._check(self._L.halo_direct_closes(self._h, C.byref(n)))
+        return n.value
+
+    def tile_appends(self):
+        """Launches of this backend, ever, whose trace kernel appended its records per tile (option tile_append): a cumulative count."""
+        n = C.c_uint64()
+        self._check(self._L.halo_tile_appends(self._h, C.byref(n)))
         return n.value
 
     def collect_stats(self):

@@ -136,6 +136,12 @@ struct HaloBackend {
   Marker close_done;           // the direct close queued last, on trace stream close_ts
   int close_ts = 0;
   bool cnt2_clean[2] = {false, false};   // log set s: the tile-list counters are known to be zero (the closing pass zeroes what it consumed)
+  // Per-tile append: a directly closing launch whose kernel has a kAccTileFinal twin appends its records to per-tile chunks of each
+  // workgroup (halo_trace.inl log_hit_tile) and the closing pass reads the chunks (launch_tile_route_close): the split pass and its tile lists go.
+  int tile_append = -1;        // option: -1 auto (launches that fill the chip), 0 never, 1 wherever eligible
+  uint64_t tile_appends = 0;   // launches that took the route, ever (halo_tile_appends)
+  DevBuf<HitRec> tile_chunk_s[2];   // chunk[tile][workgroup][cap], one set per log set
+  DevBuf<uint32_t> tile_cnt_s[2];   // cnt[tile][workgroup]
   HaloRouteInfo route{};       // kernels that served the current / last session (halo_last_route)
   uint32_t route_root = 0;     // ... and the root profiles among them (halo_last_root_profile): bit kRootProfile* - 1
 
@@ -589,6 +595,7 @@ int halo_destroy(halo_handle_t b) {
               b->lanes_stage, b->comp_hist, b->counters, b->ring_dev, b->tcache_dev, b->shapes_s[0], b->shapes_s[1], b->cont_cnt, b->cont_mask, b->cont_err, b->cont_base,
               b->cont_tiles, b->lanes, b->fix, b->cont[0], b->cont[1], b->exits, b->host_f, b->host_u);
   for (int k = 0; k < 2; k++) release_all(b->bin_list_s[k], b->bin_cnt_s[k], b->bin_list2_s[k], b->bin_cnt2_s[k]);
+  for (int k = 0; k < 2; k++) release_all(b->tile_chunk_s[k], b->tile_cnt_s[k]);
   if (b->ring_host) (void)hipHostFree(b->ring_host);
   if (b->tally_host) (void)hipHostFree(b->tally_host);
   for (int k = 0; k < HaloBackend::kRing; k++)
@@ -657,6 +664,7 @@ int halo_set_option(halo_handle_t b, const char* key, int64_t v) {
   else if (k == "defer_fold") b->defer_fold = v ? 1 : 0;
   else if (k == "gen_ahead") b->gen_ahead = v ? 1 : 0;
   else if (k == "close_direct") b->close_direct = v < 0 ? -1 : (v ? 1 : 0);
+  else if (k == "tile_append") b->tile_append = v < 0 ? -1 : (v ? 1 : 0);
   else if (k == "pool_entry_fast") b->pool_entry_fast = v ? 1 : 0;
   else if (k == "rehit_strategy") {
     if (b->in_session) return fail(b, HALO_FATAL, "rehit_strategy cannot change inside a session");
@@ -1057,6 +1065,7 @@ struct LaunchPlan {
   bool use_bin = false, two_level = false, use_log = false, use_log_xyz = false, canon = false, no_land = false;
   bool only = false;                    // the layer's only launch, on the session's last layer (halo_trace_layer)
   bool close = false;                   // ... that closes its session in its per-tile pass (close_direct_ok): nothing is left in the planes
+  bool tile = false;                    // ... and whose trace kernel appends per tile (bind_tile_append): the closing pass reads chunks, no split pass
   bool fixed = false;                   // a deterministic session's launch: the kAccFixed kernels, with use_log their logging twins (or, where every exit continues, kAccNone)
   uint32_t fan_log2 = 0, lists1 = 0, bin_tiles = 0, log_t_log2 = 0, log_planes = 1, log_tiles = 0;
   uint64_t cap1 = 0, cap2 = 0;          // records per region / coarse list and per tile list, as REQUESTED: reserve_log_buffers clamps the log's against free memory
@@ -1494,6 +1503,57 @@ bool close_direct_ok(const HaloBackend& b, const LaunchPlan& p, const DispatchPa
   if (P.ovf == nullptr || P.ovf_flag == nullptr || b.mono_dirty || b.acc == nullptr) return false;
   return b.close_direct > 0 || !p.alternate;   // auto: the hit log's own threshold chose the log; launches that fill the chip only
 }
+// The per-tile append of a launch that closes directly (HaloBackend::tile_append): taken where the launch's kernel has a kAccTileFinal twin — mirrored
+// from halo_trace.inl tile_kernel_exists: plain mode, one regular prism, scalar plane, last layer with a closed gate, one of the four lenses that are
+// template constants, the upper sky — and the chunk buffers of log set `ls` can be reserved.  Tiles: the close's own contiguous ones, at most
+// kTileAppendMax (a small launch's 256 become 128: the kernel holds one LDS counter per tile).  A chunk holds kListSlack (8) x its even share of the
+// 4 records per ray the log's regions are sized for, all chunks together within the lists' 8 GB (2^30 records: the kernel's 32-bit index) and half of
+// free memory; what a chunk cannot hold goes to the twin.  A reserve that fails leaves the launch on the split route.  Writes the tile fields of P.
+int bind_tile_append(HaloBackend* b, LaunchPlan& p, const EntryTables& T, int ls, DispatchParams& P) {
+  P.tile_chunk = nullptr, P.tile_cnt = nullptr, P.tile_cap = P.tile_log2 = P.tile_tiles = 0u;
+  p.tile = false;
+  // auto: launches that fill the chip, over generated roots.  (A last layer over the continuation pool — configs[2]: five times the records per
+  // launch, hot tiles past their chunks — measured slower with the append, profiles/tile_append_ab.txt: 1 takes it, auto does not.)
+  if (!p.close || b->tile_append == 0 || (b->tile_append < 0 && (p.alternate || P.source != kSrcGen))) return HALO_OK;
+  const int lens = P.proj.proj_type;
+  const bool lens_known = lens == HALO_LENS_LINEAR || lens == HALO_LENS_FISHEYE_EQUAL_AREA || lens == HALO_LENS_DUAL_FISHEYE_EQUAL_AREA || lens == HALO_LENS_RECTANGULAR;
+  const bool hex = p.geom == 0 && T.entry_fast && b->hex_fast && T.hex_regular;   // (queue_launch's launch_geom == 3)
+  if (T.mode != 0 || !hex || !b->mono_session || P.final_layer == 0u || P.prob > 0.0f || P.cont_mask != nullptr || P.no_land != 0u || P.fix != nullptr ||
+      P.mono_by_wl != 0u || P.proj.visible_range != HALO_VISIBLE_UPPER || !lens_known)
+    return HALO_OK;
+  const uint32_t t_log2 = std::min<uint32_t>(p.log_t_log2, static_cast<uint32_t>(__builtin_ctz(kTileAppendMax)));
+  if (b->mono_s_log2 + 10u < t_log2 || b->mono_s_log2 + 10u - t_log2 > kBinTileLog2) return HALO_OK;
+  const uint64_t tiles = 1ull << t_log2, blocks = static_cast<uint64_t>(p.blocks), chunks = tiles * blocks;
+  const uint64_t per_wg = (p.m + blocks - 1u) / blocks;
+  uint64_t cap = std::max<uint64_t>(8ull * 4ull * per_wg / tiles, 16ull);
+  cap = std::min<uint64_t>(cap, (1ull << 30) / chunks);
+  if (b->hit_log_cap) cap = std::max<uint64_t>(b->hit_log_cap / tiles, 2ull);   // tests: chunks that overflow
+  size_t free_b = 0, total_b = 0;
+  const uint64_t have = b->tile_chunk_s[ls].cap * sizeof(HitRec), need = cap * chunks * sizeof(HitRec);
+  if (need > have && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need - have > free_b / 2u)
+    cap = (have + free_b / 2u) / (chunks * sizeof(HitRec));
+  cap &= ~1ull;   // a chunk starts on 16 bytes
+  if (cap < 2u) return HALO_OK;
+  hipError_t e1 = hipSuccess, e2 = hipSuccess;
+  if (int rc = reserve_idle(b, b->tile_chunk_s[ls], cap * chunks, &e1)) return rc;
+  if (e1 == hipSuccess)
+    if (int rc = reserve_idle(b, b->tile_cnt_s[ls], chunks, &e2)) return rc;
+  if (e1 != hipSuccess || e2 != hipSuccess) {
+    (void)hipGetLastError();   // out of memory: not this launch's route
+    return HALO_OK;
+  }
+  if (b->overlap && p.alternate) {   // the other set with it, as reserve_log_buffers does (a speed matter only)
+    hipError_t e3 = hipSuccess, e4 = hipSuccess;
+    if (int rc = reserve_idle(b, b->tile_chunk_s[ls ^ 1], cap * chunks, &e3)) return rc;
+    if (e3 == hipSuccess)
+      if (int rc = reserve_idle(b, b->tile_cnt_s[ls ^ 1], chunks, &e4)) return rc;
+    if (e3 != hipSuccess || e4 != hipSuccess) (void)hipGetLastError();
+  }
+  p.tile = true;
+  P.tile_chunk = b->tile_chunk_s[ls].ptr, P.tile_cnt = b->tile_cnt_s[ls].ptr;
+  P.tile_cap = static_cast<uint32_t>(cap), P.tile_tiles = static_cast<uint32_t>(tiles), P.tile_log2 = b->mono_s_log2 + 10u - t_log2;
+  return HALO_OK;
+}
 // HaloRouteInfo (halo_last_route: what the GPU tests assert routes with).  The masks name the instantiation that launch_mode / launch_mono /
 // launch_lens / launch_vis in halo_trace.inl pick for this launch — mirrored here — not the request: the regular-prism search exists for
 // the production-shaped kernels off the binned route, the no-accumulation kernels for their one-shape dispatches.
@@ -1562,6 +1622,23 @@ int queue_passes(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, c
     } else if (int rc = wait_for_aux(b, ts_i)) return rc;
   }
   HIPCHK(b, hipEventRecord(b->ring_ev2[k], ps));
+  if (p.close && p.tile) {
+    // the closing pass over the chunks the trace kernel filled: no split, no list counters; the twin's flag is cleared behind the pass as below
+    const float coef[3] = {b->plane_coef[0][0], b->plane_coef[0][1], b->plane_coef[0][2]};
+    hipError_t ce = launch_tile_route_close(b->acc, static_cast<uint32_t>(b->acc_w) * static_cast<uint32_t>(b->acc_h), coef, P.tile_chunk, P.tile_cap, P.tile_cnt,
+                                            static_cast<uint32_t>(p.blocks), P.tile_tiles, b->mono_s_log2, frac_bits, P.ovf, P.ovf_flag, ps, before_sums);
+    if (ce != hipSuccess) return hip_fail(b, ce, "halo_tile_close_kernel launch");
+    b->direct_closes++;
+    b->tile_appends++;
+    HIPCHK(b, b->close_done.mark(ps));
+    b->close_ts = ts_i;
+    HIPCHK(b, hipEventRecord(b->ring_ev3[k], ps));
+    HIPCHK(b, b->set_free[S.ls].mark(ps));
+    if (b->overlap && p.alternate) b->log_set ^= 1;
+    b->ring_posts[k] = true;
+    HIPCHK(b, hipEventRecord(b->ring_done[k], ps));
+    return HALO_OK;
+  }
   if (p.close) {
     // the split and the closing per-tile pass, which leaves nothing behind: counters zeroed by the workgroups that consumed them (the memset in front
     // of the split goes: 4-7 us per launch, profiles/direct_close_ab.txt), the twin's flag cleared behind the pass, the planes untouched (mono_dirty stays false: no fold follows)
@@ -1757,6 +1834,7 @@ int trace_launch(HaloBackend* b, const LayerCtx& c, LaunchPlan& p, EntryTables& 
   S.ls = (b->overlap && p.alternate) ? b->log_set : 0;   // the buffer set of this launch
   if (int rc = bind_route(b, p, S.ls, P)) return rc;
   p.close = close_direct_ok(*b, p, P);
+  if (int rc = bind_tile_append(b, p, T, S.ls, P)) return rc;
   if (int rc = queue_launch(b, p, E, T, P, S)) return rc;
   if (p.host_pool) HIPCHK(b, hipStreamSynchronize(b->stream));  // the pageable shape pool must outlive its copy (the copy is on the main stream)
   if (P.source == kSrcGen) b->gen_count += m;
@@ -2028,6 +2106,12 @@ int halo_last_route(halo_handle_t b, HaloRouteInfo* out) {
 int halo_direct_closes(halo_handle_t b, uint64_t* out) {
   if (!b || !out) return HALO_FATAL;
   *out = b->direct_closes;
+  return HALO_OK;
+}
+
+int halo_tile_appends(halo_handle_t b, uint64_t* out) {
+  if (!b || !out) return HALO_FATAL;
+  *out = b->tile_appends;
   return HALO_OK;
 }
 

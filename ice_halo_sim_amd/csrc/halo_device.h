@@ -337,7 +337,16 @@ struct DispatchParams {
                                // adds floor(double(v) * 2^fix_frac + 0.5) with an integer atomic, halo_fold_fixed_kernel reads and zeroes them
   uint32_t fix_frac;           // F of the pending plane set (halo_host_fixed_frac_bits): the same for every add between two folds
   uint32_t fix_frac_landed;    // F_L of the landed-weight integer (tally slot kSumFixLanded of each line)
+  // --- per-tile append (option "tile_append": the kAccTileFinal kernels; with bin_log, whose regions stay bound but unused) ---------
+  HitRec* tile_chunk;          // chunk[tile][workgroup][tile_cap] (nullptr = not a tile-append launch): a hit that misses the pixel cache goes to the
+                               // workgroup's own chunk of its tile — the split pass's scatter, done by the trace kernel — and what a full chunk
+                               // cannot hold to the twin, like a full log region's
+  uint32_t* tile_cnt;          // cnt[tile][workgroup]: every workgroup writes all its tile_tiles counts (records MET, kept or not), zeros included
+  uint32_t tile_cap;           // records per chunk (even: a chunk starts on 16 bytes)
+  uint32_t tile_log2;          // slots per tile, log2: tile of a record = slot >> tile_log2
+  uint32_t tile_tiles;         // tiles of the plane, <= kTileAppendMax
 };
+constexpr uint32_t kTileAppendMax = 128u;   // counters of a kAccTileFinal workgroup (LDS)
 
 // Pixel → slot map of the mono plane.  The plane is kMonoRows rows of S = 2^s_log2 slots; pixel p sits in row p % kMonoRows
 // at column hash(p / kMonoRows).  Horizontal neighbours are a whole row (>= 8 KB) apart and vertical neighbours are

@@ -328,6 +328,36 @@ __device__ __forceinline__ void close_done(const CloseArgsOf<true>& cl, uint32_t
   __syncthreads();   // every thread has the count it loaded
   if (threadIdx.x == 0u) cl.cnt[static_cast<size_t>(tile) * kBinCntStride] = 0u;
 }
+// The closing form's write-out, shared by the pass over tile lists (halo_bin_accumulate_range_kernel<false, true>) and the pass over per-tile chunks
+// (halo_tile_close_kernel): `acc` holds the tile's fixed-point sums, every thread of the workgroup is behind the barrier that completes them.
+template <typename Acc>   // (the LDS array itself, not a pointer to it: the sums are read with LDS instructions)
+__device__ __forceinline__ void close_write_out(const Acc& acc, const FixQ fq, const uint32_t tile, const uint32_t tile_log2, const uint32_t slots, const bool take_twin,
+                                                const CloseArgsOf<true> cl) {
+  // Consecutive lanes take consecutive ROWS of one column — consecutive pixels — in runs of up to eight (96 bytes of XYZ; the fold's own runs are
+  // 48 bytes and more), then the next column.  A tile-local slot is row bits above `cb` column bits.
+  const uint32_t s_mask = (1u << cl.s_log2) - 1u;
+  const uint32_t cb = min(cl.s_log2, tile_log2), rl = min(tile_log2 - cb, 3u);
+  const uint32_t base = tile << tile_log2;
+  for (uint32_t i = threadIdx.x; i < slots; i += kBinBlock) {
+    const uint32_t rest = i >> rl;
+    const uint32_t j = (((((rest >> cb) << rl) | (i & ((1u << rl) - 1u))) << cb) | (rest & ((1u << cb) - 1u)));
+    const uint32_t slot = base | j;
+    float v = fq.unfix(acc[j]);
+    if (take_twin) {
+      const double o = cl.twin[slot];
+      if (o != 0.0) {
+        cl.twin[slot] = 0.0;
+        v = static_cast<float>(static_cast<double>(v) + o);
+      }
+    }
+    if (v == 0.0f) continue;
+    const uint32_t pix = (((slot & s_mask) * kMonoMulInv) & s_mask) * kMonoRows + (slot >> cl.s_log2);   // MonoSlot inverted, as the fold does
+    if (pix >= cl.n_pix) continue;
+    float* q = cl.xyz + 3u * static_cast<size_t>(pix);
+#pragma unroll
+    for (uint32_t c = 0; c < 3u; ++c) q[c] = close_add(q[c], cl.coef[c], v);
+  }
+}
 template <bool kFix>
 using PlaneOf = typename std::conditional<kFix, unsigned long long, float>::type;
 template <bool kFix = false, bool kClose = false>
@@ -401,30 +431,7 @@ __global__ void __launch_bounds__(kBinBlock) halo_bin_accumulate_range_kernel(Pl
   }
   __syncthreads();
   if constexpr (kClose) {
-    // Consecutive lanes take consecutive ROWS of one column — consecutive pixels — in runs of up to eight (96 bytes of XYZ; the fold's own runs are
-    // 48 bytes and more), then the next column.  A tile-local slot is row bits above `cb` column bits.
-    const uint32_t s_mask = (1u << cl.s_log2) - 1u;
-    const uint32_t cb = min(cl.s_log2, tile_log2), rl = min(tile_log2 - cb, 3u);
-    const uint32_t base = tile << tile_log2;
-    for (uint32_t i = threadIdx.x; i < slots; i += kBinBlock) {
-      const uint32_t rest = i >> rl;
-      const uint32_t j = (((((rest >> cb) << rl) | (i & ((1u << rl) - 1u))) << cb) | (rest & ((1u << cb) - 1u)));
-      const uint32_t slot = base | j;
-      float v = fq.unfix(acc[j]);
-      if (take_twin) {
-        const double o = cl.twin[slot];
-        if (o != 0.0) {
-          cl.twin[slot] = 0.0;
-          v = static_cast<float>(static_cast<double>(v) + o);
-        }
-      }
-      if (v == 0.0f) continue;
-      const uint32_t pix = (((slot & s_mask) * kMonoMulInv) & s_mask) * kMonoRows + (slot >> cl.s_log2);   // MonoSlot inverted, as the fold does
-      if (pix >= cl.n_pix) continue;
-      float* q = cl.xyz + 3u * static_cast<size_t>(pix);
-#pragma unroll
-      for (uint32_t c = 0; c < 3u; ++c) q[c] = close_add(q[c], cl.coef[c], v);
-    }
+    close_write_out(acc, fq, tile, tile_log2, slots, take_twin, cl);
     close_done(cl, tile);
   } else if constexpr (kFix) {
     unsigned long long* dst = plane + (static_cast<size_t>(tile) << tile_log2);
@@ -620,6 +627,103 @@ hipError_t launch_log_route_close(float* xyz, uint32_t n_pix, const float* coef,
   const CloseArgsOf<true> cl{xyz, n_pix, s_log2, {coef[0], coef[1], coef[2]}, cnt2, ovf, ovf_flag};
   hipLaunchKernelGGL((halo_bin_accumulate_range_kernel<false, true>), dim3(tiles), dim3(kBinBlock), 0, stream, static_cast<float*>(nullptr), reinterpret_cast<const uint2*>(list2), cap2,
                      static_cast<const uint32_t*>(nullptr), tile_log2, frac_bits, cl);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  return hipMemsetAsync(ovf_flag, 0, sizeof(uint32_t), stream);   // every workgroup has seen it; the pass zeroed what it took
+}
+
+// ---- the closing per-tile pass over per-tile CHUNKS (option "tile_append": a kAccTileFinal trace kernel wrote them, halo_trace.inl log_hit_tile) ----
+// One workgroup per tile of 2^tile_log2 consecutive slots, as in the closing form above; the tile's records lie in one chunk per trace workgroup,
+// chunk[tile][wg][cap] with cnt[tile][wg] records met (clamped to cap here: what a chunk could not hold went to the twin).  A chunk is short — a few
+// hundred records at most — so ONE WAVE takes a chunk, reads the counts of 64 chunks at a time (one per lane) and keeps kChunksInFlight chunks'
+// loads in the air (the first 64 x kLoads pairs of each; what a longer chunk holds beyond them follows in a loop): two records per 16-byte load (a chunk starts on 16 bytes: cap is even), non-temporal — the chunks are read once, a moment
+// after they were written — and the same fixed-point LDS sums.  The write-out is the closing form's own (close_write_out).  Nothing is reset:
+// the trace kernel writes every count of every launch, and the twin's flag is cleared by the memset behind the pass, as above.
+// (Measured on configs[1], passes per launch, chunks in flight x 16-byte loads per lane and chunk: 2 x 2 317 us, 4 x 2 280, 8 x 2 268, 8 x 1 252,
+// 16 x 1 247 — profiles/tile_append_ab.txt: the chunks of that launch hold ~160 records, and what a second load per chunk would fetch is mostly
+// not there.)
+constexpr uint32_t kChunksInFlight = 16u, kLoads = 1u;
+__global__ void __launch_bounds__(kBinBlock) halo_tile_close_kernel(const uint2* __restrict__ chunk, uint32_t cap, const uint32_t* __restrict__ cnt, uint32_t wgs,
+                                                                    uint32_t tile_log2, uint32_t frac_bits, const CloseArgsOf<true> cl) {
+  __shared__ __attribute__((aligned(16))) unsigned long long acc[1u << kBinTileLog2];   // fixed point (FixQ); tile_log2 <= kBinTileLog2
+  const FixQ fq(frac_bits);
+  const uint32_t tile = blockIdx.x;
+  const uint32_t* tcnt = cnt + static_cast<size_t>(tile) * wgs;
+  const bool take_twin = *cl.flag != 0u;   // workgroup-uniform
+  uint32_t any = 0u;
+  for (uint32_t c = threadIdx.x; c < wgs; c += kBinBlock) any |= tcnt[c];
+  if (!__syncthreads_or(static_cast<int>(any != 0u)) && !take_twin) return;
+  const uint32_t slots = 1u << tile_log2, mask = slots - 1u;
+  for (uint32_t j = threadIdx.x; j < slots; j += kBinBlock) acc[j] = 0ull;
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, waves = kBinBlock / 64u;
+  const uint2* tsrc = chunk + static_cast<size_t>(tile) * wgs * cap;
+  auto add = [&](uint32_t slot, uint32_t w_bits) { atomicAdd(&acc[slot & mask], fq.fix(__uint_as_float(w_bits))); };
+  for (uint32_t c0 = wave * 64u; c0 < wgs; c0 += waves * 64u) {   // wave-uniform
+    const uint32_t mine = c0 + lane < wgs ? min(tcnt[c0 + lane], cap) : 0u;
+    if (__ballot(mine != 0u) == 0ull) continue;
+    for (uint32_t g = 0; g < 64u; g += kChunksInFlight) {
+      uint32_t n[kChunksInFlight], most = 0u;
+#pragma unroll
+      for (uint32_t k = 0; k < kChunksInFlight; ++k) {
+        n[k] = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(mine), static_cast<int>(g + k)));
+        most = max(most, n[k]);
+      }
+      if (most == 0u) continue;
+      // the first 64 x kLoads pairs of each chunk, all requested before the first add
+      uint4 h[kChunksInFlight][kLoads];
+#pragma unroll
+      for (uint32_t k = 0; k < kChunksInFlight; ++k) {
+        const uint4* src4 = reinterpret_cast<const uint4*>(tsrc + static_cast<size_t>(c0 + g + k) * cap);
+#pragma unroll
+        for (uint32_t u = 0; u < kLoads; ++u) {
+          const uint32_t i = lane + 64u * u;
+          h[k][u] = i < n[k] / 2u ? load_list_u4<true>(&src4[i]) : make_uint4(0u, 0u, 0u, 0u);   // (a zero weight adds nothing to slot 0)
+        }
+      }
+#pragma unroll
+      for (uint32_t k = 0; k < kChunksInFlight; ++k) {
+#pragma unroll
+        for (uint32_t u = 0; u < kLoads; ++u) {
+          if (lane + 64u * u < n[k] / 2u) {
+            add(h[k][u].x, h[k][u].y);
+            add(h[k][u].z, h[k][u].w);
+          }
+        }
+      }
+      // what is left: the pairs behind those, and an odd last record
+#pragma unroll
+      for (uint32_t k = 0; k < kChunksInFlight; ++k) {
+        const uint2* src = tsrc + static_cast<size_t>(c0 + g + k) * cap;
+        const uint4* src4 = reinterpret_cast<const uint4*>(src);
+        for (uint32_t i = lane + 64u * kLoads; i < n[k] / 2u; i += 64u) {
+          const uint4 q = load_list_u4<true>(&src4[i]);
+          add(q.x, q.y);
+          add(q.z, q.w);
+        }
+        if ((n[k] & 1u) != 0u && lane == 0u) {
+          const uint2 q = src[n[k] - 1u];
+          add(q.x, q.y);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  close_write_out(acc, fq, tile, tile_log2, slots, take_twin, cl);
+}
+
+// The closing form over per-tile chunks: chunk[tiles][wgs][cap] and cnt[tiles][wgs] as a kAccTileFinal trace kernel of `wgs` workgroups left them ->
+// coef x sum added to the XYZ image.  No split pass, no tile lists, no counter to reset; the 4-byte memset of the twin's flag behind the pass stays.
+hipError_t launch_tile_route_close(float* xyz, uint32_t n_pix, const float* coef, const HitRec* chunk, uint32_t cap, const uint32_t* cnt, uint32_t wgs, uint32_t tiles,
+                                   uint32_t s_log2, uint32_t frac_bits, double* ovf, uint32_t* ovf_flag, hipStream_t stream, hipEvent_t before_sums) {
+  if (tiles == 0u || (tiles & (tiles - 1u)) != 0u || tiles > kTileAppendMax || wgs == 0u || cap == 0u || (cap & 1u) != 0u) return hipErrorInvalidValue;
+  if (xyz == nullptr || coef == nullptr || chunk == nullptr || cnt == nullptr || ovf == nullptr || ovf_flag == nullptr) return hipErrorInvalidValue;
+  const uint32_t tiles_log2 = static_cast<uint32_t>(__builtin_ctz(tiles));
+  if (s_log2 + 10u < tiles_log2 || s_log2 + 10u - tiles_log2 > kBinTileLog2) return hipErrorInvalidValue;
+  if (static_cast<uint64_t>(tiles) * wgs * cap > (1ull << 30)) return hipErrorInvalidValue;   // (the trace kernel's 32-bit record index)
+  hipError_t e = hipSuccess;
+  if (before_sums && (e = hipStreamWaitEvent(stream, before_sums, 0)) != hipSuccess) return e;
+  const CloseArgsOf<true> cl{xyz, n_pix, s_log2, {coef[0], coef[1], coef[2]}, nullptr, ovf, ovf_flag};
+  hipLaunchKernelGGL(halo_tile_close_kernel, dim3(tiles), dim3(kBinBlock), 0, stream, reinterpret_cast<const uint2*>(chunk), cap, cnt, wgs, s_log2 + 10u - tiles_log2, frac_bits, cl);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   return hipMemsetAsync(ovf_flag, 0, sizeof(uint32_t), stream);   // every workgroup has seen it; the pass zeroed what it took
 }
@@ -1238,6 +1342,7 @@ hipError_t launch_trace_m4(const DispatchParams& P, int blocks, hipStream_t stre
 // mode: halo_trace.inl kMode* — 0 plain, 1 filter (fast form), 2 capture (tests), 3 generic filter / colour, 4 filter + colour (fast form)
 // geom: 0 = one shape per dispatch, 1 = shape pool, 2 = shape pool of prisms (compact LDS slots), 3 = one regular hexagonal prism
 hipError_t launch_trace(const DispatchParams& P, int blocks, hipStream_t stream, int mode, int geom, bool mono) {
+  if (P.tile_chunk != nullptr) return mode == 0 ? launch_trace_tl0(P, blocks, stream, geom, mono) : hipErrorNotSupported;   // the per-tile append: its kernel, or an error
   switch (mode) {
     case 0: return launch_trace_m0(P, blocks, stream, geom, mono);
     case 1: return launch_trace_m1(P, blocks, stream, geom, mono);

@@ -26,6 +26,9 @@ hipError_t launch_log_route_xyz(float* planes, uint32_t plane_stride, const HitR
 hipError_t launch_log_route_close(float* xyz, uint32_t n_pix, const float* coef, const HitRec* log, uint32_t cap1, const uint32_t* cnt1, uint32_t regions, HitRec* list2,
                                   uint32_t cap2, uint32_t* cnt2, uint32_t tiles, uint32_t s_log2, uint32_t frac_bits, double* ovf, uint32_t* ovf_flag,
                                   hipStream_t stream, hipEvent_t before_sums);
+// (the same close over the per-tile chunks of a kAccTileFinal trace kernel of `wgs` workgroups: chunk[tiles][wgs][cap], cnt[tiles][wgs]; no split pass)
+hipError_t launch_tile_route_close(float* xyz, uint32_t n_pix, const float* coef, const HitRec* chunk, uint32_t cap, const uint32_t* cnt, uint32_t wgs, uint32_t tiles,
+                                   uint32_t s_log2, uint32_t frac_bits, double* ovf, uint32_t* ovf_flag, hipStream_t stream, hipEvent_t before_sums);
 // (the deterministic route's log: integer planes, the session's F, atomics only — no fp64 twin, no ordering event)
 hipError_t launch_log_route_fixed(unsigned long long* fix, const HitRec* log, uint32_t cap1, const uint32_t* cnt1, uint32_t regions, HitRec* list2, uint32_t cap2,
                                   uint32_t* cnt2, uint32_t tiles, uint32_t s_log2, bool interleaved, uint32_t frac_bits, hipStream_t stream);

@@ -566,6 +566,8 @@ static_assert(offsetof(FixCache<true>, val) % 8 == 0 && offsetof(FixCache<false>
 constexpr int kAccDirect = 0, kAccBin = 1, kAccLog = 2, kAccNone = 3, kAccLogFinal = 4;   // halo_trace_kernel ACC (None: a layer whose every exit continues — nothing lands)
 constexpr int kAccFixed = 5;   // the integer twin of kAccDirect (option "deterministic"): FixCache in LDS, 64-bit integer atomics onto DispatchParams::fix
 constexpr int kAccFixedLog = 6;   // ... and of the logging kernels: the same cache, but a hit that loses the claim leaves as a raw {slot, weight} record (log_hit_fixed)
+constexpr int kAccTileFinal = 7;   // kAccLogFinal whose records go to per-tile chunks of the workgroup instead of its one region (log_hit_tile): no split pass
+constexpr int kCtxFloat = 0, kCtxFixedLog = 1, kCtxTile = 2;   // AccCtx FL: which record a cache miss of a logging kernel leaves as (a type, so that no other kernel compiles the branch)
 constexpr int kHitBuf = 1536;                 // staged hits per workgroup (16 KB)
 // (kBinTileLog2, slots per tile, and kBinCntStride, the spacing of the tile counters: halo_device.h)
 constexpr int kBinMaxTiles = 512;
@@ -625,7 +627,7 @@ struct ProjLds {
 };
 static_assert(offsetof(ProjLds, half_w) == sizeof(ProjDev) && offsetof(DispatchParams, proj_pre) == offsetof(DispatchParams, proj) + sizeof(ProjDev),
               "the four floats lie directly behind the ProjDev, in LDS and in the dispatch record");
-template <bool MONO, bool SMALLC, bool FIXLOG = false>   // FIXLOG: the context of a kAccFixedLog kernel (a type, so that no other kernel compiles its branch)
+template <bool MONO, bool SMALLC, int FL = kCtxFloat>   // FL: kCtxFixedLog, the context of a kAccFixedLog kernel; kCtxTile, of a kAccTileFinal kernel
 struct AccCtx {
   int lens, vis;     // >= 0: instantiated for this lens / visible range (the projection's dispatch folds away)
   bool nogate;       // instantiated for prob <= 0: no candidate ever passes the gate, the gate stream and its code fold away
@@ -639,7 +641,7 @@ struct AccCtx {
   const uint32_t* fast_ee;  // ... the first kFastEeLds entry/exit matrices, staged in LDS
   PixCache<MONO, SMALLC>* cache;
   HitBuffer* hits;   // nullptr = accumulate directly
-  uint32_t* log_n;   // hit-log kernels: the workgroup's log cursor (LDS); nullptr otherwise
+  uint32_t* log_n;   // hit-log kernels: the workgroup's log cursor (LDS; kCtxTile: its kTileAppendMax per-tile counters); nullptr otherwise
   const ProjLds* proj;   // HALO_PROJ_LDS: the projection's constants staged in LDS for the exit queue's drain (nullptr = the dispatch record's)
 };
 
@@ -708,6 +710,23 @@ HD void log_hit(const DispatchParams& P, uint32_t* log_n, uint32_t slot, float w
   }
 }
 
+// The per-tile append (kAccTileFinal kernels, scalar plane): the record goes to the workgroup's own chunk of the record's tile — tile = slot >>
+// tile_log2, contiguous tiles as the closing per-tile pass takes them — at a position drawn from the tile's counter in LDS, one returning ds_add
+// per lane.  Scattered 8-byte stores beside the trace's ALU work run at twice the rate the launch needs (tools/atomic_rate_bench.hip, the
+// "tile append" rows), and the split pass, which existed to do this scatter, goes.  A full chunk overflows as a full region does.  The counter
+// counts every record it met: the reader clamps.  Call with any subset of a wave's lanes active.
+HD void log_hit_tile(const DispatchParams& P, uint32_t* tile_n, uint32_t slot, float w) {
+  const uint32_t tile = slot >> P.tile_log2;   // < tile_tiles: a slot lies inside the plane whatever the pixel (MonoSlot)
+  // (32-bit index: the host keeps tiles x workgroups x tile_cap within 2^30 records, the 8 GB of the other lists)
+  const uint32_t first = tile * (gridDim.x * P.tile_cap) + blockIdx.x * P.tile_cap;
+  const uint32_t pos = atomicAdd(&tile_n[tile], 1u);
+  if (pos < P.tile_cap) {
+    reinterpret_cast<uint2*>(P.tile_chunk)[first + pos] = make_uint2(slot, __float_as_uint(w));
+  } else {
+    overflow_add(P, slot, w);   // copy 0
+  }
+}
+
 // What a hit of scalar plane `pl` (0, or the ray's wavelength-pool entry) on pixel `pix` is called in the log: its slot in the array of planes.
 HD uint32_t log_slot(const DispatchParams& P, uint32_t pl, uint32_t pix) { return (pl << (P.mono_s_log2 + 10u)) + MonoSlot(pix, P.mono_s_log2); }
 // X/Y/Z kernels under the hit log: the slot in ONE plane with the CMF code above it (the per-tile pass makes X, Y, Z)
@@ -743,7 +762,7 @@ HD void log_hit_fixed(const DispatchParams& P, uint32_t* log_n, uint32_t pix, ui
   }
 }
 
-template <bool MONO, bool SMALLC, bool FL>
+template <bool MONO, bool SMALLC, int FL>
 HD void accumulate_fixed(const DispatchParams& P, const AccCtx<MONO, SMALLC, FL>& ctx, uint32_t pix, uint32_t wl_idx, float w, float cx, float cy, float cz) {
   static_assert(!SMALLC, "the fixed-point cache is a view of the full-size float cache");
   if (P.aggregate == 2u) return;  // diagnostic: trace + project only
@@ -792,7 +811,7 @@ HD void accumulate_fixed(const DispatchParams& P, const AccCtx<MONO, SMALLC, FL>
     }
     if (P.aggregate == 3u) return;  // diagnostic: cache only, misses dropped
   }
-  if constexpr (FL) {   // kAccFixedLog kernels: the raw record (aggregate = 0: every hit is one)
+  if constexpr (FL == kCtxFixedLog) {   // kAccFixedLog kernels: the raw record (aggregate = 0: every hit is one)
     log_hit_fixed<MONO>(P, ctx.log_n, pix, wl_idx, w, q0, q1, q2);
   } else {
   atomicAdd(fix_slot(P, 0u, pix), q0);   // global_atomic_add_x2, no return value
@@ -805,7 +824,7 @@ HD void accumulate_fixed(const DispatchParams& P, const AccCtx<MONO, SMALLC, FL>
 
 // MONO: one scalar per hit into plane 0 (discrete wavelength) or plane wl_idx (illuminant session with one plane per
 // pool entry); the CMF is applied by halo_fold_kernel.  !MONO: X, Y, Z into planes 0..2.
-template <bool MONO, bool SMALLC, bool FL>
+template <bool MONO, bool SMALLC, int FL>
 HD void accumulate(const DispatchParams& P, const AccCtx<MONO, SMALLC, FL>& ctx, uint32_t pix, uint32_t wl_idx, float w, float cx, float cy, float cz) {
   if constexpr (!SMALLC) {
     if (ctx.fixed) {   // (a constant of the instantiation, like lens / vis / none: the other route folds away)
@@ -878,7 +897,8 @@ HD void accumulate(const DispatchParams& P, const AccCtx<MONO, SMALLC, FL>& ctx,
     if (P.aggregate == 3u) return;  // diagnostic: cache only, misses dropped
   }
   if (ctx.log_n != nullptr) {   // hit-log kernels: a scalar record; for X/Y/Z planes it names the ray's pool entry instead of three products
-    log_hit<!MONO>(P, ctx.log_n, MONO ? log_slot(P, pl, pix) : log_slot_xyz(P, wl_idx, pix), w);
+    if constexpr (FL == kCtxTile) log_hit_tile(P, ctx.log_n, log_slot(P, pl, pix), w);
+    else log_hit<!MONO>(P, ctx.log_n, MONO ? log_slot(P, pl, pix) : log_slot_xyz(P, wl_idx, pix), w);
     return;
   }
   if (MONO) {
@@ -1441,7 +1461,7 @@ HD void stage_shape(SlotT* slot, const RecT* g, uint32_t l32) {
                            // around it) and the projection's FMAs take VGPR operands (an SGPR operand makes a VALU instruction 1.56x dearer on this part).  0 = off
 #endif
 // One exit that goes to the image: project, accumulate, tally (the tail of CollectData, simulator.cpp:719-760).
-template <int MODE, bool MONO, bool SMALLC, bool FL>
+template <int MODE, bool MONO, bool SMALLC, int FL>
 HD int land_exit(const DispatchParams& P, const AccCtx<MONO, SMALLC, FL>& cache, const ColorDev* color, uint64_t cmask, float wx, float wy, float wz, float w,
                  float cmf_x, float cmf_y, float cmf_z, uint32_t wl_idx, RaySums& sums, Probe& pr) {
 #if HALO_PROJ_LDS
@@ -1521,7 +1541,7 @@ HD DispatchParams reload_params() {
 
 // Pop exits off the wave's queue, one per active lane and round, until fewer than 64 are left (`all`: until it is empty).
 // Called where every lane that took part in the pushes is active (their counts agree).
-template <int MODE, bool MONO, bool SMALLC, bool FL>
+template <int MODE, bool MONO, bool SMALLC, int FL>
 HD void drain_exits(const DispatchParams& P_kernel, const AccCtx<MONO, SMALLC, FL>& cache, RaySums& sums, bool all, Probe& pr) {
 #if HALO_RELOAD & 1
   const DispatchParams P = reload_params();
@@ -1553,7 +1573,7 @@ HD void drain_exits(const DispatchParams& P_kernel, const AccCtx<MONO, SMALLC, F
 
 
 
-template <int MODE, bool MONO, bool SMALLC, bool FL>
+template <int MODE, bool MONO, bool SMALLC, int FL>
 HD void emit_gate(const DispatchParams& P, const AccCtx<MONO, SMALLC, FL>& cache, const FilterDev* filter, const ColorDev* color, uint64_t carried, Stream& gate, const float* R, bool live,
                   float lx, float ly, float lz, float w, float cmf_x, float cmf_y, float cmf_z, uint32_t wl_idx, uint32_t root, uint32_t seq,
                   const PathView& pv, uint32_t uni_len, RaySums& sums, Probe& pr) {
@@ -2083,7 +2103,7 @@ struct Wl0 {   // entry 0 of the wavelength pool and 1 / n, loaded once per kern
   float inv_n;
 };
 
-template <int MODE, bool MONO, bool SMALLC, bool HEX, int ROOT, bool FL, typename ShapePtr, typename NextT = NextShape>
+template <int MODE, bool MONO, bool SMALLC, bool HEX, int ROOT, int FL, typename ShapePtr, typename NextT = NextShape>
 HD void trace_one(const DispatchParams& P, LdsTables<MONO, SMALLC>& T, const AccCtx<MONO, SMALLC, FL>& acc, const FilterDev* filter, const ColorDev* color, ShapePtr sh,
                   const Wl0& wl0, uint32_t tid, RaySums& sums, Probe& pr, NextT* next = nullptr, const WlEntryDev* wl_lds = nullptr,
                   const SlotFast* slot_fast = nullptr) {
@@ -2659,7 +2679,7 @@ HD unsigned long long wave_sum(unsigned long long v) {
 // logging ones of them halve the pixel cache (a miss is an 8-byte log record there, not a memory-side atomic: 1024 slots measure the same
 // as 2048 at four and five waves) for 26 KB and SIX waves: configs[1] 20.24 -> 19.60 ms per step.
 template <int MODE, int GEOM, bool MONO, int ACC>
-constexpr bool small_cache_hex() { return (MODE == kModePlain || (HALO_FILTER_SIX && MODE == kModeFilter)) && GEOM == kGeomOneHex && MONO && (ACC == kAccLog || ACC == kAccLogFinal); }
+constexpr bool small_cache_hex() { return (MODE == kModePlain || (HALO_FILTER_SIX && MODE == kModeFilter)) && GEOM == kGeomOneHex && MONO && (ACC == kAccLog || ACC == kAccLogFinal || ACC == kAccTileFinal); }
 template <int MODE, int GEOM, bool MONO, int ACC>
 constexpr int min_waves() {
   if (ACC == kAccFixed || ACC == kAccFixedLog) return min_waves<MODE, GEOM, MONO, kAccDirect>();   // the integer twins keep the direct float kernel's bound (and its LDS: FixCache)
@@ -2678,7 +2698,8 @@ constexpr int min_waves() {
 // ROOT: a root profile (kRoot*, at sample_lat_lon_roll) — the last-layer plain hit-log kernels of the regular prism, which launch_vis fans out.
 template <int MODE, int GEOM, bool MONO, int ACC, int LENS = -1, int VIS = -1, bool NOGATE = false, bool CANON = false, int ROOT = kRootAny>   // ACC: kAccDirect, kAccBin (staged + binned hit lists), kAccLog (per-workgroup hit log), ...
 __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) halo_trace_kernel(const DispatchParams P) {
-  constexpr bool BIN = ACC == kAccBin, LOG = ACC == kAccLog || ACC == kAccLogFinal, NONE = ACC == kAccNone, LAST = ACC == kAccLogFinal, FIXLOG = ACC == kAccFixedLog, FIXED = ACC == kAccFixed || FIXLOG;
+  constexpr bool BIN = ACC == kAccBin, TILE = ACC == kAccTileFinal, LOG = ACC == kAccLog || ACC == kAccLogFinal || TILE, NONE = ACC == kAccNone, LAST = ACC == kAccLogFinal || TILE, FIXLOG = ACC == kAccFixedLog, FIXED = ACC == kAccFixed || FIXLOG;
+  static_assert(!TILE || (MODE == kModePlain && GEOM == kGeomOneHex && MONO), "the per-tile append exists for the headline's kernels: plain mode, one regular prism, scalar plane");
   static_assert(!FIXLOG || !CANON, "a canonical layer before the last never logs");
   static_assert(!FIXED || ((MODE == kModePlain || MODE == kModeFilter) && LENS < 0 && VIS < 0 && !NOGATE && ROOT == kRootAny), "kAccFixed: the plain and the fast-filter kernels, in the generic run-time lens form");
   static_assert(!LOG || ModeTraits<MODE>::kFast, "the hit log is a production-mode route");
@@ -2702,7 +2723,7 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
   __shared__ __attribute__((aligned(16))) ExitQueues<QUEUE> s_queue;
   __shared__ __attribute__((aligned(16))) ExitQueueMasks<QUEUE && MODE == kModeColor> s_queue_mask;
   __shared__ uint32_t s_fast_ee[ModeTraits<MODE>::kFastPath ? kFastEeLds * 32u : 1u];
-  AccCtx<MONO, SMALLC, ACC == kAccFixedLog> acc;
+  AccCtx<MONO, SMALLC, FIXLOG ? kCtxFixedLog : TILE ? kCtxTile : kCtxFloat> acc;
   acc.q = nullptr;
   acc.qm = nullptr;
   acc.fast = nullptr;
@@ -2738,10 +2759,14 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
     acc.proj = &s_proj;
   }
 #endif
-  __shared__ uint32_t s_log_n;
-  if constexpr (LOG) {
-    acc.log_n = &s_log_n;
-    if (threadIdx.x == 0) s_log_n = 0u;
+  __shared__ uint32_t s_log_n[TILE ? kTileAppendMax : 1u];   // the log cursor; kAccTileFinal: a counter per tile
+  if constexpr (TILE) {
+    static_assert(kTileAppendMax <= static_cast<uint32_t>(kBlock), "one thread per tile counter");
+    acc.log_n = s_log_n;
+    if (threadIdx.x < kTileAppendMax) s_log_n[threadIdx.x] = 0u;
+  } else if constexpr (LOG) {
+    acc.log_n = s_log_n;
+    if (threadIdx.x == 0) s_log_n[0] = 0u;
   }
   if constexpr (FIXLOG) {
     // (the cursor of a kAccFixedLog kernel: the word behind the FixCache, inside the float cache's 16 KB that the kernel owns anyway — a word of
@@ -2988,12 +3013,13 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
       if (MONO) {
         const float v = T.cache.val[i];
         if (v == 0.0f) continue;
-        if (LOG) log_hit<false>(P, &s_log_n, log_slot(P, pl, pix), v);
+        if constexpr (TILE) log_hit_tile(P, s_log_n, log_slot(P, pl, pix), v);
+        else if (LOG) log_hit<false>(P, s_log_n, log_slot(P, pl, pix), v);
         else atomic_add_f32(mono_slot(P, pl, pix), v);
       } else if (LOG) {   // a cached pixel leaves as three records whose weights ARE X, Y, Z (codes pool size + channel)
         for (uint32_t c = 0; c < 3u; ++c) {
           const float v = T.cache.val[i * 3 + c];
-          if (v != 0.0f) log_hit<true>(P, &s_log_n, log_slot_xyz(P, P.wl_pool_size + c, pix), v);
+          if (v != 0.0f) log_hit<true>(P, s_log_n, log_slot_xyz(P, P.wl_pool_size + c, pix), v);
         }
       } else {
         atomic_add_f32(mono_slot(P, 0u, pix), T.cache.val[i * 3 + 0]);
@@ -3002,9 +3028,12 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
       }
     }
   }
-  if constexpr (LOG) {   // the region's fill count, for the split pass
+  if constexpr (TILE) {   // ALL the workgroup's counts, zeros included: nobody has to clear the counters between launches
     __syncthreads();
-    if (threadIdx.x == 0) P.bin_cnt[blockIdx.x] = min(s_log_n, P.bin_cap);
+    if (threadIdx.x < P.tile_tiles) P.tile_cnt[threadIdx.x * gridDim.x + blockIdx.x] = s_log_n[threadIdx.x];
+  } else if constexpr (LOG) {   // the region's fill count, for the split pass
+    __syncthreads();
+    if (threadIdx.x == 0) P.bin_cnt[blockIdx.x] = min(s_log_n[0], P.bin_cap);
   }
   if constexpr (FIXLOG) {
     __syncthreads();
@@ -3068,7 +3097,7 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
 // halo_backend.cpp root_profile_of) — taken only when the record itself says what the profile assumes: a record that does not runs the generic form.
 template <int MODE, int GEOM, bool MONO, int ACC, int LENS, int VIS, bool NOGATE>
 static void launch_root(const DispatchParams& P, dim3 grid, dim3 block, hipStream_t stream) {
-  if constexpr (MODE == kModePlain && GEOM == kGeomOneHex && MONO && ACC == kAccLogFinal && NOGATE) {
+  if constexpr (MODE == kModePlain && GEOM == kGeomOneHex && MONO && (ACC == kAccLogFinal || ACC == kAccTileFinal) && NOGATE) {
     const bool lut_uniform = P.lat_path == kLatLut && P.az_type == HALO_DIST_UNIFORM && P.roll_type == HALO_DIST_UNIFORM;
     if (lut_uniform && P.root_profile == kRootProfileGen && P.source == kSrcGen) {
       hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, MONO, ACC, LENS, VIS, NOGATE, false, kRootGenLutUniform>), grid, block, 0, stream, P);
@@ -3216,6 +3245,34 @@ static hipError_t launch_fixed(const DispatchParams& P, int blocks, hipStream_t 
   else if (geom == kGeomPoolPrism) launch_fixed_geom<MODE, kGeomPoolPrism>(P, grid, block, stream, mono);
   else if (geom == kGeomPool) launch_fixed_geom<MODE, kGeomPool>(P, grid, block, stream, mono);
   else launch_fixed_geom<MODE, kGeomOne>(P, grid, block, stream, mono);
+  return hipGetLastError();
+}
+
+// The per-tile append (DispatchParams::tile_chunk set: option "tile_append", halo_backend.cpp tile_append_ok): the kAccTileFinal twins of the
+// headline's kernels — plain mode, one regular prism, scalar plane, last layer with a closed gate, lens and root form as constants, the upper
+// sky (the closing per-tile pass, which reads the chunks, takes no full-sky render).  Instantiated in a translation unit of their own
+// (halo_trace_tl0.hip).  A dispatch without an instantiation is an error: the host asks for the route only where one exists.
+hipError_t launch_trace_tl0(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);
+template <int MODE, int LENS>
+static void launch_tile_lens(const DispatchParams& P, dim3 grid, dim3 block, hipStream_t stream) {
+  launch_root<MODE, kGeomOneHex, true, kAccTileFinal, LENS, HALO_VISIBLE_UPPER, true>(P, grid, block, stream);
+}
+static inline bool tile_kernel_exists(const DispatchParams& P, int geom, bool mono) {
+  const int lens = P.proj.proj_type;
+  return geom == kGeomOneHex && mono && P.final_layer != 0u && P.bin_log != 0u && P.prob <= 0.0f && P.cont_mask == nullptr && P.no_land == 0u && P.fix == nullptr &&
+         P.mono_by_wl == 0u && P.proj.visible_range == HALO_VISIBLE_UPPER &&
+         (lens == HALO_LENS_LINEAR || lens == HALO_LENS_FISHEYE_EQUAL_AREA || lens == HALO_LENS_DUAL_FISHEYE_EQUAL_AREA || lens == HALO_LENS_RECTANGULAR);
+}
+template <int MODE>   // (a template so that only halo_trace_tl0.hip instantiates the kernels)
+static hipError_t launch_tile(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono) {
+  if (!tile_kernel_exists(P, geom, mono) || P.tile_cnt == nullptr || P.tile_tiles == 0u || P.tile_tiles > kTileAppendMax || (P.tile_cap & 1u) != 0u) return hipErrorNotSupported;
+  dim3 grid(blocks), block(kBlock);
+  switch (P.proj.proj_type) {
+    case HALO_LENS_LINEAR: launch_tile_lens<MODE, HALO_LENS_LINEAR>(P, grid, block, stream); break;
+    case HALO_LENS_FISHEYE_EQUAL_AREA: launch_tile_lens<MODE, HALO_LENS_FISHEYE_EQUAL_AREA>(P, grid, block, stream); break;
+    case HALO_LENS_DUAL_FISHEYE_EQUAL_AREA: launch_tile_lens<MODE, HALO_LENS_DUAL_FISHEYE_EQUAL_AREA>(P, grid, block, stream); break;
+    default: launch_tile_lens<MODE, HALO_LENS_RECTANGULAR>(P, grid, block, stream); break;
+  }
   return hipGetLastError();
 }
 

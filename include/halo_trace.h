@@ -341,7 +341,10 @@ const char* halo_last_error(halo_handle_t h);
  * "close_direct" (-1 [default]: a hit-log launch that is its whole session — last layer, one crystal entry, one chunk, nothing pending in the
  * planes — on the float route's contiguous-tile scalar path (one plane, one copy, twin present, not a full-sky render) and large enough to fill
  * the chip has its per-tile pass add CMF x sum to the XYZ image itself: bit-equal to plane-then-fold, no closing fold; 0: never; 1: wherever
- * eligible, whatever the launch size; halo_direct_closes counts them). */
+ * eligible, whatever the launch size; halo_direct_closes counts them), "tile_append" (-1 [default]: a launch that closes directly, fills the chip and
+ * runs a trace kernel with a per-tile twin — plain mode, one regular prism, scalar plane, closed gate, a lens that is a template constant — appends
+ * its records to per-tile chunks of each workgroup, and the closing pass reads the chunks: no split pass; the same records reach the same integer
+ * tile sums; 0: never; 1: wherever eligible, whatever the launch size; halo_tile_appends counts them). */
 int halo_set_option(halo_handle_t h, const char* key, int64_t value);
 /* Use an external HIP stream (e.g. torch's current stream) for all launches. NULL = own stream. */
 int halo_set_stream(halo_handle_t h, void* hip_stream);
@@ -415,6 +418,9 @@ int halo_last_root_profile(halo_handle_t h, uint32_t* profile_mask);
 /* Launches, since halo_create, that closed their session in their own per-tile pass (option "close_direct"; additive in ABI 6, no struct changed —
  * such a launch still reports accum_mask bit 4).  A cumulative count: take the difference around the sessions of interest. */
 int halo_direct_closes(halo_handle_t h, uint64_t* count);
+/* Launches, since halo_create, whose trace kernel appended its records per tile (option "tile_append"; additive in ABI 6, no struct changed — such a
+ * launch is also counted by halo_direct_closes and still reports accum_mask bit 4).  A cumulative count. */
+int halo_tile_appends(halo_handle_t h, uint64_t* count);
 /* Bring the accumulator up to date WITHOUT a host wait: the closing folds of the ended sessions are queued and the backend's stream is made
  * to wait for them, so that work queued on that stream afterwards (a collective on a bound accumulator, a copy) sees the finished image.
  * Needed with option "defer_fold" = 1 (halo_end then leaves the fold of a caller-bound accumulator pending so that the next session's trace

@@ -7,6 +7,8 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <string>
+#include <utility>
 
 __device__ __forceinline__ uint32_t pcg(uint32_t x) {
   x = x * 747796405u + 2891336453u;
@@ -82,7 +84,116 @@ static void run(const char* name, uint32_t foot_mb, uint32_t copies, uint32_t la
   std::fflush(stdout);
 }
 
-int main() {
+// The per-tile append ("tile append"): would the trace kernel sustain the split's scatter itself?  256-thread workgroups, six per CU
+// (the 22 960 B of the trace kernel's LDS stand in as s_pad), 128 tiles.  Each lane draws a tile, takes its position from a returning LDS add on
+// that tile's counter and stores 8 bytes to the workgroup's own chunk of that tile; at the end the workgroup writes all 128 counts.
+// LAYOUT 0: chunk[tile][wg][pos]; 1: chunk[wg][tile][pos]; 2: one region per workgroup with a wave-aggregated cursor (today's log, for scale);
+// 3: the LDS add alone, no store.
+template <int LAYOUT>
+__global__ void __launch_bounds__(256, 6) tile_append(uint2* chunk, uint32_t* cnt, uint32_t* over, uint32_t cap, uint32_t tile_mask, uint32_t iters, uint32_t alu,
+                                                      float* sink) {
+  __shared__ uint32_t s_tile_n[128];
+  __shared__ uint32_t s_pad[5740];
+  const uint32_t wg = blockIdx.x, nwg = gridDim.x;
+  const uint32_t t = wg * 256u + threadIdx.x;
+  if (threadIdx.x < 128u) s_tile_n[threadIdx.x] = 0u;
+  s_pad[threadIdx.x] = t;
+  __syncthreads();
+  uint32_t s = pcg(t + 1u);
+  float acc = 0.0f;
+  for (uint32_t i = 0; i < iters; i++) {
+    s = pcg(s);
+    float v = __uint_as_float(0x3f800000u | (s >> 9)) - 1.0f;
+    for (uint32_t a = 0; a < alu; a++) v = fmaf(v, 0.999f, 1e-3f);
+    acc += v;
+    const uint32_t tile = pcg(s ^ 0x9e3779b9u) & tile_mask;
+    const uint2 rec = make_uint2(s, __float_as_uint(v));
+    if (LAYOUT == 2) {
+      const uint64_t m = __ballot(1);
+      const uint32_t leader = __ffsll(static_cast<unsigned long long>(m)) - 1u;
+      uint32_t base = 0u;
+      if ((threadIdx.x & 63u) == leader) base = atomicAdd(&s_tile_n[0], static_cast<uint32_t>(__popcll(m)));
+      base = __shfl(base, static_cast<int>(leader));
+      const uint32_t pos = base + __popcll(m & ((1ull << (threadIdx.x & 63u)) - 1ull));
+      if (pos < 128u * cap) chunk[static_cast<size_t>(wg) * 128u * cap + pos] = rec;
+      else atomicAdd(over, 1u);
+    } else {
+      const uint32_t pos = atomicAdd(&s_tile_n[tile], 1u);
+      if (LAYOUT == 3) {
+        acc += static_cast<float>(pos);
+      } else if (pos < cap) {
+        const size_t c = LAYOUT == 0 ? static_cast<size_t>(tile) * nwg + wg : static_cast<size_t>(wg) * 128u + tile;
+        chunk[c * cap + pos] = rec;
+      } else {
+        atomicAdd(over, 1u);
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 128u) cnt[static_cast<size_t>(threadIdx.x) * nwg + wg] = s_tile_n[threadIdx.x];
+  if (acc == 12345.678f) sink[t] = acc + static_cast<float>(s_pad[(threadIdx.x * 7u) % 5740u]);
+}
+
+template <int LAYOUT>
+static void run_tile(const char* name, uint32_t tiles_on, uint32_t alu, uint2* chunk, uint32_t* cnt, uint32_t* over, float* sink) {
+  const uint32_t blocks = 6104, iters = 40, cap = 640;   // 10 240 records per workgroup, 80 per tile: cap = 8 x the even share
+  hipEvent_t e0, e1;
+  hipEventCreate(&e0);
+  hipEventCreate(&e1);
+  float best = 1e30f, all[5];
+  for (int rep = 0; rep < 5; rep++) {
+    hipMemset(over, 0, 4);
+    hipEventRecord(e0);
+    hipLaunchKernelGGL(tile_append<LAYOUT>, dim3(blocks), dim3(256), 0, 0, chunk, cnt, over, cap, tiles_on - 1u, iters, alu, sink);
+    hipEventRecord(e1);
+    hipEventSynchronize(e1);
+    hipEventElapsedTime(&all[rep], e0, e1);
+    if (all[rep] < best) best = all[rep];
+  }
+  for (int i = 1; i < 5; i++)
+    for (int j = i; j > 0 && all[j] < all[j - 1]; j--) std::swap(all[j], all[j - 1]);
+  // every record is counted, kept or not: the counts the reader would clamp
+  static uint32_t h_cnt[128 * 6104];
+  uint32_t h_over = 0;
+  hipMemcpy(h_cnt, cnt, sizeof(h_cnt), hipMemcpyDeviceToHost);
+  hipMemcpy(&h_over, over, 4, hipMemcpyDeviceToHost);
+  uint64_t sum = 0;
+  for (uint32_t c : h_cnt) sum += c;
+  const double n = double(blocks) * 256 * iters;
+  std::printf("%-26s tiles %3u/128 alu %3u : min %6.3f median %6.3f ms  %6.2f G records/s (median)  counted %llu of %.0f, past cap %u  [%s]\n", name, tiles_on, alu,
+              best, all[2], n / all[2] * 1e-6, static_cast<unsigned long long>(sum), n, h_over, hipGetErrorString(hipGetLastError()));
+  std::fflush(stdout);
+}
+
+static void tile_rows(float* sink) {
+  uint2* chunk;
+  uint32_t *cnt, *over;
+  if (hipMalloc(&chunk, 6104ull * 128 * 640 * 8) != hipSuccess) {   // 4.0 GB
+    std::printf("tile append: no memory for the chunks\n");
+    return;
+  }
+  hipMalloc(&cnt, 6104ull * 128 * 4);
+  hipMalloc(&over, 4);
+  for (uint32_t alu : {0u, 200u}) {
+    run_tile<3>("tile append: LDS add only", 128, alu, chunk, cnt, over, sink);
+    run_tile<2>("tile append: one region/wg", 128, alu, chunk, cnt, over, sink);
+    for (uint32_t tiles_on : {128u, 64u}) {   // (the fisheye disc fills about half the tiles)
+      run_tile<0>("tile append: [tile][wg]", tiles_on, alu, chunk, cnt, over, sink);
+      run_tile<1>("tile append: [wg][tile]", tiles_on, alu, chunk, cnt, over, sink);
+    }
+  }
+  hipFree(chunk);
+  hipFree(cnt);
+  hipFree(over);
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1 && std::string(argv[1]) == "tile") {   // the per-tile append rows alone
+    float* s;
+    hipMalloc(&s, 6104ull * 256 * 4);
+    tile_rows(s);
+    return 0;
+  }
   float *plane, *sink;
   uint2* log;
   uint32_t* cnt;
@@ -109,5 +220,6 @@ int main() {
       run<3>("shard log (ret. atomic)", 64, 8, lanes, alu, plane, log, cnt, sink);
     }
   }
+  tile_rows(sink);
   return 0;
 }

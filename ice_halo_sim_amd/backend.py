@@ -49,6 +49,8 @@ def load_library():
         "halo_bind_accumulator": (C.c_int, [H, C.c_void_p, C.c_uint64]),
         "halo_set_filters": (C.c_int, [H, C.POINTER(abi.HaloFilter), C.c_int32]),
         "halo_begin": (C.c_int, [H, C.POINTER(abi.HaloScene), C.POINTER(abi.HaloRender), C.POINTER(abi.HaloWl), C.c_uint64]),
+        "halo_begin_spectrum": (C.c_int, [H, C.POINTER(abi.HaloScene), C.POINTER(abi.HaloRender), C.POINTER(abi.HaloWl), C.c_int32, C.c_uint64]),
+        "halo_host_spectrum_entry": (C.c_uint32, [C.c_uint64, C.c_uint32, C.c_uint64]),
         "halo_trace_layer": (C.c_int, [H, C.c_uint64, C.POINTER(abi.HaloHostRays), C.POINTER(abi.HaloLayerStats)]),
         "halo_recombine": (C.c_int, [H, C.c_int, C.POINTER(C.c_uint64)]),
         "halo_drain_exits": (C.c_int, [H, C.POINTER(abi.HaloExitRecord), C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -107,7 +109,7 @@ EXPORTED_SYMBOLS = [
     "halo_drain_exits", "halo_end", "halo_readback_xyz", "halo_readback_xyz64", "halo_sync", "halo_flush", "halo_collect_timing", "halo_last_sample_counts", "halo_last_route", "halo_last_root_profile", "halo_direct_closes", "halo_tile_appends", "halo_set_color", "halo_readback_class_lanes", "halo_generate_shapes", "halo_collect_stats", "halo_take_landed", "halo_consumer_fold", "halo_consumer_consume", "halo_consumer_snapshot", "halo_consumer_reset", "halo_consumer_composite", "halo_consumer_load_lanes", "halo_host_parse_composite_mode", "halo_host_prism_geometry",
     "halo_host_pyramid_geometry", "halo_host_shape_scalars", "halo_host_build_lat_lut", "halo_host_build_proj_params", "halo_host_partition",
     "halo_host_refractive_index", "halo_host_reduce_raypath", "halo_host_filter_fast_check", "halo_host_color_fast_mask", "halo_host_illuminant_spd", "halo_host_wl_pool", "halo_reduce_accumulator",
-    "halo_peek_fixed", "halo_host_fixed_frac_bits",
+    "halo_peek_fixed", "halo_host_fixed_frac_bits", "halo_begin_spectrum", "halo_host_spectrum_entry",
 ]
 
 
@@ -265,6 +267,17 @@ class HipTraceBackend:
         self._lanes_shape = None   # the session's lanes take the render's size
         self._check(self._L.halo_begin(self._h, C.byref(scene), C.byref(render), C.byref(wl), int(ray_num)))
 
+    def BeginSpectrumSession(self, scene, render, wls, ray_num=0):
+        """One session for a whole discrete spectrum (halo_begin_spectrum): `wls` is a sequence of 1..255 discrete abi.HaloWl.  Root r of a crystal
+        entry's share of m roots takes entry min(r // ceil(m / len(wls)), len(wls) - 1) — blocks of consecutive roots, no draw; everything after
+        BeginSession (TraceLayer, Recombine, EndSession, readbacks) is the same.  One entry is that wavelength's discrete session."""
+        wls = list(wls)
+        arr = (abi.HaloWl * max(1, len(wls)))(*wls)
+        self._render = render
+        self._scene = scene
+        self._lanes_shape = None
+        self._check(self._L.halo_begin_spectrum(self._h, C.byref(scene), C.byref(render), arr, len(wls), int(ray_num)))
+
     def TraceLayer(self, count=0, host_rays=None):
         """First layer: `count` self-generated roots, or injected crystal-local rays (d, p, w, tf arrays).
         Later layers: consumes the continuation from Recombine.  Returns HaloLayerStats."""
@@ -364,6 +377,11 @@ class HipTraceBackend:
         self._check(self._L.halo_consumer_composite(self._h, C.byref(spec), lin.ctypes.data_as(C.POINTER(C.c_float)),
                                                     srgb.ctypes.data_as(C.POINTER(C.c_uint8)) if want_srgb else None, C.byref(p99), C.byref(produced)))
         return bool(produced.value), lin, srgb, p99.value
+
+
+def host_spectrum_entry(m, count, r):
+    """halo_host_spectrum_entry: the spectrum entry of root r among the m roots of a crystal entry's share, `count` entries (no device needed)."""
+    return int(load_library().halo_host_spectrum_entry(int(m), int(count), int(r)))
 
 
 def host_fixed_frac_bits(max_w, hits):

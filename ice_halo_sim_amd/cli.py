@@ -21,11 +21,13 @@ DISPATCH_RAYS_MULTI = 1 << 24  # ... for scenes with more than one scattering la
                                # and a one-shot CLI run pays for their allocation (64 Mi roots x 8 hits: two pools of 10 GB, 0.5 s of hipMalloc)
 
 
-def run_job(job, render_id=None, seed=42, device=0, max_rays=None, progress=None, canonical_order=False, deterministic=False):
+def run_job(job, render_id=None, seed=42, device=0, max_rays=None, progress=None, canonical_order=False, deterministic=False, spectrum_session=False):
     """Trace `job` (config.TraceJob) on one GPU. Returns dict(rays, setup_sec, active_sec, backend, render).  canonical_order: option
     cont_order = 1 (the continuation pool of every layer but the last in (root, interaction) order).  deterministic: option deterministic = 1
     (fixed-point accumulation; with it a multi-layer document takes cont_order = 1 as well) — BackendError when the document needs what that
-    route refuses."""
+    route refuses.  spectrum_session: a document whose spectrum is a list of discrete wavelengths is traced as spectrum sessions
+    (HipTraceBackend.BeginSpectrumSession) — one session chain per dispatch of len(wavelengths) x n rays, n rays of every wavelength in it —
+    instead of one session per wavelength; ignored for an illuminant (which is one session already) and for a single wavelength."""
     if not job.renders:
         raise config.ConfigError("config has no render entry")
     rid = render_id if render_id is not None else sorted(job.renders)[0]  # the seam supports ONE renderer (simulator.cpp:937-944)
@@ -56,7 +58,23 @@ def run_job(job, render_id=None, seed=42, device=0, max_rays=None, progress=None
     setup = time.perf_counter() - t0
     t1 = time.perf_counter()
     rays = 0
-    for wl in job.wavelengths:
+    spectrum = spectrum_session and len(job.wavelengths) > 1 and all(wl.illuminant < 0 for wl in job.wavelengths)
+    left = per_wl if spectrum else 0
+    while left > 0:   # spectrum sessions: every dispatch holds n rays of each wavelength, block by block within each crystal entry's share
+        n = min(left, max(1, (DISPATCH_RAYS if job.scene.layer_count == 1 else DISPATCH_RAYS_MULTI) // n_wl))
+        be.BeginSpectrumSession(job.scene, render, job.wavelengths, n * n_wl)
+        for li in range(job.scene.layer_count):
+            be.TraceLayer(n * n_wl if li == 0 else 0)
+            if li + 1 < job.scene.layer_count:
+                be.Recombine(True)
+        be.EndSession()
+        left -= n
+        rays += n * n_wl
+        if left == 0:
+            be.ConsumeDeviceFused()  # drain window
+        if progress:
+            progress(rays)
+    for wl in ([] if spectrum else job.wavelengths):
         left = per_wl
         while left > 0:
             n = min(left, DISPATCH_RAYS if job.scene.layer_count == 1 else DISPATCH_RAYS_MULTI)
@@ -103,7 +121,8 @@ def save_all_renders(job, args):
     rc = 0
     for rid in sorted(job.renders):
         try:
-            res = run_job(job, rid, args.seed, args.device, args.max_rays, canonical_order=args.canonical_order, deterministic=args.deterministic)
+            res = run_job(job, rid, args.seed, args.device, args.max_rays, canonical_order=args.canonical_order, deterministic=args.deterministic,
+                          spectrum_session=args.spectrum_session)
         except BackendUnavailableError as e:
             print("backend unavailable: %s" % e, file=sys.stderr)
             return 3
@@ -155,6 +174,10 @@ def main(argv=None):
                     "(option deterministic = 1; multi-scattering configs take cont_order = 1 with it), so a fixed --seed gives the same XYZ bytes on "
                     "every run, whose sha256 is printed.  A config that needs what the route does not cover (raypath_color, a filter outside the fast "
                     "form) is refused with the reason and a non-zero exit; a multi-GPU run is reproducible per rank")
+    ap.add_argument("--spectrum-session", action="store_true",
+                    help="a spectrum that is a list of discrete wavelengths: trace it as spectrum sessions — every dispatch one session that holds rays of "
+                    "ALL the wavelengths, dealt out in blocks of consecutive rays — instead of one session per wavelength (which cannot fill the GPU "
+                    "when the rays per wavelength are few).  The same rays when the scene has one crystal entry; ignored for an illuminant")
     ap.add_argument("--display-ev", type=float, default=0.0, help="display-time EV of the composite (display_exposure_scale = 2^EV)")
     args = ap.parse_args(argv)
     if not 1 <= args.quality <= 100:
@@ -171,7 +194,8 @@ def main(argv=None):
         if args.output_dir is not None:
             print("[warning] -o / --output-dir is ignored with --render / --benchmark (nothing is saved)", file=sys.stderr)
         wall0 = time.perf_counter()
-        res = run_job(job, args.render, args.seed, args.device, args.max_rays, canonical_order=args.canonical_order, deterministic=args.deterministic)
+        res = run_job(job, args.render, args.seed, args.device, args.max_rays, canonical_order=args.canonical_order, deterministic=args.deterministic,
+                      spectrum_session=args.spectrum_session)
     except BackendUnavailableError as e:
         print("backend unavailable: %s" % e, file=sys.stderr)
         return 3

@@ -233,6 +233,8 @@ struct HaloBackend {
   DevBuf<DispatchSlot> tcache_dev;     // HALO_MAX_LAYERS x HALO_MAX_ENTRIES x 2 slots, reserved on first use
   HaloScene tcache_scene{};            // what the valid entries were built for
   HaloWl tcache_wl{};
+  std::vector<HaloWl> tcache_spec;   // ... and the entry table of a spectrum session (empty otherwise)
+  uint32_t spec_count = 0;           // entries of the open spectrum session (halo_begin_spectrum with count >= 2), 0 = not one
   int table_cache = 1;                 // option: 0 uploads the tables with every dispatch (round 4 behaviour)
   std::map<std::string, int64_t> opt_last;   // halo_set_option: the value each key was last set to (an unchanged option keeps the table cache)
   HaloLayerStats pending{};    // harvested tallies not yet handed to the caller (async mode)
@@ -760,7 +762,9 @@ int halo_set_filters(halo_handle_t b, const HaloFilter* filters, int32_t count) 
 }
 
 
-int halo_begin(halo_handle_t b, const HaloScene* scene, const HaloRender* render, const HaloWl* wl, uint64_t ray_num) {
+// BeginSession for both entry points.  spec_n >= 2: a spectrum session over the discrete entries spec[0 .. spec_n) (halo_begin_spectrum; `wl` is then
+// spec[0], kept for the members that describe "the session's wavelength"); spec_n == 0: halo_begin's session of `wl`.
+static int begin_session(halo_handle_t b, const HaloScene* scene, const HaloRender* render, const HaloWl* wl, const HaloWl* spec, int32_t spec_n, uint64_t ray_num) {
   if (!b || !scene || !render || !wl) return HALO_FATAL;
   if (b->in_session) return fail(b, HALO_FATAL, "BeginSession inside a session");
   if (scene->layer_count < 1 || scene->layer_count > HALO_MAX_LAYERS) return fail(b, HALO_FATAL, "layer_count out of range");
@@ -803,16 +807,25 @@ int halo_begin(halo_handle_t b, const HaloScene* scene, const HaloRender* render
       }
   }
   HIPCHK(b, hipSetDevice(b->device));
-  if (std::memcmp(&b->tcache_scene, scene, sizeof(HaloScene)) != 0 || std::memcmp(&b->tcache_wl, wl, sizeof(HaloWl)) != 0) {
-    drop_table_cache(b);   // another scene or wavelength: the cached tables are not this session's
+  // (the cached slots hold the session's wavelength pool: a spectrum session's key is its whole entry table)
+  const bool same_spec = b->tcache_spec.size() == static_cast<size_t>(spec_n) &&
+                         (spec_n == 0 || std::memcmp(b->tcache_spec.data(), spec, sizeof(HaloWl) * static_cast<size_t>(spec_n)) == 0);
+  if (std::memcmp(&b->tcache_scene, scene, sizeof(HaloScene)) != 0 || std::memcmp(&b->tcache_wl, wl, sizeof(HaloWl)) != 0 || !same_spec) {
+    drop_table_cache(b);   // another scene, wavelength or spectrum: the cached tables are not this session's
     b->tcache_scene = *scene;
     b->tcache_wl = *wl;
+    b->tcache_spec.assign(spec, spec + spec_n);
   }
   b->scene = *scene;
   b->render = *render;
   b->wl = *wl;
   b->proj = host::BuildProj(*render);
   std::vector<WlEntryDev> pool = host::BuildWlPool(*wl);
+  for (int32_t k = 1; k < spec_n; k++) {   // a spectrum session's pool: what each entry's own discrete session would read, one behind the other
+    const std::vector<WlEntryDev> one = host::BuildWlPool(spec[k]);
+    pool.insert(pool.end(), one.begin(), one.end());
+  }
+  b->spec_count = static_cast<uint32_t>(spec_n);
   b->wl_pool_size = static_cast<uint32_t>(pool.size());
   if (pool.empty() || pool.size() > HALO_WL_POOL_MAX) return fail(b, HALO_FATAL, "wavelength pool size out of range");
   b->wl_pool_host = pool;  // travels to the device inside each dispatch slot
@@ -826,7 +839,8 @@ int halo_begin(halo_handle_t b, const HaloScene* scene, const HaloRender* render
   // 2^25 pixels (an 8192x4096 panorama) is what the workgroup cache's 32-bit key names on its own; with a plane index beside the pixel the
   // key keeps 23 bits for the pixel, so sessions above 2^23 pixels take the layouts without per-entry planes (below: mono_by_wl)
   if (npix > (1u << 25)) return fail(b, HALO_UNAVAILABLE, "more than 2^25 pixels");   // recoverable: the caller falls back (INTEGRATION.md limits table)
-  const bool discrete = wl->illuminant < 0;
+  // (a spectrum session is a pool session wherever layouts are chosen: per-ray entries, X/Y/Z or per-entry planes)
+  const bool discrete = wl->illuminant < 0 && spec_n == 0;
   //  * illuminant, batch >= 2 Mi rays, hit log on (the default): X, Y, Z planes too, but the launches log {slot, pool entry, w} and
   //    the per-tile pass applies the CMF (halo_log_accumulate_kernel<3>): no plane per entry, no two-level split, a 3-plane fold
   //    (images above 512 Ki pixels: on small ones most hits land in the pixel cache, and the X/Y/Z cache pays three fp32 LDS adds — the
@@ -954,6 +968,35 @@ int halo_begin(halo_handle_t b, const HaloScene* scene, const HaloRender* render
   return HALO_OK;
 }
 
+int halo_begin(halo_handle_t b, const HaloScene* scene, const HaloRender* render, const HaloWl* wl, uint64_t ray_num) {
+  return begin_session(b, scene, render, wl, nullptr, 0, ray_num);
+}
+
+int halo_begin_spectrum(halo_handle_t b, const HaloScene* scene, const HaloRender* render, const HaloWl* entries, int32_t count, uint64_t ray_num) {
+  if (!b) return HALO_FATAL;
+  if (!scene) return fail(b, HALO_FATAL, "halo_begin_spectrum: scene is NULL");
+  if (!render) return fail(b, HALO_FATAL, "halo_begin_spectrum: render is NULL");
+  if (!entries) return fail(b, HALO_FATAL, "halo_begin_spectrum: entries is NULL");
+  if (count < 1 || count > HALO_WL_POOL_MAX) return fail(b, HALO_FATAL, "halo_begin_spectrum: count " + std::to_string(count) + " outside 1..HALO_WL_POOL_MAX (255)");
+  for (int32_t k = 0; k < count; k++)
+    if (entries[k].illuminant >= 0)
+      return fail(b, HALO_FATAL, "halo_begin_spectrum: entries[" + std::to_string(k) + "] is an illuminant (illuminant >= 0); a spectrum is made of discrete wavelengths");
+  // one entry: the discrete session of that wavelength, by the same route
+  if (count == 1) return begin_session(b, scene, render, entries, nullptr, 0, ray_num);
+  return begin_session(b, scene, render, entries, entries, count, ray_num);
+}
+
+uint32_t halo_host_spectrum_entry(uint64_t m, uint32_t count, uint64_t r) {
+  // The kernels' own function, given what the host would hand a launch that holds ray r — two ways: the launch that starts as late as a 32-bit
+  // thread index allows (a long way into the launch, across many block edges), and one that starts at a multiple of 65521 rays (an offset in the
+  // middle of a block).  They must agree; 0xFFFFFFFF says they did not.
+  const uint64_t reach = 0xFFFFFFFEull, off_a = r > reach ? r - reach : 0ull, off_b = r - r % 65521ull;
+  const SpectrumChunkDev a = SpectrumChunk(m, count, off_a), c = SpectrumChunk(m, count, off_b);
+  const uint32_t ka = SpectrumEntry(a.per, a.k0, a.rem, a.last, static_cast<uint32_t>(r - off_a));
+  const uint32_t kb = SpectrumEntry(c.per, c.k0, c.rem, c.last, static_cast<uint32_t>(r - off_b));
+  return ka == kb ? ka : 0xFFFFFFFFu;
+}
+
 // Fractional bits of the per-tile fixed-point sums for a launch of `m` rays whose weights are at most `max_w`: the largest F <= 32 with
 // 4 * max_w * m * 2^F < 2^62 (see halo_kernels.hip FixQ for the factor 4).
 // The deterministic route applies the same bound to the rays a plane set may take before it is folded (kFixBudgetHits) and to the landed integer
@@ -1059,6 +1102,7 @@ struct LayerCtx {
 struct LaunchPlan {
   int ci = 0;
   uint64_t m = 0, off = 0, first = 0;   // rays; offset within the entry's share; index of the first ray within the layer
+  uint64_t share = 0;                   // the entry's whole share of the layer's rays (off + left when the launch was planned)
   bool deterministic = false, host_pool = false, alternate = false;
   int geom = 0, blocks = 0;             // geom: 0 = one shape per dispatch, 1 = pool of ShapeDev records, 2 = pool of ShapePrism records (device-generated prisms)
   uint32_t shape_cnt = 1;
@@ -1128,7 +1172,7 @@ int blocks_of(const HaloBackend& b, uint64_t m, bool pool) {
 LaunchPlan plan_launch(const HaloBackend& b, const LayerCtx& c, int ci, uint64_t first_ci, uint64_t off, uint64_t left) {
   const HaloCrystal& crystal = b.scene.layers[c.layer].entries[ci].crystal;
   LaunchPlan p;
-  p.ci = ci, p.off = off, p.first = first_ci + off;
+  p.ci = ci, p.off = off, p.first = first_ci + off, p.share = off + left;
   p.m = chunk_of(b, left, crystal, c.host_crystal);
   p.deterministic = c.host_crystal || host::IsDeterministic(crystal);
   p.shape_cnt = p.deterministic ? 1u : static_cast<uint32_t>((p.m + b.geom_clock - 1) / b.geom_clock);
@@ -1447,7 +1491,7 @@ DispatchParams fill_params(HaloBackend* b, const LayerCtx& c, int ci) {
   P.geom_clock = b->geom_clock;
   P.lanes = b->lanes.ptr;
   P.lane_stride = static_cast<uint32_t>(b->acc_w) * static_cast<uint32_t>(b->acc_h);
-  P.root_profile = b->spec_root ? root_profile_of(P) : kRootProfileNone;
+  P.root_profile = (b->spec_root && b->spec_count == 0u) ? root_profile_of(P) : kRootProfileNone;   // (a spectrum session picks its entry in the generic root generation)
   P.fix = b->det_session ? b->fix.ptr : nullptr;   // (fix_frac, fix_frac_landed: trace_launch, once fix_prepare has settled them)
   return P;
 }
@@ -1814,6 +1858,11 @@ int trace_launch(HaloBackend* b, const LayerCtx& c, LaunchPlan& p, EntryTables& 
   P.shape_cnt = p.shape_cnt;
   P.n_rays = static_cast<uint32_t>(m);
   P.ci_start = static_cast<uint32_t>(p.first);
+  P.spec_per = P.spec_k0 = P.spec_rem = P.spec_last = 0u;
+  if (b->spec_count != 0u && c.layer == 0) {   // the blocks lie within this crystal entry's share (p.share rays), whatever the launches cut out of it
+    const SpectrumChunkDev sc = SpectrumChunk(p.share, b->spec_count, p.off);
+    P.spec_per = sc.per, P.spec_k0 = sc.k0, P.spec_rem = sc.rem, P.spec_last = sc.last;
+  }
   auto split = [](uint64_t v, uint32_t& lo, uint32_t& hi) { lo = static_cast<uint32_t>(v & 0xFFFFFFFFull), hi = static_cast<uint32_t>(v >> 32); };  // SplitPcgRayBase trace_backend.hpp:184-190
   split(b->gen_count, P.gen_lo, P.gen_hi);
   split(b->gate_count, P.gate_lo, P.gate_hi);

@@ -345,6 +345,11 @@ struct DispatchParams {
   uint32_t tile_cap;           // records per chunk (even: a chunk starts on 16 bytes)
   uint32_t tile_log2;          // slots per tile, log2: tile of a record = slot >> tile_log2
   uint32_t tile_tiles;         // tiles of the plane, <= kTileAppendMax
+  // --- spectrum sessions (halo_begin_spectrum: a pool session whose rays take their pool entry by index, not by a draw) -------------
+  uint32_t spec_per;           // rays per spectrum entry within this crystal entry's share, ceil(share / entries); 0 = not a spectrum session (the entry is drawn)
+  uint32_t spec_k0;            // the spectrum entry of this launch's first ray ...
+  uint32_t spec_rem;           // ... and how many rays of the launch, from the first on, still belong to it (>= 1): SpectrumChunk, SpectrumEntry
+  uint32_t spec_last;          // entries - 1
 };
 constexpr uint32_t kTileAppendMax = 128u;   // counters of a kAccTileFinal workgroup (LDS)
 
@@ -387,6 +392,33 @@ __host__ __device__
 #endif
 inline size_t TwinOffset(size_t off, uint32_t plane_log2, uint32_t copies_log2) {
   return ((off >> (plane_log2 + copies_log2)) << plane_log2) | (off & ((static_cast<size_t>(1) << plane_log2) - 1u));
+}
+
+// Spectrum sessions (halo_begin_spectrum): ray r (0-based within its crystal entry's share of `share` rays, counted across launches) takes pool
+// entry min(r / per, count - 1), per = ceil(share / count).  A launch covers rays [off, off + n_rays) of the share, n_rays < 2^32, and thread tid
+// of it is ray off + tid: the host works out, once per launch and in 64 bits, the entry k0 = off / per of the launch's first ray and the rays
+// rem = (k0 + 1) * per - off that are left of that entry's block, and the kernel is left with a compare for the rays of that block — for most
+// launches all of them, and wave-uniform for every wave that does not straddle a block edge — and an exact 32-bit quotient behind it.  Values past
+// 32 bits saturate: a block that outlasts the launch (rem or per >= 2^32, with tid <= 2^32 - 2) never reaches the quotient, or gets 0 from it.
+struct SpectrumChunkDev {
+  uint32_t per, k0, rem, last;
+};
+inline SpectrumChunkDev SpectrumChunk(uint64_t share, uint32_t count, uint64_t off) {
+  const uint64_t c = count ? count : 1u, per = share ? (share + c - 1u) / c : 1u;
+  const uint64_t k0 = off / per, rem = (k0 + 1u) * per - off, cap = 0xFFFFFFFFull;
+  return SpectrumChunkDev{static_cast<uint32_t>(per < cap ? per : cap), static_cast<uint32_t>(k0 < cap ? k0 : cap), static_cast<uint32_t>(rem < cap ? rem : cap),
+                          static_cast<uint32_t>(c - 1u)};
+}
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline uint32_t SpectrumEntry(uint32_t per, uint32_t k0, uint32_t rem, uint32_t last, uint32_t tid) {
+  uint32_t k = k0;
+  if (tid >= rem) {
+    const uint32_t q = (tid - rem) / per, room = last - (k0 < last ? k0 : last);   // (no wrap: the sum is clamped before it is made)
+    k = q < room ? k0 + 1u + q : last;
+  }
+  return k < last ? k : last;
 }
 
 // DispatchParams::root_profile: none (the generic root generation), or LUT latitude + uniform azimuth and roll over generated roots / over the

@@ -919,6 +919,8 @@ struct RaySums {
   uint32_t pix_n;
   uint32_t qn;   // exit queue fill (see ExitQueue)
   unsigned long long landed_q;   // kAccFixed kernels: the landed weight as an integer, FixQ(fix_frac_landed) of every primary hit (`landed` is not tallied)
+  double landed64;               // capture kernels (MODE == kModeCapture): the landed weight in fp64 from the first add, so that a session whose exits were
+                                 // captured lands exactly the sum of its records' weights (`landed` is not tallied); a member no other kernel touches
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -1488,7 +1490,8 @@ HD int land_exit(const DispatchParams& P, const AccCtx<MONO, SMALLC, FL>& cache,
     accumulate<MONO, SMALLC>(P, cache, pix, wl_idx, w, cmf_x, cmf_y, cmf_z);
     if (ModeTraits<MODE>::kTables && color != nullptr) fan_lanes(P, *color, cmask, pix, cmf_y * w);
     if constexpr (MODE == kModeColor) fan_lanes_fast(P, *cache.fast, cmask, pix, cmf_y * w);
-    sums.landed += w;  // bump_landed: primary hit only (scatter_accum.hpp:96-108)
+    if constexpr (MODE == kModeCapture) sums.landed64 += static_cast<double>(w);   // (fp64 all the way: RaySums::landed64)
+    else sums.landed += w;  // bump_landed: primary hit only (scatter_accum.hpp:96-108)
     if constexpr (!SMALLC && (MODE == kModePlain || MODE == kModeFilter)) {   // (only these have kAccFixed twins; the test is not even compiled into the others)
       if (cache.fixed) sums.landed_q += FixQ(P.fix_frac_landed).fix(w);     // ... which tally this integer instead
     }
@@ -2130,8 +2133,13 @@ HD void trace_one(const DispatchParams& P, LdsTables<MONO, SMALLC>& T, const Acc
     Stream wls = s;
     wls.seed ^= kNonceWl;
     if (G.wl_pool_size > 1u) {  // a one-entry pool needs no draw: floor(u * 1) is 0 for every u in [0, 1) (own stream, nothing to keep aligned)
-      wl_idx = static_cast<uint32_t>(uniform(wls) * static_cast<float>(G.wl_pool_size));
-      if (wl_idx >= G.wl_pool_size) wl_idx = G.wl_pool_size - 1u;
+      // a spectrum session (halo_begin_spectrum) deals its entries out in blocks of consecutive rays of the crystal entry's share: no draw, the
+      // wavelength stream is not touched.  (The root profiles are a discrete session's kernels first of all: the host gives a spectrum session none.)
+      if (ROOT == kRootAny && G.spec_per != 0u) wl_idx = SpectrumEntry(G.spec_per, G.spec_k0, G.spec_rem, G.spec_last, tid);
+      else {
+        wl_idx = static_cast<uint32_t>(uniform(wls) * static_cast<float>(G.wl_pool_size));
+        if (wl_idx >= G.wl_pool_size) wl_idx = G.wl_pool_size - 1u;
+      }
     }
     float lon, lat, roll;
     PROBE_MARK(pr, kPhStream);
@@ -2220,6 +2228,7 @@ HD void trace_one(const DispatchParams& P, LdsTables<MONO, SMALLC>& T, const Acc
     }
     w = G.host_w[tid];
     face = static_cast<int>(G.host_tf[tid]);
+    if (G.wl_pool_size > 1u && G.spec_per != 0u) wl_idx = SpectrumEntry(G.spec_per, G.spec_k0, G.spec_rem, G.spec_last, tid);   // injected rays of a spectrum session: the same blocks over the batch, their own weights
 #pragma unroll
     for (int k = 0; k < 3; k++) {
       HALO_ARRIVED(pinned, d[k]);
@@ -2645,6 +2654,11 @@ HD float wave_sum(float v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
   return v;
 }
+HD double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+  return v;
+}
 HD unsigned long long wave_sum(unsigned long long v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
@@ -3062,6 +3076,18 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
       if (v != 0.0) atomicAdd(&P.tally[(blockIdx.x & (kTallyLines - 1u)) * kTallyStride + threadIdx.x], v);
     }
   }
+  if constexpr (MODE == kModeCapture) {   // the capture kernels' landed weight: fp64 in the lane, the wave and the workgroup (their `landed` above is 0)
+    __shared__ double s_landed64[kBlock / 64];
+    const double l64 = wave_sum(sums.landed64);
+    if ((threadIdx.x & 63) == 0) s_landed64[threadIdx.x >> 6] = l64;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double v = 0.0;
+#pragma unroll
+      for (int w = 0; w < kBlock / 64; ++w) v += s_landed64[w];
+      if (v != 0.0) atomicAdd(&P.tally[(blockIdx.x & (kTallyLines - 1u)) * kTallyStride + kSumLanded], v);
+    }
+  }
   if constexpr (FIXED) {   // the landed weight as an integer: lanes (RaySums::landed_q), the wave, the workgroup, then ONE 64-bit integer atomic onto the line's integer slot
     // (no LDS of its own — 32 bytes more and the prism-pool kernels would lose their fifth workgroup per CU: the cache is flushed and every
     //  thread is past the barrier above, so its first words serve)
@@ -3099,7 +3125,7 @@ template <int MODE, int GEOM, bool MONO, int ACC, int LENS, int VIS, bool NOGATE
 static void launch_root(const DispatchParams& P, dim3 grid, dim3 block, hipStream_t stream) {
   if constexpr (MODE == kModePlain && GEOM == kGeomOneHex && MONO && (ACC == kAccLogFinal || ACC == kAccTileFinal) && NOGATE) {
     const bool lut_uniform = P.lat_path == kLatLut && P.az_type == HALO_DIST_UNIFORM && P.roll_type == HALO_DIST_UNIFORM;
-    if (lut_uniform && P.root_profile == kRootProfileGen && P.source == kSrcGen) {
+    if (lut_uniform && P.root_profile == kRootProfileGen && P.source == kSrcGen && P.spec_per == 0u) {
       hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, MONO, ACC, LENS, VIS, NOGATE, false, kRootGenLutUniform>), grid, block, 0, stream, P);
       return;
     }

@@ -58,6 +58,14 @@ class HipTraceBackend {
     width_ = render.width;
     height_ = render.height;
   }
+  // Beyond the reference's seam (its caller opens one session per wavelength, simulator.cpp:1098-1109): ONE session for a whole discrete spectrum,
+  // halo_begin_spectrum — 1..HALO_WL_POOL_MAX discrete entries, dealt out to the roots of each crystal entry's share in blocks of consecutive
+  // roots (halo_trace.h).  Everything after BeginSession is the same; one entry is that wavelength's discrete session.
+  void BeginSpectrumSession(const HaloScene& scene, const HaloRender& render, const std::vector<HaloWl>& wls, size_t ray_num = 0) {
+    Check(halo_begin_spectrum(h_, &scene, &render, wls.empty() ? nullptr : wls.data(), static_cast<int32_t>(wls.size()), ray_num));
+    width_ = render.width;
+    height_ = render.height;
+  }
   // First call: host mode (count roots generated on device, or injected golden rays); later calls consume the
   // continuation returned by Recombine (trace_backend.hpp:380-389).
   LayerHandle TraceLayer(size_t count, const HaloHostRays* host = nullptr) {

@@ -361,6 +361,23 @@ int halo_set_filters(halo_handle_t h, const HaloFilter* filters, int32_t count);
  * is the number of roots the session is going to trace; it only selects the accumulation layout of illuminant sessions
  * (see "lambda_planes"), results do not depend on it. */
 int halo_begin(halo_handle_t h, const HaloScene* scene, const HaloRender* render, const HaloWl* wl, uint64_t ray_num);
+/* A SPECTRUM session (additive in ABI 6, no struct changed): one session for a whole list of discrete wavelengths, where the reference — and
+ * halo_begin — take one session per wavelength (simulator.cpp:1098-1109).  entries[0 .. count) are discrete HaloWl (illuminant == -1),
+ * 1 <= count <= HALO_WL_POOL_MAX; anything else is HALO_FATAL with a message that names the argument, and the handle stays usable.  The session's
+ * wavelength pool is what halo_host_wl_pool gives for each entry, one behind the other: {n(lambda_k), weight_k, CMF(round lambda_k)} — n = 1 outside
+ * 350-900 nm and CMF 0 outside 360-830 nm, as a discrete session has them.  count == 1 IS the discrete session of entries[0]: same route, same bytes.
+ * For count > 1 the session is an illuminant-like pool session wherever layouts are chosen (X/Y/Z or per-entry planes, "lambda_planes", "hit_log",
+ * "bin", the deterministic X/Y/Z planes), with the largest |weight_k| as the bound of the fixed-point sums; halo_trace_layer, halo_recombine,
+ * halo_end, the readbacks and the consumer are what they are for any session.
+ * WHICH RAY TAKES WHICH ENTRY — by index, not by a draw: in layer 0 crystal entry ci gets m_ci roots from the partition, back to back as always; its
+ * root r (0-based within ci's range, counted across the launches "chunk" cuts, not within one) takes spectrum entry min(r / per_ci, count - 1) with
+ * per_ci = ceil(m_ci / count): blocks of consecutive roots INSIDE each crystal entry's range, so that no crystal is lit by a part of the spectrum
+ * only; when count > m_ci the blocks are single roots and entries >= m_ci get none.  Host-injected rays follow the same rule over the injected
+ * batch and keep their injected weight.  Layers >= 1 read the entry from the continuation pool, as every pool session does.  No RNG draw is
+ * consumed for the pick and the wavelength stream is not touched; every other stream keeps its slots, so root r is the ray a discrete session
+ * generates at that counter (with "ray_base" = B, block k of a one-entry scene is entry k's discrete session at ray_base B + k * per).
+ * ray_num: as for halo_begin — the roots the session is going to trace; it selects the accumulation layout only. */
+int halo_begin_spectrum(halo_handle_t h, const HaloScene* scene, const HaloRender* render, const HaloWl* entries, int32_t count, uint64_t ray_num);
 /* TraceBackend::TraceLayer(RootRaySource) — trace_backend.hpp:380-389.  First call of a session:
  * host mode, `count` roots self-generated on device (rays == NULL) or injected (rays != NULL).
  * Later calls: device mode, consumes the continuation produced by halo_recombine (count ignored). */
@@ -575,6 +592,10 @@ float halo_host_illuminant_spd(int illuminant, float wavelength_nm);
  * {refractive index, SPD weight, cmf_x, cmf_y, cmf_z}; a discrete HaloWl gives one entry.  Returns the entry count (<= cap
  * entries are written), 0 on error. */
 int halo_host_wl_pool(const HaloWl* wl, float* entries5, int cap);
+/* The spectrum entry of root r among the m roots of one crystal entry's share in a spectrum session of `count` entries (halo_begin_spectrum):
+ * min(r / ceil(m / count), count - 1), evaluated by the function the kernels call, with the per-launch constants the host hands them — for two
+ * different cuts of the share into launches, which must agree (0xFFFFFFFF if they did not).  Parity-test hook, no device needed. */
+uint32_t halo_host_spectrum_entry(uint64_t m, uint32_t count, uint64_t r);
 int halo_abi_version(void);
 /* sizeof() of boundary structs as compiled (0 scene, 1 render, 2 wl, 3 exit record, 4 geom tables, 5 layer stats, 6 entry, 7 colour set, 8 colour class, 9 filter, 10 route info, 11 composite). */
 uint64_t halo_abi_sizeof(int which);

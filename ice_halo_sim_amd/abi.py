@@ -132,6 +132,12 @@ class HaloDisplay(C.Structure):
     _fields_ = [("intensity_factor", C.c_float), ("ray_color", C.c_float * 3), ("background", C.c_float * 3)]
 
 
+class HaloAutoEv(C.Structure):
+    """halo_consumer_auto_ev's result (reference gui/gui_ev_auto.hpp: ComputeP99Y + ComputeEvAuto)."""
+    _fields_ = [("p99_y", C.c_float), ("per_pixel_intensity", C.c_float), ("ev_auto", C.c_float), ("produced", C.c_int32),
+                ("value_count", C.c_uint32), ("coarse_w", C.c_int32), ("coarse_h", C.c_int32)]
+
+
 COMPOSITE_DOMINANT, COMPOSITE_ADDITIVE, COMPOSITE_PAINTER = 0, 1, 2
 
 

@@ -76,6 +76,8 @@ def load_library():
         "halo_consumer_consume": (C.c_int, [H, f32p, C.c_int, C.c_int, C.c_float, f32p, C.c_int]),
         "halo_consumer_snapshot": (C.c_int, [H, C.POINTER(abi.HaloDisplay), C.POINTER(C.c_uint8), f32p, C.POINTER(C.c_double)]),
         "halo_consumer_reset": (C.c_int, [H]),
+        "halo_consumer_auto_ev": (C.c_int, [H, C.c_int32, C.c_float, C.POINTER(abi.HaloAutoEv)]),
+        "halo_host_ev_auto": (C.c_float, [C.c_float, C.c_float, C.c_float]),
         "halo_consumer_composite": (C.c_int, [H, C.POINTER(abi.HaloComposite), f32p, C.POINTER(C.c_uint8), f32p, C.POINTER(C.c_int32)]),
         "halo_consumer_load_lanes": (C.c_int, [H, f32p, C.c_int, C.c_int, C.c_int, C.c_double]),
         "halo_host_parse_composite_mode": (C.c_int, [C.c_char_p]),
@@ -110,6 +112,7 @@ EXPORTED_SYMBOLS = [
     "halo_host_pyramid_geometry", "halo_host_shape_scalars", "halo_host_build_lat_lut", "halo_host_build_proj_params", "halo_host_partition",
     "halo_host_refractive_index", "halo_host_reduce_raypath", "halo_host_filter_fast_check", "halo_host_color_fast_mask", "halo_host_illuminant_spd", "halo_host_wl_pool", "halo_reduce_accumulator",
     "halo_peek_fixed", "halo_host_fixed_frac_bits", "halo_begin_spectrum", "halo_host_spectrum_entry",
+    "halo_consumer_auto_ev", "halo_host_ev_auto",
 ]
 
 
@@ -343,8 +346,23 @@ class HipTraceBackend:
         self._check(self._L.halo_consumer_consume(self._h, xyz.ctypes.data_as(C.POINTER(C.c_float)), w, h, float(landed), lp, nc))
         self._cons_size = (w, h)
 
-    def Snapshot(self, intensity_factor=1.0, ray_color=(-1.0, -1.0, -1.0), background=(0.0, 0.0, 0.0), want_xyz=True):
-        """PrepareSnapshot + PostSnapshot: returns (rgb uint8[H,W,3], xyz float32[H,W,3] | None, total_intensity)."""
+    def AutoEv(self, downsample=8, target_white=135.0):
+        """The reference GUI's Adaptive Brightness anchor on the device consumer (halo_consumer_auto_ev: gui_ev_auto.hpp ComputeP99Y over the
+        `downsample`-times coarser box sums of Y, ComputeEvAuto against the per-pixel landed intensity).  Returns a dict: p99_y (fine-equivalent),
+        per_pixel_intensity, ev_auto (stops in [-6, 6]; 0 without data), produced (False = "auto: no data"), value_count, coarse_w, coarse_h
+        (0, 0 = the fine path).  Reads the consumer only; apply it with Snapshot(intensity_factor=factor * 2 ** ev_auto) or Snapshot(auto_ev=True)."""
+        r = abi.HaloAutoEv()
+        self._check(self._L.halo_consumer_auto_ev(self._h, int(downsample), float(target_white), C.byref(r)))
+        return {"p99_y": r.p99_y, "per_pixel_intensity": r.per_pixel_intensity, "ev_auto": r.ev_auto, "produced": bool(r.produced),
+                "value_count": int(r.value_count), "coarse_w": int(r.coarse_w), "coarse_h": int(r.coarse_h)}
+
+    def Snapshot(self, intensity_factor=1.0, ray_color=(-1.0, -1.0, -1.0), background=(0.0, 0.0, 0.0), want_xyz=True, auto_ev=False, target_white=135.0):
+        """PrepareSnapshot + PostSnapshot: returns (rgb uint8[H,W,3], xyz float32[H,W,3] | None, total_intensity).  auto_ev=True: the image is
+        exposed with intensity_factor * 2 ** ev_auto (AutoEv(8, target_white)) and the EV comes back as a FOURTH value; without it the
+        three-tuple is what it always was."""
+        if auto_ev:
+            ev = self.AutoEv(8, target_white)["ev_auto"]
+            return self.Snapshot(float(intensity_factor) * 2.0 ** ev, ray_color, background, want_xyz) + (ev,)
         w, h = getattr(self, "_cons_size", None) or (self._render.width, self._render.height)
         d = abi.HaloDisplay(float(intensity_factor), (C.c_float * 3)(*ray_color), (C.c_float * 3)(*background))
         rgb = np.empty((h, w, 3), np.uint8)
@@ -382,6 +400,11 @@ class HipTraceBackend:
 def host_spectrum_entry(m, count, r):
     """halo_host_spectrum_entry: the spectrum entry of root r among the m roots of a crystal entry's share, `count` entries (no device needed)."""
     return int(load_library().halo_host_spectrum_entry(int(m), int(count), int(r)))
+
+
+def host_ev_auto(p99_y, per_pixel_intensity, target_white=135.0):
+    """halo_host_ev_auto: ComputeEvAuto of the reference (gui_ev_auto.hpp:143-155) in fp32 (no device needed)."""
+    return float(load_library().halo_host_ev_auto(float(p99_y), float(per_pixel_intensity), float(target_white)))
 
 
 def host_fixed_frac_bits(max_w, hits):

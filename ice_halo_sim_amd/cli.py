@@ -110,6 +110,19 @@ def write_image(path, rgb, fmt, quality):
     print("Saved: %s (%dx%d)" % (path, rgb.shape[1], rgb.shape[0]))
 
 
+def exposure_factor(be, rid, factor, args):
+    """--auto-ev: the config's intensity_factor times 2^ev_auto of the device consumer (HipTraceBackend.AutoEv: the reference GUI's Adaptive
+    Brightness, P99 of the 8 x 8 box sums against the per-pixel landed intensity), and the line that says which EV was chosen."""
+    if not args.auto_ev:
+        return factor
+    a = be.AutoEv(8, args.target_white)
+    if a["produced"]:
+        print("ev_auto (render %d): %+.2f EV (p99_y=%.6g, per_pixel_intensity=%.6g)" % (rid, a["ev_auto"], a["p99_y"], a["per_pixel_intensity"]))
+    else:
+        print("ev_auto (render %d): (auto: no data)" % rid)
+    return factor * 2.0 ** a["ev_auto"]
+
+
 def save_all_renders(job, args):
     """`-f cfg -o dir [--format png] [--quality q]`: what the reference CLI leaves in the output directory (SaveRenderResults /
     SaveCompositeResults, main.cpp:251-315): img_<id>.<fmt> per render entry, img_<id>_components.<fmt> with raypath_color."""
@@ -133,7 +146,8 @@ def save_all_renders(job, args):
             return 4
         be = res["backend"]
         meta = job.render_meta.get(rid, {})
-        rgb, xyz, total_intensity = be.Snapshot(intensity_factor=meta.get("intensity_factor", 1.0), ray_color=meta.get("ray_color", (-1.0, -1.0, -1.0)),
+        rgb, xyz, total_intensity = be.Snapshot(intensity_factor=exposure_factor(be, rid, meta.get("intensity_factor", 1.0), args),
+                                                ray_color=meta.get("ray_color", (-1.0, -1.0, -1.0)),
                                                 background=meta.get("background", (0.0, 0.0, 0.0)), want_xyz=args.deterministic)
         if args.deterministic:
             print("xyz sha256 (render %d): %s" % (rid, hashlib.sha256(xyz.tobytes()).hexdigest()))
@@ -178,8 +192,16 @@ def main(argv=None):
                     help="a spectrum that is a list of discrete wavelengths: trace it as spectrum sessions — every dispatch one session that holds rays of "
                     "ALL the wavelengths, dealt out in blocks of consecutive rays — instead of one session per wavelength (which cannot fill the GPU "
                     "when the rays per wavelength are few).  The same rays when the scene has one crystal entry; ignored for an illuminant")
+    ap.add_argument("--auto-ev", action="store_true",
+                    help="expose the mono images of -o and --out-rgb automatically: the config's intensity_factor times 2^ev_auto, the reference GUI's "
+                    "Adaptive Brightness computed on the device (P99 of the 8 x 8 box sums of Y against the per-pixel landed intensity, mapped to "
+                    "--target-white, clamped to +-6 EV).  The EV chosen is printed per render; the class composite keeps its own P99 anchor")
+    ap.add_argument("--target-white", type=float, default=135.0, help="sRGB level (0, 255] the P99 maps to with --auto-ev (default 135)")
     ap.add_argument("--display-ev", type=float, default=0.0, help="display-time EV of the composite (display_exposure_scale = 2^EV)")
     args = ap.parse_args(argv)
+    if not 0.0 < args.target_white <= 255.0:
+        print("Error: --target-white must lie in (0, 255], got %g" % args.target_white, file=sys.stderr)
+        return 2
     if not 1 <= args.quality <= 100:
         print("Error: --quality must be between 1 and 100, got %d" % args.quality, file=sys.stderr)
         return 2
@@ -209,8 +231,8 @@ def main(argv=None):
         return 4
     be = res["backend"]
     meta = job.render_meta.get(res["render_id"], {})
-    rgb, xyz, total_intensity = be.Snapshot(intensity_factor=meta.get("intensity_factor", 1.0), ray_color=meta.get("ray_color", (-1.0, -1.0, -1.0)),
-                                            background=meta.get("background", (0.0, 0.0, 0.0)))
+    rgb, xyz, total_intensity = be.Snapshot(intensity_factor=exposure_factor(be, res["render_id"], meta.get("intensity_factor", 1.0), args),
+                                            ray_color=meta.get("ray_color", (-1.0, -1.0, -1.0)), background=meta.get("background", (0.0, 0.0, 0.0)))
     wall = time.perf_counter() - wall0
     if args.deterministic:
         print("xyz sha256: %s" % hashlib.sha256(xyz.tobytes()).hexdigest())

@@ -192,6 +192,11 @@ struct HaloBackend {
   DevBuf<uint8_t> cons_rgb;
   DevBuf<float> comp_rgb, lanes_stage;   // halo_consumer_composite's linear image, halo_consumer_load_lanes' staging
   DevBuf<uint32_t> comp_hist;            // radix-select histogram (2048 bins)
+  // halo_consumer_auto_ev: the candidate values, and one block of words — the select's AevRecord, then the multi-block select's histograms
+  DevBuf<float> aev_vals;
+  DevBuf<uint32_t> aev_ws;
+  int aev_agg_hist = 0;                  // option "auto_ev_hist": 1 = wave-aggregated adds in the histogram passes (measured slower: DESIGN 3.5, tools/auto_ev_cost.py)
+  int aev_select = -1;                   // option "auto_ev_select": -1 by size (kAevSmallMax), 0 the multi-block select, 1 the one-workgroup select
   int cons_w = 0, cons_h = 0;
   double total_intensity = 0.0;
   DevBuf<double> tally;        // kTallyLines x kTallyStride doubles, [kSum*] per line: CUMULATIVE tallies of every kernel this backend ever launched
@@ -594,7 +599,7 @@ int halo_destroy(halo_handle_t b) {
   for (int k = 0; k < 2; k++)
     if (b->cs[k]) (void)hipStreamSynchronize(b->cs[k]);
   release_all(b->acc_own, b->tally, b->mono, b->ovf, b->ovf_flag, b->filter_dev, b->cons_sum, b->cons_comp, b->cons_xyz_out, b->cons_stage, b->cons_rgb, b->comp_rgb,
-              b->lanes_stage, b->comp_hist, b->counters, b->ring_dev, b->tcache_dev, b->shapes_s[0], b->shapes_s[1], b->cont_cnt, b->cont_mask, b->cont_err, b->cont_base,
+              b->lanes_stage, b->comp_hist, b->aev_vals, b->aev_ws, b->counters, b->ring_dev, b->tcache_dev, b->shapes_s[0], b->shapes_s[1], b->cont_cnt, b->cont_mask, b->cont_err, b->cont_base,
               b->cont_tiles, b->lanes, b->fix, b->cont[0], b->cont[1], b->exits, b->host_f, b->host_u);
   for (int k = 0; k < 2; k++) release_all(b->bin_list_s[k], b->bin_cnt_s[k], b->bin_list2_s[k], b->bin_cnt2_s[k]);
   for (int k = 0; k < 2; k++) release_all(b->tile_chunk_s[k], b->tile_cnt_s[k]);
@@ -664,6 +669,8 @@ int halo_set_option(halo_handle_t b, const char* key, int64_t v) {
     b->overlap = v ? 1 : 0;
   }
   else if (k == "defer_fold") b->defer_fold = v ? 1 : 0;
+  else if (k == "auto_ev_hist") b->aev_agg_hist = v ? 1 : 0;
+  else if (k == "auto_ev_select") b->aev_select = v < 0 ? -1 : (v ? 1 : 0);
   else if (k == "gen_ahead") b->gen_ahead = v ? 1 : 0;
   else if (k == "close_direct") b->close_direct = v < 0 ? -1 : (v ? 1 : 0);
   else if (k == "tile_append") b->tile_append = v < 0 ? -1 : (v ? 1 : 0);
@@ -2479,6 +2486,58 @@ int halo_consumer_snapshot(halo_handle_t b, const HaloDisplay* dsp, uint8_t* rgb
   return HALO_OK;
 }
 
+// ---- auto exposure (gui/gui_ev_auto.hpp) ---------------------------------------------------------------------
+float halo_host_ev_auto(float p99_y, float per_pixel_intensity, float target_white) {   // ComputeEvAuto, gui_ev_auto.hpp:143-155
+  if (per_pixel_intensity <= 0.0f || p99_y <= 0.0f) return 0.0f;
+  const float p99_norm = p99_y / per_pixel_intensity;
+  const float t = target_white / 255.0f;
+  const float target_linear = t <= 0.04045f ? t / 12.92f : std::pow((t + 0.055f) / 1.055f, 2.4f);
+  if (target_linear <= 0.0f || p99_norm <= 0.0f) return 0.0f;
+  const float ev = std::log2f(target_linear / p99_norm);
+  return std::min(std::max(ev, -6.0f), 6.0f);
+}
+
+int halo_consumer_auto_ev(halo_handle_t b, int32_t downsample_factor, float target_white, HaloAutoEv* out) {
+  if (!b) return HALO_FATAL;
+  if (!out) return fail(b, HALO_FATAL, "consumer_auto_ev: out is NULL");
+  if (!b->cons_sum.ptr) return fail(b, HALO_FATAL, "consumer_auto_ev before consumer_fold");
+  if (!(target_white > 0.0f && target_white <= 255.0f)) return fail(b, HALO_FATAL, "consumer_auto_ev: target_white must lie in (0, 255]");
+  HIPCHK(b, hipSetDevice(b->device));
+  const uint32_t w = static_cast<uint32_t>(b->cons_w), h = static_cast<uint32_t>(b->cons_h), npix = w * h;
+  // ComputeP99Y's fallback order (:80-86): the coarse path only for f > 1 and a grid that does not collapse
+  const uint32_t f = downsample_factor > 1 ? static_cast<uint32_t>(downsample_factor) : 1u;
+  const bool coarse = f > 1u && w / f > 0u && h / f > 0u;
+  const uint32_t wc = coarse ? w / f : 0u, hc = coarse ? h / f : 0u;
+  const uint32_t n_vals = coarse ? wc * hc : npix;
+  HIPCHK(b, b->aev_vals.reserve(n_vals));
+  constexpr size_t kRecWords = sizeof(AevRecord) / sizeof(uint32_t);
+  HIPCHK(b, b->aev_ws.reserve(kRecWords + kAevHistWords));
+  AevRecord* rec_dev = reinterpret_cast<AevRecord*>(b->aev_ws.ptr);
+  hipError_t e = launch_aev_values(b->cons_sum.ptr, b->cons_comp.ptr, w, h, f, wc, hc, b->aev_vals.ptr, b->cu_count * 8, b->stream);
+  if (e != hipSuccess) return hip_fail(b, e, "halo_aev value kernel launch");
+  const bool one_wg = b->aev_select < 0 ? n_vals <= kAevSmallMax : b->aev_select == 1;
+  e = launch_aev_select(b->aev_vals.ptr, n_vals, rec_dev, b->aev_ws.ptr + kRecWords, one_wg, b->aev_agg_hist != 0, b->cu_count, b->stream);
+  if (e != hipSuccess) return hip_fail(b, e, "halo_aev select kernel launch");
+  AevRecord rec{};
+  HIPCHK(b, hipMemcpyAsync(&rec, rec_dev, sizeof(rec), hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(b, hipStreamSynchronize(b->stream));
+  float p99 = 0.0f;
+  if (rec.count) std::memcpy(&p99, &rec.p99_bits, sizeof(float));
+  if (coarse) p99 = p99 / (static_cast<float>(f) * static_cast<float>(f));   // the fine-equivalent P99 (:112-113)
+  // GetRawXyzResult (render.cpp:586-587), in float like the reference
+  const float snapshot_intensity = static_cast<float>(b->total_intensity);
+  const int total_pix = b->cons_w * b->cons_h;
+  const float per_pixel = total_pix > 0 ? snapshot_intensity / (0.08f * total_pix) : 0.0f;
+  out->p99_y = p99;
+  out->per_pixel_intensity = per_pixel;
+  out->ev_auto = halo_host_ev_auto(p99, per_pixel, target_white);
+  out->produced = (p99 > 0.0f && per_pixel > 0.0f) ? 1 : 0;
+  out->value_count = rec.count;
+  out->coarse_w = static_cast<int32_t>(wc);
+  out->coarse_h = static_cast<int32_t>(hc);
+  return HALO_OK;
+}
+
 // ---- display-side composite of the class lanes (server/component_compositor.cpp) -------------------------
 int halo_host_parse_composite_mode(const char* mode) {   // ParseCompositeMode, component_compositor.cpp:118-134
   if (mode && std::strcmp(mode, "dominant") == 0) return HALO_COMPOSITE_DOMINANT;
@@ -2722,6 +2781,7 @@ uint64_t halo_abi_sizeof(int which) {
     case 9: return sizeof(HaloFilter);
     case 10: return sizeof(HaloRouteInfo);
     case 11: return sizeof(HaloComposite);
+    case 12: return sizeof(HaloAutoEv);
     default: return 0;
   }
 }

@@ -50,6 +50,19 @@ hipError_t launch_lanes_drain(double* lanes, float* dst, uint64_t n, int blocks,
 hipError_t launch_lanes_add(const float* src, double* lanes, uint64_t n, int blocks, hipStream_t stream);
 hipError_t launch_post_snapshot(const float* sum, const float* comp, uint8_t* rgb_out, float* xyz_out, uint32_t n_pix, float scale,
                                 const float ray_color[3], const float background[3], int blocks, hipStream_t stream);
+// halo_autoev.hip — the auto-exposure stage.  AevRecord is what the select leaves in device memory: the count of positive values, the index the
+// reference's rule picks among them, the bit pattern of that order statistic (0 when count is 0); prefix / rank carry the select from pass to pass.
+struct AevRecord {
+  uint32_t count, idx, p99_bits, prefix, rank, reserved[3];
+};
+constexpr uint32_t kAevHistWords = 3u * 2048u;   // the multi-block select's three global histograms
+// up to this many values one workgroup does the whole select: measured, it is 10-20 us ahead of the seven launches of the multi-block select up
+// to 16 Ki values, level with them at 32 400 (the production shape) and 25 us behind at 64 Ki (profiles/auto_ev_cost.txt)
+constexpr uint32_t kAevSmallMax = 1u << 15;
+// (wc, hc > 0: box sums of f x f pixels into vals[wc * hc]; wc = hc = 0: the fine path, Y of every pixel into vals[width * height])
+hipError_t launch_aev_values(const float* sum, const float* comp, uint32_t width, uint32_t height, uint32_t f, uint32_t wc, uint32_t hc, float* vals, int blocks,
+                             hipStream_t stream);
+hipError_t launch_aev_select(const float* vals, uint32_t n, AevRecord* rec, uint32_t* hist, bool one_workgroup, bool aggregate, int blocks, hipStream_t stream);
 hipError_t launch_cont_reorder(const float* in, uint32_t in_stride, uint32_t region, const uint32_t* cnt, uint32_t max_fill, const uint32_t* mask, uint32_t n_roots,
                                uint32_t* tile_sum, uint32_t* base, float* out, uint32_t out_stride, uint32_t n_cont, uint32_t planes, uint32_t* err, hipStream_t stream);
 

@@ -151,6 +151,13 @@ class HipTraceBackend {
     Check(halo_consumer_snapshot(h_, &display, rgb_out, xyz_out, &total));
     return total;
   }
+  // The reference GUI's Adaptive Brightness anchor (gui/gui_ev_auto.hpp ComputeP99Y + ComputeEvAuto) on the device consumer: expose a
+  // snapshot with display.intensity_factor * exp2(result.ev_auto); result.produced == 0 is the GUI's "auto: no data"
+  HaloAutoEv AutoEv(int downsample = 8, float target_white = 135.f) {
+    HaloAutoEv r{};
+    Check(halo_consumer_auto_ev(h_, downsample, target_white, &r));
+    return r;
+  }
   // trace_backend.hpp:587,625 — real counts of the last session's stochastic draws (never stand-ins)
   size_t GetLastBatchStochasticCrystalSampleCount() const {
     uint64_t c = 0, o = 0;

@@ -494,6 +494,29 @@ int halo_consumer_consume(halo_handle_t h, const float* xyz, int width, int heig
 int halo_consumer_snapshot(halo_handle_t h, const HaloDisplay* display, uint8_t* rgb_out, float* xyz_out, double* total_intensity);
 int halo_consumer_reset(halo_handle_t h);
 
+/* --- auto exposure: the reference GUI's Adaptive Brightness anchor on the device (gui/gui_ev_auto.hpp, doc/adaptive-brightness.md) --- */
+typedef struct HaloAutoEv {
+  float p99_y;               /* fine-equivalent P99 (coarse P99 / f^2 on the coarse path) */
+  float per_pixel_intensity; /* total_intensity / (0.08 * n_pix) */
+  float ev_auto;             /* stops, clamped to [-6, 6]; 0 when there is no data */
+  int32_t produced;          /* 0: no positive value or no landed intensity ("auto: no data") */
+  uint32_t value_count;      /* positive values the percentile was taken over */
+  int32_t coarse_w, coarse_h;/* 0, 0 = fine path */
+} HaloAutoEv;
+/* ComputeP99Y (gui_ev_auto.hpp:92-138) of the consumer's snapshot Y = sum + compensation (exactly halo_consumer_snapshot's xyz_out), the
+ * per-pixel landed intensity of RenderConsumer::GetRawXyzResult (render.cpp:584-593) and ComputeEvAuto of the two, all in fp32 like the
+ * reference.  downsample_factor > 1 with W / f > 0 and H / f > 0: Y is box-summed onto the f-times coarser grid (each bin's f x f pixels added
+ * one after another, rows outside, columns inside; trailing rows / columns that fill no bin are dropped), the percentile is taken over the bins
+ * > 0 and divided by f * f — a coarse grid with no positive bin gives 0, never the fine path.  Otherwise (f <= 1, or the grid collapses) it is
+ * taken over the pixels with Y > 0.  The percentile is the exact order statistic at index (size_t)((float)count * 0.99f), clamped to count - 1:
+ * a radix select on the device, one 32-byte record read back.  The reference's GUI passes downsample_factor 8 and target_white 135.
+ * Applying the result is the caller's multiplication: snapshot with intensity_factor * 2^ev_auto.  Reads the consumer only: image, lanes and
+ * total intensity stay as they are.  HALO_FATAL (handle still usable) before any fold / consume, with out == NULL, or with target_white outside (0, 255]. */
+int halo_consumer_auto_ev(halo_handle_t h, int32_t downsample_factor, float target_white, HaloAutoEv* out);
+/* ComputeEvAuto (gui_ev_auto.hpp:143-155): 0 if either input is <= 0, else clamp(log2f(target_linear / (p99_y / per_pixel_intensity)), -6, 6)
+ * with target_linear the sRGB decoding of target_white / 255.  No GPU needed. */
+float halo_host_ev_auto(float p99_y, float per_pixel_intensity, float target_white);
+
 /* --- display-side composite of the raypath-colour class lanes (server/component_compositor.cpp) ------------- */
 /* CompositeMode (component_compositor.hpp:21): how the per-class Y lanes become one colour per pixel. */
 enum { HALO_COMPOSITE_DOMINANT = 0, HALO_COMPOSITE_ADDITIVE = 1, HALO_COMPOSITE_PAINTER = 2 };
@@ -597,7 +620,7 @@ int halo_host_wl_pool(const HaloWl* wl, float* entries5, int cap);
  * different cuts of the share into launches, which must agree (0xFFFFFFFF if they did not).  Parity-test hook, no device needed. */
 uint32_t halo_host_spectrum_entry(uint64_t m, uint32_t count, uint64_t r);
 int halo_abi_version(void);
-/* sizeof() of boundary structs as compiled (0 scene, 1 render, 2 wl, 3 exit record, 4 geom tables, 5 layer stats, 6 entry, 7 colour set, 8 colour class, 9 filter, 10 route info, 11 composite). */
+/* sizeof() of boundary structs as compiled (0 scene, 1 render, 2 wl, 3 exit record, 4 geom tables, 5 layer stats, 6 entry, 7 colour set, 8 colour class, 9 filter, 10 route info, 11 composite, 12 auto ev). */
 uint64_t halo_abi_sizeof(int which);
 
 #ifdef __cplusplus
@@ -632,6 +655,7 @@ HALO_STATIC_ASSERT(sizeof(HaloLayerStats) == 56, "HaloLayerStats");
 HALO_STATIC_ASSERT(sizeof(HaloExitRecord) == 40 + HALO_PATH_CAP, "HaloExitRecord");
 HALO_STATIC_ASSERT(sizeof(HaloRouteInfo) == 40, "HaloRouteInfo");
 HALO_STATIC_ASSERT(sizeof(HaloDisplay) == 28, "HaloDisplay");
+HALO_STATIC_ASSERT(sizeof(HaloAutoEv) == 28, "HaloAutoEv");
 HALO_STATIC_ASSERT(sizeof(HaloCompositeClass) == 24, "HaloCompositeClass");
 HALO_STATIC_ASSERT(sizeof(HaloComposite) == 16 + HALO_COLOR_MAX_CLASSES * 24, "HaloComposite");
 HALO_STATIC_ASSERT(sizeof(HaloGeomTables) == 4 + HALO_MAX_FACES * 20 + 4 + HALO_MAX_TRIS * (36 + 12 + 4 + 4), "HaloGeomTables");

@@ -118,6 +118,7 @@ CLOSE_AUTO, CLOSE_NEVER, CLOSE_ALWAYS = -1, 0, 1                                
 
 ACCUM_XYZ, ACCUM_SCALAR, ACCUM_BIN1, ACCUM_BIN2, ACCUM_LOG, ACCUM_LOG_XYZ, ACCUM_NONE = 1, 2, 4, 8, 16, 32, 64   # HaloRouteInfo.accum_mask bits
 ACCUM_FIXED = 128   # ... fixed-point planes (option "deterministic"): beside it ACCUM_NONE, and ACCUM_LOG or ACCUM_LOG_XYZ for launches that took the hit log's integer twins
+FIX_BUDGET_RAYS = 1 << 30   # rays one unfolded fixed-point plane set takes: the longest run between two folds (or exchanges: halo_export_fixed / halo_import_fixed) that is exact
 ACCUM_FIXED_LOG, ACCUM_FIXED_LOG_XYZ = ACCUM_FIXED | ACCUM_LOG, ACCUM_FIXED | ACCUM_LOG_XYZ   # a deterministic session whose launches were logged (scalar plane; X, Y, Z planes)
 
 

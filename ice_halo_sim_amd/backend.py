@@ -70,6 +70,10 @@ def load_library():
         "halo_take_landed": (C.c_int, [H, C.POINTER(C.c_double)]),
         "halo_peek_fixed": (C.c_int, [H, C.c_int32, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
         "halo_host_fixed_frac_bits": (C.c_uint32, [C.c_double, C.c_uint64]),
+        "halo_set_shard": (C.c_int, [H, C.c_uint32, C.c_uint32]),
+        "halo_host_shard_slice": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "halo_export_fixed": (C.c_int, [H, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "halo_import_fixed": (C.c_int, [H, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64]),
         "halo_flush": (C.c_int, [H]),
         "halo_collect_timing": (C.c_int, [H, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
         "halo_consumer_fold": (C.c_int, [H]),
@@ -113,6 +117,7 @@ EXPORTED_SYMBOLS = [
     "halo_host_refractive_index", "halo_host_reduce_raypath", "halo_host_filter_fast_check", "halo_host_color_fast_mask", "halo_host_illuminant_spd", "halo_host_wl_pool", "halo_reduce_accumulator",
     "halo_peek_fixed", "halo_host_fixed_frac_bits", "halo_begin_spectrum", "halo_host_spectrum_entry",
     "halo_consumer_auto_ev", "halo_host_ev_auto",
+    "halo_set_shard", "halo_host_shard_slice", "halo_export_fixed", "halo_import_fixed",
 ]
 
 
@@ -257,6 +262,36 @@ class HipTraceBackend:
         self._check(self._L.halo_peek_fixed(self._h, int(plane), sums.ctypes.data_as(C.POINTER(C.c_uint64)), w * h, C.byref(f), C.byref(landed), C.byref(fl)))
         return sums, f.value, np.uint64(landed.value), fl.value
 
+    # --- shards: N handles trace one session's rays between them (halo_set_shard, halo_export_fixed, halo_import_fixed) ---
+    def set_shard(self, index, count):
+        """This handle is shard `index` of `count` ((0, 1) = the default, everything): BeginSession / TraceLayer then take the WHOLE session's
+        ray count, the handle plans it as one rank would and launches its slice of every crystal entry's share (host_shard_slice).  Not inside
+        a session; BackendError for what sharding refuses."""
+        self._check(self._L.halo_set_shard(self._h, int(index), int(count)))
+
+    def fixed_words(self, planes=None):
+        """Words halo_export_fixed writes for the current render: planes * W * H + 1 (planes: default the last session's plane count)."""
+        n = self.last_route().plane_cnt if planes is None else int(planes)
+        return n * self._render.width * self._render.height + 1
+
+    def export_fixed(self, out):
+        """MOVE the pending fixed-point planes of this handle's deterministic sessions into device memory: `out` is a torch.int64 device tensor of
+        fixed_words() elements (anything with data_ptr() and numel()) or a (device pointer, n_words) pair.  Words [p * W * H, (p + 1) * W * H)
+        are plane p in pixel order, the last word the landed integer nobody has taken yet.  The planes are left zero and not pending, the
+        landed integer taken.  Returns (plane_cnt, frac_bits, landed_frac_bits).  Waits for the device."""
+        ptr, n = (out.data_ptr(), out.numel()) if hasattr(out, "data_ptr") else (int(out[0]), int(out[1]))
+        pc, f, fl = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._check(self._L.halo_export_fixed(self._h, C.c_void_p(ptr), n, C.byref(pc), C.byref(f), C.byref(fl)))
+        return pc.value, f.value, fl.value
+
+    def import_fixed(self, words, plane_cnt, frac_bits, landed_frac_bits, rays):
+        """ADD exported words (a torch.int64 device tensor or a (device pointer, n_words) pair; e.g. the integer sum of every shard's export) into
+        the planes of this handle's last deterministic session, modulo 2^64, in stream order; the planes become pending, the landed word joins
+        the handle's untaken landed integer, `rays` count against the 2^30-ray budget.  flush() / ReadbackXyzAccum() then fold as after the
+        handle's own session.  BackendError for a layout that is not the handle's."""
+        ptr, n = (words.data_ptr(), words.numel()) if hasattr(words, "data_ptr") else (int(words[0]), int(words[1]))
+        self._check(self._L.halo_import_fixed(self._h, C.c_void_p(ptr), n, int(plane_cnt), int(frac_bits), int(landed_frac_bits), int(rays)))
+
     # --- the seam (trace_backend.hpp:374-632) ---
     def SupportsDeviceXyzAccum(self):
         return True
@@ -400,6 +435,18 @@ class HipTraceBackend:
 def host_spectrum_entry(m, count, r):
     """halo_host_spectrum_entry: the spectrum entry of root r among the m roots of a crystal entry's share, `count` entries (no device needed)."""
     return int(load_library().halo_host_spectrum_entry(int(m), int(count), int(r)))
+
+
+def host_shard_slice(share, clock, index, count):
+    """halo_host_shard_slice: (first, n) — the rays shard `index` of `count` takes of a crystal entry's share of `share` rays, cut in units of
+    `clock` rays (no device needed).  ValueError for arguments the library refuses."""
+    first, n = C.c_uint64(), C.c_uint64()
+    for name, v, top in (("share", share, 1 << 64), ("clock", clock, 1 << 32), ("index", index, 1 << 32), ("count", count, 1 << 32)):
+        if not 0 <= int(v) < top:
+            raise ValueError("host_shard_slice: %s = %r out of range" % (name, v))
+    if load_library().halo_host_shard_slice(int(share), int(clock), int(index), int(count), C.byref(first), C.byref(n)) != abi.HALO_OK:
+        raise ValueError("host_shard_slice: refused (clock %r, index %r, count %r)" % (clock, index, count))
+    return first.value, n.value
 
 
 def host_ev_auto(p99_y, per_pixel_intensity, target_white=135.0):

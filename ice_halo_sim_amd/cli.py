@@ -21,19 +21,29 @@ DISPATCH_RAYS_MULTI = 1 << 24  # ... for scenes with more than one scattering la
                                # and a one-shot CLI run pays for their allocation (64 Mi roots x 8 hits: two pools of 10 GB, 0.5 s of hipMalloc)
 
 
-def run_job(job, render_id=None, seed=42, device=0, max_rays=None, progress=None, canonical_order=False, deterministic=False, spectrum_session=False):
+def run_job(job, render_id=None, seed=42, device=0, max_rays=None, progress=None, canonical_order=False, deterministic=False, spectrum_session=False, shard=None):
     """Trace `job` (config.TraceJob) on one GPU. Returns dict(rays, setup_sec, active_sec, backend, render).  canonical_order: option
     cont_order = 1 (the continuation pool of every layer but the last in (root, interaction) order).  deterministic: option deterministic = 1
     (fixed-point accumulation; with it a multi-layer document takes cont_order = 1 as well) — BackendError when the document needs what that
     route refuses.  spectrum_session: a document whose spectrum is a list of discrete wavelengths is traced as spectrum sessions
     (HipTraceBackend.BeginSpectrumSession) — one session chain per dispatch of len(wavelengths) x n rays, n rays of every wavelength in it —
-    instead of one session per wavelength; ignored for an illuminant (which is one session already) and for a single wavelength."""
+    instead of one session per wavelength; ignored for an illuminant (which is one session already) and for a single wavelength.
+    shard = (rank, world), with deterministic: this process is one rank of `world` (torch.distributed is initialised); the same sessions go
+    through dist.ExactShardedTracer, the ranks' integer planes are exchanged where this function's one-rank run folds them, and rank 0 ends
+    up with the one-rank run's consumer, bit for bit — the other ranks with an empty one."""
     if not job.renders:
         raise config.ConfigError("config has no render entry")
     rid = render_id if render_id is not None else sorted(job.renders)[0]  # the seam supports ONE renderer (simulator.cpp:937-944)
     render = job.renders[rid]
     t0 = time.perf_counter()
-    be = HipTraceBackend(device=device, seed=seed)
+    tracer = None
+    if shard is not None:
+        from .dist import ExactShardedTracer
+        tracer = ExactShardedTracer(job.scene, render, seed=seed, device=device, rank=shard[0], world=shard[1])
+        be = tracer.backend
+        be.set_shard(0, 1)   # the warm-up below is every rank's own, whole: the counters move as they do on one rank
+    else:
+        be = HipTraceBackend(device=device, seed=seed)
     if canonical_order or (deterministic and job.scene.layer_count > 1):
         be.set_option("cont_order", 1)
     if deterministic:
@@ -55,6 +65,8 @@ def run_job(job, render_id=None, seed=42, device=0, max_rays=None, progress=None
     be.ReadbackXyzAccum()
     if job.color_classes:
         be.ReadbackClassLanes()   # the warm-up rays must not stay in the lanes
+    if tracer is not None:
+        be.set_shard(shard[0], shard[1])
     setup = time.perf_counter() - t0
     t1 = time.perf_counter()
     rays = 0
@@ -62,15 +74,20 @@ def run_job(job, render_id=None, seed=42, device=0, max_rays=None, progress=None
     left = per_wl if spectrum else 0
     while left > 0:   # spectrum sessions: every dispatch holds n rays of each wavelength, block by block within each crystal entry's share
         n = min(left, max(1, (DISPATCH_RAYS if job.scene.layer_count == 1 else DISPATCH_RAYS_MULTI) // n_wl))
-        be.BeginSpectrumSession(job.scene, render, job.wavelengths, n * n_wl)
-        for li in range(job.scene.layer_count):
-            be.TraceLayer(n * n_wl if li == 0 else 0)
-            if li + 1 < job.scene.layer_count:
-                be.Recombine(True)
-        be.EndSession()
+        if tracer is not None:
+            tracer.trace_session(list(job.wavelengths), n * n_wl)
+        else:
+            be.BeginSpectrumSession(job.scene, render, job.wavelengths, n * n_wl)
+            for li in range(job.scene.layer_count):
+                be.TraceLayer(n * n_wl if li == 0 else 0)
+                if li + 1 < job.scene.layer_count:
+                    be.Recombine(True)
+            be.EndSession()
         left -= n
         rays += n * n_wl
         if left == 0:
+            if tracer is not None:
+                tracer.exchange()   # where the one-rank run folds its planes: the consumer's fold is a reader of the image
             be.ConsumeDeviceFused()  # drain window
         if progress:
             progress(rays)
@@ -78,14 +95,19 @@ def run_job(job, render_id=None, seed=42, device=0, max_rays=None, progress=None
         left = per_wl
         while left > 0:
             n = min(left, DISPATCH_RAYS if job.scene.layer_count == 1 else DISPATCH_RAYS_MULTI)
-            be.BeginSession(job.scene, render, wl, n)
-            for li in range(job.scene.layer_count):
-                be.TraceLayer(n if li == 0 else 0)
-                if li + 1 < job.scene.layer_count:
-                    be.Recombine(True)
-            be.EndSession()
+            if tracer is not None:
+                tracer.trace_session(wl, n)
+            else:
+                be.BeginSession(job.scene, render, wl, n)
+                for li in range(job.scene.layer_count):
+                    be.TraceLayer(n if li == 0 else 0)
+                    if li + 1 < job.scene.layer_count:
+                        be.Recombine(True)
+                be.EndSession()
             left -= n
             rays += n
+        if tracer is not None:
+            tracer.exchange()
         be.ConsumeDeviceFused()  # drain window
         if progress:
             progress(rays)
@@ -188,6 +210,12 @@ def main(argv=None):
                     "(option deterministic = 1; multi-scattering configs take cont_order = 1 with it), so a fixed --seed gives the same XYZ bytes on "
                     "every run, whose sha256 is printed.  A config that needs what the route does not cover (raypath_color, a filter outside the fast "
                     "form) is refused with the reason and a non-zero exit; a multi-GPU run is reproducible per rank")
+    ap.add_argument("--ranks", type=int, default=1,
+                    help="with --deterministic: trace the job as N ranks, one per GPU, that share every session's rays (each rank plans the whole "
+                    "session and launches its slice) and exchange their integer pixel sums where one rank folds them — the XYZ bytes, and the sha256 "
+                    "printed, are those of the run without --ranks.  Started plainly, the command launches its own N ranks (torch.distributed.run); "
+                    "HALO_DIST_BACKEND=gloo lets the ranks share one device (a rehearsal; default nccl = RCCL, one device per rank).  Single-layer "
+                    "configs; not with -o")
     ap.add_argument("--spectrum-session", action="store_true",
                     help="a spectrum that is a list of discrete wavelengths: trace it as spectrum sessions — every dispatch one session that holds rays of "
                     "ALL the wavelengths, dealt out in blocks of consecutive rays — instead of one session per wavelength (which cannot fill the GPU "
@@ -205,9 +233,23 @@ def main(argv=None):
     if not 1 <= args.quality <= 100:
         print("Error: --quality must be between 1 and 100, got %d" % args.quality, file=sys.stderr)
         return 2
+    shard = None
+    if args.ranks < 1 or (args.ranks > 1 and not args.deterministic):
+        print("Error: --ranks needs --deterministic and N >= 1 (ranks are merged exactly only through the fixed-point sums)", file=sys.stderr)
+        return 2
+    if args.ranks > 1:
+        if args.output_dir is not None and not args.benchmark and args.render is None:
+            print("Error: --ranks traces one render entry: pass --render (or --benchmark), not -o alone", file=sys.stderr)
+            return 2
+        if "WORLD_SIZE" not in os.environ:
+            return launch_ranks(args.ranks, sys.argv[1:] if argv is None else list(argv))
+        shard = join_ranks(args)
+        if shard is None:
+            return 2
+    rank0 = shard is None or shard[0] == 0
     try:
         job = config.load_config(args.config)
-        for w in getattr(job, "warnings", []):
+        for w in getattr(job, "warnings", []) if rank0 else []:
             print("[warning] " + w)
         if job.ray_num is None and args.max_rays is None:
             raise config.ConfigError('ray_num is "infinite": pass --max-rays')
@@ -217,7 +259,7 @@ def main(argv=None):
             print("[warning] -o / --output-dir is ignored with --render / --benchmark (nothing is saved)", file=sys.stderr)
         wall0 = time.perf_counter()
         res = run_job(job, args.render, args.seed, args.device, args.max_rays, canonical_order=args.canonical_order, deterministic=args.deterministic,
-                      spectrum_session=args.spectrum_session)
+                      spectrum_session=args.spectrum_session, shard=shard)
     except BackendUnavailableError as e:
         print("backend unavailable: %s" % e, file=sys.stderr)
         return 3
@@ -227,9 +269,16 @@ def main(argv=None):
     except BackendError as e:
         if not args.deterministic:
             raise
-        print("refused: %s" % e, file=sys.stderr)
+        if rank0 or shard is not None:
+            print("refused: %s%s" % (e, "" if shard is None else " [rank %d]" % shard[0]), file=sys.stderr)
+        if shard is not None:
+            leave_ranks(barrier=False)   # (no barrier: a refusal need not be every rank's — the launcher ends the ranks that are left)
         return 4
     be = res["backend"]
+    if not rank0:   # the image is rank 0's
+        be.close()
+        leave_ranks()
+        return 0
     meta = job.render_meta.get(res["render_id"], {})
     rgb, xyz, total_intensity = be.Snapshot(intensity_factor=exposure_factor(be, res["render_id"], meta.get("intensity_factor", 1.0), args),
                                             ray_color=meta.get("ray_color", (-1.0, -1.0, -1.0)), background=meta.get("background", (0.0, 0.0, 0.0)))
@@ -259,7 +308,60 @@ def main(argv=None):
     else:
         print("traced %d root rays in %.3f s (setup %.3f s); landed intensity %.6g" % (res["rays"], res["active_sec"], res["setup_sec"], total_intensity))
     be.close()
+    if shard is not None:
+        leave_ranks()
     return 0
+
+
+def launch_ranks(n, argv):
+    """`--ranks N` started plainly: re-run this command line as N ranks under torch.distributed.run (as bench.py --gpus N does) and return its
+    exit code.  Under RCCL every rank needs a device of its own; HALO_DIST_BACKEND=gloo lets them share."""
+    import socket
+    import subprocess
+    import torch
+    nccl = os.environ.get("HALO_DIST_BACKEND", "nccl") == "nccl"   # (the launcher itself opens no device when the ranks share them)
+    have = torch.cuda.device_count() if nccl and torch.cuda.is_available() else 0
+    if nccl and have < n:
+        print("Error: --ranks %d: only %d HIP device(s) visible (one rank per GPU under RCCL; HALO_DIST_BACKEND=gloo shares devices)" % (n, have), file=sys.stderr)
+        return 2
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        port = sk.getsockname()[1]
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
+           "--master-port", str(port), "-m", "ice_halo_sim_amd.cli"] + list(argv)
+    env = dict(os.environ, OMP_NUM_THREADS=os.environ.get("OMP_NUM_THREADS", "1"))
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env["PYTHONPATH"] = root + (os.pathsep + env["PYTHONPATH"] if env.get("PYTHONPATH") else "")
+    return subprocess.call(cmd, env=env)
+
+
+def join_ranks(args):
+    """This process is one of the launcher's ranks: take its device, join the process group.  Returns (rank, world)."""
+    import torch
+    import torch.distributed as dist
+    world, rank, local = int(os.environ["WORLD_SIZE"]), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
+    if world != args.ranks:
+        print("Error: --ranks %d but the launcher started WORLD_SIZE=%d ranks" % (args.ranks, world), file=sys.stderr)
+        return None
+    backend = os.environ.get("HALO_DIST_BACKEND", "nccl")
+    args.device = local % max(1, torch.cuda.device_count()) if backend != "nccl" else local
+    torch.cuda.set_device(args.device)
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+    if backend == "nccl":
+        dist.init_process_group(backend="nccl", device_id=torch.device("cuda", args.device))
+    else:
+        dist.init_process_group(backend=backend)
+    return rank, world
+
+
+def leave_ranks(barrier=True):
+    """Leave the process group: after the job with a barrier; after a refusal without one — this rank may be the only one that was refused, and
+    the others may already wait in a collective: torch.distributed.run ends the remaining ranks when one exits with an error."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        if barrier:
+            dist.barrier()
+        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -276,6 +276,12 @@ struct HaloBackend {
   uint64_t fix_hits = 0;                     // rays traced into the pending plane set since its last fold (<= kFixBudgetHits)
   unsigned long long fix_landed_seen = 0;    // the cumulative landed integer already handed on (like tally_seen)
   double landed_carry = 0.0;                 // landed integers converted when F_L had to change before anybody took them
+  // Shards (halo_set_shard): the handle plans every session whole — partition, launches, counters — and launches only the part of each
+  // planned launch that lies in its slice of the launch's crystal entry (shard_slice).  (0, 1), the default, is the whole of everything.
+  uint32_t shard_index = 0, shard_count = 1;
+  int64_t rank_opt = 0;                      // what option "rank" was last set to (0 again after "ray_base"): not to be combined with shards
+  bool fix_imported = false;                 // the pending fixed-point planes came through halo_import_fixed: a whole image, which a sharded handle may fold
+  bool landed_own = false;                   // count > 1: the untaken landed integer holds weight of this shard's own launches (a part, until it is exported)
   DevBuf<float> cont[2];       // SoA continuation pools, 5 planes
   uint32_t cont_stride[2] = {0, 0};
   uint32_t cont_region[2] = {0, 0};          // slots per shard region
@@ -710,6 +716,8 @@ int halo_set_option(halo_handle_t b, const char* key, int64_t v) {
     return fail(b, HALO_FATAL, k + " cannot change inside a session");
   }
   else if (k == "rank") {
+    if (v != 0 && b->shard_count > 1) return fail(b, HALO_FATAL, "rank: not with halo_set_shard count > 1 (shards trace the one-rank run's rays: they share its counter range)");
+    b->rank_opt = v;
     // disjoint 64-bit counter ranges per shard: the hi word feeds pcg_seed_with_high, so ranks never share a stream
     const uint64_t base = static_cast<uint64_t>(v) << 40;
     b->gen_count = b->gate_count = b->transit_count = b->shape_count = base;
@@ -721,6 +729,7 @@ int halo_set_option(halo_handle_t b, const char* key, int64_t v) {
     // the session's first 64-bit ray index (SplitPcgRayBase, trace_backend.hpp:184: lo feeds the stream index, hi pcg_seed_with_high)
     const uint64_t base = static_cast<uint64_t>(v);
     b->gen_count = b->gate_count = b->transit_count = b->shape_count = base;
+    b->rank_opt = 0;
   } else return fail(b, HALO_FATAL, "unknown option: " + k);
   return HALO_OK;
 }
@@ -791,6 +800,8 @@ static int begin_session(halo_handle_t b, const HaloScene* scene, const HaloRend
       if (kind != HALO_CRYSTAL_PRISM && kind != HALO_CRYSTAL_PYRAMID) return fail(b, HALO_FATAL, "unknown crystal kind");
     }
   }
+  if (b->shard_count > 1 && scene->layer_count > 1)
+    return fail(b, HALO_FATAL, "halo_set_shard count > 1: a multi-layer scene is not supported (the next layer's pool order and shuffle are global over all roots; shards do not exchange continuation pools)");
   const bool det = b->deterministic != 0;
   if (det) {
     // A deterministic session runs the kAccFixed kernels or nothing: what they do not cover is refused here, by name, before any state changes —
@@ -1030,6 +1041,10 @@ static double* twin_of(HaloBackend* b, int set) {
 // Queue the closing fold of the pending planes on the post stream (behind everything both streams hold); the main stream does NOT wait.
 static int fold_queue(HaloBackend* b) {
   if (!b->mono_dirty) return HALO_OK;
+  // a shard's own integer planes are a part of the image: they leave through halo_export_fixed, never through a fold
+  if (b->fix_planes && b->shard_count > 1 && !b->fix_imported)
+    return fail(b, HALO_FATAL, "shard " + std::to_string(b->shard_index) + " of " + std::to_string(b->shard_count) +
+                                   ": the pending fixed-point planes hold a part of the image; move them out with halo_export_fixed (and fold what halo_import_fixed brings in)");
   HIPCHK(b, hipSetDevice(b->device));
   if (int rc = fork_aux(b)) return rc;
   hipStream_t ps = post_stream(b);
@@ -1042,6 +1057,7 @@ static int fold_queue(HaloBackend* b) {
     if (e != hipSuccess) return hip_fail(b, e, "halo_fold_fixed_kernel launch");
     b->fix_hits = 0;
     b->fix_planes = false;
+    b->fix_imported = false;
     b->mono_dirty = false;
     return HALO_OK;
   }
@@ -1094,11 +1110,23 @@ static int cont_order_fail(HaloBackend* b, uint32_t err) {
 // ---- The steps of halo_trace_layer: plan (no HIP call) -> entry tables -> parameters -> route buffers -> launch + passes -> route record -> close ----
 namespace {
 
+// Shard `index` of `count` takes rays [first, first + n) of a crystal entry's share: the share is cut in units of `clock` rays (the rays of one
+// sampled shape; 1 for a fixed one), u = ceil(share / clock) of them, and the shard gets units [floor(index * u / count), floor((index + 1) * u / count)) —
+// the last unit may be short.  Every shard gets a part of every entry, the parts differ by at most one unit, no unit is cut.
+void shard_slice(uint64_t share, uint32_t clock, uint32_t index, uint32_t count, uint64_t* first, uint64_t* n) {
+  typedef unsigned __int128 u128;
+  const u128 c = clock ? clock : 1u, u = (static_cast<u128>(share) + c - 1u) / c;
+  const u128 lo = std::min<u128>(c * (static_cast<u128>(index) * u / count), share), hi = std::min<u128>(c * ((static_cast<u128>(index) + 1u) * u / count), share);
+  *first = static_cast<uint64_t>(lo);
+  *n = static_cast<uint64_t>(hi - lo);
+}
+
 // What the launches of one halo_trace_layer call share.
 struct LayerCtx {
   int layer = 0, out_slot = 0;
   uint32_t source = kSrcGen, out_cap = 0;
   uint64_t n = 0;
+  uint64_t traced = 0;   // the roots this handle launched: n, or its slices of them (halo_set_shard)
   const HaloHostRays* rays = nullptr;
   // host_crystal — HostRayBatch::crystal (trace_backend.hpp:230-239): injected rays may bring the crystal they were sampled on; it is traced as it
   // is — one shape for the whole batch, no draw from the shape stream, no stochastic sample counted (test_cpu_trace_backend.cpp:737-777)
@@ -1803,6 +1831,11 @@ int fix_prepare(HaloBackend* b, uint64_t m) {
   }
   b->fix_hits += m;
   if (fl != b->fix_frac_landed) {
+    // (a shard's own landed integer is a part of the whole and leaves as the integer it is: converted here it would stay behind on this handle.
+    //  What halo_import_fixed brought in is whole, and goes to landed_carry exactly as one handle's own integer does)
+    if (b->shard_count > 1 && b->landed_own)
+      return fail(b, HALO_FATAL, "shard " + std::to_string(b->shard_index) + " of " + std::to_string(b->shard_count) +
+                                     ": this session's weights change the scale of the landed integer (F_landed) while the shard still holds landed weight of its own; move it out with halo_export_fixed first");
     if (int rc = join_aux(b)) return rc;
     double now[kSumNum];
     unsigned long long fix_now = 0ull;
@@ -1898,14 +1931,69 @@ int trace_launch(HaloBackend* b, const LayerCtx& c, LaunchPlan& p, EntryTables& 
   b->gate_count += m;
   return HALO_OK;
 }
+// The launch loop of a shard (halo_set_shard count > 1; one layer, generated roots): the whole layer's plan is walked and the counters — root, gate
+// and shape streams — move on by every planned launch as they do on one rank, but only the part of a launch inside this shard's slice of its crystal
+// entry is queued, as a launch of its own that keeps the bases it has in the whole run: stream counters at its first ray, the shape stream at its
+// first shape, `off` and `share` of the entry (the spectrum blocks), `first` within the layer (HaloExitRecord::root).  A trace kernel reads shape
+// tid / geom_clock of ITS launch, so a part must start on a shape of its planned launch: slices start at clock multiples within the entry, planned
+// launches start at multiples of the chunk — a sampled entry whose launches do not start on shapes is refused, before anything is queued.
+int trace_shard(HaloBackend* b, LayerCtx& c, std::vector<LaunchPlan>& plans, const std::vector<uint64_t>& per_ci) {
+  for (const LaunchPlan& p : plans)
+    if (!p.deterministic && p.off % b->geom_clock != 0u)
+      return fail(b, HALO_FATAL, "halo_set_shard count > 1: a sampled crystal entry is cut into launches (chunk, stoch_chunk) that are not multiples of geom_clock; a shard cannot start inside a sampled shape");
+  // (checked here, before a counter has moved; fix_prepare holds the same line for every launch)
+  if (b->det_session && b->landed_own && fix_frac_bits(b->sess_max_w, kFixLandedHits) != b->fix_frac_landed)
+    return fail(b, HALO_FATAL, "shard " + std::to_string(b->shard_index) + " of " + std::to_string(b->shard_count) +
+                                   ": this session's weights change the scale of the landed integer (F_landed) while the shard still holds landed weight of its own; move it out with halo_export_fixed first");
+  EntryTables T;
+  DispatchParams P{};
+  int cur = -1;
+  c.traced = 0;
+  for (const LaunchPlan& whole : plans) {
+    uint64_t s0 = 0, sn = 0;
+    shard_slice(per_ci[static_cast<size_t>(whole.ci)], whole.deterministic ? 1u : b->geom_clock, b->shard_index, b->shard_count, &s0, &sn);
+    const uint64_t lo = std::max(whole.off, s0), hi = std::min(whole.off + whole.m, s0 + sn);
+    const uint64_t gen0 = b->gen_count, gate0 = b->gate_count, shape0 = b->shape_count;
+    if (lo < hi) {
+      LaunchPlan p = plan_launch(*b, c, whole.ci, whole.first - whole.off, lo, hi - lo);   // (hi - lo <= whole.m: one launch)
+      p.share = whole.share;
+      b->gen_count = gen0 + (lo - whole.off);
+      b->gate_count = gate0 + (lo - whole.off);
+      if (!whole.deterministic) b->shape_count = shape0 + (lo - whole.off) / b->geom_clock;
+      if (p.ci != cur) {
+        cur = p.ci;
+        prepare_entry_tables(b, c, cur, T);
+        P = fill_params(b, c, cur);
+      }
+      // (trace_launch may first fold pending planes whose budget or scale is spent — fix_prepare: imported ones, which are whole, fold; the
+      //  shard's own are refused)
+      if (int rc = trace_launch(b, c, p, T, P)) return rc;
+      b->fix_imported = false;   // what is pending from here on is, at least in part, this shard's own
+      b->landed_own = b->det_session;
+      c.traced += p.m;
+    }
+    b->gen_count = gen0 + whole.m;
+    b->gate_count = gate0 + whole.m;
+    if (!whole.deterministic) b->shape_count = shape0 + whole.shape_cnt;
+  }
+  if (b->det_session && !(b->mono_dirty && b->fix_planes)) {
+    // nothing of this shard's is in the planes (empty slices): they are pending all the same — all zero, at the session's scales — so that the shard
+    // exports like every other
+    if (int rc = fix_prepare(b, 0)) return rc;
+    b->mono_dirty = true;
+    b->fix_planes = true;
+    b->fix_imported = false;
+  }
+  return HALO_OK;
+}
 // The end of a layer: counters, shard fill counts and the error word come back, the next layer's segment table and the statistics are made.
 int close_layer(HaloBackend* b, const LayerCtx& c, bool defer, HaloLayerStats* stats) {
   const uint64_t n = c.n;
   if (defer) {  // queued, not waited for: the tallies arrive through halo_collect_stats
-    b->layer_acc.root_count += n;
+    b->layer_acc.root_count += c.traced;
     if (stats) {
       std::memset(stats, 0, sizeof(*stats));
-      stats->root_count = n;
+      stats->root_count = c.traced;
     }
     b->cont_in_n = 0;
     return HALO_OK;
@@ -1940,7 +2028,7 @@ int close_layer(HaloBackend* b, const LayerCtx& c, bool defer, HaloLayerStats* s
     b->cont_roots = n;
   }
   b->exits_pending = std::min<uint64_t>(cnt[kCntExit], b->exits.cap);
-  b->layer_acc.root_count = n;
+  b->layer_acc.root_count = c.traced;
   b->layer_acc.continuation_count = n_cont;
   if (stats) *stats = b->layer_acc;
   add_stats(b->pending, b->layer_acc);
@@ -1959,10 +2047,11 @@ int halo_trace_layer(halo_handle_t b, uint64_t count, const HaloHostRays* rays, 
   if (layer >= b->scene.layer_count) return fail(b, HALO_FATAL, "TraceLayer past the last layer");
   HIPCHK(b, hipSetDevice(b->device));
   const HaloLayer& L = b->scene.layers[layer];
-  const uint64_t n = c.n = (layer == 0) ? count : b->cont_in_n;
+  const uint64_t n = c.n = c.traced = (layer == 0) ? count : b->cont_in_n;
   c.final_layer = (layer == b->scene.layer_count - 1);
   if (n > 0xFFFFFFF0ull) return fail(b, HALO_FATAL, "more than 2^32 rays in one layer dispatch; split the batch");
   if (layer > 0 && rays) return fail(b, HALO_FATAL, "host rays are first-layer only");
+  if (rays && b->shard_count > 1) return fail(b, HALO_FATAL, "halo_set_shard count > 1: host-injected rays are not supported (a shard generates its slice of the session's roots)");
   if (rays && rays->crystal) {   // an injected crystal is copied into fixed-size device tables: its counts and indices are the caller's, check them
     const HaloGeomTables& g = *rays->crystal;
     if (g.face_cnt < 0 || g.face_cnt > HALO_MAX_FACES || g.tri_cnt < 0 || g.tri_cnt > HALO_MAX_TRIS)   // (0 faces = the empty crystal: its rays carry no weight)
@@ -2056,6 +2145,10 @@ int halo_trace_layer(halo_handle_t b, uint64_t count, const HaloHostRays* rays, 
   DispatchParams P{};
   int cur = -1;
   if (plans.size() == 1u) plans[0].only = c.final_layer;
+  if (b->shard_count > 1) {
+    if (int rc = trace_shard(b, c, plans, per_ci)) return rc;
+    return close_layer(b, c, defer, stats);
+  }
   for (LaunchPlan& p : plans) {
     if (p.ci != cur) {
       cur = p.ci;
@@ -2354,6 +2447,92 @@ int halo_peek_fixed(halo_handle_t b, int32_t plane, uint64_t* sums, uint64_t n_p
     *landed = fix_now - b->fix_landed_seen;
   }
   if (landed_frac_bits) *landed_frac_bits = b->fix_frac_landed;
+  return HALO_OK;
+}
+
+int halo_set_shard(halo_handle_t b, uint32_t index, uint32_t count) {
+  if (!b) return HALO_FATAL;
+  if (b->in_session) return fail(b, HALO_FATAL, "halo_set_shard inside a session");
+  if (count == 0u || index >= count) return fail(b, HALO_FATAL, "halo_set_shard: index " + std::to_string(index) + " outside count " + std::to_string(count) + " (needs count >= 1 and index < count)");
+  if (count > 1u && b->rank_opt != 0) return fail(b, HALO_FATAL, "halo_set_shard count > 1: option rank is set (shards trace the one-rank run's rays: they share its counter range)");
+  b->shard_index = index;
+  b->shard_count = count;
+  return HALO_OK;
+}
+
+int halo_host_shard_slice(uint64_t share, uint32_t clock, uint32_t index, uint32_t count, uint64_t* first, uint64_t* n) {
+  if (!first || !n || clock == 0u || count == 0u || index >= count) return HALO_FATAL;
+  shard_slice(share, clock, index, count, first, n);
+  return HALO_OK;
+}
+
+// What halo_export_fixed and halo_import_fixed ask of the handle: its last session was a deterministic one, on the backend's own accumulator.
+static int fixed_layout_check(HaloBackend* b, const char* who, uint64_t n_words) {
+  if (b->in_session) return fail(b, HALO_FATAL, std::string(who) + " inside a session");
+  if (!b->det_session || !b->fix.ptr || !b->acc || b->acc != b->acc_own.ptr)
+    return fail(b, HALO_FATAL, std::string(who) + ": the handle's last session was not a deterministic one on the backend's own accumulator");
+  const uint64_t want = static_cast<uint64_t>(b->plane_cnt) * static_cast<uint64_t>(b->acc_w) * static_cast<uint64_t>(b->acc_h) + 1u;
+  if (n_words != want)
+    return fail(b, HALO_FATAL, std::string(who) + ": n_words " + std::to_string(n_words) + " is not plane_cnt * width * height + 1 = " + std::to_string(want) + " of the handle's last session (image size or plane count differ)");
+  return HALO_OK;
+}
+
+int halo_export_fixed(halo_handle_t b, void* dev_words, uint64_t n_words, uint32_t* plane_cnt, uint32_t* frac_bits, uint32_t* landed_frac_bits) {
+  if (!b) return HALO_FATAL;
+  if (!dev_words) return fail(b, HALO_FATAL, "halo_export_fixed: dev_words is NULL");
+  if (b->in_session) return fail(b, HALO_FATAL, "halo_export_fixed inside a session");
+  if (!b->mono_dirty || !b->fix_planes || b->acc != b->acc_own.ptr)
+    return fail(b, HALO_FATAL, "halo_export_fixed: no fixed-point planes are pending (needs deterministic = 1, lazy_fold = 1 and the backend's own accumulator, after halo_end and before any reader)");
+  if (int rc = fixed_layout_check(b, "halo_export_fixed", n_words)) return rc;
+  HIPCHK(b, hipSetDevice(b->device));
+  if (int rc = join_aux(b)) return rc;   // the copy runs on the backend's stream, behind everything that adds to the planes
+  double now[kSumNum];
+  unsigned long long fix_now = 0ull;
+  if (int rc = read_tally(b, now, &fix_now)) return rc;   // (waits for the device)
+  const uint32_t npix = static_cast<uint32_t>(b->acc_w) * static_cast<uint32_t>(b->acc_h);
+  hipError_t e = launch_export_fixed(b->fix.ptr, static_cast<unsigned long long*>(dev_words), npix, b->mono_s_log2, b->plane_cnt, fix_now - b->fix_landed_seen, b->stream);
+  if (e != hipSuccess) return hip_fail(b, e, "halo_export_fixed_kernel launch");
+  HIPCHK(b, hipStreamSynchronize(b->stream));   // the words are the caller's from here on, whatever stream it reads them on
+  b->fix_landed_seen = fix_now;   // taken: nothing is counted twice
+  b->landed_own = false;
+  // (landed_carry — landed weight converted to a double when F_landed changed — stays with the handle and goes to its next taker: on a shard it
+  //  can only come from imported words, fix_prepare sees to that, so it is weight of the whole image on the handle that folds it)
+  if (plane_cnt) *plane_cnt = b->plane_cnt;
+  if (frac_bits) *frac_bits = b->fix_frac;
+  if (landed_frac_bits) *landed_frac_bits = b->fix_frac_landed;
+  b->fix_hits = 0;
+  b->fix_planes = false;
+  b->fix_imported = false;
+  b->mono_dirty = false;
+  return HALO_OK;
+}
+
+int halo_import_fixed(halo_handle_t b, const void* dev_words, uint64_t n_words, uint32_t plane_cnt, uint32_t frac_bits, uint32_t landed_frac_bits, uint64_t rays) {
+  if (!b) return HALO_FATAL;
+  if (!dev_words) return fail(b, HALO_FATAL, "halo_import_fixed: dev_words is NULL");
+  if (b->mono_dirty && !b->fix_planes) return fail(b, HALO_FATAL, "halo_import_fixed: float planes are pending (fold them first: halo_flush)");
+  if (b->det_session && plane_cnt != b->plane_cnt)
+    return fail(b, HALO_FATAL, "halo_import_fixed: plane count " + std::to_string(plane_cnt) + " is not the " + std::to_string(b->plane_cnt) + " of the handle's last session");
+  if (int rc = fixed_layout_check(b, "halo_import_fixed", n_words)) return rc;
+  if (frac_bits != b->fix_frac) return fail(b, HALO_FATAL, "halo_import_fixed: frac_bits (F) " + std::to_string(frac_bits) + " is not the handle's " + std::to_string(b->fix_frac));
+  if (landed_frac_bits != b->fix_frac_landed)
+    return fail(b, HALO_FATAL, "halo_import_fixed: landed_frac_bits (F_landed) " + std::to_string(landed_frac_bits) + " is not the handle's " + std::to_string(b->fix_frac_landed));
+  const uint64_t held = b->mono_dirty ? b->fix_hits : 0u;
+  if (rays > kFixBudgetHits || held + rays > kFixBudgetHits)
+    return fail(b, HALO_FATAL, "halo_import_fixed: " + std::to_string(held) + " + " + std::to_string(rays) + " rays would pass the budget of 2^30 rays of one unfolded plane set");
+  HIPCHK(b, hipSetDevice(b->device));
+  if (int rc = join_aux(b)) return rc;   // behind everything that adds to (or folds) the planes; what follows waits for the main stream
+  const uint32_t npix = static_cast<uint32_t>(b->acc_w) * static_cast<uint32_t>(b->acc_h);
+  hipError_t e = launch_import_fixed(b->fix.ptr, static_cast<const unsigned long long*>(dev_words), npix, b->mono_s_log2, b->plane_cnt, b->stream);
+  if (e != hipSuccess) return hip_fail(b, e, "halo_import_fixed_kernel launch");
+  unsigned long long landed = 0ull;
+  HIPCHK(b, hipMemcpyAsync(&landed, static_cast<const unsigned long long*>(dev_words) + (n_words - 1u), sizeof(landed), hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(b, hipStreamSynchronize(b->stream));
+  b->fix_landed_seen -= landed;   // untaken landed integer = device tally - seen (modulo 2^64): the word joins it
+  b->fix_imported = !b->mono_dirty || b->fix_imported;   // (own pending planes stay a part: still not to be folded)
+  b->fix_hits = held + rays;
+  b->fix_planes = true;
+  b->mono_dirty = true;
   return HALO_OK;
 }
 

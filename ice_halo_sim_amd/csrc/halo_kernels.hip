@@ -947,6 +947,64 @@ __global__ void __launch_bounds__(kBlock) halo_fold_fixed_kernel(float* __restri
   fold_store_tile<R>(tile, xyz, n_pix, s_log2, row0, col0);
 }
 
+// Moving the fixed-point planes between handles (halo_export_fixed / halo_import_fixed): `words` is pixel order, plane p at [p * n_pix, (p + 1) * n_pix);
+// the planes lie [plane][MonoSlot(pix)].  A thread takes V consecutive words (V = 2: one 16-byte access on the pixel-order side, when `words` is
+// 16-byte aligned), so that side is coalesced; the plane side is a gather / scatter of 8-byte words through the slot hash — consecutive pixels are a
+// plane row apart, by design (halo_device.h MonoSlot).  Grid-stride; word indices are 64-bit (3 planes of 2^25 pixels stay below 2^32, the products do not).
+template <uint32_t V>
+__global__ void __launch_bounds__(kBlock) halo_export_fixed_kernel(unsigned long long* __restrict__ planes, unsigned long long* __restrict__ words, uint32_t n_pix,
+                                                                    uint32_t s_log2, uint32_t n_planes, unsigned long long landed) {
+  const uint64_t total = static_cast<uint64_t>(n_pix) * n_planes;
+  const size_t plane = static_cast<size_t>(kMonoRows) << s_log2;
+  const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock * V;
+  for (uint64_t i = (static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x) * V; i < total; i += stride) {
+    unsigned long long v[V];
+#pragma unroll
+    for (uint32_t u = 0; u < V; ++u) {
+      v[u] = 0ull;
+      if (i + u < total) {
+        const uint32_t pl = static_cast<uint32_t>((i + u) / n_pix), pix = static_cast<uint32_t>((i + u) - static_cast<uint64_t>(pl) * n_pix);
+        unsigned long long* q = planes + static_cast<size_t>(pl) * plane + MonoSlot(pix, s_log2);
+        v[u] = *q;
+        if (v[u] != 0ull) *q = 0ull;   // moved out: the planes are all-zero afterwards, as after a fold
+      }
+    }
+    if (V == 2u && i + 1u < total) {
+      *reinterpret_cast<ulonglong2*>(words + i) = make_ulonglong2(v[0], v[V - 1u]);
+    } else {
+#pragma unroll
+      for (uint32_t u = 0; u < V; ++u)
+        if (i + u < total) words[i + u] = v[u];
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) words[total] = landed;   // the landed integer nobody has taken yet, behind the planes
+}
+// ... and back in: planes[plane][MonoSlot(pix)] += words[plane * n_pix + pix], modulo 2^64.  Plain read-modify-writes: every slot has one word, and
+// the launch is ordered behind everything that adds to the planes (halo_import_fixed).
+template <uint32_t V>
+__global__ void __launch_bounds__(kBlock) halo_import_fixed_kernel(unsigned long long* __restrict__ planes, const unsigned long long* __restrict__ words, uint32_t n_pix,
+                                                                    uint32_t s_log2, uint32_t n_planes) {
+  const uint64_t total = static_cast<uint64_t>(n_pix) * n_planes;
+  const size_t plane = static_cast<size_t>(kMonoRows) << s_log2;
+  const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock * V;
+  for (uint64_t i = (static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x) * V; i < total; i += stride) {
+    unsigned long long v[V];
+    if (V == 2u && i + 1u < total) {
+      const ulonglong2 t = *reinterpret_cast<const ulonglong2*>(words + i);
+      v[0] = t.x, v[V - 1u] = t.y;
+    } else {
+#pragma unroll
+      for (uint32_t u = 0; u < V; ++u) v[u] = i + u < total ? words[i + u] : 0ull;
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < V; ++u) {
+      if (v[u] == 0ull) continue;   // (also every word past the end)
+      const uint32_t pl = static_cast<uint32_t>((i + u) / n_pix), pix = static_cast<uint32_t>((i + u) - static_cast<uint64_t>(pl) * n_pix);
+      planes[static_cast<size_t>(pl) * plane + MonoSlot(pix, s_log2)] += v[u];
+    }
+  }
+}
+
 // Consumer fold: running image += drained accumulator, Neumaier-compensated (accum_shared.h:70-74), accumulator zeroed.
 __global__ void __launch_bounds__(kBlock) halo_consumer_fold_kernel(float* __restrict__ acc, float* __restrict__ sum,
                                                                      float* __restrict__ comp, uint32_t n) {
@@ -1189,6 +1247,31 @@ hipError_t launch_fold_fixed(float* xyz, unsigned long long* planes, uint32_t n_
     hipLaunchKernelGGL(halo_fold_fixed_kernel<16u>, dim3(tiles_c * (kMonoRows / 16u)), dim3(kBlock), 0, stream, xyz, planes, n_pix, s_log2, n_planes, coef, frac_bits);
   else
     hipLaunchKernelGGL(halo_fold_fixed_kernel<4u>, dim3(tiles_c * (kMonoRows / 4u)), dim3(kBlock), 0, stream, xyz, planes, n_pix, s_log2, n_planes, coef, frac_bits);
+  return hipGetLastError();
+}
+
+// (memory-bound copies: one workgroup per kBlock * V words up to eight per CU, the rest by the grid stride)
+static uint32_t fixed_copy_blocks(uint64_t total, uint32_t v) {
+  const uint64_t want = (total + static_cast<uint64_t>(kBlock) * v - 1u) / (static_cast<uint64_t>(kBlock) * v);
+  return static_cast<uint32_t>(std::min<uint64_t>(std::max<uint64_t>(want, 1u), 2048u));
+}
+hipError_t launch_export_fixed(unsigned long long* planes, unsigned long long* words, uint32_t n_pix, uint32_t s_log2, uint32_t n_planes, unsigned long long landed,
+                               hipStream_t stream) {
+  if (n_planes == 0u || n_planes > kFixPlanesMax || n_pix == 0u || (static_cast<uint64_t>(kMonoRows) << s_log2) < n_pix) return hipErrorInvalidValue;
+  const uint64_t total = static_cast<uint64_t>(n_pix) * n_planes;
+  if ((reinterpret_cast<uintptr_t>(words) & 15u) == 0u)
+    hipLaunchKernelGGL(halo_export_fixed_kernel<2u>, dim3(fixed_copy_blocks(total, 2u)), dim3(kBlock), 0, stream, planes, words, n_pix, s_log2, n_planes, landed);
+  else
+    hipLaunchKernelGGL(halo_export_fixed_kernel<1u>, dim3(fixed_copy_blocks(total, 1u)), dim3(kBlock), 0, stream, planes, words, n_pix, s_log2, n_planes, landed);
+  return hipGetLastError();
+}
+hipError_t launch_import_fixed(unsigned long long* planes, const unsigned long long* words, uint32_t n_pix, uint32_t s_log2, uint32_t n_planes, hipStream_t stream) {
+  if (n_planes == 0u || n_planes > kFixPlanesMax || n_pix == 0u || (static_cast<uint64_t>(kMonoRows) << s_log2) < n_pix) return hipErrorInvalidValue;
+  const uint64_t total = static_cast<uint64_t>(n_pix) * n_planes;
+  if ((reinterpret_cast<uintptr_t>(words) & 15u) == 0u)
+    hipLaunchKernelGGL(halo_import_fixed_kernel<2u>, dim3(fixed_copy_blocks(total, 2u)), dim3(kBlock), 0, stream, planes, words, n_pix, s_log2, n_planes);
+  else
+    hipLaunchKernelGGL(halo_import_fixed_kernel<1u>, dim3(fixed_copy_blocks(total, 1u)), dim3(kBlock), 0, stream, planes, words, n_pix, s_log2, n_planes);
   return hipGetLastError();
 }
 

@@ -41,6 +41,11 @@ hipError_t launch_fold(float* xyz, float* planes, uint32_t n_pix, uint32_t s_log
                        double* ovf, const uint32_t* ovf_flag, hipStream_t stream);
 hipError_t launch_fold_fixed(float* xyz, unsigned long long* planes, uint32_t n_pix, uint32_t s_log2, uint32_t n_planes, const FoldCoef& coef, uint32_t frac_bits,
                              hipStream_t stream);
+// (halo_export_fixed / halo_import_fixed: the fixed-point planes [plane][slot] out to / in from n_planes * n_pix words in pixel order; the export
+//  zeroes what it takes and writes `landed` as word n_planes * n_pix, the import adds modulo 2^64)
+hipError_t launch_export_fixed(unsigned long long* planes, unsigned long long* words, uint32_t n_pix, uint32_t s_log2, uint32_t n_planes, unsigned long long landed,
+                               hipStream_t stream);
+hipError_t launch_import_fixed(unsigned long long* planes, const unsigned long long* words, uint32_t n_pix, uint32_t s_log2, uint32_t n_planes, hipStream_t stream);
 hipError_t launch_consumer_fold(float* acc, float* sum, float* comp, uint32_t n, int blocks, hipStream_t stream);
 hipError_t launch_lane_hist(const double* lanes, uint32_t n_pix, const CompositeDev& cd, uint32_t shift, uint32_t bits, uint32_t prefix, uint32_t* hist, int blocks,
                             hipStream_t stream);

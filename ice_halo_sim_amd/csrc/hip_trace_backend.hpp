@@ -116,6 +116,26 @@ class HipTraceBackend {
     lane_data.assign(class_count_ * static_cast<size_t>(width_) * static_cast<size_t>(height_), 0.0f);
     if (class_count_) Check(halo_readback_class_lanes(h_, lane_data.data(), width_, height_, static_cast<int>(class_count_)));
   }
+  // Shards (halo_trace.h halo_set_shard): this backend is shard `index` of `count` of every session from here on — BeginSession / TraceLayer take the
+  // WHOLE session's ray count, the backend plans it as one rank would and launches its slice.  With SetDeterministic(true) the shard's integer planes
+  // leave through ExportFixed; the integer sum of all shards' words, imported into one backend (ImportFixed) that then reads back, is the one-rank
+  // image bit for bit.  Throws for what sharding refuses (a multi-layer scene, host rays, option "rank").
+  void SetShard(uint32_t index, uint32_t count) { Check(halo_set_shard(h_, index, count)); }
+  struct FixedLayout {
+    uint32_t plane_cnt = 0, frac_bits = 0, landed_frac_bits = 0;
+  };
+  // words the export of a session with `planes` planes writes: planes * W * H, then the landed integer
+  uint64_t FixedWords(uint32_t planes) const { return static_cast<uint64_t>(planes) * static_cast<uint64_t>(width_) * static_cast<uint64_t>(height_) + 1u; }
+  // MOVES the pending fixed-point planes and the untaken landed integer into n_words 64-bit words of DEVICE memory (pixel order, plane by plane)
+  FixedLayout ExportFixed(void* dev_words, uint64_t n_words) {
+    FixedLayout l;
+    Check(halo_export_fixed(h_, dev_words, n_words, &l.plane_cnt, &l.frac_bits, &l.landed_frac_bits));
+    return l;
+  }
+  // ADDS such words (device memory) into the planes of this backend's last deterministic session; `rays` = the rays they stand for
+  void ImportFixed(const void* dev_words, uint64_t n_words, const FixedLayout& l, uint64_t rays) {
+    Check(halo_import_fixed(h_, dev_words, n_words, l.plane_cnt, l.frac_bits, l.landed_frac_bits, rays));
+  }
   // multi-GPU drain from a C++ host: one ncclReduce of the accumulator onto `root`, the other ranks drained (halo_reduce_accumulator)
   void ReduceAccumulator(void* nccl_comm, int root, int this_rank) { Check(halo_reduce_accumulator(h_, nccl_comm, root, this_rank)); }
   double TakeLanded() {

@@ -9,6 +9,8 @@ import time
 
 import numpy as np
 
+from .abi import FIX_BUDGET_RAYS   # rays one unfolded fixed-point plane set takes (halo_trace.h, option "deterministic")
+
 
 def shard_range(total, rank, world):
     """Contiguous split of `total` root rays: rank r gets [start, start+count); counts differ by at most one."""
@@ -266,3 +268,109 @@ class ShardedTracer:
             return None
         self.backend.LoadClassLanes(lanes, tot)
         return self.backend.CompositeColorClasses(classes, mode, display_exposure_scale, intensity_factor)
+
+
+class ExactShardedTracer:
+    """One rank of a DETERMINISTIC job whose image does not depend on the number of ranks: every rank is shard `rank` of `world` of every
+    session (HipTraceBackend.set_shard: the whole session is planned on every rank, each launches its slice of the same rays), the ranks'
+    64-bit fixed-point planes are summed as integers — sums that no order changes — and rank 0 folds the sum where one rank would have
+    folded its own planes.  N ranks on one box, on several, or N handles on one GPU then leave the XYZ bytes and landed weight of ONE rank.
+
+    One rank (option lazy_fold, the default) folds its pending planes (1) before a session whose wavelength (or spectrum table) or image size
+    differ from the previous session's, (2) before a session with which the planes would pass 2^30 rays and (3) when the image is read.
+    exchange() runs at exactly those points: export into a torch.int64 device tensor, all_reduce(SUM) (gloo and RCCL both sum int64; gloo on
+    one device is the rehearsal), then import + flush on rank 0.  The other ranks keep nothing.  Single-layer scenes without host rays
+    (what sharding refuses is refused with the engine's message).
+
+    PRECONDITION of point (2): one rank folds before the first LAUNCH that would pass the budget, this class exchanges before the SESSION.
+    The two are the same point when a session is one launch (one crystal entry, at most `chunk` rays) or when the sessions' sizes divide 2^30
+    (the CLI's 2^26-ray dispatches).  A session of several launches that straddles the budget would make one rank fold between two of its
+    launches: trace_session refuses it (ValueError) rather than fold somewhere else in silence.
+
+    Sessions of different weights may give the landed integer another scale (F_landed: 27 for weights up to 1, 28 for 0.8, 26 for 2): the
+    wavelength's weight is part of the session key, so an exchange always lies between two scales, rank 0 converts the imported integer
+    exactly where one rank converts its own, and the landed weight comes out bit for bit as well."""
+
+    def __init__(self, scene, render, seed=42, device=0, rank=0, world=1, ray_base=None, group=None, **options):
+        import torch
+        from .backend import HipTraceBackend
+        self.torch = torch
+        self.scene, self.render = scene, render
+        self.rank, self.world, self.group = int(rank), int(world), group
+        self.device = torch.device("cuda", device)
+        self._chunk = options.get("chunk", options.get("stoch_chunk"))   # (a caller that sets its own chunking gets no "one launch" shortcut)
+        self.backend = HipTraceBackend(device=device, seed=seed, **options)
+        self.backend.set_option("deterministic", 1)
+        if ray_base is not None:
+            self.backend.set_option("ray_base", ray_base)
+        self.backend.set_shard(self.rank, self.world)           # (no option "rank": the shards share the one-rank run's counter range)
+        self.backend.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
+        self._key = None          # what the pending planes were traced for
+        self._rays = 0            # whole-session rays since the last exchange
+        self.exchanges = 0
+
+    def _session_key(self, wl):
+        one = lambda w: (float(w.wavelength), float(w.weight), int(w.illuminant), int(w.pool_size))
+        spec = tuple(one(w) for w in wl) if isinstance(wl, (list, tuple)) else one(wl)
+        return spec, int(self.render.width), int(self.render.height)
+
+    def _one_launch(self, n_total):
+        """the session is ONE planned launch: one crystal entry and no more rays than the default chunk (2^28; 2^26 for sampled shapes)"""
+        L = self.scene.layers[0]
+        if L.entry_count != 1 or self._chunk is not None:
+            return False
+        c = L.entries[0].crystal
+        fixed = all(d.type == 0 for d in list(c.height) + list(c.face_dist))
+        return n_total <= ((1 << 28) if fixed else (1 << 26))
+
+    def trace_session(self, wl, n_total):
+        """One session of `n_total` roots IN ALL (every rank passes the same count); `wl` is an abi.HaloWl or, for a spectrum session, a
+        sequence of discrete ones.  COLLECTIVE when an exchange is due.  Returns this rank's layer stats (root_count = its slices)."""
+        n_total = int(n_total)
+        if n_total > FIX_BUDGET_RAYS:
+            raise ValueError("a session of more than 2^30 rays cannot be merged exactly: split it")
+        key = self._session_key(wl)
+        if self._rays and key == self._key and self._rays + n_total > FIX_BUDGET_RAYS and self._rays < FIX_BUDGET_RAYS and not self._one_launch(n_total):
+            raise ValueError("a session of several launches (%d rays after %d since the last exchange) would straddle the 2^30-ray budget of one "
+                             "plane set: one rank folds between two of its launches; size the sessions so that they divide 2^30" % (n_total, self._rays))
+        if self._rays and (key != self._key or self._rays + n_total > FIX_BUDGET_RAYS):
+            self.exchange()
+        b = self.backend
+        if isinstance(wl, (list, tuple)):
+            b.BeginSpectrumSession(self.scene, self.render, wl, n_total)
+        else:
+            b.BeginSession(self.scene, self.render, wl, n_total)
+        try:
+            st = b.TraceLayer(n_total)
+        finally:
+            b.EndSession()
+        self._key = key
+        self._rays += n_total
+        return st
+
+    def exchange(self):
+        """COLLECTIVE: every rank's pending integer planes and landed integer leave it, are summed, and rank 0 folds the sum into its image."""
+        if not self._rays:
+            return
+        torch, b = self.torch, self.backend
+        words = torch.empty(b.fixed_words(), dtype=torch.int64, device=self.device)
+        planes, frac, frac_landed = b.export_fixed(words)
+        if self.world > 1:
+            import torch.distributed as dist
+            dist.all_reduce(words, op=dist.ReduceOp.SUM, group=self.group)   # int64 adds wrap: sums modulo 2^64, in any order
+        if self.rank == 0:
+            # (torch's default stream is stream 0, for which the backend keeps a stream of its own: the sum must be complete before the import reads
+            #  it — one host wait per exchange; import_fixed returns with the words read)
+            torch.cuda.current_stream(self.device).synchronize()
+            b.import_fixed(words, planes, frac, frac_landed, self._rays)
+            b.flush()
+        self._rays = 0
+        self._key = None
+        self.exchanges += 1
+
+    def readback(self):
+        """COLLECTIVE: (image float32[H, W, 3], landed weight) on rank 0 — the bytes one rank gives — and (None, 0.0) elsewhere."""
+        self.exchange()
+        if self.rank != 0:
+            return None, 0.0
+        return self.backend.ReadbackXyzAccum(self.render.width, self.render.height)

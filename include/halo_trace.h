@@ -327,8 +327,10 @@ const char* halo_last_error(halo_handle_t h);
  * caller's sessions (a plane value is float32(double(S) * 2^-F)), so a fixed seed and ray_base give the same bytes on every run.  Over several
  * layers this holds together with cont_order = 1.  F is the largest scale <= 32 at which 2^30 rays of the session's largest weight cannot wrap a
  * slot (halo_host_fixed_frac_bits: 29 for weights up to 1); a plane set that has taken 2^30 rays is folded before the next launch, at a launch
- * boundary — beyond that budget the image, not the sums of each fold, depends on chunk.  NOT covered: a multi-GPU run is reproducible per rank,
- * the collective's order is RCCL's.  REFUSED, by name, at halo_begin (nothing is ever run on
+ * boundary — beyond that budget the image, not the sums of each fold, depends on chunk.  ACROSS RANKS (halo_set_shard,
+ * halo_export_fixed, halo_import_fixed): N shards that export at points P, whose words are summed as integers and imported into one handle that then
+ * folds, leave the XYZ bytes and landed weight of one unsharded handle that folds (halo_flush) at the same points P, for sessions of at most 2^30
+ * rays between two points; a float reduce of per-rank images (halo_reduce_accumulator, dist.ShardedTracer) stays reproducible per rank only.  REFUSED, by name, at halo_begin (nothing is ever run on
  * a float route in silence): a multi-layer session without cont_order = 1, raypath-colour tables, capture_exits = 1, rehit_strategy = 0, a
  * filter that needs the generic filter kernels.  On the direct route every hit outside the pixel cache is a memory-side 64-bit integer atomic
  * (configs[1]'s step +62 %, a full-sky X/Y/Z session 5 x); launches of 2 Mi rays and more take the hit log's integer twins instead (see "hit_log":
@@ -463,6 +465,45 @@ int halo_take_landed(halo_handle_t h, double* landed_weight);
  * deterministic sessions nobody has taken yet, in units of 2^-*landed_frac_bits.  Every out pointer may be NULL.  Folds, zeroes and takes
  * nothing.  HALO_FATAL when no fixed-point planes are pending. */
 int halo_peek_fixed(halo_handle_t h, int32_t plane, uint64_t* sums, uint64_t n_pix, uint32_t* frac_bits, uint64_t* landed, uint32_t* landed_frac_bits);
+
+/* --- shards: N handles (ranks, boxes, or handles on one GPU) trace ONE session's rays between them (additive in ABI 6, no struct changed) --- */
+/* Shard `index` of `count`; (0, 1) is the default and the whole of everything.  From then on halo_begin / halo_begin_spectrum / halo_trace_layer take
+ * the WHOLE session's ray_num / count: every shard runs the same partition with the same carry, walks the same plan of launches and moves its root,
+ * gate and shape counters on by the whole layer, exactly as one rank does — and launches only the part of each planned launch that lies in its
+ * slice of the launch's crystal entry (halo_host_shard_slice), with the counter bases, spectrum blocks and HaloExitRecord::root it has in the whole
+ * run.  The shards of a session trace exactly the one-rank session's rays, each once.  HaloLayerStats::root_count and halo_last_sample_counts
+ * report what the shard traced; a shard whose slices are empty launches nothing and still moves the counters.  With deterministic = 1 the shard's
+ * integer planes are a PART of the image: they leave through halo_export_fixed, and whatever would fold them — a readback, halo_flush,
+ * halo_take_landed, a halo_begin with other planes — is HALO_FATAL with a message that names halo_export_fixed (the handle stays usable).  With
+ * deterministic = 0 (capture_exits included) the shards trace the same rays and each folds its own float image: their sum differs from one rank's by
+ * summation order only.  REFUSED, by name, handle usable: inside a session; count == 0 or index >= count; and with count > 1 a multi-layer scene (at
+ * halo_begin: the next layer's pool order and shuffle are global over all roots), host-injected rays (at halo_trace_layer), option "rank" != 0,
+ * a sampled crystal entry whose launches ("chunk", "stoch_chunk") are not multiples of geom_clock (at halo_trace_layer, before anything is queued),
+ * and a launch whose session's weights change F_landed while the shard still holds landed weight of its own (export first: the integer leaves
+ * as an integer).  WHERE TO EXCHANGE so that the merged image is one handle's: wherever one handle folds — before a session with other planes
+ * (wavelength, spectrum, image size) or other weights, at every reader of the image, and before the LAUNCH with which the pending planes would pass
+ * 2^30 rays; a caller that exchanges between sessions must therefore not let a session of several launches straddle that budget. */
+int halo_set_shard(halo_handle_t h, uint32_t index, uint32_t count);
+/* The slice rule, no device needed: shard `index` of `count` takes rays [*first, *first + *n) of a crystal entry's share of `share` rays, cut in
+ * units of `clock` rays (geom_clock for an entry with sampled shapes, 1 for a fixed one): with u = ceil(share / clock),
+ * [clock * floor(index * u / count), min(clock * floor((index + 1) * u / count), share)).  Disjoint, in index order, covering the share, starting at
+ * clock multiples, sizes within one clock of each other.  HALO_FATAL for clock == 0, count == 0, index >= count or a NULL pointer. */
+int halo_host_shard_slice(uint64_t share, uint32_t clock, uint32_t index, uint32_t count, uint64_t* first, uint64_t* n);
+/* MOVE the pending fixed-point planes out, to device memory (preconditions of halo_peek_fixed: pending fixed-point planes, the backend's own
+ * accumulator, not inside a session): dev_words receives plane_cnt * W * H 64-bit words in pixel order — plane p at [p * W * H, (p + 1) * W * H),
+ * the slot hash undone by the kernel — and then ONE word, the landed integer nobody has taken yet; n_words must be plane_cnt * W * H + 1.  The planes
+ * are left all zero and no longer pending and the landed integer is taken: nothing is counted twice.  *plane_cnt, *frac_bits (F) and
+ * *landed_frac_bits (F_landed) describe the words (each may be NULL).  Waits for the device; the words are complete when it returns.  A shard that
+ * ended a session without tracing a ray exports zeros.  Landed weight that was converted to a double when F_landed changed between sessions
+ * stays with the handle for its next taker (halo_take_landed, a readback): on a shard that is imported weight only — weight of the whole image, on
+ * the handle that folds it — exactly as one handle carries it. */
+int halo_export_fixed(halo_handle_t h, void* dev_words, uint64_t n_words, uint32_t* plane_cnt, uint32_t* frac_bits, uint32_t* landed_frac_bits);
+/* ADD such words (device memory; e.g. the integer sum of every shard's export) into the planes of the handle's last ended deterministic session,
+ * modulo 2^64, in stream order on the backend's stream; the planes become pending at that F, the landed word joins the handle's untaken landed
+ * integer, and `rays` — the rays the words stand for — count against the 2^30-ray budget of one unfolded plane set.  halo_flush and the readbacks
+ * then fold exactly as after the handle's own session.  REFUSED, by name: a layout that is not the handle's (plane count, image size via n_words,
+ * F, F_landed), a budget that would be passed, float planes pending, no deterministic session on the backend's own accumulator before it. */
+int halo_import_fixed(halo_handle_t h, const void* dev_words, uint64_t n_words, uint32_t plane_cnt, uint32_t frac_bits, uint32_t landed_frac_bits, uint64_t rays);
 
 /* Multi-GPU drain for a C/C++ host (one process — or one thread — per GPU, one backend per GPU): sum-reduce this rank's XYZ
  * accumulator (width*height*3+4 floats, owned or bound) onto rank `root` with ONE ncclReduce over RCCL/xGMI, queued on the

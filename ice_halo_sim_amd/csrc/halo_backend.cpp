@@ -54,11 +54,22 @@ template <typename... B>
 void release_all(B&... bufs) { (bufs.release(), ...); }
 
 // "The last work of kind X": an event recorded behind that work, and whether anything has been recorded on it yet (nothing: nobody need wait).
+// (Several markers that fall on one point of one stream share one recorded event: mark_at names an event somebody has just recorded there — a ring
+//  slot's — instead of recording the marker's own.  Should that event be recorded again before the marker is, the marker waits for the later point.)
 struct Marker {
   hipEvent_t ev = nullptr;
+  hipEvent_t at = nullptr;   // the event that carries the marker now: `ev`, or a shared one
   bool set = false;
-  hipError_t mark(hipStream_t s) { const hipError_t e = hipEventRecord(ev, s); set = set || e == hipSuccess; return e; }
-  hipError_t wait_on(hipStream_t s) const { return set ? hipStreamWaitEvent(s, ev, 0) : hipSuccess; }
+  hipError_t mark(hipStream_t s) {
+    const hipError_t e = hipEventRecord(ev, s);
+    if (e == hipSuccess) at = ev, set = true;
+    return e;
+  }
+  hipError_t mark_at(hipEvent_t shared) {
+    at = shared, set = true;
+    return hipSuccess;
+  }
+  hipError_t wait_on(hipStream_t s) const { return set ? hipStreamWaitEvent(s, at, 0) : hipSuccess; }
   void clear() { set = false; }
 };
 
@@ -104,6 +115,9 @@ struct HaloBackend {
   hipEvent_t ev_cs[2] = {nullptr, nullptr}, ev_main = nullptr, ev_aux = nullptr;
   bool cs_pending[2] = {false, false};
   int cs_next = 0;
+  bool main_dirty[2] = {true, true};    // the main stream has been given work (main_q) since trace stream i last waited for it
+  int lean_events = 1;                  // option: 1 = one recorded event where several markers fall on one point of a stream, no hop from a main stream
+                                        // that holds nothing new (queue_passes, next_trace_stream); 0 = every marker its own record, every launch the hop
   uint64_t aux_seq = 0, cs_seen_aux[2] = {0, 0};   // (a trace stream waits for the auxiliary stream only when that holds work it has not waited for yet)
   int overlap = 1;                      // option: 0 queues the passes and folds on the main stream (round 4 behaviour)
   int defer_fold = 0;                   // option: 1 = halo_end leaves the fold pending even when the accumulator is the caller's memory; the caller asks for
@@ -211,6 +225,10 @@ struct HaloBackend {
   DevBuf<DispatchSlot> ring_dev;
   DispatchSlot* ring_host = nullptr;   // hipHostMalloc
   hipEvent_t ring_ev0[kRing] = {}, ring_ev1[kRing] = {}, ring_ev2[kRing] = {}, ring_ev3[kRing] = {}, ring_done[kRing] = {};   // ev0..ev1 the trace kernel (main stream), ev2..ev3 its passes (post stream)
+  // (the events that CARRY a slot's "passes begin" and "slot done" for its current launch: ring_ev2 / ring_done themselves, or — option
+  //  lean_events — the neighbour recorded at the same point of the same stream: ring_ev1 where no wait lies between it and the passes, ring_ev3
+  //  behind a direct close)
+  hipEvent_t ring_t2[kRing] = {}, ring_fin[kRing] = {};
   bool ring_posts[kRing] = {};
   bool ring_final[kRing] = {};         // the slot's launch belongs to its session's last layer (halo_collect_timing counts those)
   bool ring_busy[kRing] = {};
@@ -325,6 +343,11 @@ int hip_fail(HaloBackend* b, hipError_t e, const char* what) {
     if (e__ != hipSuccess) return hip_fail(b, e__, #call); \
   } while (0)
 
+// The main stream, for whoever queues work on it (or waits for it): the trace streams have not seen that work yet (next_trace_stream).
+inline hipStream_t main_q(HaloBackend* b) {
+  b->main_dirty[0] = b->main_dirty[1] = true;
+  return b->stream;
+}
 // The plane set the open / pending session adds to (HaloBackend::mono_two).
 inline float* planes_of(HaloBackend* b) { return b->mono.ptr + (b->mono_two ? static_cast<size_t>(b->mono_set) * b->mono_half : 0u); }
 // The stream the plane-touching passes of logged launches and the folds are queued on.
@@ -332,7 +355,7 @@ inline hipStream_t post_stream(HaloBackend* b) { return b->overlap ? b->aux : b-
 // What is queued on the auxiliary stream from here on runs behind everything the main stream and the trace streams hold now.
 int fork_aux(HaloBackend* b) {
   if (!b->overlap) return HALO_OK;
-  HIPCHK(b, hipEventRecord(b->ev_fork, b->stream));
+  HIPCHK(b, hipEventRecord(b->ev_fork, main_q(b)));
   HIPCHK(b, hipStreamWaitEvent(b->aux, b->ev_fork, 0));
   for (int k = 0; k < 2; k++)
     if (b->cs_pending[k]) {
@@ -347,13 +370,13 @@ int fork_aux(HaloBackend* b) {
 int join_aux(HaloBackend* b) {
   if (b->aux_pending) {
     HIPCHK(b, hipEventRecord(b->ev_join, b->aux));
-    HIPCHK(b, hipStreamWaitEvent(b->stream, b->ev_join, 0));
+    HIPCHK(b, hipStreamWaitEvent(main_q(b), b->ev_join, 0));   // (main_q: the trace streams reach this wait through their next hop)
     b->aux_pending = false;
   }
   for (int k = 0; k < 2; k++)
     if (b->cs_pending[k]) {
       HIPCHK(b, hipEventRecord(b->ev_cs[k], b->cs[k]));
-      HIPCHK(b, hipStreamWaitEvent(b->stream, b->ev_cs[k], 0));
+      HIPCHK(b, hipStreamWaitEvent(main_q(b), b->ev_cs[k], 0));
       b->cs_pending[k] = false;
       b->rmw[k].clear();   // (every later launch waits for the main stream, which now waits for these sums)
       if (b->close_ts == k) b->close_done.clear();   // ... and for this direct close
@@ -382,8 +405,13 @@ int next_trace_stream(HaloBackend* b, bool touches_planes, bool alternate, hipSt
   // from a neighbour and keeps stream 0, where its HIP events time it undisturbed.
   const int i = alternate ? b->cs_next : 0;
   if (alternate) b->cs_next ^= 1;
-  HIPCHK(b, hipEventRecord(b->ev_main, b->stream));
-  HIPCHK(b, hipStreamWaitEvent(b->cs[i], b->ev_main, 0));
+  // (the hop is for what the main stream has been given since this trace stream last waited for it — table uploads, counter resets: main_q.  With
+  //  nothing new there it orders nothing, and option lean_events leaves it out.  A caller's stream may hold work this backend never saw: always hopped.)
+  if (!b->lean_events || b->main_dirty[i] || b->stream != b->own_stream) {
+    HIPCHK(b, hipEventRecord(b->ev_main, b->stream));
+    HIPCHK(b, hipStreamWaitEvent(b->cs[i], b->ev_main, 0));
+    b->main_dirty[i] = false;
+  }
   if (touches_planes)
     if (int rc = wait_for_aux(b, i)) return rc;
   b->cs_pending[i] = true;
@@ -399,7 +427,7 @@ inline uint64_t log_min_rays(int visible) { return visible == HALO_VISIBLE_FULL 
 // Host waits for all streams.
 int sync_all(HaloBackend* b) {
   if (int rc = join_aux(b)) return rc;
-  HIPCHK(b, hipStreamSynchronize(b->stream));
+  HIPCHK(b, hipStreamSynchronize(main_q(b)));
   return HALO_OK;
 }
 // DevBuf::reserve frees the old allocation when it grows: nothing on either stream may still be using it.
@@ -442,7 +470,7 @@ int ensure_accumulator(HaloBackend* b, int w, int h) {
     if (int rc = join_aux(b)) return rc;   // (a fold of the old image may still be queued there)
     if (b->own_w != 0 || b->own_h != 0)
       if (int rc = forget_landed(b)) return rc;   // the old image goes, and its landed weight with it
-    HIPCHK(b, hipMemsetAsync(b->acc_own.ptr, 0, need * sizeof(float), b->stream));
+    HIPCHK(b, hipMemsetAsync(b->acc_own.ptr, 0, need * sizeof(float), main_q(b)));
     b->own_w = w;
     b->own_h = h;
   }
@@ -456,10 +484,10 @@ int ensure_accumulator(HaloBackend* b, int w, int h) {
 // take the timing of one finished ring slot (the tallies are cumulative device counters: pull_tally)
 void harvest_slot(HaloBackend* b, int k) {
   if (!b->ring_busy[k]) return;
-  (void)hipEventSynchronize(b->ring_done[k]);
+  (void)hipEventSynchronize(b->ring_fin[k]);
   float ms = 0.0f, ms2 = 0.0f;
   (void)hipEventElapsedTime(&ms, b->ring_ev0[k], b->ring_ev1[k]);
-  if (b->ring_posts[k]) (void)hipEventElapsedTime(&ms2, b->ring_ev2[k], b->ring_ev3[k]);   // the passes' own span
+  if (b->ring_posts[k]) (void)hipEventElapsedTime(&ms2, b->ring_t2[k], b->ring_ev3[k]);   // the passes' own span
   static const bool debug_timing = std::getenv("HALO_DEBUG_TIMING") != nullptr;
   if (debug_timing) std::fprintf(stderr, "[halo timing] slot %d final %d posts %d trace %.4f ms passes %.4f ms\n", k, int(b->ring_final[k]), int(b->ring_posts[k]), ms, ms2);
   // An event pair that reads backwards (seen once: two twelve-launch runs of one bench process summed to -10 ms; the rocprofv3 trace of the same
@@ -476,8 +504,8 @@ void harvest_slot(HaloBackend* b, int k) {
 }
 // Snapshot of the cumulative tallies (one 1 KB D2H copy + a stream sync): the sum over the lines, per tally.
 int read_tally(HaloBackend* b, double out[kSumNum], unsigned long long* fix_landed = nullptr) {
-  HIPCHK(b, hipMemcpyAsync(b->tally_host, b->tally.ptr, kTallyLines * kTallyStride * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-  HIPCHK(b, hipStreamSynchronize(b->stream));
+  HIPCHK(b, hipMemcpyAsync(b->tally_host, b->tally.ptr, kTallyLines * kTallyStride * sizeof(double), hipMemcpyDeviceToHost, main_q(b)));
+  HIPCHK(b, hipStreamSynchronize(main_q(b)));
   if (fix_landed) {   // the lines' integer slot (deterministic sessions), summed modulo 2^64
     *fix_landed = 0ull;
     for (uint32_t l = 0; l < kTallyLines; l++) {
@@ -591,8 +619,8 @@ int halo_create(int device_ordinal, uint32_t seed, halo_handle_t* out) {
     halo_destroy(b);  // releases the stream, the ring, the pinned mirrors and the events as well
     return HALO_UNAVAILABLE;
   }
-  (void)hipMemsetAsync(b->tally.ptr, 0, kTallyLines * kTallyStride * sizeof(double), b->stream);
-  (void)hipMemsetAsync(b->counters.ptr, 0, kCntNum * sizeof(uint32_t), b->stream);
+  (void)hipMemsetAsync(b->tally.ptr, 0, kTallyLines * kTallyStride * sizeof(double), main_q(b));
+  (void)hipMemsetAsync(b->counters.ptr, 0, kCntNum * sizeof(uint32_t), main_q(b));
   *out = b;
   return HALO_OK;
 }
@@ -600,7 +628,7 @@ int halo_create(int device_ordinal, uint32_t seed, halo_handle_t* out) {
 int halo_destroy(halo_handle_t b) {
   if (!b) return HALO_OK;
   (void)hipSetDevice(b->device);
-  (void)hipStreamSynchronize(b->stream);
+  (void)hipStreamSynchronize(main_q(b));
   if (b->aux) (void)hipStreamSynchronize(b->aux);
   for (int k = 0; k < 2; k++)
     if (b->cs[k]) (void)hipStreamSynchronize(b->cs[k]);
@@ -679,6 +707,7 @@ int halo_set_option(halo_handle_t b, const char* key, int64_t v) {
   else if (k == "auto_ev_select") b->aev_select = v < 0 ? -1 : (v ? 1 : 0);
   else if (k == "gen_ahead") b->gen_ahead = v ? 1 : 0;
   else if (k == "close_direct") b->close_direct = v < 0 ? -1 : (v ? 1 : 0);
+  else if (k == "lean_events") b->lean_events = v ? 1 : 0;
   else if (k == "tile_append") b->tile_append = v < 0 ? -1 : (v ? 1 : 0);
   else if (k == "pool_entry_fast") b->pool_entry_fast = v ? 1 : 0;
   else if (k == "rehit_strategy") {
@@ -738,6 +767,7 @@ int halo_set_stream(halo_handle_t b, void* s) {
   if (!b) return HALO_FATAL;
   (void)sync_all(b);
   b->stream = s ? static_cast<hipStream_t>(s) : b->own_stream;
+  b->main_dirty[0] = b->main_dirty[1] = true;   // another main stream: the trace streams have seen nothing of it
   return HALO_OK;
 }
 
@@ -930,7 +960,7 @@ static int begin_session(halo_handle_t b, const HaloScene* scene, const HaloRend
     b->mono_set = 0;
     if (b->fix.cap < need) {
       if (int rc = reserve_idle(b, b->fix, need)) return rc;
-      HIPCHK(b, hipMemsetAsync(b->fix.ptr, 0, b->fix.cap * sizeof(unsigned long long), b->stream));
+      HIPCHK(b, hipMemsetAsync(b->fix.ptr, 0, b->fix.cap * sizeof(unsigned long long), main_q(b)));
     }
     b->mono_s_log2 = s_log2;
   } else {
@@ -941,7 +971,7 @@ static int begin_session(halo_handle_t b, const HaloScene* scene, const HaloRend
     const size_t need = one * (b->mono_two ? 2u : 1u);
     if (b->mono.cap < need) {
       if (int rc = reserve_idle(b, b->mono, need)) return rc;
-      HIPCHK(b, hipMemsetAsync(b->mono.ptr, 0, b->mono.cap * sizeof(float), b->stream));
+      HIPCHK(b, hipMemsetAsync(b->mono.ptr, 0, b->mono.cap * sizeof(float), main_q(b)));
     }
     b->mono_s_log2 = s_log2;  // planes are all-zero whenever the layout changes (folded above), so it may change freely
     // the twin: one double per float of every plane's copy 0 (2.1 MB x planes at configs[1]'s image; a 64-plane session on 2048x1024 takes
@@ -953,9 +983,9 @@ static int begin_session(halo_handle_t b, const HaloScene* scene, const HaloRend
       hipError_t oe = hipSuccess;
       if (int rc = reserve_idle(b, b->ovf, 2u * twin_need, &oe)) return rc;
       bool ok = oe == hipSuccess;
-      if (ok && !b->ovf_flag.ptr) ok = b->ovf_flag.reserve(2) == hipSuccess && hipMemsetAsync(b->ovf_flag.ptr, 0, 2 * sizeof(uint32_t), b->stream) == hipSuccess;
+      if (ok && !b->ovf_flag.ptr) ok = b->ovf_flag.reserve(2) == hipSuccess && hipMemsetAsync(b->ovf_flag.ptr, 0, 2 * sizeof(uint32_t), main_q(b)) == hipSuccess;
       if (ok) {
-        HIPCHK(b, hipMemsetAsync(b->ovf.ptr, 0, b->ovf.cap * sizeof(double), b->stream));
+        HIPCHK(b, hipMemsetAsync(b->ovf.ptr, 0, b->ovf.cap * sizeof(double), main_q(b)));
       } else {
         (void)hipGetLastError();   // out of memory is not this session's failure: the launches run without a twin
         b->ovf.release();
@@ -968,7 +998,7 @@ static int begin_session(halo_handle_t b, const HaloScene* scene, const HaloRend
     if (b->lanes.cap < need || b->lanes_w != render->width || b->lanes_h != render->height) {
       if (int rc = reserve_idle(b, b->lanes, need)) return rc;
       if (int rc = join_aux(b)) return rc;
-      HIPCHK(b, hipMemsetAsync(b->lanes.ptr, 0, b->lanes.cap * sizeof(double), b->stream));
+      HIPCHK(b, hipMemsetAsync(b->lanes.ptr, 0, b->lanes.cap * sizeof(double), main_q(b)));
       b->lanes_w = render->width;
       b->lanes_h = render->height;
     }
@@ -1188,6 +1218,11 @@ int blocks_of(const HaloBackend& b, uint64_t m, bool pool) {
   // per-workgroup fixed costs (table staging, pixel-cache zero + flush) are paid per launch, a long tail is paid per
   // round of resident workgroups: aim at >= 32 passes of the ray loop per workgroup, between 4 and blocks_per_cu per CU
   // (measured: 1 M rays 0.27 -> 0.20 ms at 4/CU; 50 M rays 4.02 -> 3.67 ms at 24/CU instead of 8/CU)
+  // (Measured again on the per-tile-append kernel, six resident workgroups per CU, where every workgroup also leaves a chunk and a count per tile
+  //  for the closing pass: the trace kernel of configs[1] at 6 / 8 / 12 / 16 / 24 / 32 / 48 per CU 1.74 / 1.71 / 1.60 / 1.55 / 1.53 / 1.51 / 1.51 ms
+  //  (32 and 48 are capped by `want` like 24) — ONE round of resident workgroups ends with its slowest, 0.2 ms behind several rounds that even the
+  //  tail out — and that is four times what the closing pass gains from the longer chunks of the smaller grid (0.20 -> 0.14 ms at 6 per CU, 0.16
+  //  at 12): 24 stays, for these launches too.  profiles/resident_grid_ab.txt.)
   // Small launches — a Lumice server that keeps a GPU route's small dispatch (2^15 .. 2^18 rays per session, server.cpp:140-151) sends nothing
   // else — are latency: one pass of the ray loop is ~11 us on a wave that has its SIMD to itself, so they spread over as many workgroups as
   // a CU holds (five) before a workgroup takes a second pass.  (Round 4 had found the opposite — one per CU best — while every WAVE ended
@@ -1442,9 +1477,12 @@ int upload_tables(HaloBackend* b, const LayerCtx& c, const LaunchPlan& p, const 
   // shape (tests/test_gpu_production_routes.py::test_async_sessions_alternating_wavelengths).
   if (ce && ce->read_ring[ce->cur] >= 0) {
     const int rk = ce->read_ring[ce->cur];
-    if (b->ring_busy[rk] && b->ring_use[rk] == ce->read_use[ce->cur]) HIPCHK(b, hipStreamWaitEvent(b->stream, b->ring_done[rk], 0));
+    if (b->ring_busy[rk] && b->ring_use[rk] == ce->read_use[ce->cur]) {
+      HIPCHK(b, hipStreamWaitEvent(b->stream, b->ring_fin[rk], 0));
+      b->main_dirty[0] = b->main_dirty[1] = true;
+    }
   }
-  HIPCHK(b, hipMemcpyAsync(ds, &hs, T.fast_host ? sizeof(DispatchSlot) : offsetof(DispatchSlot, fast), hipMemcpyHostToDevice, b->stream));
+  HIPCHK(b, hipMemcpyAsync(ds, &hs, T.fast_host ? sizeof(DispatchSlot) : offsetof(DispatchSlot, fast), hipMemcpyHostToDevice, main_q(b)));
   if (ce) {   // the next dispatch of this entry — the layer's next chunk, the next equal session — finds the tables in place
     ce->valid = true, ce->mode = T.mode, ce->use_filter = T.use_filter, ce->use_color = T.use_color;
     ce->entry_fast = T.entry_fast, ce->hex_regular = T.hex_regular, ce->has_fast = T.has_fast;
@@ -1542,14 +1580,14 @@ int bind_route(HaloBackend* b, LaunchPlan& p, int ls, DispatchParams& P) {
   if (p.use_log) {
     if (int rc = reserve_idle(b, bin_cnt, std::max<size_t>(static_cast<size_t>(p.blocks), static_cast<size_t>(512) * 16u))) return rc;
     if (int rc = reserve_idle(b, bin_cnt2, static_cast<size_t>(512) * 16u)) return rc;
-    HIPCHK(b, b->set_free[ls].wait_on(b->stream));   // the passes of the launch that last wrote this set
+    HIPCHK(b, b->set_free[ls].wait_on(main_q(b)));   // the passes of the launch that last wrote this set
   } else if (p.use_bin) {
     if (int rc = reserve_idle(b, bin_cnt, static_cast<size_t>(512) * 16u)) return rc;
-    HIPCHK(b, hipMemsetAsync(bin_cnt.ptr, 0, static_cast<size_t>(p.two_level ? 512u : p.bin_tiles) * 16u * sizeof(uint32_t), b->stream));
+    HIPCHK(b, hipMemsetAsync(bin_cnt.ptr, 0, static_cast<size_t>(p.two_level ? 512u : p.bin_tiles) * 16u * sizeof(uint32_t), main_q(b)));
     if (int rc = reserve_idle(b, bin_list, p.cap1 * p.lists1)) return rc;
     if (p.two_level) {
       if (int rc = reserve_idle(b, bin_cnt2, static_cast<size_t>(p.bin_tiles) * 16u)) return rc;
-      HIPCHK(b, hipMemsetAsync(bin_cnt2.ptr, 0, static_cast<size_t>(p.bin_tiles) * 16u * sizeof(uint32_t), b->stream));
+      HIPCHK(b, hipMemsetAsync(bin_cnt2.ptr, 0, static_cast<size_t>(p.bin_tiles) * 16u * sizeof(uint32_t), main_q(b)));
       b->cnt2_clean[ls] = false;
       if (int rc = reserve_idle(b, bin_list2, p.cap2 * p.bin_tiles)) return rc;
     }
@@ -1688,6 +1726,7 @@ int queue_passes(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, c
     HIPCHK(b, hipEventRecord(b->ring_ev1[k], ts));
     b->ring_posts[k] = false;
     HIPCHK(b, hipEventRecord(b->ring_done[k], ts));
+    b->ring_fin[k] = b->ring_done[k];
     return HALO_OK;
   }
   // the accumulation passes of this launch: behind the trace kernel on its stream.  (Round 5 tried them on the auxiliary stream, under the
@@ -1700,7 +1739,28 @@ int queue_passes(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, c
       HIPCHK(b, b->set_folded[b->mono_set].wait_on(ps));
     } else if (int rc = wait_for_aux(b, ts_i)) return rc;
   }
-  HIPCHK(b, hipEventRecord(b->ring_ev2[k], ps));
+  // (nothing between ev1 and here unless the passes wait for a fold: one record serves as both, the spans stay the trace kernel's and the passes')
+  if (b->lean_events && !p.under_fold()) b->ring_t2[k] = b->ring_ev1[k];
+  else {
+    HIPCHK(b, hipEventRecord(b->ring_ev2[k], ps));
+    b->ring_t2[k] = b->ring_ev2[k];
+  }
+  // behind a direct close four markers fall on one point of the stream — the close, the end of the passes' span, the log set free again, the slot
+  // done: one record, ring_ev3, and the others name it
+  auto close_marks = [&]() -> hipError_t {
+    hipError_t e = hipEventRecord(b->ring_ev3[k], ps);
+    if (e != hipSuccess) return e;
+    if (b->lean_events) {
+      (void)b->close_done.mark_at(b->ring_ev3[k]);
+      (void)b->set_free[S.ls].mark_at(b->ring_ev3[k]);
+      b->ring_fin[k] = b->ring_ev3[k];
+      return hipSuccess;
+    }
+    if ((e = b->close_done.mark(ps)) != hipSuccess) return e;
+    if ((e = b->set_free[S.ls].mark(ps)) != hipSuccess) return e;
+    b->ring_fin[k] = b->ring_done[k];
+    return hipEventRecord(b->ring_done[k], ps);
+  };
   if (p.close && p.tile) {
     // the closing pass over the chunks the trace kernel filled: no split, no list counters; the twin's flag is cleared behind the pass as below
     const float coef[3] = {b->plane_coef[0][0], b->plane_coef[0][1], b->plane_coef[0][2]};
@@ -1709,13 +1769,21 @@ int queue_passes(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, c
     if (ce != hipSuccess) return hip_fail(b, ce, "halo_tile_close_kernel launch");
     b->direct_closes++;
     b->tile_appends++;
-    HIPCHK(b, b->close_done.mark(ps));
+    static const bool debug_counts = std::getenv("HALO_DEBUG_TILE_COUNTS") != nullptr;
+    if (debug_counts) {   // (a host sync per launch: what the chunks of this launch hold, for profiles/ — never on a timed path)
+      std::vector<uint32_t> cnt(static_cast<size_t>(P.tile_tiles) * static_cast<size_t>(p.blocks));
+      HIPCHK(b, hipStreamSynchronize(ps));
+      HIPCHK(b, hipMemcpy(cnt.data(), P.tile_cnt, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      uint64_t met = 0, over = 0, most = 0, empty = 0;
+      for (uint32_t c : cnt) met += c, over += c > P.tile_cap ? 1u : 0u, most = std::max<uint64_t>(most, c), empty += c == 0u ? 1u : 0u;
+      std::fprintf(stderr, "[halo tile counts] workgroups %d tiles %u cap %u chunks %zu records %llu per chunk %.1f longest %llu empty %llu over cap %llu\n", p.blocks, P.tile_tiles,
+                   P.tile_cap, cnt.size(), static_cast<unsigned long long>(met), static_cast<double>(met) / static_cast<double>(cnt.size()), static_cast<unsigned long long>(most),
+                   static_cast<unsigned long long>(empty), static_cast<unsigned long long>(over));
+    }
+    HIPCHK(b, close_marks());
     b->close_ts = ts_i;
-    HIPCHK(b, hipEventRecord(b->ring_ev3[k], ps));
-    HIPCHK(b, b->set_free[S.ls].mark(ps));
     if (b->overlap && p.alternate) b->log_set ^= 1;
     b->ring_posts[k] = true;
-    HIPCHK(b, hipEventRecord(b->ring_done[k], ps));
     return HALO_OK;
   }
   if (p.close) {
@@ -1729,13 +1797,10 @@ int queue_passes(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, c
     if (ce != hipSuccess) return hip_fail(b, ce, "halo_split_kernel launch (direct close)");
     b->cnt2_clean[S.ls] = true;
     b->direct_closes++;
-    HIPCHK(b, b->close_done.mark(ps));
+    HIPCHK(b, close_marks());
     b->close_ts = ts_i;
-    HIPCHK(b, hipEventRecord(b->ring_ev3[k], ps));
-    HIPCHK(b, b->set_free[S.ls].mark(ps));
     if (b->overlap && p.alternate) b->log_set ^= 1;
     b->ring_posts[k] = true;
-    HIPCHK(b, hipEventRecord(b->ring_done[k], ps));
     return HALO_OK;
   }
   HIPCHK(b, hipMemsetAsync(bin_cnt2.ptr, 0, static_cast<size_t>(p.log_tiles) * 16u * sizeof(uint32_t), ps));
@@ -1758,6 +1823,7 @@ int queue_passes(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, c
   if (b->overlap && p.alternate) b->log_set ^= 1;
   b->ring_posts[k] = true;
   HIPCHK(b, hipEventRecord(b->ring_done[k], ps));
+  b->ring_fin[k] = b->ring_done[k];
   return HALO_OK;
 }
 // Stream choice, plane gates, generator, trace kernel, route record and passes of one launch whose tables, shapes and buffers are in place.
@@ -1889,8 +1955,8 @@ int trace_launch(HaloBackend* b, const LayerCtx& c, LaunchPlan& p, EntryTables& 
     if (turn)   // (its twin with it, for the same reason as the log's second buffer set)
       if (int rc = reserve_idle(b, b->shapes_s[S.shape_set ^ 1], p.shape_cnt)) return rc;
     if (p.host_pool) {
-      HIPCHK(b, b->shapes_free[S.shape_set].wait_on(b->stream));
-      HIPCHK(b, hipMemcpyAsync(shapes.ptr, pool.data(), pool.size() * sizeof(ShapeDev), hipMemcpyHostToDevice, b->stream));
+      HIPCHK(b, b->shapes_free[S.shape_set].wait_on(main_q(b)));
+      HIPCHK(b, hipMemcpyAsync(shapes.ptr, pool.data(), pool.size() * sizeof(ShapeDev), hipMemcpyHostToDevice, main_q(b)));
     }
     // (device generator: queued by queue_launch on the launch's trace stream, in front of the trace kernel)
     P.shapes = shapes.ptr;
@@ -1925,7 +1991,7 @@ int trace_launch(HaloBackend* b, const LayerCtx& c, LaunchPlan& p, EntryTables& 
   p.close = close_direct_ok(*b, p, P);
   if (int rc = bind_tile_append(b, p, T, S.ls, P)) return rc;
   if (int rc = queue_launch(b, p, E, T, P, S)) return rc;
-  if (p.host_pool) HIPCHK(b, hipStreamSynchronize(b->stream));  // the pageable shape pool must outlive its copy (the copy is on the main stream)
+  if (p.host_pool) HIPCHK(b, hipStreamSynchronize(main_q(b)));  // the pageable shape pool must outlive its copy (the copy is on the main stream)
   if (P.source == kSrcGen) b->gen_count += m;
   if (P.source == kSrcTransit) b->transit_count += m;
   b->gate_count += m;
@@ -2001,14 +2067,14 @@ int close_layer(HaloBackend* b, const LayerCtx& c, bool defer, HaloLayerStats* s
   if (int rc = join_aux(b)) return rc;   // the copies below (and the caller) want this layer's kernels done: the main stream waits for the trace streams
   uint32_t cnt[kCntNum] = {0, 0, 0, 0};
   std::vector<uint32_t> fill(c.final_layer ? 0 : kContShards * kContCntStride);
-  HIPCHK(b, hipMemcpyAsync(cnt, b->counters.ptr, sizeof(cnt), hipMemcpyDeviceToHost, b->stream));
-  if (!c.final_layer) HIPCHK(b, hipMemcpyAsync(fill.data(), b->cont_cnt.ptr, fill.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(b, hipMemcpyAsync(cnt, b->counters.ptr, sizeof(cnt), hipMemcpyDeviceToHost, main_q(b)));
+  if (!c.final_layer) HIPCHK(b, hipMemcpyAsync(fill.data(), b->cont_cnt.ptr, fill.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, main_q(b)));
   uint32_t cont_err = 0;
-  if (c.canon_check) HIPCHK(b, hipMemcpyAsync(&cont_err, b->cont_err.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+  if (c.canon_check) HIPCHK(b, hipMemcpyAsync(&cont_err, b->cont_err.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, main_q(b)));
   if (b->tally_unread) {
     if (int rc = pull_tally(b)) return rc;   // (one more small copy and THE stream sync of this call: the two copies above are complete behind it)
   } else {
-    HIPCHK(b, hipStreamSynchronize(b->stream));
+    HIPCHK(b, hipStreamSynchronize(main_q(b)));
   }
   harvest_all(b);
   if (cont_err != 0u)   // never a pool handed on (or traced) out of canonical order in silence
@@ -2097,14 +2163,14 @@ int halo_trace_layer(halo_handle_t b, uint64_t count, const HaloHostRays* rays, 
     b->cont_region[c.out_slot] = static_cast<uint32_t>(region);
     c.out_cap = static_cast<uint32_t>(region);
     HIPCHK(b, b->cont_cnt.reserve(kContShards * kContCntStride));
-    HIPCHK(b, hipMemsetAsync(b->cont_cnt.ptr, 0, kContShards * kContCntStride * sizeof(uint32_t), b->stream));
+    HIPCHK(b, hipMemsetAsync(b->cont_cnt.ptr, 0, kContShards * kContCntStride * sizeof(uint32_t), main_q(b)));
     if (b->cont_order) {   // the roots' masks start empty: queued on the stream, behind the scatter that read the previous layer's
       if (b->rehit_strategy == 0) return fail(b, HALO_FATAL, "cont_order = 1 needs rehit_strategy = 1 (the legacy strategy can emit twice at one interaction)");
       if (int rc = reserve_idle(b, b->cont_mask, kContMaskWords * std::max<uint64_t>(c.n, 1))) return rc;
-      HIPCHK(b, hipMemsetAsync(b->cont_mask.ptr, 0, kContMaskWords * c.n * sizeof(uint32_t), b->stream));
+      HIPCHK(b, hipMemsetAsync(b->cont_mask.ptr, 0, kContMaskWords * c.n * sizeof(uint32_t), main_q(b)));
       if (c.layer == 0) {   // a session starts with a clean error word (a session that set one was refused)
         if (int rc = reserve_idle(b, b->cont_err, 16)) return rc;
-        HIPCHK(b, hipMemsetAsync(b->cont_err.ptr, 0, sizeof(uint32_t), b->stream));
+        HIPCHK(b, hipMemsetAsync(b->cont_err.ptr, 0, sizeof(uint32_t), main_q(b)));
       }
     }
   }
@@ -2121,7 +2187,7 @@ int halo_trace_layer(halo_handle_t b, uint64_t count, const HaloHostRays* rays, 
       DevBuf<HaloExitRecord> bigger;
       HIPCHK(b, bigger.reserve(need));
       if (b->exits_pending)
-        HIPCHK(b, hipMemcpyAsync(bigger.ptr, b->exits.ptr, b->exits_pending * sizeof(HaloExitRecord), hipMemcpyDeviceToDevice, b->stream));
+        HIPCHK(b, hipMemcpyAsync(bigger.ptr, b->exits.ptr, b->exits_pending * sizeof(HaloExitRecord), hipMemcpyDeviceToDevice, main_q(b)));
       if (int rc = sync_all(b)) return rc;
       b->exits.release();
       b->exits = bigger;
@@ -2134,11 +2200,11 @@ int halo_trace_layer(halo_handle_t b, uint64_t count, const HaloHostRays* rays, 
     if (int rc = join_aux(b)) return rc;
     if (int rc = reserve_idle(b, b->host_f, n * 7)) return rc;
     if (int rc = reserve_idle(b, b->host_u, n)) return rc;
-    HIPCHK(b, hipMemcpyAsync(b->host_f.ptr, rays->d, n * 3 * sizeof(float), hipMemcpyHostToDevice, b->stream));
-    HIPCHK(b, hipMemcpyAsync(b->host_f.ptr + n * 3, rays->p, n * 3 * sizeof(float), hipMemcpyHostToDevice, b->stream));
-    HIPCHK(b, hipMemcpyAsync(b->host_f.ptr + n * 6, rays->w, n * sizeof(float), hipMemcpyHostToDevice, b->stream));
-    HIPCHK(b, hipMemcpyAsync(b->host_u.ptr, rays->tf, n * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
-    HIPCHK(b, hipStreamSynchronize(b->stream));
+    HIPCHK(b, hipMemcpyAsync(b->host_f.ptr, rays->d, n * 3 * sizeof(float), hipMemcpyHostToDevice, main_q(b)));
+    HIPCHK(b, hipMemcpyAsync(b->host_f.ptr + n * 3, rays->p, n * 3 * sizeof(float), hipMemcpyHostToDevice, main_q(b)));
+    HIPCHK(b, hipMemcpyAsync(b->host_f.ptr + n * 6, rays->w, n * sizeof(float), hipMemcpyHostToDevice, main_q(b)));
+    HIPCHK(b, hipMemcpyAsync(b->host_u.ptr, rays->tf, n * sizeof(uint32_t), hipMemcpyHostToDevice, main_q(b)));
+    HIPCHK(b, hipStreamSynchronize(main_q(b)));
   }
   // the launches: an entry's tables and shared parameters are made when its first launch comes up
   EntryTables T;
@@ -2170,8 +2236,8 @@ int halo_generate_shapes(halo_handle_t b, const HaloCrystal* crystal, uint64_t f
     HIPCHK(b, dev.reserve(n));
     std::vector<ShapePrism> recs(n);
     hipError_t ge = launch_shapegen(dev.ptr, true, n, b->seed, host::MakeRecipe(*crystal), first_index, b->stream, b->gen_serial != 0);
-    if (ge == hipSuccess) ge = hipMemcpyAsync(recs.data(), dev.ptr, static_cast<size_t>(n) * sizeof(ShapePrism), hipMemcpyDeviceToHost, b->stream);
-    if (ge == hipSuccess) ge = hipStreamSynchronize(b->stream);
+    if (ge == hipSuccess) ge = hipMemcpyAsync(recs.data(), dev.ptr, static_cast<size_t>(n) * sizeof(ShapePrism), hipMemcpyDeviceToHost, main_q(b));
+    if (ge == hipSuccess) ge = hipStreamSynchronize(main_q(b));
     dev.release();
     if (ge != hipSuccess) return hip_fail(b, ge, "halo_prismgen_team_kernel");
     for (uint32_t k = 0; k < n; k++) {   // same members, shorter rows: widen to the general record
@@ -2192,8 +2258,8 @@ int halo_generate_shapes(halo_handle_t b, const HaloCrystal* crystal, uint64_t f
     DevBuf<ShapeDev> dev;
     HIPCHK(b, dev.reserve(n));
     hipError_t ge = launch_shapegen(dev.ptr, false, n, b->seed, host::MakeRecipe(*crystal), first_index, b->stream, b->gen_serial != 0);
-    if (ge == hipSuccess) ge = hipMemcpyAsync(pool.data(), dev.ptr, static_cast<size_t>(n) * sizeof(ShapeDev), hipMemcpyDeviceToHost, b->stream);
-    if (ge == hipSuccess) ge = hipStreamSynchronize(b->stream);
+    if (ge == hipSuccess) ge = hipMemcpyAsync(pool.data(), dev.ptr, static_cast<size_t>(n) * sizeof(ShapeDev), hipMemcpyDeviceToHost, main_q(b));
+    if (ge == hipSuccess) ge = hipStreamSynchronize(main_q(b));
     dev.release();
     if (ge != hipSuccess) return hip_fail(b, ge, "halo_shapegen_kernel");
   } else {
@@ -2232,10 +2298,10 @@ int halo_readback_class_lanes(halo_handle_t b, float* lanes, int width, int heig
   // the lanes are summed in fp64 on the device (hot pixels), the seam hands out floats (trace_backend.hpp:471-493): narrowed and drained by
   // one kernel into the staging buffer, so half the bytes cross the bus and no host pass follows
   HIPCHK(b, b->lanes_stage.reserve(n));
-  hipError_t e = launch_lanes_drain(b->lanes.ptr, b->lanes_stage.ptr, n, b->cu_count * 8, b->stream);
+  hipError_t e = launch_lanes_drain(b->lanes.ptr, b->lanes_stage.ptr, n, b->cu_count * 8, main_q(b));
   if (e != hipSuccess) return hip_fail(b, e, "halo_lanes_drain_kernel launch");
-  HIPCHK(b, hipMemcpyAsync(lanes, b->lanes_stage.ptr, n * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-  HIPCHK(b, hipStreamSynchronize(b->stream));
+  HIPCHK(b, hipMemcpyAsync(lanes, b->lanes_stage.ptr, n * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
+  HIPCHK(b, hipStreamSynchronize(main_q(b)));
   return HALO_OK;
 }
 
@@ -2289,9 +2355,9 @@ int halo_reduce_accumulator(halo_handle_t b, void* nccl_comm, int root, int this
   if (rc != HALO_OK) return rc;
   const size_t n = static_cast<size_t>(b->acc_w) * static_cast<size_t>(b->acc_h) * 3 + 4;
   if (n > b->acc_floats) return fail(b, HALO_FATAL, "reduce_accumulator: the bound accumulator is smaller than width*height*3+4 floats");
-  const int nr = reduce(b->acc, b->acc, n, 7 /* ncclFloat32 */, 0 /* ncclSum */, root, nccl_comm, b->stream);
+  const int nr = reduce(b->acc, b->acc, n, 7 /* ncclFloat32 */, 0 /* ncclSum */, root, nccl_comm, main_q(b));
   if (nr != 0) return fail(b, HALO_FATAL, "ncclReduce failed with code " + std::to_string(nr));
-  if (this_rank != root) HIPCHK(b, hipMemsetAsync(b->acc, 0, n * sizeof(float), b->stream));   // drained, in stream order
+  if (this_rank != root) HIPCHK(b, hipMemsetAsync(b->acc, 0, n * sizeof(float), main_q(b)));   // drained, in stream order
   return HALO_OK;
 }
 
@@ -2299,7 +2365,7 @@ int halo_collect_stats(halo_handle_t b, HaloLayerStats* out) {
   if (!b || !out) return HALO_FATAL;
   HIPCHK(b, hipSetDevice(b->device));
   if (int rc = join_aux(b)) return rc;   // (kernels of queued sessions may still be running on the trace / auxiliary streams)
-  HIPCHK(b, hipStreamSynchronize(b->stream));
+  HIPCHK(b, hipStreamSynchronize(main_q(b)));
   harvest_all(b);
   if (int rc = pull_tally(b)) return rc;
   add_stats(b->pending, b->layer_acc);
@@ -2343,13 +2409,13 @@ int halo_recombine(halo_handle_t b, int shuffle, uint64_t* continuation_count) {
       if (int rc = reserve_idle(b, b->cont_tiles, std::max<uint64_t>(tiles, 1))) return rc;
       const hipError_t e = launch_cont_reorder(b->cont[src].ptr, b->cont_stride[src], b->cont_region[src], b->cont_cnt.ptr, b->cont_fill_max, b->cont_mask.ptr,
                                                static_cast<uint32_t>(b->cont_roots), b->cont_tiles.ptr, b->cont_base.ptr, b->cont[dst].ptr, static_cast<uint32_t>(stride),
-                                               static_cast<uint32_t>(n_cont), static_cast<uint32_t>(planes), b->cont_err.ptr, b->stream);
+                                               static_cast<uint32_t>(n_cont), static_cast<uint32_t>(planes), b->cont_err.ptr, main_q(b));
       if (e != hipSuccess) return hip_fail(b, e, "halo_cont_scatter_kernel launch");
       // the reorder's invariants, checked before any layer reads the pool: one 4-byte read behind the scatter (which the next layer's kernels
       // wait for in any case)
       uint32_t err = 0;
-      HIPCHK(b, hipMemcpyAsync(&err, b->cont_err.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
-      HIPCHK(b, hipStreamSynchronize(b->stream));
+      HIPCHK(b, hipMemcpyAsync(&err, b->cont_err.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, main_q(b)));
+      HIPCHK(b, hipStreamSynchronize(main_q(b)));
       if (err != 0u) return cont_order_fail(b, err);
     }
     b->cont_stride[dst] = static_cast<uint32_t>(stride);
@@ -2372,7 +2438,7 @@ int halo_drain_exits(halo_handle_t b, HaloExitRecord* out, uint64_t cap, uint64_
   if (!b) return HALO_FATAL;
   HIPCHK(b, hipSetDevice(b->device));
   if (int rc = join_aux(b)) return rc;   // (kernels of queued sessions may still be running on the trace / auxiliary streams)
-  HIPCHK(b, hipStreamSynchronize(b->stream));
+  HIPCHK(b, hipStreamSynchronize(main_q(b)));
   // Piecewise drain (trace_backend.hpp:430-448): a call takes at most `cap` records from the front and the rest stays
   // pending; *count = records copied by THIS call.  out == NULL reports how many are pending without consuming any.
   const uint64_t n = b->exits_pending;
@@ -2393,8 +2459,8 @@ int halo_drain_exits(halo_handle_t b, HaloExitRecord* out, uint64_t cap, uint64_
   }
   b->exits_pending = left;
   const uint32_t left32 = static_cast<uint32_t>(left);  // the device append counter continues behind the kept tail
-  HIPCHK(b, hipMemcpyAsync(b->counters.ptr + kCntExit, &left32, sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
-  HIPCHK(b, hipStreamSynchronize(b->stream));
+  HIPCHK(b, hipMemcpyAsync(b->counters.ptr + kCntExit, &left32, sizeof(uint32_t), hipMemcpyHostToDevice, main_q(b)));
+  HIPCHK(b, hipStreamSynchronize(main_q(b)));
   return HALO_OK;
 }
 
@@ -2490,9 +2556,9 @@ int halo_export_fixed(halo_handle_t b, void* dev_words, uint64_t n_words, uint32
   unsigned long long fix_now = 0ull;
   if (int rc = read_tally(b, now, &fix_now)) return rc;   // (waits for the device)
   const uint32_t npix = static_cast<uint32_t>(b->acc_w) * static_cast<uint32_t>(b->acc_h);
-  hipError_t e = launch_export_fixed(b->fix.ptr, static_cast<unsigned long long*>(dev_words), npix, b->mono_s_log2, b->plane_cnt, fix_now - b->fix_landed_seen, b->stream);
+  hipError_t e = launch_export_fixed(b->fix.ptr, static_cast<unsigned long long*>(dev_words), npix, b->mono_s_log2, b->plane_cnt, fix_now - b->fix_landed_seen, main_q(b));
   if (e != hipSuccess) return hip_fail(b, e, "halo_export_fixed_kernel launch");
-  HIPCHK(b, hipStreamSynchronize(b->stream));   // the words are the caller's from here on, whatever stream it reads them on
+  HIPCHK(b, hipStreamSynchronize(main_q(b)));   // the words are the caller's from here on, whatever stream it reads them on
   b->fix_landed_seen = fix_now;   // taken: nothing is counted twice
   b->landed_own = false;
   // (landed_carry — landed weight converted to a double when F_landed changed — stays with the handle and goes to its next taker: on a shard it
@@ -2523,11 +2589,11 @@ int halo_import_fixed(halo_handle_t b, const void* dev_words, uint64_t n_words, 
   HIPCHK(b, hipSetDevice(b->device));
   if (int rc = join_aux(b)) return rc;   // behind everything that adds to (or folds) the planes; what follows waits for the main stream
   const uint32_t npix = static_cast<uint32_t>(b->acc_w) * static_cast<uint32_t>(b->acc_h);
-  hipError_t e = launch_import_fixed(b->fix.ptr, static_cast<const unsigned long long*>(dev_words), npix, b->mono_s_log2, b->plane_cnt, b->stream);
+  hipError_t e = launch_import_fixed(b->fix.ptr, static_cast<const unsigned long long*>(dev_words), npix, b->mono_s_log2, b->plane_cnt, main_q(b));
   if (e != hipSuccess) return hip_fail(b, e, "halo_import_fixed_kernel launch");
   unsigned long long landed = 0ull;
-  HIPCHK(b, hipMemcpyAsync(&landed, static_cast<const unsigned long long*>(dev_words) + (n_words - 1u), sizeof(landed), hipMemcpyDeviceToHost, b->stream));
-  HIPCHK(b, hipStreamSynchronize(b->stream));
+  HIPCHK(b, hipMemcpyAsync(&landed, static_cast<const unsigned long long*>(dev_words) + (n_words - 1u), sizeof(landed), hipMemcpyDeviceToHost, main_q(b)));
+  HIPCHK(b, hipStreamSynchronize(main_q(b)));
   b->fix_landed_seen -= landed;   // untaken landed integer = device tally - seen (modulo 2^64): the word joins it
   b->fix_imported = !b->mono_dirty || b->fix_imported;   // (own pending planes stay a part: still not to be folded)
   b->fix_hits = held + rays;
@@ -2545,8 +2611,8 @@ int halo_readback_xyz64(halo_handle_t b, float* xyz, int width, int height, doub
     if (rc != HALO_OK) return rc;
   }
   const size_t n = static_cast<size_t>(width) * height * 3;
-  HIPCHK(b, hipMemcpyAsync(xyz, b->acc, n * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-  HIPCHK(b, hipMemsetAsync(b->acc, 0, (n + 4) * sizeof(float), b->stream));  // readback ZEROES the accumulator (cu:4832-4846)
+  HIPCHK(b, hipMemcpyAsync(xyz, b->acc, n * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
+  HIPCHK(b, hipMemsetAsync(b->acc, 0, (n + 4) * sizeof(float), main_q(b)));  // readback ZEROES the accumulator (cu:4832-4846)
   double l = 0.0;
   if (int rc = take_landed_delta(b, &l)) return rc;   // (syncs the stream: the image copy above is complete behind it)
   if (landed) *landed = l;
@@ -2567,10 +2633,10 @@ int halo_consumer_reset(halo_handle_t b) {
   if (int rc = join_aux(b)) return rc;   // (kernels of queued sessions may still be running on the trace / auxiliary streams)
   if (b->cons_sum.ptr) {
     const size_t n = static_cast<size_t>(b->cons_w) * b->cons_h * 3;
-    HIPCHK(b, hipMemsetAsync(b->cons_sum.ptr, 0, n * sizeof(float), b->stream));
-    HIPCHK(b, hipMemsetAsync(b->cons_comp.ptr, 0, n * sizeof(float), b->stream));
+    HIPCHK(b, hipMemsetAsync(b->cons_sum.ptr, 0, n * sizeof(float), main_q(b)));
+    HIPCHK(b, hipMemsetAsync(b->cons_comp.ptr, 0, n * sizeof(float), main_q(b)));
   }
-  if (b->lanes.ptr) HIPCHK(b, hipMemsetAsync(b->lanes.ptr, 0, b->lanes.cap * sizeof(double), b->stream));   // RenderConsumer::Reset clears the class lanes too (render.cpp:598-612)
+  if (b->lanes.ptr) HIPCHK(b, hipMemsetAsync(b->lanes.ptr, 0, b->lanes.cap * sizeof(double), main_q(b)));   // RenderConsumer::Reset clears the class lanes too (render.cpp:598-612)
   b->total_intensity = 0.0;
   return HALO_OK;
 }
@@ -2587,11 +2653,11 @@ int halo_consumer_fold(halo_handle_t b) {
     HIPCHK(b, b->cons_comp.reserve(n));
     b->cons_w = b->acc_w;
     b->cons_h = b->acc_h;
-    HIPCHK(b, hipMemsetAsync(b->cons_sum.ptr, 0, n * sizeof(float), b->stream));
-    HIPCHK(b, hipMemsetAsync(b->cons_comp.ptr, 0, n * sizeof(float), b->stream));
+    HIPCHK(b, hipMemsetAsync(b->cons_sum.ptr, 0, n * sizeof(float), main_q(b)));
+    HIPCHK(b, hipMemsetAsync(b->cons_comp.ptr, 0, n * sizeof(float), main_q(b)));
     b->total_intensity = 0.0;
   }
-  hipError_t e = launch_consumer_fold(b->acc, b->cons_sum.ptr, b->cons_comp.ptr, static_cast<uint32_t>(n), b->cu_count * 8, b->stream);
+  hipError_t e = launch_consumer_fold(b->acc, b->cons_sum.ptr, b->cons_comp.ptr, static_cast<uint32_t>(n), b->cu_count * 8, main_q(b));
   if (e != hipSuccess) return hip_fail(b, e, "halo_consumer_fold_kernel launch");
   double landed = 0.0;
   if (int rc = take_landed_delta(b, &landed)) return rc;
@@ -2613,31 +2679,31 @@ int halo_consumer_consume(halo_handle_t b, const float* xyz, int width, int heig
     HIPCHK(b, b->cons_comp.reserve(n));
     b->cons_w = width;
     b->cons_h = height;
-    HIPCHK(b, hipMemsetAsync(b->cons_sum.ptr, 0, n * sizeof(float), b->stream));
-    HIPCHK(b, hipMemsetAsync(b->cons_comp.ptr, 0, n * sizeof(float), b->stream));
+    HIPCHK(b, hipMemsetAsync(b->cons_sum.ptr, 0, n * sizeof(float), main_q(b)));
+    HIPCHK(b, hipMemsetAsync(b->cons_comp.ptr, 0, n * sizeof(float), main_q(b)));
     b->total_intensity = 0.0;
   }
   // the caller's image goes through the staging buffer and the same Neumaier fold kernel the device accumulator takes (the kernel zeroes
   // what it folds: the staging buffer here)
   HIPCHK(b, b->cons_stage.reserve(n));
-  HIPCHK(b, hipMemcpyAsync(b->cons_stage.ptr, xyz, n * sizeof(float), hipMemcpyHostToDevice, b->stream));
-  hipError_t e = launch_consumer_fold(b->cons_stage.ptr, b->cons_sum.ptr, b->cons_comp.ptr, static_cast<uint32_t>(n), b->cu_count * 8, b->stream);
+  HIPCHK(b, hipMemcpyAsync(b->cons_stage.ptr, xyz, n * sizeof(float), hipMemcpyHostToDevice, main_q(b)));
+  hipError_t e = launch_consumer_fold(b->cons_stage.ptr, b->cons_sum.ptr, b->cons_comp.ptr, static_cast<uint32_t>(n), b->cu_count * 8, main_q(b));
   if (e != hipSuccess) return hip_fail(b, e, "halo_consumer_fold_kernel launch");
   if (lanes != nullptr && class_count > 0) {   // lane_pixel_data_: dst[p] += src[p] per class (render.cpp:176-185)
     if (class_count != static_cast<int>(b->color_classes.size())) return fail(b, HALO_FATAL, "consumer_consume: class count must equal halo_set_color's");
     const size_t nl = static_cast<size_t>(class_count) * width * height;
     if (!b->lanes.ptr || b->lanes_w != width || b->lanes_h != height) {
       HIPCHK(b, b->lanes.reserve(nl));
-      HIPCHK(b, hipMemsetAsync(b->lanes.ptr, 0, b->lanes.cap * sizeof(double), b->stream));
+      HIPCHK(b, hipMemsetAsync(b->lanes.ptr, 0, b->lanes.cap * sizeof(double), main_q(b)));
       b->lanes_w = width;
       b->lanes_h = height;
     }
     HIPCHK(b, b->lanes_stage.reserve(nl));
-    HIPCHK(b, hipMemcpyAsync(b->lanes_stage.ptr, lanes, nl * sizeof(float), hipMemcpyHostToDevice, b->stream));
-    e = launch_lanes_add(b->lanes_stage.ptr, b->lanes.ptr, nl, b->cu_count * 8, b->stream);
+    HIPCHK(b, hipMemcpyAsync(b->lanes_stage.ptr, lanes, nl * sizeof(float), hipMemcpyHostToDevice, main_q(b)));
+    e = launch_lanes_add(b->lanes_stage.ptr, b->lanes.ptr, nl, b->cu_count * 8, main_q(b));
     if (e != hipSuccess) return hip_fail(b, e, "halo_lanes_add_kernel launch");
   }
-  HIPCHK(b, hipStreamSynchronize(b->stream));   // `xyz` / `lanes` are the caller's (pageable) memory
+  HIPCHK(b, hipStreamSynchronize(main_q(b)));   // `xyz` / `lanes` are the caller's (pageable) memory
   b->total_intensity += static_cast<double>(landed);   // total_intensity_ += xyz_landed_weight_ (render.cpp:149)
   return HALO_OK;
 }
@@ -2655,11 +2721,11 @@ int halo_consumer_snapshot(halo_handle_t b, const HaloDisplay* dsp, uint8_t* rgb
   if (xyz_out) HIPCHK(b, b->cons_xyz_out.reserve(n));
   hipError_t e = launch_post_snapshot(b->cons_sum.ptr, b->cons_comp.ptr, rgb_out ? b->cons_rgb.ptr : nullptr,
                                       xyz_out ? b->cons_xyz_out.ptr : nullptr, npix, scale, dsp->ray_color, dsp->background,
-                                      b->cu_count * 8, b->stream);
+                                      b->cu_count * 8, main_q(b));
   if (e != hipSuccess) return hip_fail(b, e, "halo_post_snapshot_kernel launch");
-  if (rgb_out) HIPCHK(b, hipMemcpyAsync(rgb_out, b->cons_rgb.ptr, n, hipMemcpyDeviceToHost, b->stream));
-  if (xyz_out) HIPCHK(b, hipMemcpyAsync(xyz_out, b->cons_xyz_out.ptr, n * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-  HIPCHK(b, hipStreamSynchronize(b->stream));
+  if (rgb_out) HIPCHK(b, hipMemcpyAsync(rgb_out, b->cons_rgb.ptr, n, hipMemcpyDeviceToHost, main_q(b)));
+  if (xyz_out) HIPCHK(b, hipMemcpyAsync(xyz_out, b->cons_xyz_out.ptr, n * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
+  HIPCHK(b, hipStreamSynchronize(main_q(b)));
   if (rgb_out && scale == 0.0f) std::memset(rgb_out, 0, n);  // PostSnapshot early-out (render.cpp:515-518)
   if (total_intensity) *total_intensity = b->total_intensity;
   return HALO_OK;
@@ -2692,14 +2758,14 @@ int halo_consumer_auto_ev(halo_handle_t b, int32_t downsample_factor, float targ
   constexpr size_t kRecWords = sizeof(AevRecord) / sizeof(uint32_t);
   HIPCHK(b, b->aev_ws.reserve(kRecWords + kAevHistWords));
   AevRecord* rec_dev = reinterpret_cast<AevRecord*>(b->aev_ws.ptr);
-  hipError_t e = launch_aev_values(b->cons_sum.ptr, b->cons_comp.ptr, w, h, f, wc, hc, b->aev_vals.ptr, b->cu_count * 8, b->stream);
+  hipError_t e = launch_aev_values(b->cons_sum.ptr, b->cons_comp.ptr, w, h, f, wc, hc, b->aev_vals.ptr, b->cu_count * 8, main_q(b));
   if (e != hipSuccess) return hip_fail(b, e, "halo_aev value kernel launch");
   const bool one_wg = b->aev_select < 0 ? n_vals <= kAevSmallMax : b->aev_select == 1;
-  e = launch_aev_select(b->aev_vals.ptr, n_vals, rec_dev, b->aev_ws.ptr + kRecWords, one_wg, b->aev_agg_hist != 0, b->cu_count, b->stream);
+  e = launch_aev_select(b->aev_vals.ptr, n_vals, rec_dev, b->aev_ws.ptr + kRecWords, one_wg, b->aev_agg_hist != 0, b->cu_count, main_q(b));
   if (e != hipSuccess) return hip_fail(b, e, "halo_aev select kernel launch");
   AevRecord rec{};
-  HIPCHK(b, hipMemcpyAsync(&rec, rec_dev, sizeof(rec), hipMemcpyDeviceToHost, b->stream));
-  HIPCHK(b, hipStreamSynchronize(b->stream));
+  HIPCHK(b, hipMemcpyAsync(&rec, rec_dev, sizeof(rec), hipMemcpyDeviceToHost, main_q(b)));
+  HIPCHK(b, hipStreamSynchronize(main_q(b)));
   float p99 = 0.0f;
   if (rec.count) std::memcpy(&p99, &rec.p99_bits, sizeof(float));
   if (coarse) p99 = p99 / (static_cast<float>(f) * static_cast<float>(f));   // the fine-equivalent P99 (:112-113)
@@ -2737,10 +2803,10 @@ int halo_consumer_load_lanes(halo_handle_t b, const float* lanes, int width, int
   b->lanes_w = width;
   b->lanes_h = height;
   HIPCHK(b, b->lanes_stage.reserve(n));
-  HIPCHK(b, hipMemcpyAsync(b->lanes_stage.ptr, lanes, n * sizeof(float), hipMemcpyHostToDevice, b->stream));
-  hipError_t e = launch_lanes_load(b->lanes_stage.ptr, b->lanes.ptr, n, b->cu_count * 8, b->stream);
+  HIPCHK(b, hipMemcpyAsync(b->lanes_stage.ptr, lanes, n * sizeof(float), hipMemcpyHostToDevice, main_q(b)));
+  hipError_t e = launch_lanes_load(b->lanes_stage.ptr, b->lanes.ptr, n, b->cu_count * 8, main_q(b));
   if (e != hipSuccess) return hip_fail(b, e, "halo_lanes_load_kernel launch");
-  HIPCHK(b, hipStreamSynchronize(b->stream));   // `lanes` is the caller's (pageable) memory
+  HIPCHK(b, hipStreamSynchronize(main_q(b)));   // `lanes` is the caller's (pageable) memory
   if (total_intensity >= 0.0) b->total_intensity = total_intensity;
   return HALO_OK;
 }
@@ -2793,11 +2859,11 @@ int halo_consumer_composite(halo_handle_t b, const HaloComposite* spec, float* l
     bool empty = false;
     for (int pass = 0; pass < 3 && !empty; pass++) {
       const uint32_t nb = 1u << widths[pass];
-      HIPCHK(b, hipMemsetAsync(b->comp_hist.ptr, 0, nb * sizeof(uint32_t), b->stream));
-      hipError_t e = launch_lane_hist(b->lanes.ptr, npix, cd, shifts[pass], widths[pass], prefix, b->comp_hist.ptr, blocks, b->stream);
+      HIPCHK(b, hipMemsetAsync(b->comp_hist.ptr, 0, nb * sizeof(uint32_t), main_q(b)));
+      hipError_t e = launch_lane_hist(b->lanes.ptr, npix, cd, shifts[pass], widths[pass], prefix, b->comp_hist.ptr, blocks, main_q(b));
       if (e != hipSuccess) return hip_fail(b, e, "halo_lane_hist_kernel launch");
-      HIPCHK(b, hipMemcpyAsync(hist.data(), b->comp_hist.ptr, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
-      HIPCHK(b, hipStreamSynchronize(b->stream));
+      HIPCHK(b, hipMemcpyAsync(hist.data(), b->comp_hist.ptr, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, main_q(b)));
+      HIPCHK(b, hipStreamSynchronize(main_q(b)));
       if (pass == 0) {
         uint64_t count = 0;
         for (uint32_t i = 0; i < nb; i++) count += hist[i];
@@ -2839,11 +2905,11 @@ int halo_consumer_composite(halo_handle_t b, const HaloComposite* spec, float* l
   if (linear_rgb_out) HIPCHK(b, b->comp_rgb.reserve(n3));
   if (srgb_out) HIPCHK(b, b->cons_rgb.reserve(n3));
   if (linear_rgb_out || srgb_out) {
-    hipError_t e = launch_composite(b->lanes.ptr, npix, cd, linear_rgb_out ? b->comp_rgb.ptr : nullptr, srgb_out ? b->cons_rgb.ptr : nullptr, blocks, b->stream);
+    hipError_t e = launch_composite(b->lanes.ptr, npix, cd, linear_rgb_out ? b->comp_rgb.ptr : nullptr, srgb_out ? b->cons_rgb.ptr : nullptr, blocks, main_q(b));
     if (e != hipSuccess) return hip_fail(b, e, "halo_composite_kernel launch");
-    if (linear_rgb_out) HIPCHK(b, hipMemcpyAsync(linear_rgb_out, b->comp_rgb.ptr, n3 * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-    if (srgb_out) HIPCHK(b, hipMemcpyAsync(srgb_out, b->cons_rgb.ptr, n3, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(b, hipStreamSynchronize(b->stream));
+    if (linear_rgb_out) HIPCHK(b, hipMemcpyAsync(linear_rgb_out, b->comp_rgb.ptr, n3 * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
+    if (srgb_out) HIPCHK(b, hipMemcpyAsync(srgb_out, b->cons_rgb.ptr, n3, hipMemcpyDeviceToHost, main_q(b)));
+    HIPCHK(b, hipStreamSynchronize(main_q(b)));
   }
   *produced = 1;
   return HALO_OK;

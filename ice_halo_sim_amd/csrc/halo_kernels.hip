@@ -633,15 +633,34 @@ hipError_t launch_log_route_close(float* xyz, uint32_t n_pix, const float* coef,
 
 // ---- the closing per-tile pass over per-tile CHUNKS (option "tile_append": a kAccTileFinal trace kernel wrote them, halo_trace.inl log_hit_tile) ----
 // One workgroup per tile of 2^tile_log2 consecutive slots, as in the closing form above; the tile's records lie in one chunk per trace workgroup,
-// chunk[tile][wg][cap] with cnt[tile][wg] records met (clamped to cap here: what a chunk could not hold went to the twin).  A chunk is short — a few
-// hundred records at most — so ONE WAVE takes a chunk, reads the counts of 64 chunks at a time (one per lane) and keeps kChunksInFlight chunks'
-// loads in the air (the first 64 x kLoads pairs of each; what a longer chunk holds beyond them follows in a loop): two records per 16-byte load (a chunk starts on 16 bytes: cap is even), non-temporal — the chunks are read once, a moment
-// after they were written — and the same fixed-point LDS sums.  The write-out is the closing form's own (close_write_out).  Nothing is reset:
-// the trace kernel writes every count of every launch, and the twin's flag is cleared by the memset behind the pass, as above.
-// (Measured on configs[1], passes per launch, chunks in flight x 16-byte loads per lane and chunk: 2 x 2 317 us, 4 x 2 280, 8 x 2 268, 8 x 1 252,
-// 16 x 1 247 — profiles/tile_append_ab.txt: the chunks of that launch hold ~160 records, and what a second load per chunk would fetch is mostly
-// not there.)
-constexpr uint32_t kChunksInFlight = 16u, kLoads = 1u;
+// chunk[tile][wg][cap] with cnt[tile][wg] records met (clamped to cap here: what a chunk could not hold went to the twin).  A chunk is short — the
+// headline's 781 184 chunks hold 74 - 76 records each, the longest 560 (profiles/resident_grid_traffic.txt; the "~160" this comment used to give was
+// wrong) — so ONE WAVE takes a chunk.  A wave holds the counts of kCloseBatch chunks at a time, one per lane, each read ONCE (the pre-pass that asks
+// whether the tile is empty keeps what it loaded), and walks the batch in STEPS: kLoads 16-byte loads per lane — 64 x kLoads pairs of records —
+// of each of kChunksInFlight chunks, in one of two register sets; the next step's loads are issued before this step's ds_add_u64, so the memory
+// system always holds a whole step of the wave while it adds (the form before this one requested 16 chunks, waited, added, and then walked what
+// was left of each chunk in a serial loop of load, wait, add).  Two records per 16-byte load (a chunk starts on 16 bytes: cap is even), an odd last
+// record in the chunk's last pair, non-temporal — the chunks are read once, a moment after they were written — and the same fixed-point LDS sums,
+// whose order does not matter.  The write-out is the closing form's own (close_write_out).  Nothing is reset: the trace kernel writes every count
+// of every launch, and the twin's flag is cleared by the memset behind the pass, as above.
+// (Measured on configs[1], passes per launch, chunks in flight x loads per lane and chunk, profiles/resident_grid_ab.txt: the form before 246 us;
+// 8 x 1 177 [kept: 84 VGPRs, no scratch], 4 x 1 181, 4 x 2 203, 2 x 3 256, 2 x 4 278, 4 x 3 307; 8 x 2 and 16 x 1 need more than the 128 VGPRs a
+// 1024-thread workgroup may have and spill, 306 / 313.  On chunks four times as long — a grid of six workgroups per CU — 2 x 4, 2 x 3 and 4 x 2 lead
+// at 141 - 144 and 8 x 1 takes 155, but the trace kernel loses 210 us on that grid: blocks_of.  Batches of 16 / 32 / 64 counts: level.)
+#ifndef HALO_TILE_CHUNKS   // (the sweep's builds set these; the committed values are the defaults)
+#define HALO_TILE_CHUNKS 8
+#endif
+#ifndef HALO_TILE_LOADS
+#define HALO_TILE_LOADS 1
+#endif
+#ifndef HALO_TILE_BATCH
+#define HALO_TILE_BATCH 32
+#endif
+constexpr uint32_t kChunksInFlight = HALO_TILE_CHUNKS, kLoads = HALO_TILE_LOADS;
+constexpr uint32_t kCloseBatch = HALO_TILE_BATCH;   // chunks whose counts one wave holds at a time, one per lane (lanes 0 .. kCloseBatch - 1): 32 spreads a
+                                                    // small grid's chunks evenly over the 16 waves (1536 chunks: three batches each, not two or one of 64)
+constexpr uint32_t kCloseKeep = 4u;     // batches per wave whose counts stay in registers from the `any` pre-pass on (16 waves x 32 x 4 = 2048 chunks)
+static_assert(kCloseBatch % kChunksInFlight == 0u && kCloseBatch <= 64u, "a batch is whole groups of chunks, one count per lane");
 __global__ void __launch_bounds__(kBinBlock) halo_tile_close_kernel(const uint2* __restrict__ chunk, uint32_t cap, const uint32_t* __restrict__ cnt, uint32_t wgs,
                                                                     uint32_t tile_log2, uint32_t frac_bits, const CloseArgsOf<true> cl) {
   __shared__ __attribute__((aligned(16))) unsigned long long acc[1u << kBinTileLog2];   // fixed point (FixQ); tile_log2 <= kBinTileLog2
@@ -649,64 +668,92 @@ __global__ void __launch_bounds__(kBinBlock) halo_tile_close_kernel(const uint2*
   const uint32_t tile = blockIdx.x;
   const uint32_t* tcnt = cnt + static_cast<size_t>(tile) * wgs;
   const bool take_twin = *cl.flag != 0u;   // workgroup-uniform
-  uint32_t any = 0u;
-  for (uint32_t c = threadIdx.x; c < wgs; c += kBinBlock) any |= tcnt[c];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  constexpr uint32_t kRound = (kBinBlock / 64u) * kCloseBatch;   // chunks the workgroup's waves take per round: wave w the batch at r x kRound + w x kCloseBatch
+  // the count of this lane's chunk in round r, clamped (what a chunk could not hold went to the twin); 0 past the last chunk and on lanes >= kCloseBatch
+  auto count_at = [&](uint32_t r) -> uint32_t {
+    const uint32_t c = r * kRound + wave * kCloseBatch + lane;
+    return (lane < kCloseBatch && c < wgs) ? min(tcnt[c], cap) : 0u;
+  };
+  // every count is read once: the pre-pass keeps the first kCloseKeep rounds' (a resident grid's all), later rounds are read when their turn comes —
+  // a tile of a grid that large is not asked whether it is empty (an empty one adds zeros and writes nothing out)
+  const uint32_t rounds = (wgs + kRound - 1u) / kRound;
+  uint32_t kept[kCloseKeep], any = rounds > kCloseKeep ? 1u : 0u;
+#pragma unroll
+  for (uint32_t r = 0; r < kCloseKeep; ++r) any |= kept[r] = count_at(r);
   if (!__syncthreads_or(static_cast<int>(any != 0u)) && !take_twin) return;
   const uint32_t slots = 1u << tile_log2, mask = slots - 1u;
   for (uint32_t j = threadIdx.x; j < slots; j += kBinBlock) acc[j] = 0ull;
   __syncthreads();
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, waves = kBinBlock / 64u;
   const uint2* tsrc = chunk + static_cast<size_t>(tile) * wgs * cap;
   auto add = [&](uint32_t slot, uint32_t w_bits) { atomicAdd(&acc[slot & mask], fq.fix(__uint_as_float(w_bits))); };
-  for (uint32_t c0 = wave * 64u; c0 < wgs; c0 += waves * 64u) {   // wave-uniform
-    const uint32_t mine = c0 + lane < wgs ? min(tcnt[c0 + lane], cap) : 0u;
-    if (__ballot(mine != 0u) == 0ull) continue;
-    for (uint32_t g = 0; g < 64u; g += kChunksInFlight) {
-      uint32_t n[kChunksInFlight], most = 0u;
+  // One batch: chunks c0 .. c0 + kCloseBatch - 1, their counts in `mine` of lanes 0 .. kCloseBatch - 1.  The unit of work is a STEP: kLoads 16-byte
+  // loads per lane (64 x kLoads pairs of records) of each of the kChunksInFlight chunks of one group; a group has as many steps as its longest chunk
+  // needs, and the steps of the batch are walked in order, the next step's loads issued before this step's adds (two register sets, taken in turn).
+  // An odd last record rides in the chunk's last pair: cap is even, so the 16 bytes are the chunk's own, and its second half is not added.
+  auto batch = [&](uint32_t c0, uint32_t mine) {   // wave-uniform c0
+    if (__ballot(mine != 0u) == 0ull) return;
+    auto count_of = [&](uint32_t j) { return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(mine), static_cast<int>(j))); };
+    auto steps_of = [&](uint32_t g) {
+      uint32_t most = 0u;
+#pragma unroll
+      for (uint32_t k = 0; k < kChunksInFlight; ++k) most = max(most, count_of(g + k));
+      return (most + 128u * kLoads - 1u) / (128u * kLoads);
+    };
+    uint32_t g = 0u, it = 0u, steps = 0u;   // the cursor: step `it` of the group at chunk g
+    auto seek = [&]() {
+      while (g < kCloseBatch && (steps = steps_of(g)) == 0u) g += kChunksInFlight;
+      return g < kCloseBatch;
+    };
+    auto advance = [&]() {
+      if (++it < steps) return true;
+      it = 0u, g += kChunksInFlight;
+      return seek();
+    };
+    auto issue = [&](uint32_t sg, uint32_t si, uint4 (&h)[kChunksInFlight][kLoads]) {
 #pragma unroll
       for (uint32_t k = 0; k < kChunksInFlight; ++k) {
-        n[k] = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(mine), static_cast<int>(g + k)));
-        most = max(most, n[k]);
-      }
-      if (most == 0u) continue;
-      // the first 64 x kLoads pairs of each chunk, all requested before the first add
-      uint4 h[kChunksInFlight][kLoads];
-#pragma unroll
-      for (uint32_t k = 0; k < kChunksInFlight; ++k) {
-        const uint4* src4 = reinterpret_cast<const uint4*>(tsrc + static_cast<size_t>(c0 + g + k) * cap);
+        const uint32_t n = count_of(sg + k);
+        const uint4* src4 = reinterpret_cast<const uint4*>(tsrc + static_cast<size_t>(c0 + sg + k) * cap);
 #pragma unroll
         for (uint32_t u = 0; u < kLoads; ++u) {
-          const uint32_t i = lane + 64u * u;
-          h[k][u] = i < n[k] / 2u ? load_list_u4<true>(&src4[i]) : make_uint4(0u, 0u, 0u, 0u);   // (a zero weight adds nothing to slot 0)
+          const uint32_t i = (si * kLoads + u) * 64u + lane;
+          if (2u * i < n) h[k][u] = load_list_u4<true>(&src4[i]);
         }
       }
+    };
+    auto take = [&](uint32_t sg, uint32_t si, const uint4 (&h)[kChunksInFlight][kLoads]) {
 #pragma unroll
       for (uint32_t k = 0; k < kChunksInFlight; ++k) {
+        const uint32_t n = count_of(sg + k);
 #pragma unroll
         for (uint32_t u = 0; u < kLoads; ++u) {
-          if (lane + 64u * u < n[k] / 2u) {
-            add(h[k][u].x, h[k][u].y);
-            add(h[k][u].z, h[k][u].w);
-          }
+          const uint32_t i = (si * kLoads + u) * 64u + lane;
+          if (2u * i < n) add(h[k][u].x, h[k][u].y);
+          if (2u * i + 1u < n) add(h[k][u].z, h[k][u].w);
         }
       }
-      // what is left: the pairs behind those, and an odd last record
-#pragma unroll
-      for (uint32_t k = 0; k < kChunksInFlight; ++k) {
-        const uint2* src = tsrc + static_cast<size_t>(c0 + g + k) * cap;
-        const uint4* src4 = reinterpret_cast<const uint4*>(src);
-        for (uint32_t i = lane + 64u * kLoads; i < n[k] / 2u; i += 64u) {
-          const uint4 q = load_list_u4<true>(&src4[i]);
-          add(q.x, q.y);
-          add(q.z, q.w);
-        }
-        if ((n[k] & 1u) != 0u && lane == 0u) {
-          const uint2 q = src[n[k] - 1u];
-          add(q.x, q.y);
-        }
-      }
+    };
+    if (!seek()) return;
+    uint4 ha[kChunksInFlight][kLoads], hb[kChunksInFlight][kLoads];
+    issue(g, it, ha);
+    for (;;) {
+      uint32_t tg = g, ti = it;
+      bool more = advance();
+      if (more) issue(g, it, hb);
+      take(tg, ti, ha);
+      if (!more) break;
+      tg = g, ti = it;
+      more = advance();
+      if (more) issue(g, it, ha);
+      take(tg, ti, hb);
+      if (!more) break;
     }
-  }
+  };
+#pragma unroll
+  for (uint32_t r = 0; r < kCloseKeep; ++r)
+    if (r < rounds) batch(r * kRound + wave * kCloseBatch, kept[r]);
+  for (uint32_t r = kCloseKeep; r < rounds; ++r) batch(r * kRound + wave * kCloseBatch, count_at(r));
   __syncthreads();
   close_write_out(acc, fq, tile, tile_log2, slots, take_twin, cl);
 }

@@ -346,7 +346,9 @@ const char* halo_last_error(halo_handle_t h);
  * eligible, whatever the launch size; halo_direct_closes counts them), "tile_append" (-1 [default]: a launch that closes directly, fills the chip and
  * runs a trace kernel with a per-tile twin — plain mode, one regular prism, scalar plane, closed gate, a lens that is a template constant — appends
  * its records to per-tile chunks of each workgroup, and the closing pass reads the chunks: no split pass; the same records reach the same integer
- * tile sums; 0: never; 1: wherever eligible, whatever the launch size; halo_tile_appends counts them). */
+ * tile sums; 0: never; 1: wherever eligible, whatever the launch size; halo_tile_appends counts them), "lean_events" (1 [default]: markers that
+ * fall on one point of one stream share one recorded event, and a trace stream does not wait again for a main stream that has been given nothing
+ * since it last did; 0: every marker its own record, every launch the wait — the A/B switch; same results either way). */
 int halo_set_option(halo_handle_t h, const char* key, int64_t value);
 /* Use an external HIP stream (e.g. torch's current stream) for all launches. NULL = own stream. */
 int halo_set_stream(halo_handle_t h, void* hip_stream);

@@ -63,6 +63,11 @@ def load_library():
         "halo_last_root_profile": (C.c_int, [H, C.POINTER(C.c_uint32)]),
         "halo_direct_closes": (C.c_int, [H, C.POINTER(C.c_uint64)]),
         "halo_tile_appends": (C.c_int, [H, C.POINTER(C.c_uint64)]),
+        "halo_tile_tickets": (C.c_int, [H, C.POINTER(C.c_uint64)]),
+        "halo_host_ticket_size": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+        "halo_host_ticket_groups": (C.c_uint32, []),
+        "halo_host_ticket_range": (None, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "halo_host_ticket_next": (C.c_uint32, [C.c_uint64, C.c_uint32]),
         "halo_set_color": (C.c_int, [H, C.POINTER(abi.HaloColorSet), C.c_int, C.POINTER(abi.HaloColorClass), C.c_int]),
         "halo_readback_class_lanes": (C.c_int, [H, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int]),
         "halo_generate_shapes": (C.c_int, [H, C.POINTER(abi.HaloCrystal), C.c_uint64, C.c_uint32, C.c_int, C.POINTER(abi.HaloGeomTables)]),
@@ -112,7 +117,7 @@ def load_library():
 EXPORTED_SYMBOLS = [
     "halo_abi_version", "halo_abi_sizeof", "halo_device_count", "halo_create", "halo_destroy", "halo_last_error",
     "halo_set_option", "halo_set_stream", "halo_bind_accumulator", "halo_set_filters", "halo_begin", "halo_trace_layer", "halo_recombine",
-    "halo_drain_exits", "halo_end", "halo_readback_xyz", "halo_readback_xyz64", "halo_sync", "halo_flush", "halo_collect_timing", "halo_last_sample_counts", "halo_last_route", "halo_last_root_profile", "halo_direct_closes", "halo_tile_appends", "halo_set_color", "halo_readback_class_lanes", "halo_generate_shapes", "halo_collect_stats", "halo_take_landed", "halo_consumer_fold", "halo_consumer_consume", "halo_consumer_snapshot", "halo_consumer_reset", "halo_consumer_composite", "halo_consumer_load_lanes", "halo_host_parse_composite_mode", "halo_host_prism_geometry",
+    "halo_drain_exits", "halo_end", "halo_readback_xyz", "halo_readback_xyz64", "halo_sync", "halo_flush", "halo_collect_timing", "halo_last_sample_counts", "halo_last_route", "halo_last_root_profile", "halo_direct_closes", "halo_tile_appends", "halo_tile_tickets", "halo_host_ticket_size", "halo_host_ticket_groups", "halo_host_ticket_range", "halo_host_ticket_next", "halo_set_color", "halo_readback_class_lanes", "halo_generate_shapes", "halo_collect_stats", "halo_take_landed", "halo_consumer_fold", "halo_consumer_consume", "halo_consumer_snapshot", "halo_consumer_reset", "halo_consumer_composite", "halo_consumer_load_lanes", "halo_host_parse_composite_mode", "halo_host_prism_geometry",
     "halo_host_pyramid_geometry", "halo_host_shape_scalars", "halo_host_build_lat_lut", "halo_host_build_proj_params", "halo_host_partition",
     "halo_host_refractive_index", "halo_host_reduce_raypath", "halo_host_filter_fast_check", "halo_host_color_fast_mask", "halo_host_illuminant_spd", "halo_host_wl_pool", "halo_reduce_accumulator",
     "halo_peek_fixed", "halo_host_fixed_frac_bits", "halo_begin_spectrum", "halo_host_spectrum_entry",
@@ -237,6 +242,12 @@ class HipTraceBackend:
         """Launches of this backend, ever, whose trace kernel appended its records per tile (option tile_append): a cumulative count."""
         n = C.c_uint64()
         self._check(self._L.halo_tile_appends(self._h, C.byref(n)))
+        return n.value
+
+    def tile_tickets(self):
+        """Launches of this backend, ever, whose trace kernel drew its rays by wave tickets (option tile_ticket): a cumulative count."""
+        n = C.c_uint64()
+        self._check(self._L.halo_tile_tickets(self._h, C.byref(n)))
         return n.value
 
     def collect_stats(self):
@@ -457,6 +468,28 @@ def host_ev_auto(p99_y, per_pixel_intensity, target_white=135.0):
 def host_fixed_frac_bits(max_w, hits):
     """halo_host_fixed_frac_bits: the scale F of a 64-bit fixed-point sum of up to `hits` addends of at most `max_w` (no device needed)."""
     return int(load_library().halo_host_fixed_frac_bits(float(max_w), int(hits)))
+
+
+def host_ticket_size(total, seen, waves, lo, hi):
+    """halo_host_ticket_size: the wave-passes a wave of a ticketed launch asks for, the kernel's own rule (no device needed)."""
+    return int(load_library().halo_host_ticket_size(int(total), int(seen), int(waves), int(lo), int(hi)))
+
+
+def host_ticket_groups():
+    """halo_host_ticket_groups: the ranges, each with a counter, that a ticketed launch's wave-passes are cut into."""
+    return int(load_library().halo_host_ticket_groups())
+
+
+def host_ticket_range(all_passes, g):
+    """halo_host_ticket_range: (first, n) of range g of a launch of all_passes wave-passes."""
+    first, n = C.c_uint32(), C.c_uint32()
+    load_library().halo_host_ticket_range(int(all_passes), int(g), C.byref(first), C.byref(n))
+    return first.value, n.value
+
+
+def host_ticket_next(open_mask, home):
+    """halo_host_ticket_next: the range a wave at home on range `home` turns to, given the mask of ranges with passes left."""
+    return int(load_library().halo_host_ticket_next(int(open_mask), int(home)))
 
 
 EXIT_DTYPE = np.dtype([("dir", np.float32, 3), ("weight", np.float32), ("root", np.uint32), ("seq", np.uint16),

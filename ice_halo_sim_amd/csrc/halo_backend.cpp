@@ -126,7 +126,8 @@ struct HaloBackend {
   int lambda_planes = -1;      // illuminant sessions: -1 auto (by batch size), 0 never, 1 always one plane per pool entry
   int mono_copies = 8;         // power of two; copy = blockIdx & (copies-1)
   uint32_t mono_s_log2 = 0;    // log2 of the columns per row of the plane (kMonoRows rows; see MonoSlot)
-  int blocks_per_cu = 24;      // cap on workgroups per CU of a launch (5 resident: several rounds even out the tail)
+  int blocks_per_cu = 24;      // cap on workgroups per CU of a launch's STATIC ray loop (five or six resident: several rounds even out the tail; a ticketed
+                               // launch — tile_ticket — runs one resident round instead and evens the tail out wave by wave)
   int host_shapes = 0;         // 1: stochastic shape pools are built on the host and uploaded (A/B and test path)
   int gen_serial = 0;          // 1: pyramids are generated one thread per crystal (the serial builder) instead of one team of 32 lanes
   int small_blocks_per_cu = 0; // experiment knob: workgroups per CU that a small launch may spread over (0 = five, see blocks_of)
@@ -156,6 +157,15 @@ struct HaloBackend {
   uint64_t tile_appends = 0;   // launches that took the route, ever (halo_tile_appends)
   DevBuf<HitRec> tile_chunk_s[2];   // chunk[tile][workgroup][cap], one set per log set
   DevBuf<uint32_t> tile_cnt_s[2];   // cnt[tile][workgroup]
+  // Wave tickets: a per-tile-append launch runs ONE resident round of workgroups whose waves draw their passes of the ray loop from a
+  // counter (halo_device.h TicketSize, halo_trace.inl) — no static round's tail, and chunks four times as long for the closing pass.
+  int tile_ticket = -2;        // option: -2 auto (as -1, and the launch's static grid is more than one resident round), -1 auto (launches that take the
+                               // append by tile_append's auto rule), 0 never, 1 every launch that appends per tile
+  uint64_t tile_tickets = 0;   // launches that took tickets, ever (halo_tile_tickets)
+  uint32_t ticket_min = kTicketMin, ticket_max = kTicketMax, ticket_div = kTicketDiv;   // experiment knobs, unsupported: the sweep of profiles/wave_tickets_ab.txt,
+                                                                                        // and the tests' way to guided tickets on launches of a few milliseconds' worth
+  bool ticket_zeroed = false;  // the counters below exist and the one-time memset behind their reserve has completed
+  DevBuf<uint32_t> ticket_cnt; // kTicketGroups counters per log set, kTicketStride words apart: zeroed when reserved, and by every closing pass after
   HaloRouteInfo route{};       // kernels that served the current / last session (halo_last_route)
   uint32_t route_root = 0;     // ... and the root profiles among them (halo_last_root_profile): bit kRootProfile* - 1
 
@@ -637,6 +647,7 @@ int halo_destroy(halo_handle_t b) {
               b->cont_tiles, b->lanes, b->fix, b->cont[0], b->cont[1], b->exits, b->host_f, b->host_u);
   for (int k = 0; k < 2; k++) release_all(b->bin_list_s[k], b->bin_cnt_s[k], b->bin_list2_s[k], b->bin_cnt2_s[k]);
   for (int k = 0; k < 2; k++) release_all(b->tile_chunk_s[k], b->tile_cnt_s[k]);
+  release_all(b->ticket_cnt);
   if (b->ring_host) (void)hipHostFree(b->ring_host);
   if (b->tally_host) (void)hipHostFree(b->tally_host);
   for (int k = 0; k < HaloBackend::kRing; k++)
@@ -709,6 +720,10 @@ int halo_set_option(halo_handle_t b, const char* key, int64_t v) {
   else if (k == "close_direct") b->close_direct = v < 0 ? -1 : (v ? 1 : 0);
   else if (k == "lean_events") b->lean_events = v ? 1 : 0;
   else if (k == "tile_append") b->tile_append = v < 0 ? -1 : (v ? 1 : 0);
+  else if (k == "tile_ticket") b->tile_ticket = v < -1 ? -2 : v < 0 ? -1 : (v ? 1 : 0);
+  else if (k == "ticket_min") b->ticket_min = static_cast<uint32_t>(std::min<int64_t>(std::max<int64_t>(v, 1), 1024));
+  else if (k == "ticket_max") b->ticket_max = static_cast<uint32_t>(std::min<int64_t>(std::max<int64_t>(v, 1), 1024));
+  else if (k == "ticket_div") b->ticket_div = static_cast<uint32_t>(std::min<int64_t>(std::max<int64_t>(v, 1), 64));
   else if (k == "pool_entry_fast") b->pool_entry_fast = v ? 1 : 0;
   else if (k == "rehit_strategy") {
     if (b->in_session) return fail(b, HALO_FATAL, "rehit_strategy cannot change inside a session");
@@ -1175,6 +1190,7 @@ struct LaunchPlan {
   bool only = false;                    // the layer's only launch, on the session's last layer (halo_trace_layer)
   bool close = false;                   // ... that closes its session in its per-tile pass (close_direct_ok): nothing is left in the planes
   bool tile = false;                    // ... and whose trace kernel appends per tile (bind_tile_append): the closing pass reads chunks, no split pass
+  bool ticket = false;                  // ... in its ticketed form: `blocks` is then one resident round at the most (bind_tile_append)
   bool fixed = false;                   // a deterministic session's launch: the kAccFixed kernels, with use_log their logging twins (or, where every exit continues, kAccNone)
   uint32_t fan_log2 = 0, lists1 = 0, bin_tiles = 0, log_t_log2 = 0, log_planes = 1, log_tiles = 0;
   uint64_t cap1 = 0, cap2 = 0;          // records per region / coarse list and per tile list, as REQUESTED: reserve_log_buffers clamps the log's against free memory
@@ -1222,7 +1238,9 @@ int blocks_of(const HaloBackend& b, uint64_t m, bool pool) {
   //  for the closing pass: the trace kernel of configs[1] at 6 / 8 / 12 / 16 / 24 / 32 / 48 per CU 1.74 / 1.71 / 1.60 / 1.55 / 1.53 / 1.51 / 1.51 ms
   //  (32 and 48 are capped by `want` like 24) — ONE round of resident workgroups ends with its slowest, 0.2 ms behind several rounds that even the
   //  tail out — and that is four times what the closing pass gains from the longer chunks of the smaller grid (0.20 -> 0.14 ms at 6 per CU, 0.16
-  //  at 12): 24 stays, for these launches too.  profiles/resident_grid_ab.txt.)
+  //  at 12): 24 stays, for the static loop of these launches too.  profiles/resident_grid_ab.txt.  With wave tickets — option tile_ticket,
+  //  bind_tile_append — such a launch runs ONE resident round whose waves draw their passes from counters: the round's tail is one short ticket
+  //  long: five rounds against the parent, medians, trace kernel 1.513 -> 1.484 ms AND closing pass 0.179 -> 0.150.  profiles/wave_tickets_ab.txt.)
   // Small launches — a Lumice server that keeps a GPU route's small dispatch (2^15 .. 2^18 rays per session, server.cpp:140-151) sends nothing
   // else — are latency: one pass of the ray loop is ~11 us on a wave that has its SIMD to itself, so they spread over as many workgroups as
   // a CU holds (five) before a workgroup takes a second pass.  (Round 4 had found the opposite — one per CU best — while every WAVE ended
@@ -1628,7 +1646,8 @@ bool close_direct_ok(const HaloBackend& b, const LaunchPlan& p, const DispatchPa
 // free memory; what a chunk cannot hold goes to the twin.  A reserve that fails leaves the launch on the split route.  Writes the tile fields of P.
 int bind_tile_append(HaloBackend* b, LaunchPlan& p, const EntryTables& T, int ls, DispatchParams& P) {
   P.tile_chunk = nullptr, P.tile_cnt = nullptr, P.tile_cap = P.tile_log2 = P.tile_tiles = 0u;
-  p.tile = false;
+  P.ticket = nullptr, P.ticket_waves = P.ticket_min = P.ticket_max = 0u;
+  p.tile = p.ticket = false;
   // auto: launches that fill the chip, over generated roots.  (A last layer over the continuation pool — configs[2]: five times the records per
   // launch, hot tiles past their chunks — measured slower with the append, profiles/tile_append_ab.txt: 1 takes it, auto does not.)
   if (!p.close || b->tile_append == 0 || (b->tile_append < 0 && (p.alternate || P.source != kSrcGen))) return HALO_OK;
@@ -1640,6 +1659,30 @@ int bind_tile_append(HaloBackend* b, LaunchPlan& p, const EntryTables& T, int ls
     return HALO_OK;
   const uint32_t t_log2 = std::min<uint32_t>(p.log_t_log2, static_cast<uint32_t>(__builtin_ctz(kTileAppendMax)));
   if (b->mono_s_log2 + 10u < t_log2 || b->mono_s_log2 + 10u - t_log2 > kBinTileLog2) return HALO_OK;
+  // Wave tickets: auto follows tile_append's auto rule (a launch that fills the chip, over generated roots), whatever tile_append itself is set to.
+  // The grid is the workgroups that are resident at once — chunks and counts below are sized from it.  A wave may trace more than its even share
+  // now; the chunk's cap stays 8 x the even share, and what runs over goes to the twin as before.
+  // (mirrored from halo_trace.inl ticket_kernel_exists: every lens of the append but the dual fisheye)
+  // The default (-2) asks for more: a static grid of more than one resident round — a launch that fits into one round has no rounds to even out,
+  // and its landed tally stays the static loop's to the last digit (tests/test_gpu_tile_append_sessions.py compares it at 1e-12).
+  const int round = (b->tile_ticket != 0 && lens != HALO_LENS_DUAL_FISHEYE_EQUAL_AREA) ? tile_ticket_resident_per_cu() * b->cu_count : 0;
+  const bool want_ticket = round > 0 && (b->tile_ticket > 0 || (!p.alternate && P.source == kSrcGen && (b->tile_ticket == -1 || p.blocks > round)));
+  const int resident = want_ticket ? round : 0;
+  uint32_t* ticket = nullptr;
+  if (resident > 0) {
+    if (!b->ticket_zeroed) {   // (counters that were reserved but never seen zeroed are not used: a kernel that finds them past its passes traces nothing)
+      hipError_t e0 = hipSuccess;
+      if (int rc = reserve_idle(b, b->ticket_cnt, 2u * kTicketGroups * kTicketStride, &e0)) return rc;
+      if (e0 == hipSuccess) {
+        HIPCHK(b, hipMemsetAsync(b->ticket_cnt.ptr, 0, 2u * kTicketGroups * kTicketStride * sizeof(uint32_t), main_q(b)));
+        HIPCHK(b, hipStreamSynchronize(main_q(b)));   // (once per handle: the trace streams are not ordered behind the main stream's memset)
+        b->ticket_zeroed = true;
+      } else (void)hipGetLastError();
+    }
+    if (b->ticket_zeroed && b->ticket_cnt.ptr != nullptr) ticket = b->ticket_cnt.ptr + static_cast<size_t>(ls) * kTicketGroups * kTicketStride;
+  }
+  const int blocks_was = p.blocks;
+  if (ticket != nullptr) p.blocks = std::min(p.blocks, resident);
   const uint64_t tiles = 1ull << t_log2, blocks = static_cast<uint64_t>(p.blocks), chunks = tiles * blocks;
   const uint64_t per_wg = (p.m + blocks - 1u) / blocks;
   uint64_t cap = std::max<uint64_t>(8ull * 4ull * per_wg / tiles, 16ull);
@@ -1650,13 +1693,17 @@ int bind_tile_append(HaloBackend* b, LaunchPlan& p, const EntryTables& T, int ls
   if (need > have && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need - have > free_b / 2u)
     cap = (have + free_b / 2u) / (chunks * sizeof(HitRec));
   cap &= ~1ull;   // a chunk starts on 16 bytes
-  if (cap < 2u) return HALO_OK;
+  if (cap < 2u) {
+    p.blocks = blocks_was;
+    return HALO_OK;
+  }
   hipError_t e1 = hipSuccess, e2 = hipSuccess;
   if (int rc = reserve_idle(b, b->tile_chunk_s[ls], cap * chunks, &e1)) return rc;
   if (e1 == hipSuccess)
     if (int rc = reserve_idle(b, b->tile_cnt_s[ls], chunks, &e2)) return rc;
   if (e1 != hipSuccess || e2 != hipSuccess) {
     (void)hipGetLastError();   // out of memory: not this launch's route
+    p.blocks = blocks_was;
     return HALO_OK;
   }
   if (b->overlap && p.alternate) {   // the other set with it, as reserve_log_buffers does (a speed matter only)
@@ -1667,6 +1714,10 @@ int bind_tile_append(HaloBackend* b, LaunchPlan& p, const EntryTables& T, int ls
     if (e3 != hipSuccess || e4 != hipSuccess) (void)hipGetLastError();
   }
   p.tile = true;
+  p.ticket = ticket != nullptr;
+  P.ticket = ticket;
+  P.ticket_waves = std::max<uint32_t>(static_cast<uint32_t>(p.blocks) * static_cast<uint32_t>(kBlock / 64) * b->ticket_div / kTicketGroups, 1u);
+  P.ticket_min = b->ticket_min, P.ticket_max = b->ticket_max;
   P.tile_chunk = b->tile_chunk_s[ls].ptr, P.tile_cnt = b->tile_cnt_s[ls].ptr;
   P.tile_cap = static_cast<uint32_t>(cap), P.tile_tiles = static_cast<uint32_t>(tiles), P.tile_log2 = b->mono_s_log2 + 10u - t_log2;
   return HALO_OK;
@@ -1765,10 +1816,11 @@ int queue_passes(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, c
     // the closing pass over the chunks the trace kernel filled: no split, no list counters; the twin's flag is cleared behind the pass as below
     const float coef[3] = {b->plane_coef[0][0], b->plane_coef[0][1], b->plane_coef[0][2]};
     hipError_t ce = launch_tile_route_close(b->acc, static_cast<uint32_t>(b->acc_w) * static_cast<uint32_t>(b->acc_h), coef, P.tile_chunk, P.tile_cap, P.tile_cnt,
-                                            static_cast<uint32_t>(p.blocks), P.tile_tiles, b->mono_s_log2, frac_bits, P.ovf, P.ovf_flag, ps, before_sums);
+                                            static_cast<uint32_t>(p.blocks), P.tile_tiles, b->mono_s_log2, frac_bits, P.ovf, P.ovf_flag, ps, before_sums, P.ticket);
     if (ce != hipSuccess) return hip_fail(b, ce, "halo_tile_close_kernel launch");
     b->direct_closes++;
     b->tile_appends++;
+    if (p.ticket) b->tile_tickets++;
     static const bool debug_counts = std::getenv("HALO_DEBUG_TILE_COUNTS") != nullptr;
     if (debug_counts) {   // (a host sync per launch: what the chunks of this launch hold, for profiles/ — never on a timed path)
       std::vector<uint32_t> cnt(static_cast<size_t>(P.tile_tiles) * static_cast<size_t>(p.blocks));
@@ -2329,6 +2381,23 @@ int halo_tile_appends(halo_handle_t b, uint64_t* out) {
   *out = b->tile_appends;
   return HALO_OK;
 }
+
+int halo_tile_tickets(halo_handle_t b, uint64_t* out) {
+  if (!b || !out) return HALO_FATAL;
+  *out = b->tile_tickets;
+  return HALO_OK;
+}
+
+// The ticket rule the ticketed kernels apply (halo_device.h TicketSize), for tests/test_ticket_size.py: no device needed.
+uint32_t halo_host_ticket_size(uint32_t total, uint32_t seen, uint32_t waves, uint32_t lo, uint32_t hi) { return TicketSize(total, seen, waves, lo, hi); }
+// ... and the ranges of a launch's passes with a counter each, and the range a wave turns to (TicketRangeOf, TicketNextRange)
+uint32_t halo_host_ticket_groups(void) { return kTicketGroups; }
+void halo_host_ticket_range(uint32_t all, uint32_t g, uint32_t* first, uint32_t* n) {
+  const TicketRange r = TicketRangeOf(all, g);
+  if (first) *first = r.first;
+  if (n) *n = r.n;
+}
+uint32_t halo_host_ticket_next(uint64_t open, uint32_t home) { return open ? TicketNextRange(open, home) : kTicketGroups; }
 
 int halo_last_root_profile(halo_handle_t b, uint32_t* out) {
   if (!b || !out) return HALO_FATAL;

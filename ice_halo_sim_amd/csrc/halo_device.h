@@ -350,8 +350,63 @@ struct DispatchParams {
   uint32_t spec_k0;            // the spectrum entry of this launch's first ray ...
   uint32_t spec_rem;           // ... and how many rays of the launch, from the first on, still belong to it (>= 1): SpectrumChunk, SpectrumEntry
   uint32_t spec_last;          // entries - 1
+  // --- wave tickets (option "tile_ticket": the ticketed form of the kAccTileFinal kernels, one resident round of workgroups) --------
+  uint32_t* ticket;            // the launch's kTicketGroups counters of wave-passes handed out, kTicketStride words apart (nullptr = the static ray loop):
+                               // zero when the kernel starts, returned to zero by the closing pass behind it (halo_tile_close_kernel)
+  uint32_t ticket_waves;       // the rule's divisor: ticket_div x the waves of the grid that are at home on one counter (>= 1)
+  uint32_t ticket_min;         // smallest and largest ticket, in wave-passes (TicketSize)
+  uint32_t ticket_max;
 };
 constexpr uint32_t kTileAppendMax = 128u;   // counters of a kAccTileFinal workgroup (LDS)
+
+// Wave tickets.  A launch of n rays is ceil(n / 64) wave-passes (pass q: lane l traces ray 64 q + l), cut into kTicketGroups ranges with a counter
+// each; `total` below is the passes of one range.  A wave of a ticketed kernel reserves passes [old, old + size) of a range with one returning add
+// of `size` on its counter and turns to the next range when old >= total.  The size is guided: the share
+// one wave would get of what was left when the wave last looked (`seen`: a plain read of the counter just before the add), between lo and hi —
+// long tickets while there is plenty (few adds on the counter's line: they serialise memory-side), short ones at the end (the tail of the launch
+// is one last ticket long).  Any size is correct: the add reserves the range, whatever the other waves believe.  The kernel and the host
+// (halo_host_ticket_size: tests/test_ticket_size.py) share this one function.
+constexpr uint32_t kTicketMin = 4u, kTicketMax = 64u;   // the defaults (profiles/wave_tickets_ab.txt: the sweep)
+constexpr uint32_t kTicketDiv = 2u;      // `waves` of the rule = kTicketDiv x the waves of the grid: a wave takes HALF its even share of what is left, so
+                                         // the others need longer for the rest than the wave for its ticket — no ticket outlasts the counter by much
+constexpr uint32_t kTicketGroups = 64u;  // ranges of a launch's passes, each with a counter of its own: one per lane of a wave, which reads them all at once;
+                                         // 96 waves of the headline's grid are at home on each
+constexpr uint32_t kTicketStride = 32u;  // words between two counters: a 128-byte line each; a log set has kTicketGroups of them
+// The ranges: range g of kTicketGroups is passes [first, first + n) with first = min(g x per, all), per = ceil(all / kTicketGroups) — the last ranges
+// of a small launch are empty.  A wave that needs a range holds a 64-bit mask of the ranges that have passes left (lane g's bit: counter g read
+// below n of range g) and takes the first one at or after its home range, home = workgroup index mod kTicketGroups, wrapping round.
+// (halo_host_ticket_range / halo_host_ticket_next: the same functions, for tests/test_ticket_size.py.)
+struct TicketRange {
+  uint32_t first, n;
+};
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline TicketRange TicketRangeOf(uint32_t all, uint32_t g) {
+  const uint32_t per = all / kTicketGroups + (all % kTicketGroups != 0u ? 1u : 0u);
+  const uint64_t lo = static_cast<uint64_t>(g) * per;   // (64 bits: g x per passes `all` by up to 63 x per)
+  const uint32_t first = lo < all ? static_cast<uint32_t>(lo) : all;
+  const uint32_t left = all - first;
+  return TicketRange{first, left < per ? left : per};
+}
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline uint32_t TicketNextRange(uint64_t open, uint32_t home) {   // open != 0
+  home &= kTicketGroups - 1u;
+  const uint64_t rot = home != 0u ? (open >> home) | (open << (64u - home)) : open;
+  return (home + static_cast<uint32_t>(__builtin_ctzll(rot))) & (kTicketGroups - 1u);
+}
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline uint32_t TicketSize(uint32_t total, uint32_t seen, uint32_t waves, uint32_t lo, uint32_t hi) {
+  lo = lo ? lo : 1u;
+  hi = hi > lo ? hi : lo;
+  const uint32_t left = total > seen ? total - seen : 0u;
+  const uint32_t share = left / (waves ? waves : 1u);
+  return share < lo ? lo : (share > hi ? hi : share);
+}
 
 // Pixel → slot map of the mono plane.  The plane is kMonoRows rows of S = 2^s_log2 slots; pixel p sits in row p % kMonoRows
 // at column hash(p / kMonoRows).  Horizontal neighbours are a whole row (>= 8 KB) apart and vertical neighbours are

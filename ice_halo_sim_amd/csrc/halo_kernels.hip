@@ -662,8 +662,11 @@ constexpr uint32_t kCloseBatch = HALO_TILE_BATCH;   // chunks whose counts one w
 constexpr uint32_t kCloseKeep = 4u;     // batches per wave whose counts stay in registers from the `any` pre-pass on (16 waves x 32 x 4 = 2048 chunks)
 static_assert(kCloseBatch % kChunksInFlight == 0u && kCloseBatch <= 64u, "a batch is whole groups of chunks, one count per lane");
 __global__ void __launch_bounds__(kBinBlock) halo_tile_close_kernel(const uint2* __restrict__ chunk, uint32_t cap, const uint32_t* __restrict__ cnt, uint32_t wgs,
-                                                                    uint32_t tile_log2, uint32_t frac_bits, const CloseArgsOf<true> cl) {
+                                                                    uint32_t tile_log2, uint32_t frac_bits, const CloseArgsOf<true> cl, uint32_t* __restrict__ ticket) {
   __shared__ __attribute__((aligned(16))) unsigned long long acc[1u << kBinTileLog2];   // fixed point (FixQ); tile_log2 <= kBinTileLog2
+  // the ticket counters of the trace kernel in front of this pass (wave tickets: nullptr without them) goes back to zero here — no stream operation
+  // of its own; the log set's next user waits for this pass (set_free)
+  if (ticket != nullptr && blockIdx.x == 0u && threadIdx.x < kTicketGroups) ticket[threadIdx.x * kTicketStride] = 0u;
   const FixQ fq(frac_bits);
   const uint32_t tile = blockIdx.x;
   const uint32_t* tcnt = cnt + static_cast<size_t>(tile) * wgs;
@@ -761,7 +764,7 @@ __global__ void __launch_bounds__(kBinBlock) halo_tile_close_kernel(const uint2*
 // The closing form over per-tile chunks: chunk[tiles][wgs][cap] and cnt[tiles][wgs] as a kAccTileFinal trace kernel of `wgs` workgroups left them ->
 // coef x sum added to the XYZ image.  No split pass, no tile lists, no counter to reset; the 4-byte memset of the twin's flag behind the pass stays.
 hipError_t launch_tile_route_close(float* xyz, uint32_t n_pix, const float* coef, const HitRec* chunk, uint32_t cap, const uint32_t* cnt, uint32_t wgs, uint32_t tiles,
-                                   uint32_t s_log2, uint32_t frac_bits, double* ovf, uint32_t* ovf_flag, hipStream_t stream, hipEvent_t before_sums) {
+                                   uint32_t s_log2, uint32_t frac_bits, double* ovf, uint32_t* ovf_flag, hipStream_t stream, hipEvent_t before_sums, uint32_t* ticket) {
   if (tiles == 0u || (tiles & (tiles - 1u)) != 0u || tiles > kTileAppendMax || wgs == 0u || cap == 0u || (cap & 1u) != 0u) return hipErrorInvalidValue;
   if (xyz == nullptr || coef == nullptr || chunk == nullptr || cnt == nullptr || ovf == nullptr || ovf_flag == nullptr) return hipErrorInvalidValue;
   const uint32_t tiles_log2 = static_cast<uint32_t>(__builtin_ctz(tiles));
@@ -770,7 +773,7 @@ hipError_t launch_tile_route_close(float* xyz, uint32_t n_pix, const float* coef
   hipError_t e = hipSuccess;
   if (before_sums && (e = hipStreamWaitEvent(stream, before_sums, 0)) != hipSuccess) return e;
   const CloseArgsOf<true> cl{xyz, n_pix, s_log2, {coef[0], coef[1], coef[2]}, nullptr, ovf, ovf_flag};
-  hipLaunchKernelGGL(halo_tile_close_kernel, dim3(tiles), dim3(kBinBlock), 0, stream, reinterpret_cast<const uint2*>(chunk), cap, cnt, wgs, s_log2 + 10u - tiles_log2, frac_bits, cl);
+  hipLaunchKernelGGL(halo_tile_close_kernel, dim3(tiles), dim3(kBinBlock), 0, stream, reinterpret_cast<const uint2*>(chunk), cap, cnt, wgs, s_log2 + 10u - tiles_log2, frac_bits, cl, ticket);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   return hipMemsetAsync(ovf_flag, 0, sizeof(uint32_t), stream);   // every workgroup has seen it; the pass zeroed what it took
 }

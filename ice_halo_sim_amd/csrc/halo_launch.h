@@ -13,6 +13,8 @@ struct CrystalRecipe;
 }
 
 hipError_t launch_trace(const DispatchParams& P, int blocks, hipStream_t stream, int mode, int geom, bool mono);
+// workgroups of a ticketed kAccTileFinal kernel (DispatchParams::ticket) that one CU holds at once: the occupancy query, made once
+int tile_ticket_resident_per_cu();
 hipError_t launch_bin_accumulate(float* plane, const HitRec* list, uint32_t cap, uint32_t* cnt, uint32_t tiles, uint32_t frac_bits, hipStream_t stream);
 hipError_t launch_bin_two_level(float* plane, const HitRec* list1, uint32_t cap1, uint32_t* cnt1, uint32_t lists1, HitRec* list2, uint32_t cap2,
                                 uint32_t* cnt2, uint32_t tiles, uint32_t fan_log2, uint32_t frac_bits, double* ovf, uint32_t* ovf_flag, hipStream_t stream, hipEvent_t before_sums);
@@ -28,7 +30,8 @@ hipError_t launch_log_route_close(float* xyz, uint32_t n_pix, const float* coef,
                                   hipStream_t stream, hipEvent_t before_sums);
 // (the same close over the per-tile chunks of a kAccTileFinal trace kernel of `wgs` workgroups: chunk[tiles][wgs][cap], cnt[tiles][wgs]; no split pass)
 hipError_t launch_tile_route_close(float* xyz, uint32_t n_pix, const float* coef, const HitRec* chunk, uint32_t cap, const uint32_t* cnt, uint32_t wgs, uint32_t tiles,
-                                   uint32_t s_log2, uint32_t frac_bits, double* ovf, uint32_t* ovf_flag, hipStream_t stream, hipEvent_t before_sums);
+                                   uint32_t s_log2, uint32_t frac_bits, double* ovf, uint32_t* ovf_flag, hipStream_t stream, hipEvent_t before_sums,
+                                   uint32_t* ticket = nullptr);   // ticket: a ticketed trace kernel's counter, which the pass returns to zero (halo_device.h TicketSize)
 // (the deterministic route's log: integer planes, the session's F, atomics only — no fp64 twin, no ordering event)
 hipError_t launch_log_route_fixed(unsigned long long* fix, const HitRec* log, uint32_t cap1, const uint32_t* cnt1, uint32_t regions, HitRec* list2, uint32_t cap2,
                                   uint32_t* cnt2, uint32_t tiles, uint32_t s_log2, bool interleaved, uint32_t frac_bits, hipStream_t stream);

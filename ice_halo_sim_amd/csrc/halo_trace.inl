@@ -274,6 +274,11 @@ HD uint32_t lat_lut_bin(float theta, const float* lut) {
 // source, the latitude path and the five distribution kinds (three of which carry logf / cosf / sinf) fold away, and with them 60 % of the
 // kernel's code.  Same expressions, draws and stream slots.
 constexpr int kRootAny = -1, kRootGenLutUniform = 0, kRootTransitLutUniform = 1;
+// ... and the ticketed form of a kAccTileFinal kernel (DispatchParams::ticket, halo_device.h TicketSize) rides on the same template argument, so
+// that no kernel of the static form changes its name: ROOT + kRootTicket is the ticketed twin of root form ROOT.
+constexpr int kRootTicket = 16;
+constexpr bool root_ticketed(int root) { return root >= kRootTicket + kRootAny; }
+constexpr int root_form(int root) { return root_ticketed(root) ? root - kRootTicket : root; }
 
 template <int ROOT = kRootAny>
 HD void sample_lat_lon_roll(Stream& s, const DispatchParams& P, const float* lut, float& lon, float& lat, float& roll) {
@@ -635,6 +640,7 @@ struct AccCtx {
   bool canon;        // canonical-order kernels (option cont_order = 1, layers before the last): appends carry their (root, interaction) key
   bool none;         // kAccNone kernels: every outgoing candidate continues (prob >= 1, not the last layer), nothing is projected
   bool fixed;        // kAccFixed kernels: hits and landed weight are summed as 64-bit fixed point (accumulate_fixed)
+  bool sum64;        // ticketed kernels: a lane sums landed and exit weight in fp64 (RaySums::landed64 / exit_w64) — which rays a lane traces changes from run to run
   ExitQueue* q;      // this wave's exit queue; nullptr = project and accumulate at the emit site
   ExitQueueMask* qm; // ... its colour-mask planes (kModeColor)
   const FastTables __attribute__((address_space(4)))* fast;   // kModeFilter / kModeColor: the dispatch's filter + colour predicates (dispatch-uniform, scalar loads)
@@ -920,7 +926,8 @@ struct RaySums {
   uint32_t qn;   // exit queue fill (see ExitQueue)
   unsigned long long landed_q;   // kAccFixed kernels: the landed weight as an integer, FixQ(fix_frac_landed) of every primary hit (`landed` is not tallied)
   double landed64;               // capture kernels (MODE == kModeCapture): the landed weight in fp64 from the first add, so that a session whose exits were
-                                 // captured lands exactly the sum of its records' weights (`landed` is not tallied); a member no other kernel touches
+                                 // captured lands exactly the sum of its records' weights (`landed` is not tallied); the ticketed kernels sum here too
+  double exit_w64;               // ticketed kernels (AccCtx::sum64): the exit weight likewise
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -1491,6 +1498,7 @@ HD int land_exit(const DispatchParams& P, const AccCtx<MONO, SMALLC, FL>& cache,
     if (ModeTraits<MODE>::kTables && color != nullptr) fan_lanes(P, *color, cmask, pix, cmf_y * w);
     if constexpr (MODE == kModeColor) fan_lanes_fast(P, *cache.fast, cmask, pix, cmf_y * w);
     if constexpr (MODE == kModeCapture) sums.landed64 += static_cast<double>(w);   // (fp64 all the way: RaySums::landed64)
+    else if (cache.sum64) sums.landed64 += static_cast<double>(w);
     else sums.landed += w;  // bump_landed: primary hit only (scatter_accum.hpp:96-108)
     if constexpr (!SMALLC && (MODE == kModePlain || MODE == kModeFilter)) {   // (only these have kAccFixed twins; the test is not even compiled into the others)
       if (cache.fixed) sums.landed_q += FixQ(P.fix_frac_landed).fix(w);     // ... which tally this integer instead
@@ -1653,7 +1661,8 @@ HD void emit_gate(const DispatchParams& P, const AccCtx<MONO, SMALLC, FL>& cache
   if (queued) {
     if (P.prob >= 1.0f) return;   // dispatch-uniform: every candidate of this layer continues, nothing goes to the image
     const bool out = live && !pass;
-    sums.exit_w += out ? w : 0.0f;
+    if (cache.sum64) sums.exit_w64 += out ? static_cast<double>(w) : 0.0;
+    else sums.exit_w += out ? w : 0.0f;
     sums.exit_n += out ? 1u : 0u;   // (counted per lane: one popcount of the ballot per emit, a scalar add, measured 2.7 % SLOWER at configs[1])
     // (taking the cull's view axis from the LDS copy of the projection as well — HALO_PROJ_LDS — measured the same: 1.668 vs 1.669 ms)
     const bool want = out && exit_may_land(P.proj, wx, wy, wz, cache.lens, cache.vis);
@@ -2710,8 +2719,11 @@ constexpr int min_waves() {
 // 2.96 -> 2.73 (lens) -> 2.60 ms per launch.  Done for the last-layer one-shape scalar kernels and the lenses of the shipped examples.
 // CANON: a layer before the last under canonical continuation order (option cont_order = 1) — its appends carry their (root, interaction) key.
 // ROOT: a root profile (kRoot*, at sample_lat_lon_roll) — the last-layer plain hit-log kernels of the regular prism, which launch_vis fans out.
-template <int MODE, int GEOM, bool MONO, int ACC, int LENS = -1, int VIS = -1, bool NOGATE = false, bool CANON = false, int ROOT = kRootAny>   // ACC: kAccDirect, kAccBin (staged + binned hit lists), kAccLog (per-workgroup hit log), ...
+template <int MODE, int GEOM, bool MONO, int ACC, int LENS = -1, int VIS = -1, bool NOGATE = false, bool CANON = false, int ROOT_ARG = kRootAny>   // ACC: kAccDirect, kAccBin (staged + binned hit lists), kAccLog (per-workgroup hit log), ...
 __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) halo_trace_kernel(const DispatchParams P) {
+  constexpr int ROOT = root_form(ROOT_ARG);
+  constexpr bool TICKET = root_ticketed(ROOT_ARG);   // every wave draws its passes of the ray loop from the launch's counter (below)
+  static_assert(!TICKET || ACC == kAccTileFinal, "wave tickets exist for the per-tile append's kernels");
   constexpr bool BIN = ACC == kAccBin, TILE = ACC == kAccTileFinal, LOG = ACC == kAccLog || ACC == kAccLogFinal || TILE, NONE = ACC == kAccNone, LAST = ACC == kAccLogFinal || TILE, FIXLOG = ACC == kAccFixedLog, FIXED = ACC == kAccFixed || FIXLOG;
   static_assert(!TILE || (MODE == kModePlain && GEOM == kGeomOneHex && MONO), "the per-tile append exists for the headline's kernels: plain mode, one regular prism, scalar plane");
   static_assert(!FIXLOG || !CANON, "a canonical layer before the last never logs");
@@ -2754,6 +2766,7 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
   }
   acc.none = NONE;
   acc.fixed = FIXED;
+  acc.sum64 = root_ticketed(ROOT_ARG);
   acc.last = LAST;
   acc.canon = CANON;
   acc.lens = LENS;
@@ -2970,6 +2983,72 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
     }
    }
   }
+  // Wave tickets: the grid is one resident round, and a WAVE that has finished its passes reserves the next ones — [old, old + size) of the launch's
+  // ceil(n_rays / 64), lane l of pass q tracing ray 64 q + l — with one returning add; a fast wave takes more, a slow one fewer, and nobody waits for
+  // anybody: a workgroup that arrives late finds no ticket and falls through to the epilogue.  The rays traced are the static form's, ray by ray.
+  // Which rays a lane traces, and in which tickets, changes from run to run (a ticket's size follows a racy read of its counter), so a lane sums
+  // landed and exit weight in fp64 from the first add (AccCtx::sum64): the tallies of two runs differ by the order of fp64 adds of fp32 terms and
+  // no more.  (Per-ticket fp32 sums joined in fp64 were the first form: reproducible only while every ticket had the smallest size — the
+  // boundaries of guided tickets move — rel 5e-11 from run to run at the headline's shape.)
+  double* ticket_sums = nullptr;
+  if constexpr (TICKET) {
+    static_assert(QUEUE && !POOL && !BIN, "the ticketed loop is the one-shape queue kernels'");
+    __shared__ double s_ticket_sums[kBlock / 64][2];
+    // (ticket state is wave-uniform and stays in SGPRs: the wave's first thread index, and through it the lane test and the ray index)
+    const uint32_t wave0 = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x))) & ~63u;
+    ticket_sums = s_ticket_sums[wave0 >> 6];
+    const bool first_lane = threadIdx.x == wave0;
+    const uint32_t total = (P.n_rays >> 6) + ((P.n_rays & 63u) != 0u ? 1u : 0u);
+    // The passes are cut into kTicketGroups equal ranges, each with a counter on a line of its own.  Returning adds on ONE line serialise memory-side,
+    // and waves that start together come back for their next ticket together: with a single counter the headline's kernel ran at the pace of that
+    // line (1.5 -> 3.7 ms), with eight every round of tickets still cost the waves a queue of 768 (profiles/wave_tickets_ab.txt).  A wave starts at
+    // the range of its workgroup's index and, when that one is handed out, looks at ALL counters at once — lane l reads counter l — and goes on to
+    // the next range after its own that has passes left: it steals, and never waits.
+    static_assert(kTicketGroups == 64u, "one lane of a wave per counter");
+    uint32_t first = 0u, gtotal = 0u;
+    uint32_t* ctr = nullptr;
+    bool have = false;   // a range in hand
+    for (;;) {
+      // what is left of the range NOW, by a plain read of its counter (a wave draws a handful of tickets in its life; the `old` of its last one
+      // is a whole ticket stale), and a range that is handed out costs no add on its line
+      uint32_t seen = 0u;
+      if (!have) {
+        const uint32_t l = threadIdx.x - wave0;
+        const uint32_t c = __hip_atomic_load(P.ticket + l * kTicketStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint64_t m = __ballot(c < TicketRangeOf(total, l).n);
+        if (m == 0ull) break;
+        const uint32_t g = TicketNextRange(m, blockIdx.x);
+        seen = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(c), static_cast<int>(g)));
+        const TicketRange range = TicketRangeOf(total, g);
+        first = range.first;
+        gtotal = range.n;
+        ctr = P.ticket + g * kTicketStride;
+        have = true;
+      } else {
+        seen = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))));
+        if (seen >= gtotal) {
+          have = false;
+          continue;
+        }
+      }
+      const uint32_t size = TicketSize(gtotal, seen, P.ticket_waves, P.ticket_min, P.ticket_max);
+      uint32_t old = 0u;
+      if (first_lane) old = atomicAdd(ctr, size);
+      old = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(old)));
+      if (old >= gtotal) {
+        have = false;
+        continue;
+      }
+      // (working out where the counter stands from the wave's own last ticket, instead of reading it, measured slower: the estimate runs late
+      //  and the last tickets come out long — profiles/wave_tickets_ab.txt, ticket_read = 0)
+      old += first;
+      const uint32_t end = min(old + size, first + gtotal);   // (no wrap: total <= 2^26, and every wave's last add on a counter is one ticket past its range)
+      for (uint32_t q = old; q < end; ++q) {
+        const uint32_t tid = ((q << 6) - wave0) + threadIdx.x;   // 64 q + lane
+        if (tid < P.n_rays) trace_one<MODE, MONO, SMALLC, GEOM == kGeomOneHex, ROOT>(P, T, acc, filter, color, &s_shape.s[0], wl0, tid, sums, pr);
+      }
+    }
+  } else
   if (!staged) {
     for (uint32_t base = blockIdx.x * kBlock; base < P.n_rays; base += stride) {   // workgroup-uniform trip count
       const uint32_t tid = base + threadIdx.x;
@@ -3060,10 +3139,14 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
   // reads differences (halo_backend.cpp pull_tally).
   __shared__ float s_tally[kBlock / 64][4];
   {
-    const float landed = FIXED ? 0.0f : wave_sum(sums.landed);   // (kAccFixed: the landed weight leaves as an integer, below)
-    const float exit_w = wave_sum(sums.exit_w);
+    const float landed = (FIXED || TICKET) ? 0.0f : wave_sum(sums.landed);   // (kAccFixed: the landed weight leaves as an integer, below; tickets: ticket_sums)
+    const float exit_w = TICKET ? 0.0f : wave_sum(sums.exit_w);
     const float exit_n = wave_sum(static_cast<float>(sums.exit_n));
     const float pix_n = wave_sum(static_cast<float>(sums.pix_n));
+    if constexpr (TICKET) {   // the fp64 lane sums: the wave's into its slot (the static form's `landed` and `exit_w` above are 0)
+      const double l64 = wave_sum(sums.landed64), e64 = wave_sum(sums.exit_w64);
+      if ((threadIdx.x & 63) == 0) ticket_sums[0] = l64, ticket_sums[1] = e64;
+    }
     if ((threadIdx.x & 63) == 0) {
       float* t = s_tally[threadIdx.x >> 6];
       t[kSumLanded] = landed, t[kSumExitW] = exit_w, t[kSumExitN] = exit_n, t[kSumPixN] = pix_n;
@@ -3073,6 +3156,10 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
       double v = 0.0;
 #pragma unroll
       for (int w = 0; w < kBlock / 64; ++w) v += static_cast<double>(s_tally[w][threadIdx.x]);
+      if constexpr (TICKET) {   // landed and exit weight: the waves' fp64 slots (written before the barriers above)
+        if (threadIdx.x < 2u)
+          for (int w = 0; w < kBlock / 64; ++w) v += ticket_sums[2 * w + static_cast<int>(threadIdx.x)];   // (wave 0's pointer: slot [0][0])
+      }
       if (v != 0.0) atomicAdd(&P.tally[(blockIdx.x & (kTallyLines - 1u)) * kTallyStride + threadIdx.x], v);
     }
   }
@@ -3121,11 +3208,21 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
 //  spilled SGPRs, 10 spilled VGPRs and scratch against 4612 / 45 / 0 / none for the dual-fisheye instantiation, tools/isa_by_line.py.)
 // ... and, for the last-layer plain hit-log kernels of the regular prism alone, the root profile the host asks for (DispatchParams::root_profile,
 // halo_backend.cpp root_profile_of) — taken only when the record itself says what the profile assumes: a record that does not runs the generic form.
+// The ticketed twins (ROOT + kRootTicket) of the kAccTileFinal kernels.  Not for the dual fisheye: that instantiation's register allocation
+// answers the ticket loop with a spilled VGPR inside the ray loop (the pixel cache's slot index), and a ticketed kernel is held to none there.
+template <int ACC, int LENS>
+constexpr bool ticket_kernel_exists() { return ACC == kAccTileFinal && LENS != HALO_LENS_DUAL_FISHEYE_EQUAL_AREA; }
 template <int MODE, int GEOM, bool MONO, int ACC, int LENS, int VIS, bool NOGATE>
 static void launch_root(const DispatchParams& P, dim3 grid, dim3 block, hipStream_t stream) {
   if constexpr (MODE == kModePlain && GEOM == kGeomOneHex && MONO && (ACC == kAccLogFinal || ACC == kAccTileFinal) && NOGATE) {
     const bool lut_uniform = P.lat_path == kLatLut && P.az_type == HALO_DIST_UNIFORM && P.roll_type == HALO_DIST_UNIFORM;
     if (lut_uniform && P.root_profile == kRootProfileGen && P.source == kSrcGen && P.spec_per == 0u) {
+      if constexpr (ticket_kernel_exists<ACC, LENS>()) {
+        if (P.ticket != nullptr) {
+          hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, MONO, ACC, LENS, VIS, NOGATE, false, kRootTicket + kRootGenLutUniform>), grid, block, 0, stream, P);
+          return;
+        }
+      }
       hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, MONO, ACC, LENS, VIS, NOGATE, false, kRootGenLutUniform>), grid, block, 0, stream, P);
       return;
     }
@@ -3133,7 +3230,19 @@ static void launch_root(const DispatchParams& P, dim3 grid, dim3 block, hipStrea
     //  answers the profile with 4 spilled VGPRs and scratch)
     constexpr bool kTransit = !(LENS == HALO_LENS_LINEAR && VIS == HALO_VISIBLE_FULL);
     if (kTransit && lut_uniform && P.root_profile == kRootProfileTransit && P.source == kSrcTransit) {
+      if constexpr (ticket_kernel_exists<ACC, LENS>()) {
+        if (P.ticket != nullptr) {
+          hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, MONO, ACC, LENS, kTransit ? VIS : HALO_VISIBLE_UPPER, NOGATE, false, kRootTicket + kRootTransitLutUniform>), grid, block, 0, stream, P);
+          return;
+        }
+      }
       hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, MONO, ACC, LENS, kTransit ? VIS : HALO_VISIBLE_UPPER, NOGATE, false, kRootTransitLutUniform>), grid, block, 0, stream, P);
+      return;
+    }
+  }
+  if constexpr (ticket_kernel_exists<ACC, LENS>()) {
+    if (P.ticket != nullptr) {
+      hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, MONO, ACC, LENS, VIS, NOGATE, false, kRootTicket + kRootAny>), grid, block, 0, stream, P);
       return;
     }
   }
@@ -3291,6 +3400,7 @@ static inline bool tile_kernel_exists(const DispatchParams& P, int geom, bool mo
 }
 template <int MODE>   // (a template so that only halo_trace_tl0.hip instantiates the kernels)
 static hipError_t launch_tile(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono) {
+  if (P.ticket != nullptr && (P.proj.proj_type == HALO_LENS_DUAL_FISHEYE_EQUAL_AREA || P.ticket_waves == 0u)) return hipErrorNotSupported;   // (ticket_kernel_exists)
   if (!tile_kernel_exists(P, geom, mono) || P.tile_cnt == nullptr || P.tile_tiles == 0u || P.tile_tiles > kTileAppendMax || (P.tile_cap & 1u) != 0u) return hipErrorNotSupported;
   dim3 grid(blocks), block(kBlock);
   switch (P.proj.proj_type) {

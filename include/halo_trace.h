@@ -346,7 +346,16 @@ const char* halo_last_error(halo_handle_t h);
  * eligible, whatever the launch size; halo_direct_closes counts them), "tile_append" (-1 [default]: a launch that closes directly, fills the chip and
  * runs a trace kernel with a per-tile twin — plain mode, one regular prism, scalar plane, closed gate, a lens that is a template constant — appends
  * its records to per-tile chunks of each workgroup, and the closing pass reads the chunks: no split pass; the same records reach the same integer
- * tile sums; 0: never; 1: wherever eligible, whatever the launch size; halo_tile_appends counts them), "lean_events" (1 [default]: markers that
+ * tile sums; 0: never; 1: wherever eligible, whatever the launch size; halo_tile_appends counts them), "tile_ticket" (-1: a launch
+ * that takes the per-tile append by "tile_append"'s auto rule — it fills the chip and runs over generated roots — runs ONE resident round of
+ * workgroups whose waves draw their passes of the ray loop, 64 rays each, from a counter: the same rays, ray by ray, traced by whichever wave is
+ * free; -2 [default]: as -1, for launches whose static grid is more than one resident round — the others have no rounds to even out and keep the
+ * static loop, and with it its landed tally to the last digit; 0: never, the static ray loop; 1: every launch that appends per tile, whatever its
+ * size; halo_tile_tickets counts them.  Counts are
+ * those of the static loop exactly; the image differs by the order of float adds; which rays a lane traces changes from run to run, so a ticketed
+ * launch sums its landed and exit weight in fp64 from the lane on, and two runs of one seed agree in them to rel 1e-12, not to the last
+ * bit), "ticket_min" / "ticket_max" / "ticket_div" (experiment knobs, UNSUPPORTED — they may go without notice: the bounds of a ticket in wave-passes and the divisor of the guided
+ * rule, halo_host_ticket_size; defaults 4 / 64 / 2), "lean_events" (1 [default]: markers that
  * fall on one point of one stream share one recorded event, and a trace stream does not wait again for a main stream that has been given nothing
  * since it last did; 0: every marker its own record, every launch the wait — the A/B switch; same results either way). */
 int halo_set_option(halo_handle_t h, const char* key, int64_t value);
@@ -442,6 +451,9 @@ int halo_direct_closes(halo_handle_t h, uint64_t* count);
 /* Launches, since halo_create, whose trace kernel appended its records per tile (option "tile_append"; additive in ABI 6, no struct changed — such a
  * launch is also counted by halo_direct_closes and still reports accum_mask bit 4).  A cumulative count. */
 int halo_tile_appends(halo_handle_t h, uint64_t* count);
+/* Launches, since halo_create, whose trace kernel drew its rays by wave tickets (option "tile_ticket"; additive, no struct changed — such a launch is
+ * also counted by halo_tile_appends and halo_direct_closes).  A cumulative count. */
+int halo_tile_tickets(halo_handle_t h, uint64_t* count);
 /* Bring the accumulator up to date WITHOUT a host wait: the closing folds of the ended sessions are queued and the backend's stream is made
  * to wait for them, so that work queued on that stream afterwards (a collective on a bound accumulator, a copy) sees the finished image.
  * Needed with option "defer_fold" = 1 (halo_end then leaves the fold of a caller-bound accumulator pending so that the next session's trace
@@ -650,6 +662,17 @@ int halo_host_color_fast_mask(const HaloColorSet* colors, const HaloAxis* axis, 
  * for the CMF rows).  The per-tile passes of the hit log use it with the rays of one launch, option "deterministic" with 2^30 for the planes
  * and 2^32 for the landed integer. */
 uint32_t halo_host_fixed_frac_bits(double max_w, uint64_t hits);
+/* The size, in wave-passes of 64 rays, of the ticket a wave of a ticketed launch (option "tile_ticket") asks for: the launch has `total` passes, the
+ * wave has just read the counter at `seen`, and the rule is clamp((total - seen) / waves, lo, hi) with lo >= 1 — the kernel
+ * passes waves = ticket_div x the waves of its grid.  The same function the kernel runs. */
+uint32_t halo_host_ticket_size(uint32_t total, uint32_t seen, uint32_t waves, uint32_t lo, uint32_t hi);
+/* The launch's `all` wave-passes are cut into halo_host_ticket_groups() ranges with a counter each: range g is passes [*first, *first + *n).  A wave
+ * whose home range is `home` (its workgroup's index; taken modulo the number of ranges) and which found the ranges of mask `open` (bit g: range g
+ * has passes left) unfinished turns to range halo_host_ticket_next(open, home): the first at or after home, wrapping round; the number of
+ * ranges when open is 0.  The same functions the kernel runs. */
+uint32_t halo_host_ticket_groups(void);
+void halo_host_ticket_range(uint32_t all, uint32_t g, uint32_t* first, uint32_t* n);
+uint32_t halo_host_ticket_next(uint64_t open, uint32_t home);
 /* IceRefractiveIndex::Get — optics.cpp:180-197. */
 double halo_host_refractive_index(double wavelength_nm);
 /* GetIlluminantSpd(type, wavelength) — util/illuminant.cpp:113-134 (HALO_ILLUM_*; 0 outside the tabulated range). */

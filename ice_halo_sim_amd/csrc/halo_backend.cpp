@@ -1510,7 +1510,7 @@ int upload_tables(HaloBackend* b, const LayerCtx& c, const LaunchPlan& p, const 
 }
 // The root profile a dispatch record matches exactly (halo_trace.inl kRoot*: LUT latitude, uniform azimuth and roll, generated roots or the
 // continuation pool); anything else keeps the generic root generation.  Whether an instantiation with that profile exists for the launch's
-// kernel is the launcher's business (launch_root) and record_route's.
+// kernel is the selector's business (halo_select.h with_root).
 uint32_t root_profile_of(const DispatchParams& P) {
   if (P.lat_path != kLatLut || P.az_type != HALO_DIST_UNIFORM || P.roll_type != HALO_DIST_UNIFORM) return kRootProfileNone;
   return P.source == kSrcGen ? kRootProfileGen : P.source == kSrcTransit ? kRootProfileTransit : kRootProfileNone;
@@ -1638,9 +1638,11 @@ bool close_direct_ok(const HaloBackend& b, const LaunchPlan& p, const DispatchPa
   if (P.ovf == nullptr || P.ovf_flag == nullptr || b.mono_dirty || b.acc == nullptr) return false;
   return b.close_direct > 0 || !p.alternate;   // auto: the hit log's own threshold chose the log; launches that fill the chip only
 }
-// The per-tile append of a launch that closes directly (HaloBackend::tile_append): taken where the launch's kernel has a kAccTileFinal twin — mirrored
-// from halo_trace.inl tile_kernel_exists: plain mode, one regular prism, scalar plane, last layer with a closed gate, one of the four lenses that are
-// template constants, the upper sky — and the chunk buffers of log set `ls` can be reserved.  Tiles: the close's own contiguous ones, at most
+// a one-shape dispatch of a regular hexagonal prism takes the literal-normal instantiation (kGeomOneHex = 3)
+int launch_geom_of(const HaloBackend& b, const LaunchPlan& p, const EntryTables& T) { return (p.geom == 0 && T.entry_fast && b.hex_fast && T.hex_regular) ? kGeomOneHex : p.geom; }
+// The per-tile append of a launch that closes directly (HaloBackend::tile_append): taken where the launch's kernel has a kAccTileFinal twin — the
+// selector is asked (halo_select.h: plain mode, one regular prism, scalar plane, last layer with a closed gate, one of the lenses that are
+// template constants, the upper sky) — and the chunk buffers of log set `ls` can be reserved.  Tiles: the close's own contiguous ones, at most
 // kTileAppendMax (a small launch's 256 become 128: the kernel holds one LDS counter per tile).  A chunk holds kListSlack (8) x its even share of the
 // 4 records per ray the log's regions are sized for, all chunks together within the lists' 8 GB (2^30 records: the kernel's 32-bit index) and half of
 // free memory; what a chunk cannot hold goes to the twin.  A reserve that fails leaves the launch on the split route.  Writes the tile fields of P.
@@ -1651,21 +1653,17 @@ int bind_tile_append(HaloBackend* b, LaunchPlan& p, const EntryTables& T, int ls
   // auto: launches that fill the chip, over generated roots.  (A last layer over the continuation pool — configs[2]: five times the records per
   // launch, hot tiles past their chunks — measured slower with the append, profiles/tile_append_ab.txt: 1 takes it, auto does not.)
   if (!p.close || b->tile_append == 0 || (b->tile_append < 0 && (p.alternate || P.source != kSrcGen))) return HALO_OK;
-  const int lens = P.proj.proj_type;
-  const bool lens_known = lens == HALO_LENS_LINEAR || lens == HALO_LENS_FISHEYE_EQUAL_AREA || lens == HALO_LENS_DUAL_FISHEYE_EQUAL_AREA || lens == HALO_LENS_RECTANGULAR;
-  const bool hex = p.geom == 0 && T.entry_fast && b->hex_fast && T.hex_regular;   // (queue_launch's launch_geom == 3)
-  if (T.mode != 0 || !hex || !b->mono_session || P.final_layer == 0u || P.prob > 0.0f || P.cont_mask != nullptr || P.no_land != 0u || P.fix != nullptr ||
-      P.mono_by_wl != 0u || P.proj.visible_range != HALO_VISIBLE_UPPER || !lens_known)
-    return HALO_OK;
+  const KernelRequest req = make_request(P, T.mode, launch_geom_of(*b, p, T), b->mono_session);
+  if (select_kernel(tile_request(req, false)).err != 0) return HALO_OK;   // this launch's kernel has no kAccTileFinal twin
   const uint32_t t_log2 = std::min<uint32_t>(p.log_t_log2, static_cast<uint32_t>(__builtin_ctz(kTileAppendMax)));
   if (b->mono_s_log2 + 10u < t_log2 || b->mono_s_log2 + 10u - t_log2 > kBinTileLog2) return HALO_OK;
   // Wave tickets: auto follows tile_append's auto rule (a launch that fills the chip, over generated roots), whatever tile_append itself is set to.
   // The grid is the workgroups that are resident at once — chunks and counts below are sized from it.  A wave may trace more than its even share
   // now; the chunk's cap stays 8 x the even share, and what runs over goes to the twin as before.
-  // (mirrored from halo_trace.inl ticket_kernel_exists: every lens of the append but the dual fisheye)
+  // (Only where the twin has a ticketed form: halo_select.h kernel_exists.)
   // The default (-2) asks for more: a static grid of more than one resident round — a launch that fits into one round has no rounds to even out,
   // and its landed tally stays the static loop's to the last digit (tests/test_gpu_tile_append_sessions.py compares it at 1e-12).
-  const int round = (b->tile_ticket != 0 && lens != HALO_LENS_DUAL_FISHEYE_EQUAL_AREA) ? tile_ticket_resident_per_cu() * b->cu_count : 0;
+  const int round = (b->tile_ticket != 0 && select_kernel(tile_request(req, true)).err == 0) ? tile_ticket_resident_per_cu() * b->cu_count : 0;
   const bool want_ticket = round > 0 && (b->tile_ticket > 0 || (!p.alternate && P.source == kSrcGen && (b->tile_ticket == -1 || p.blocks > round)));
   const int resident = want_ticket ? round : 0;
   uint32_t* ticket = nullptr;
@@ -1722,40 +1720,24 @@ int bind_tile_append(HaloBackend* b, LaunchPlan& p, const EntryTables& T, int ls
   P.tile_cap = static_cast<uint32_t>(cap), P.tile_tiles = static_cast<uint32_t>(tiles), P.tile_log2 = b->mono_s_log2 + 10u - t_log2;
   return HALO_OK;
 }
-// HaloRouteInfo (halo_last_route: what the GPU tests assert routes with).  The masks name the instantiation that launch_mode / launch_mono /
-// launch_lens / launch_vis in halo_trace.inl pick for this launch — mirrored here — not the request: the regular-prism search exists for
-// the production-shaped kernels off the binned route, the no-accumulation kernels for their one-shape dispatches.
-void record_route(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, int mode, bool fast_mode, int launch_geom) {
+// HaloRouteInfo (halo_last_route: what the GPU tests assert routes with).  The masks name the instantiation that was launched — `k`, the
+// selection launch_trace made (halo_select.h) — not the request; what the passes behind the kernel do has no counterpart in the id and comes
+// from the plan: one- or two-level lists, the scalar or the X/Y/Z log.
+void record_route(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, const KernelId& k) {
   b->route.launches++;
-  b->route.mode_mask |= 1u << mode;
-  const bool ran_hex = launch_geom == 3 && fast_mode && (P.bin_list == nullptr || P.bin_log != 0u || P.no_land != 0u);
-  const bool ran_none = P.no_land != 0u && p.geom == 0;
-  b->route.geom_mask |= 1u << (launch_geom == 3 && !ran_hex ? 0 : launch_geom);
-  b->route.accum_mask |= ran_none ? 64u : p.fixed ? (128u | (p.use_log ? (p.use_log_xyz ? 32u : 16u) : 0u)) : p.use_log ? (p.use_log_xyz ? 32u : 16u) : (p.use_bin ? (p.two_level ? 8u : 4u) : (b->mono_session ? 2u : 1u));
-  // specialisations (plain kernels only; launch_lens / launch_vis / launch_mono): bit 0 last-layer kernel (no continuation code), 1 lens as a
-  // constant, 2 visible range as a constant, 3 closed gate as a constant
-  const bool one = p.geom == 0, lens_known = P.proj.proj_type == HALO_LENS_LINEAR || P.proj.proj_type == HALO_LENS_FISHEYE_EQUAL_AREA ||
-                                             P.proj.proj_type == HALO_LENS_DUAL_FISHEYE_EQUAL_AREA || P.proj.proj_type == HALO_LENS_RECTANGULAR;
-  const bool vis_known = P.proj.visible_range == HALO_VISIBLE_UPPER || P.proj.visible_range == HALO_VISIBLE_FULL;
-  uint32_t spec = 0u;
-  const bool logged = p.use_log && !p.fixed;   // (the fixed-point kernels, logging or not, exist in the generic run-time lens form only)
-  if (fast_mode && logged && one && !ran_none && b->mono_session && P.final_layer) {
-    spec |= 1u;
-    if ((mode == 0 || mode == 1) && P.prob <= 0.0f && lens_known && vis_known) spec |= 2u | 4u | 8u;
-  }
-  if (fast_mode && logged && one && !ran_none && b->mono_session && !P.final_layer && (mode == 0 || mode == 1) && lens_known && vis_known)
-    spec |= 2u | 4u;   // (round 6: the logging kernels of the layers before the last know their lens and visible range too; their gate is open)
-  if (mode == 0 && logged && !one && !b->mono_session && P.prob <= 0.0f && P.proj.visible_range == HALO_VISIBLE_FULL) spec |= 4u | 8u;
-  if (mode == 0 && logged && !one && P.prob <= 0.0f && P.proj.visible_range == HALO_VISIBLE_FULL && P.proj.proj_type == HALO_LENS_RECTANGULAR)
-    spec |= 2u | 4u | 8u;   // (shape-pool kernels, either plane layout: bench_config_stoch.json's render as constants)
+  b->route.mode_mask |= 1u << k.mode;
+  b->route.geom_mask |= 1u << k.geom;
+  const uint32_t log_bit = p.use_log ? (p.use_log_xyz ? 32u : 16u) : 0u;
+  b->route.accum_mask |= k.acc == kAccNone                            ? 64u
+                         : (k.acc == kAccFixed || k.acc == kAccFixedLog) ? (128u | log_bit)
+                         : p.use_log                                      ? log_bit
+                                                                          : (p.use_bin ? (p.two_level ? 8u : 4u) : (b->mono_session ? 2u : 1u));
+  // specialisations: bit 0 last-layer kernel (no continuation code), 1 lens as a constant, 2 visible range as a constant, 3 closed gate as a constant
+  const uint32_t spec = ((k.acc == kAccLogFinal || k.acc == kAccTileFinal) ? 1u : 0u) | (k.lens >= 0 ? 2u : 0u) | (k.vis >= 0 ? 4u : 0u) | (k.nogate ? 8u : 0u);
   b->route.spec_mask |= spec;
   if (spec == 0u) b->route.generic_launches++;
-  // root profiles (launch_root): instantiated for the regular prism's last-layer plain kernels with lens, visible range and closed gate as constants
-  // (... except the continuation-pool profile under the linear lens over the full sky)
-  const bool no_transit = P.proj.proj_type == HALO_LENS_LINEAR && P.proj.visible_range == HALO_VISIBLE_FULL;
-  if (mode == 0 && ran_hex && P.final_layer && (spec & (2u | 4u | 8u)) == (2u | 4u | 8u) && P.root_profile != kRootProfileNone && P.root_profile == root_profile_of(P) &&
-      !(no_transit && P.root_profile == kRootProfileTransit))
-    b->route_root |= 1u << (P.root_profile - 1u);
+  static_assert(kRootProfileGen - 1u == kRootGenLutUniform && kRootProfileTransit - 1u == kRootTransitLutUniform, "route_root: bit kRootProfile* - 1");
+  if (root_form(k.root) != kRootAny) b->route_root |= 1u << root_form(k.root);
   b->route.source_mask |= 1u << P.source;
 }
 // The accumulation passes of a launch, behind its trace kernel on trace stream `ts` (index ts_i), and the ring slot's closing events.
@@ -1916,20 +1898,20 @@ int queue_launch(HaloBackend* b, const LaunchPlan& p, const HaloEntry& E, EntryT
   }
   HIPCHK(b, hipEventRecord(b->ring_ev0[k], ts));  // HIP events on the launch stream bracket the kernel alone
   b->ring_final[k] = P.final_layer != 0u;
-  // a one-shape dispatch of a regular hexagonal prism takes the literal-normal instantiation (kGeomOneHex = 3)
-  const int launch_geom = (p.geom == 0 && T.entry_fast && b->hex_fast && T.hex_regular) ? 3 : p.geom;
-  hipError_t le = launch_trace(P, p.blocks, ts, T.mode, launch_geom, b->mono_session);
+  const int launch_geom = launch_geom_of(*b, p, T);
+  KernelId launched;
+  hipError_t le = launch_trace(P, p.blocks, ts, T.mode, launch_geom, b->mono_session, &launched);
   if (T.ce) {   // the slot's last reader (see TableCacheEntry): this launch, whose ring_done event is recorded below
     T.ce->read_ring[T.ce->cur] = k;
     T.ce->read_use[T.ce->cur] = b->ring_use[k];
   }
   // (a launch that closes its session itself leaves the planes as it found them; so does one of the no-accumulation kernels — no_land on one shape,
-  // launch_mono / launch_canon: kAccNone has no cache, no exit queue and no code that touches a plane, the log or the twin.  The latter holds for
+  // halo_select.h select_kernel: kAccNone has no cache, no exit queue and no code that touches a plane, the log or the twin.  The latter holds for
   // EVERY such launch, eligible for a direct close or not: a session of such launches alone queues no fold of planes nobody wrote.)
   if (!p.close && !(p.no_land && p.geom == 0)) b->mono_dirty = true;
   b->fix_planes = b->det_session;
-  record_route(b, p, P, T.mode, T.fast_mode, launch_geom);
-  if (le != hipSuccess) return hip_fail(b, le, "halo_trace_kernel launch");
+  if (le != hipSuccess) return hip_fail(b, le, "halo_trace_kernel launch");   // (nothing ran: no route to record)
+  record_route(b, p, P, launched);
   if (!p.deterministic) HIPCHK(b, b->shapes_free[S.shape_set].mark(ts));
   if (int rc = queue_passes(b, p, P, S, ts, ts_i, before_sums)) return rc;
   b->tally_unread = true;

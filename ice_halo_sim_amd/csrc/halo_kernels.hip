@@ -1466,22 +1466,24 @@ hipError_t launch_cont_reorder(const float* in, uint32_t in_stride, uint32_t reg
   return hipGetLastError();
 }
 
-hipError_t launch_trace_m0(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);
-hipError_t launch_trace_m1(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);
-hipError_t launch_trace_m2(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);
-hipError_t launch_trace_m3(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);
-hipError_t launch_trace_m4(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);
-
-// mode: halo_trace.inl kMode* — 0 plain, 1 filter (fast form), 2 capture (tests), 3 generic filter / colour, 4 filter + colour (fast form)
+// mode: halo_select.h kMode* — 0 plain, 1 filter (fast form), 2 capture (tests), 3 generic filter / colour, 4 filter + colour (fast form)
 // geom: 0 = one shape per dispatch, 1 = shape pool, 2 = shape pool of prisms (compact LDS slots), 3 = one regular hexagonal prism
-hipError_t launch_trace(const DispatchParams& P, int blocks, hipStream_t stream, int mode, int geom, bool mono) {
-  if (P.tile_chunk != nullptr) return mode == 0 ? launch_trace_tl0(P, blocks, stream, geom, mono) : hipErrorNotSupported;   // the per-tile append: its kernel, or an error
-  switch (mode) {
-    case 0: return launch_trace_m0(P, blocks, stream, geom, mono);
-    case 1: return launch_trace_m1(P, blocks, stream, geom, mono);
-    case 2: return launch_trace_m2(P, blocks, stream, geom, mono);
-    case 3: return launch_trace_m3(P, blocks, stream, geom, mono);
-    case 4: return launch_trace_m4(P, blocks, stream, geom, mono);
+// The launch goes to the unit that instantiates the selected kernel's family (halo_select.h family_of); `launched`, if given, is that kernel.
+hipError_t launch_trace(const DispatchParams& P, int blocks, hipStream_t stream, int mode, int geom, bool mono, KernelId* launched) {
+  const Selection s = select_kernel(make_request(P, mode, geom, mono));
+  if (s.err != 0) return static_cast<hipError_t>(s.err);
+  if (launched != nullptr) *launched = s.id;
+  switch (family_of(s.id)) {
+    case kFamMode + kModePlain: return launch_trace_m0(P, blocks, stream, geom, mono);
+    case kFamMode + kModeFilter: return launch_trace_m1(P, blocks, stream, geom, mono);
+    case kFamMode + kModeCapture: return launch_trace_m2(P, blocks, stream, geom, mono);
+    case kFamMode + kModeGeneric: return launch_trace_m3(P, blocks, stream, geom, mono);
+    case kFamMode + kModeColor: return launch_trace_m4(P, blocks, stream, geom, mono);
+    case kFamFixed + kModePlain: return launch_trace_fx0(P, blocks, stream, geom, mono);
+    case kFamFixed + kModeFilter: return launch_trace_fx1(P, blocks, stream, geom, mono);
+    case kFamFixedLog + kModePlain: return launch_trace_fxl0(P, blocks, stream, geom, mono);
+    case kFamFixedLog + kModeFilter: return launch_trace_fxl1(P, blocks, stream, geom, mono);
+    case kFamTile + kModePlain: return launch_trace_tl0(P, blocks, stream, geom, mono);
   }
   return hipErrorInvalidValue;
 }

@@ -6,13 +6,15 @@
 #include <hip/hip_runtime.h>
 
 #include "halo_device.h"
+#include "halo_select.h"
 
 namespace halo {
 namespace geom {
 struct CrystalRecipe;
 }
 
-hipError_t launch_trace(const DispatchParams& P, int blocks, hipStream_t stream, int mode, int geom, bool mono);
+// (the kernel is halo_select.h select_kernel's choice for the request; `launched` receives it where the launch is made)
+hipError_t launch_trace(const DispatchParams& P, int blocks, hipStream_t stream, int mode, int geom, bool mono, KernelId* launched = nullptr);
 // workgroups of a ticketed kAccTileFinal kernel (DispatchParams::ticket) that one CU holds at once: the occupancy query, made once
 int tile_ticket_resident_per_cu();
 hipError_t launch_bin_accumulate(float* plane, const HitRec* list, uint32_t cap, uint32_t* cnt, uint32_t tiles, uint32_t frac_bits, hipStream_t stream);

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include "halo_device.h"
+#include "halo_select.h"
 
 namespace halo {
 
@@ -268,17 +269,7 @@ HD uint32_t lat_lut_bin(float theta, const float* lut) {
   return static_cast<uint32_t>(idx);
 }
 
-// Root profiles (halo_trace_kernel's ROOT): what the last-layer kernels of the regular prism know about their root generation at compile time.
-// kRootAny keeps every choice a run-time test.  The two others are the orientation the shipped column / plate examples and the BASELINE
-// configurations take — latitude by the LUT, azimuth and roll uniform — over generated roots or over the continuation pool: the tests on the
-// source, the latitude path and the five distribution kinds (three of which carry logf / cosf / sinf) fold away, and with them 60 % of the
-// kernel's code.  Same expressions, draws and stream slots.
-constexpr int kRootAny = -1, kRootGenLutUniform = 0, kRootTransitLutUniform = 1;
-// ... and the ticketed form of a kAccTileFinal kernel (DispatchParams::ticket, halo_device.h TicketSize) rides on the same template argument, so
-// that no kernel of the static form changes its name: ROOT + kRootTicket is the ticketed twin of root form ROOT.
-constexpr int kRootTicket = 16;
-constexpr bool root_ticketed(int root) { return root >= kRootTicket + kRootAny; }
-constexpr int root_form(int root) { return root_ticketed(root) ? root - kRootTicket : root; }
+// (the root profiles kRoot*, kRootTicket, root_form and root_ticketed: halo_select.h)
 
 template <int ROOT = kRootAny>
 HD void sample_lat_lon_roll(Stream& s, const DispatchParams& P, const float* lut, float& lon, float& lat, float& roll) {
@@ -568,10 +559,7 @@ static_assert(offsetof(FixCache<true>, val) % 8 == 0 && offsetof(FixCache<false>
 // flush reserves the segment, the 8-byte stores of a tile land in one or two lines — and halo_bin_accumulate_kernel then
 // sums each tile's list in a 64 KB LDS tile and adds it to the plane with plain stores.  Lists that run over (a tile much
 // hotter than average) fall back to the direct atomic, so capacity is a speed matter only.
-constexpr int kAccDirect = 0, kAccBin = 1, kAccLog = 2, kAccNone = 3, kAccLogFinal = 4;   // halo_trace_kernel ACC (None: a layer whose every exit continues — nothing lands)
-constexpr int kAccFixed = 5;   // the integer twin of kAccDirect (option "deterministic"): FixCache in LDS, 64-bit integer atomics onto DispatchParams::fix
-constexpr int kAccFixedLog = 6;   // ... and of the logging kernels: the same cache, but a hit that loses the claim leaves as a raw {slot, weight} record (log_hit_fixed)
-constexpr int kAccTileFinal = 7;   // kAccLogFinal whose records go to per-tile chunks of the workgroup instead of its one region (log_hit_tile): no split pass
+// (halo_trace_kernel ACC, kAcc*: halo_select.h)
 constexpr int kCtxFloat = 0, kCtxFixedLog = 1, kCtxTile = 2;   // AccCtx FL: which record a cache miss of a logging kernel leaves as (a type, so that no other kernel compiles the branch)
 constexpr int kHitBuf = 1536;                 // staged hits per workgroup (16 KB)
 // (kBinTileLog2, slots per tile, and kBinCntStride, the spacing of the tile counters: halo_device.h)
@@ -1369,7 +1357,7 @@ struct LdsTables {
   FaceIndex fidx;
   __attribute__((aligned(16))) EntryFastDev efast;   // staged only when P.entry_fast != nullptr (full prism, one shape per dispatch)
 };
-constexpr int kModePlain = 0, kModeFilter = 1, kModeCapture = 2, kModeGeneric = 3, kModeColor = 4;
+// (kMode*: halo_select.h)
 template <int MODE>
 struct ModeTraits {
   static constexpr bool kFast = MODE == kModePlain || MODE == kModeFilter || MODE == kModeColor;   // production-shaped kernels
@@ -1400,8 +1388,7 @@ static_assert(offsetof(ShapeDev, tri_v) % 16 == 0 && offsetof(ShapeDev, tri_na) 
               offsetof(ShapeDev, tri_face) % 4 == 0 && offsetof(ShapeDev, face_number) % 4 == 0 && offsetof(ShapeDev, single) % 4 == 0,
               "rows are copied as float4 / dwords");
 
-constexpr int kGeomOne = 0, kGeomPool = 1, kGeomPoolPrism = 2;   // GEOM: one shape per dispatch | pool of ShapeDev | pool of ShapePrism (HBM records and LDS slots)
-constexpr int kGeomOneHex = 3;   // one shape per dispatch AND it is a regular hexagonal prism (EntryFastDev::hex_regular): literal normals
+// (GEOM, kGeom*: halo_select.h)
 template <int GEOM>
 struct PoolSlotType {   // type = the LDS slot of a half-wave, rec = the record in the HBM pool
   typedef ShapeSlot48 type;
@@ -2718,7 +2705,7 @@ constexpr int min_waves() {
 // types (uniform branches, and the SGPRs their parameters hold), the visibility tests and the gate stream fold away: configs[1]
 // 2.96 -> 2.73 (lens) -> 2.60 ms per launch.  Done for the last-layer one-shape scalar kernels and the lenses of the shipped examples.
 // CANON: a layer before the last under canonical continuation order (option cont_order = 1) — its appends carry their (root, interaction) key.
-// ROOT: a root profile (kRoot*, at sample_lat_lon_roll) — the last-layer plain hit-log kernels of the regular prism, which launch_vis fans out.
+// ROOT: a root profile (kRoot*, at sample_lat_lon_roll) — the last-layer plain hit-log kernels of the regular prism (halo_select.h with_root).
 template <int MODE, int GEOM, bool MONO, int ACC, int LENS = -1, int VIS = -1, bool NOGATE = false, bool CANON = false, int ROOT_ARG = kRootAny>   // ACC: kAccDirect, kAccBin (staged + binned hit lists), kAccLog (per-workgroup hit log), ...
 __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) halo_trace_kernel(const DispatchParams P) {
   constexpr int ROOT = root_form(ROOT_ARG);
@@ -3197,241 +3184,43 @@ __global__ void __launch_bounds__(kBlock, (min_waves<MODE, GEOM, MONO, ACC>())) 
 #endif
 }
 
-// host-callable launcher pieces: each halo_trace_m<MODE>.hip translation unit instantiates the kernels of one MODE
-// (the instantiations of the three MODEs compile in parallel that way; halo_backend.cpp is plain C++ and never sees <<<>>>)
-// The specialised instantiations of the last-layer kernels: lens, visible range and "prob <= 0" (the usual last layer: nothing
-// passes the gate) as template constants.  Lenses of the reference's shipped examples (config_example.json: linear, dual fisheye
-// equal area; the BASELINE configurations: fisheye equal area; bench_config_stoch.json: rectangular) x visible upper / full;
-// anything else runs the generic kernel.
-// (NOGATE = true: the last layer with prob <= 0.  NOGATE = false, round 6: the logging kernels of the layers BEFORE the last — their gate is open, the lens
-//  and the visible range are as constant as in the last layer, and the generic-lens form of them carried every lens's code: 8723 instructions, 120
-//  spilled SGPRs, 10 spilled VGPRs and scratch against 4612 / 45 / 0 / none for the dual-fisheye instantiation, tools/isa_by_line.py.)
-// ... and, for the last-layer plain hit-log kernels of the regular prism alone, the root profile the host asks for (DispatchParams::root_profile,
-// halo_backend.cpp root_profile_of) — taken only when the record itself says what the profile assumes: a record that does not runs the generic form.
-// The ticketed twins (ROOT + kRootTicket) of the kAccTileFinal kernels.  Not for the dual fisheye: that instantiation's register allocation
-// answers the ticket loop with a spilled VGPR inside the ray loop (the pixel cache's slot index), and a ticketed kernel is held to none there.
-template <int ACC, int LENS>
-constexpr bool ticket_kernel_exists() { return ACC == kAccTileFinal && LENS != HALO_LENS_DUAL_FISHEYE_EQUAL_AREA; }
-template <int MODE, int GEOM, bool MONO, int ACC, int LENS, int VIS, bool NOGATE>
-static void launch_root(const DispatchParams& P, dim3 grid, dim3 block, hipStream_t stream) {
-  if constexpr (MODE == kModePlain && GEOM == kGeomOneHex && MONO && (ACC == kAccLogFinal || ACC == kAccTileFinal) && NOGATE) {
-    const bool lut_uniform = P.lat_path == kLatLut && P.az_type == HALO_DIST_UNIFORM && P.roll_type == HALO_DIST_UNIFORM;
-    if (lut_uniform && P.root_profile == kRootProfileGen && P.source == kSrcGen && P.spec_per == 0u) {
-      if constexpr (ticket_kernel_exists<ACC, LENS>()) {
-        if (P.ticket != nullptr) {
-          hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, MONO, ACC, LENS, VIS, NOGATE, false, kRootTicket + kRootGenLutUniform>), grid, block, 0, stream, P);
-          return;
-        }
-      }
-      hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, MONO, ACC, LENS, VIS, NOGATE, false, kRootGenLutUniform>), grid, block, 0, stream, P);
-      return;
-    }
-    // (the linear lens over the full sky keeps the generic form over the continuation pool: that one instantiation's register allocation
-    //  answers the profile with 4 spilled VGPRs and scratch)
-    constexpr bool kTransit = !(LENS == HALO_LENS_LINEAR && VIS == HALO_VISIBLE_FULL);
-    if (kTransit && lut_uniform && P.root_profile == kRootProfileTransit && P.source == kSrcTransit) {
-      if constexpr (ticket_kernel_exists<ACC, LENS>()) {
-        if (P.ticket != nullptr) {
-          hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, MONO, ACC, LENS, kTransit ? VIS : HALO_VISIBLE_UPPER, NOGATE, false, kRootTicket + kRootTransitLutUniform>), grid, block, 0, stream, P);
-          return;
-        }
-      }
-      hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, MONO, ACC, LENS, kTransit ? VIS : HALO_VISIBLE_UPPER, NOGATE, false, kRootTransitLutUniform>), grid, block, 0, stream, P);
-      return;
-    }
-  }
-  if constexpr (ticket_kernel_exists<ACC, LENS>()) {
-    if (P.ticket != nullptr) {
-      hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, MONO, ACC, LENS, VIS, NOGATE, false, kRootTicket + kRootAny>), grid, block, 0, stream, P);
-      return;
-    }
-  }
-  hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, MONO, ACC, LENS, VIS, NOGATE>), grid, block, 0, stream, P);
-}
-template <int MODE, int GEOM, bool MONO, int ACC, int LENS, bool NOGATE>
-static void launch_vis(const DispatchParams& P, dim3 grid, dim3 block, hipStream_t stream) {
-  if (P.proj.visible_range == HALO_VISIBLE_UPPER) launch_root<MODE, GEOM, MONO, ACC, LENS, HALO_VISIBLE_UPPER, NOGATE>(P, grid, block, stream);
-  else if (P.proj.visible_range == HALO_VISIBLE_FULL) launch_root<MODE, GEOM, MONO, ACC, LENS, HALO_VISIBLE_FULL, NOGATE>(P, grid, block, stream);
-  else hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, MONO, ACC>), grid, block, 0, stream, P);
-}
-template <int MODE, int GEOM, bool MONO, int ACC, bool NOGATE = true>
-static void launch_lens(const DispatchParams& P, dim3 grid, dim3 block, hipStream_t stream) {
-  if (NOGATE && P.prob > 0.0f) {
-    hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, MONO, ACC>), grid, block, 0, stream, P);
-    return;
-  }
-  switch (P.proj.proj_type) {
-    case HALO_LENS_LINEAR: launch_vis<MODE, GEOM, MONO, ACC, HALO_LENS_LINEAR, NOGATE>(P, grid, block, stream); break;
-    case HALO_LENS_FISHEYE_EQUAL_AREA: launch_vis<MODE, GEOM, MONO, ACC, HALO_LENS_FISHEYE_EQUAL_AREA, NOGATE>(P, grid, block, stream); break;
-    case HALO_LENS_DUAL_FISHEYE_EQUAL_AREA: launch_vis<MODE, GEOM, MONO, ACC, HALO_LENS_DUAL_FISHEYE_EQUAL_AREA, NOGATE>(P, grid, block, stream); break;
-    case HALO_LENS_RECTANGULAR: launch_vis<MODE, GEOM, MONO, ACC, HALO_LENS_RECTANGULAR, NOGATE>(P, grid, block, stream); break;
-    default: hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, MONO, ACC>), grid, block, 0, stream, P); break;
-  }
-}
+// The host-callable launchers.  Which instantiation a dispatch runs is halo_select.h's business (select_kernel; the kernel set: kernel_exists);
+// here the chosen id becomes template constants again and the kernel is launched.  The kernels are split into families, each instantiated by
+// one translation unit — halo_trace_m<MODE>.hip the float kernels of one MODE, halo_trace_fx<MODE>.hip / halo_trace_fxl<MODE>.hip the fixed-point
+// twins of the direct / the logging kernels (option "deterministic"), halo_trace_tl0.hip the per-tile append's (option "tile_append") — so that
+// they compile side by side; halo_kernels.hip launch_trace routes a launch to its family's unit.  halo_backend.cpp is plain C++ and never sees
+// <<<>>>.
+static_assert(kSelectInvalidValue == static_cast<int>(hipErrorInvalidValue) && kSelectNotSupported == static_cast<int>(hipErrorNotSupported), "halo_select.h's errors are hipError_t's");
+static_assert(ModeTraits<kModePlain>::kFast == mode_fast(kModePlain) && ModeTraits<kModeFilter>::kFast == mode_fast(kModeFilter) && ModeTraits<kModeCapture>::kFast == mode_fast(kModeCapture) &&
+                  ModeTraits<kModeGeneric>::kFast == mode_fast(kModeGeneric) && ModeTraits<kModeColor>::kFast == mode_fast(kModeColor),
+              "halo_select.h's mode_fast is ModeTraits::kFast");
+hipError_t launch_trace_m0(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);     // kFamMode + kModePlain
+hipError_t launch_trace_m1(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);     // ... kModeFilter
+hipError_t launch_trace_m2(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);     // ... kModeCapture
+hipError_t launch_trace_m3(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);     // ... kModeGeneric
+hipError_t launch_trace_m4(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);     // ... kModeColor
+hipError_t launch_trace_fx0(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);    // kFamFixed + kModePlain
+hipError_t launch_trace_fx1(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);    // ... kModeFilter
+hipError_t launch_trace_fxl0(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);   // kFamFixedLog + kModePlain
+hipError_t launch_trace_fxl1(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);   // ... kModeFilter
+hipError_t launch_trace_tl0(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);    // kFamTile + kModePlain
 
-// Canonical continuation order (P.cont_mask set: option cont_order = 1, a layer before the last): the CANON twins of the direct-accumulation and
-// no-accumulation kernels — the host gives such a layer neither the hit log nor binned lists, so no other instantiation needs a twin.
-template <int MODE, int GEOM>
-static void launch_canon(const DispatchParams& P, dim3 grid, dim3 block, hipStream_t stream, bool mono) {
-  if constexpr (ModeTraits<MODE>::kFast && (GEOM == kGeomOne || GEOM == kGeomOneHex)) {
-    if (P.no_land != 0u) {
-      hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, true, kAccNone, -1, -1, false, true>), grid, block, 0, stream, P);
-      return;
-    }
+struct LaunchKernel {   // expand_kernel's callable: the one launch
+  const DispatchParams& P;
+  dim3 grid, block;
+  hipStream_t stream;
+  template <int MODE, int GEOM, bool MONO, int ACC, int LENS, int VIS, bool NOGATE, bool CANON, int ROOT>
+  void operator()(KernelConst<MODE, GEOM, MONO, ACC, LENS, VIS, NOGATE, CANON, ROOT>) const {
+    hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, MONO, ACC, LENS, VIS, NOGATE, CANON, ROOT>), grid, block, 0, stream, P);
   }
-  if (mono) hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, true, kAccDirect, -1, -1, false, true>), grid, block, 0, stream, P);
-  else hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, false, kAccDirect, -1, -1, false, true>), grid, block, 0, stream, P);
-}
-
-template <int MODE, int GEOM>
-static void launch_mono(const DispatchParams& P, dim3 grid, dim3 block, hipStream_t stream, bool mono) {
-  if (P.cont_mask != nullptr) {
-    launch_canon<MODE, GEOM>(P, grid, block, stream, mono);
-    return;
-  }
-  if constexpr (ModeTraits<MODE>::kFast && (GEOM == kGeomOne || GEOM == kGeomOneHex)) {
-    if (P.no_land != 0u) {   // every exit of this layer continues: no cache, no queue, no accumulation code
-      hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, true, kAccNone>), grid, block, 0, stream, P);
-      return;
-    }
-  }
-  if constexpr (ModeTraits<MODE>::kFast) {   // the hit log exists for the production-shaped kernels: scalar planes, or X/Y/Z planes of an illuminant session
-    if (P.bin_log != 0u) {
-      if constexpr (GEOM == kGeomOne || GEOM == kGeomOneHex) {
-        if (mono && P.final_layer != 0u) {   // the last layer's one-shape scalar kernels carry no continuation-append code
-          if constexpr (MODE == kModePlain || MODE == kModeFilter) launch_lens<MODE, GEOM, true, kAccLogFinal>(P, grid, block, stream);
-          else hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, true, kAccLogFinal>), grid, block, 0, stream, P);
-          return;
-        }
-      }
-      // (round 6, end: the reference's own stochastic benchmark — bench_config_stoch.json: rectangular lens, full sky, closed gate — as constants for
-      //  the shape-pool kernels of both plane layouts.  The pool kernels project at the emit site, and the generic form of them holds every lens's
-      //  code inside the interaction loop: 14 283 instructions, 157 spilled SGPRs, 3 spilled VGPRs and scratch against 9950 / 73 / 0 / none.)
-      if constexpr (MODE == kModePlain && (GEOM == kGeomPool || GEOM == kGeomPoolPrism)) {
-        if (P.prob <= 0.0f && P.proj.visible_range == HALO_VISIBLE_FULL && P.proj.proj_type == HALO_LENS_RECTANGULAR) {
-          if (mono) hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, true, kAccLog, HALO_LENS_RECTANGULAR, HALO_VISIBLE_FULL, true>), grid, block, 0, stream, P);
-          else hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, false, kAccLog, HALO_LENS_RECTANGULAR, HALO_VISIBLE_FULL, true>), grid, block, 0, stream, P);
-          return;
-        }
-      }
-      if (mono) {
-        if constexpr ((MODE == kModePlain || MODE == kModeFilter) && (GEOM == kGeomOne || GEOM == kGeomOneHex)) launch_lens<MODE, GEOM, true, kAccLog, false>(P, grid, block, stream);
-        else hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, true, kAccLog>), grid, block, 0, stream, P);
-      } else if constexpr (GEOM == kGeomPool || GEOM == kGeomPoolPrism) {
-        // illuminant sessions over sampled crystals: a full-sky render with a closed gate (bench_config_stoch.json's shape) knows both at
-        // compile time (configs[4] 5.52 -> 5.43 ms per step; its lens as a constant gains nothing more: 4.31 vs 4.32 ms per launch)
-        if constexpr (MODE == kModePlain) {
-          if (P.prob <= 0.0f && P.proj.visible_range == HALO_VISIBLE_FULL) {
-            hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, false, kAccLog, -1, HALO_VISIBLE_FULL, true>), grid, block, 0, stream, P);
-            return;
-          }
-        }
-        hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, false, kAccLog>), grid, block, 0, stream, P);
-      } else hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, false, kAccLog>), grid, block, 0, stream, P);
-      return;
-    }
-  }
-  if constexpr (GEOM == kGeomOneHex) {   // ... and the regular-prism instantiation for the production mode's direct and logged routes
-    if (mono) hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, true, kAccDirect>), grid, block, 0, stream, P);
-    else hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, false, kAccDirect>), grid, block, 0, stream, P);
-  } else {
-    if (mono && P.bin_list != nullptr) hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, true, kAccBin>), grid, block, 0, stream, P);
-    else if (mono) hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, true, kAccDirect>), grid, block, 0, stream, P);
-    else hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, false, kAccDirect>), grid, block, 0, stream, P);
-  }
-}
-
-// The deterministic route (DispatchParams::fix set: option "deterministic"): the kAccFixed twins of the direct kernels — plain and fast-filter mode,
-// every GEOM, scalar and X/Y/Z planes, with and without the canonical order's append keys, in the generic run-time lens form.  They are
-// instantiated in translation units of their own (halo_trace_fx0.hip, halo_trace_fx1.hip), which compile beside the others.
-hipError_t launch_trace_fx0(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);   // kModePlain
-hipError_t launch_trace_fx1(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);   // kModeFilter
-template <int MODE, int GEOM>
-static void launch_fixed_geom(const DispatchParams& P, dim3 grid, dim3 block, hipStream_t stream, bool mono) {
-  const bool canon = P.cont_mask != nullptr;
-  if (mono && canon) hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, true, kAccFixed, -1, -1, false, true>), grid, block, 0, stream, P);
-  else if (mono) hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, true, kAccFixed>), grid, block, 0, stream, P);
-  else if (canon) hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, false, kAccFixed, -1, -1, false, true>), grid, block, 0, stream, P);
-  else hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, false, kAccFixed>), grid, block, 0, stream, P);
-}
-// ... and the kAccFixedLog twins of the logging kernels (DispatchParams::bin_log beside ::fix: halo_trace_fxl0.hip, halo_trace_fxl1.hip) — no
-// CANON twins, a canonical layer before the last never logs.
-hipError_t launch_trace_fxl0(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);   // kModePlain
-hipError_t launch_trace_fxl1(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);   // kModeFilter
-template <int MODE, int GEOM>
-static void launch_fixed_log_geom(const DispatchParams& P, dim3 grid, dim3 block, hipStream_t stream, bool mono) {
-  if (mono) hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, true, kAccFixedLog>), grid, block, 0, stream, P);
-  else hipLaunchKernelGGL((halo_trace_kernel<MODE, GEOM, false, kAccFixedLog>), grid, block, 0, stream, P);
-}
-template <int MODE>
-static hipError_t launch_fixed_log(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono) {
-  dim3 grid(blocks), block(kBlock);
-  if (P.cont_mask != nullptr) return hipErrorNotSupported;
-  if (geom == kGeomOneHex) launch_fixed_log_geom<MODE, kGeomOneHex>(P, grid, block, stream, mono);
-  else if (geom == kGeomPoolPrism) launch_fixed_log_geom<MODE, kGeomPoolPrism>(P, grid, block, stream, mono);
-  else if (geom == kGeomPool) launch_fixed_log_geom<MODE, kGeomPool>(P, grid, block, stream, mono);
-  else launch_fixed_log_geom<MODE, kGeomOne>(P, grid, block, stream, mono);
-  return hipGetLastError();
-}
-template <int MODE>
-static hipError_t launch_fixed(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono) {
-  dim3 grid(blocks), block(kBlock);
-  if (geom == kGeomOneHex) launch_fixed_geom<MODE, kGeomOneHex>(P, grid, block, stream, mono);
-  else if (geom == kGeomPoolPrism) launch_fixed_geom<MODE, kGeomPoolPrism>(P, grid, block, stream, mono);
-  else if (geom == kGeomPool) launch_fixed_geom<MODE, kGeomPool>(P, grid, block, stream, mono);
-  else launch_fixed_geom<MODE, kGeomOne>(P, grid, block, stream, mono);
-  return hipGetLastError();
-}
-
-// The per-tile append (DispatchParams::tile_chunk set: option "tile_append", halo_backend.cpp tile_append_ok): the kAccTileFinal twins of the
-// headline's kernels — plain mode, one regular prism, scalar plane, last layer with a closed gate, lens and root form as constants, the upper
-// sky (the closing per-tile pass, which reads the chunks, takes no full-sky render).  Instantiated in a translation unit of their own
-// (halo_trace_tl0.hip).  A dispatch without an instantiation is an error: the host asks for the route only where one exists.
-hipError_t launch_trace_tl0(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono);
-template <int MODE, int LENS>
-static void launch_tile_lens(const DispatchParams& P, dim3 grid, dim3 block, hipStream_t stream) {
-  launch_root<MODE, kGeomOneHex, true, kAccTileFinal, LENS, HALO_VISIBLE_UPPER, true>(P, grid, block, stream);
-}
-static inline bool tile_kernel_exists(const DispatchParams& P, int geom, bool mono) {
-  const int lens = P.proj.proj_type;
-  return geom == kGeomOneHex && mono && P.final_layer != 0u && P.bin_log != 0u && P.prob <= 0.0f && P.cont_mask == nullptr && P.no_land == 0u && P.fix == nullptr &&
-         P.mono_by_wl == 0u && P.proj.visible_range == HALO_VISIBLE_UPPER &&
-         (lens == HALO_LENS_LINEAR || lens == HALO_LENS_FISHEYE_EQUAL_AREA || lens == HALO_LENS_DUAL_FISHEYE_EQUAL_AREA || lens == HALO_LENS_RECTANGULAR);
-}
-template <int MODE>   // (a template so that only halo_trace_tl0.hip instantiates the kernels)
-static hipError_t launch_tile(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono) {
-  if (P.ticket != nullptr && (P.proj.proj_type == HALO_LENS_DUAL_FISHEYE_EQUAL_AREA || P.ticket_waves == 0u)) return hipErrorNotSupported;   // (ticket_kernel_exists)
-  if (!tile_kernel_exists(P, geom, mono) || P.tile_cnt == nullptr || P.tile_tiles == 0u || P.tile_tiles > kTileAppendMax || (P.tile_cap & 1u) != 0u) return hipErrorNotSupported;
-  dim3 grid(blocks), block(kBlock);
-  switch (P.proj.proj_type) {
-    case HALO_LENS_LINEAR: launch_tile_lens<MODE, HALO_LENS_LINEAR>(P, grid, block, stream); break;
-    case HALO_LENS_FISHEYE_EQUAL_AREA: launch_tile_lens<MODE, HALO_LENS_FISHEYE_EQUAL_AREA>(P, grid, block, stream); break;
-    case HALO_LENS_DUAL_FISHEYE_EQUAL_AREA: launch_tile_lens<MODE, HALO_LENS_DUAL_FISHEYE_EQUAL_AREA>(P, grid, block, stream); break;
-    default: launch_tile_lens<MODE, HALO_LENS_RECTANGULAR>(P, grid, block, stream); break;
-  }
-  return hipGetLastError();
-}
-
-template <int MODE>
-static hipError_t launch_mode(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono) {
-  dim3 grid(blocks), block(kBlock);
-  // a deterministic launch that accumulates: its kAccFixed kernel, or an error — never a float route.  (A one-shape layer whose every exit
-  // continues accumulates nothing and keeps its kAccNone kernel below.)
-  if (P.fix != nullptr && !(P.no_land != 0u && ModeTraits<MODE>::kFast && (geom == kGeomOne || geom == kGeomOneHex))) {
-    if constexpr (MODE == kModePlain) return P.bin_log != 0u ? launch_trace_fxl0(P, blocks, stream, geom, mono) : launch_trace_fx0(P, blocks, stream, geom, mono);
-    else if constexpr (MODE == kModeFilter) return P.bin_log != 0u ? launch_trace_fxl1(P, blocks, stream, geom, mono) : launch_trace_fx1(P, blocks, stream, geom, mono);
-    else return hipErrorNotSupported;
-  }
-  if constexpr (ModeTraits<MODE>::kFast) {
-    if (geom == kGeomOneHex && (P.bin_list == nullptr || P.bin_log != 0u || P.no_land != 0u)) {
-      launch_mono<MODE, kGeomOneHex>(P, grid, block, stream, mono);
-      return hipGetLastError();
-    }
-  }
-  if (geom == kGeomOneHex) geom = kGeomOne;
-  if (geom == kGeomPoolPrism) launch_mono<MODE, kGeomPoolPrism>(P, grid, block, stream, mono);
-  else if (geom == kGeomPool) launch_mono<MODE, kGeomPool>(P, grid, block, stream, mono);
-  else launch_mono<MODE, kGeomOne>(P, grid, block, stream, mono);
+};
+// A unit's entry point: the request, the selection, the launch.  (A template so that only the unit of FAMILY instantiates its kernels; a request
+// whose kernel is another family's is the caller's mistake: launch_trace routes by the same selection.)
+template <int FAMILY>
+static hipError_t launch_family(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono) {
+  const Selection s = select_kernel(make_request(P, family_mode(FAMILY), geom, mono));
+  if (s.err != 0) return static_cast<hipError_t>(s.err);
+  if (!expand_kernel<FAMILY>(s.id, LaunchKernel{P, dim3(blocks), dim3(kBlock), stream})) return hipErrorInvalidValue;
   return hipGetLastError();
 }
 

@@ -1,8 +1,8 @@
-// halo_trace_fx0.hip — the kAccFixed instantiations of halo_trace_kernel in kModePlain (option "deterministic", see halo_trace.inl launch_fixed).
+// halo_trace_fx0.hip — the kAccFixed instantiations of halo_trace_kernel in kModePlain (option "deterministic", see halo_select.h kernel_exists).
 #include "halo_trace.inl"
 
 namespace halo {
 hipError_t launch_trace_fx0(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono) {
-  return launch_fixed<kModePlain>(P, blocks, stream, geom, mono);
+  return launch_family<kFamFixed + kModePlain>(P, blocks, stream, geom, mono);
 }
 }  // namespace halo

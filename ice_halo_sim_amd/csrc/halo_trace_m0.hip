@@ -3,7 +3,7 @@
 
 namespace halo {
 hipError_t launch_trace_m0(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono) {
-  return launch_mode<kModePlain>(P, blocks, stream, geom, mono);
+  return launch_family<kFamMode + kModePlain>(P, blocks, stream, geom, mono);
 }
 }  // namespace halo
 

@@ -3,6 +3,6 @@
 
 namespace halo {
 hipError_t launch_trace_m1(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono) {
-  return launch_mode<kModeFilter>(P, blocks, stream, geom, mono);
+  return launch_family<kFamMode + kModeFilter>(P, blocks, stream, geom, mono);
 }
 }  // namespace halo

@@ -3,6 +3,6 @@
 
 namespace halo {
 hipError_t launch_trace_m2(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono) {
-  return launch_mode<kModeCapture>(P, blocks, stream, geom, mono);
+  return launch_family<kFamMode + kModeCapture>(P, blocks, stream, geom, mono);
 }
 }  // namespace halo

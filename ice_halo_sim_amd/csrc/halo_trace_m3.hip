@@ -4,6 +4,6 @@
 
 namespace halo {
 hipError_t launch_trace_m3(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono) {
-  return launch_mode<kModeGeneric>(P, blocks, stream, geom, mono);
+  return launch_family<kFamMode + kModeGeneric>(P, blocks, stream, geom, mono);
 }
 }  // namespace halo

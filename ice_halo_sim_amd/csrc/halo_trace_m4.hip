@@ -4,6 +4,6 @@
 
 namespace halo {
 hipError_t launch_trace_m4(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono) {
-  return launch_mode<kModeColor>(P, blocks, stream, geom, mono);
+  return launch_family<kFamMode + kModeColor>(P, blocks, stream, geom, mono);
 }
 }  // namespace halo

@@ -1,9 +1,9 @@
-// halo_trace_tl0.hip — the kAccTileFinal instantiations of halo_trace_kernel in kModePlain (option "tile_append", see halo_trace.inl launch_tile).
+// halo_trace_tl0.hip — the kAccTileFinal instantiations of halo_trace_kernel in kModePlain (option "tile_append", see halo_select.h kernel_exists).
 #include "halo_trace.inl"
 
 namespace halo {
 hipError_t launch_trace_tl0(const DispatchParams& P, int blocks, hipStream_t stream, int geom, bool mono) {
-  return launch_tile<kModePlain>(P, blocks, stream, geom, mono);
+  return launch_family<kFamTile + kModePlain>(P, blocks, stream, geom, mono);
 }
 // One resident round of the ticketed kernels: what the runtime says a CU holds of them (they share registers and LDS across lenses and root forms
 // to within the allocator's whim; the headline's instantiation is asked), once per process; the bound the kernels are compiled for if it will not say.

@@ -139,6 +139,29 @@ class HaloAutoEv(C.Structure):
                 ("value_count", C.c_uint32), ("coarse_w", C.c_int32), ("coarse_h", C.c_int32)]
 
 
+STATS_MAX_PERCENTILES = 16
+STATS_PLANE_Y = -1
+# the eleven percentiles of the reference's scripts/dump_xyz_stats.py, and the keys it files them under
+STATS_TOOL_PERCENTILES = (50.0, 70.0, 90.0, 95.0, 99.0, 99.3, 99.5, 99.7, 99.9, 99.95, 99.99)
+STATS_TOOL_KEYS = ("p50", "p70", "p90", "p95", "p99", "p99_3", "p99_5", "p99_7", "p99_9", "p99_95", "p99_99")
+
+
+class HaloStatsSpec(C.Structure):
+    """What halo_consumer_stats is asked for: plane (STATS_PLANE_Y or a class lane), up to 16 percentiles, the saturation divisor (<= 0: the
+    per-pixel intensity)."""
+    _fields_ = [("plane", C.c_int32), ("percentile_count", C.c_int32), ("percentiles", C.c_double * STATS_MAX_PERCENTILES), ("norm", C.c_float),
+                ("reserved", C.c_int32)]
+
+
+class HaloImageStats(C.Structure):
+    """halo_consumer_stats's result: counts, exact sums, max, and per percentile the lower rank, the two order statistics, the fraction between
+    them and the interpolated value (numpy's default rule)."""
+    _fields_ = [("pixel_count", C.c_uint64), ("positive_count", C.c_uint64), ("saturated_count", C.c_uint64), ("sum", C.c_double), ("sum_sq", C.c_double),
+                ("max", C.c_float), ("norm", C.c_float), ("produced", C.c_int32), ("percentile_count", C.c_int32),
+                ("rank", C.c_uint64 * STATS_MAX_PERCENTILES), ("lo", C.c_float * STATS_MAX_PERCENTILES), ("hi", C.c_float * STATS_MAX_PERCENTILES),
+                ("frac", C.c_double * STATS_MAX_PERCENTILES), ("value", C.c_double * STATS_MAX_PERCENTILES)]
+
+
 COMPOSITE_DOMINANT, COMPOSITE_ADDITIVE, COMPOSITE_PAINTER = 0, 1, 2
 
 

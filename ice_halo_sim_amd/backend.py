@@ -7,6 +7,7 @@ all computing happens in the HIP library, and importing this module without the 
 without a gfx950 device at create time) fails loudly — there is no CPU fallback here.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -87,6 +88,9 @@ def load_library():
         "halo_consumer_reset": (C.c_int, [H]),
         "halo_consumer_auto_ev": (C.c_int, [H, C.c_int32, C.c_float, C.POINTER(abi.HaloAutoEv)]),
         "halo_host_ev_auto": (C.c_float, [C.c_float, C.c_float, C.c_float]),
+        "halo_consumer_stats": (C.c_int, [H, C.POINTER(abi.HaloStatsSpec), C.POINTER(abi.HaloImageStats)]),
+        "halo_host_percentile_rank": (C.c_int, [C.c_double, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+        "halo_host_binned_sum": (C.c_int, [C.POINTER(C.c_uint64), C.c_int32, C.POINTER(C.c_double)]),
         "halo_consumer_composite": (C.c_int, [H, C.POINTER(abi.HaloComposite), f32p, C.POINTER(C.c_uint8), f32p, C.POINTER(C.c_int32)]),
         "halo_consumer_load_lanes": (C.c_int, [H, f32p, C.c_int, C.c_int, C.c_int, C.c_double]),
         "halo_host_parse_composite_mode": (C.c_int, [C.c_char_p]),
@@ -122,6 +126,7 @@ EXPORTED_SYMBOLS = [
     "halo_host_refractive_index", "halo_host_reduce_raypath", "halo_host_filter_fast_check", "halo_host_color_fast_mask", "halo_host_illuminant_spd", "halo_host_wl_pool", "halo_reduce_accumulator",
     "halo_peek_fixed", "halo_host_fixed_frac_bits", "halo_begin_spectrum", "halo_host_spectrum_entry",
     "halo_consumer_auto_ev", "halo_host_ev_auto",
+    "halo_consumer_stats", "halo_host_percentile_rank", "halo_host_binned_sum",
     "halo_set_shard", "halo_host_shard_slice", "halo_export_fixed", "halo_import_fixed",
 ]
 
@@ -401,6 +406,39 @@ class HipTraceBackend:
         self._check(self._L.halo_consumer_auto_ev(self._h, int(downsample), float(target_white), C.byref(r)))
         return {"p99_y": r.p99_y, "per_pixel_intensity": r.per_pixel_intensity, "ev_auto": r.ev_auto, "produced": bool(r.produced),
                 "value_count": int(r.value_count), "coarse_w": int(r.coarse_w), "coarse_h": int(r.coarse_h)}
+
+    def ImageStats(self, percentiles=abi.STATS_TOOL_PERCENTILES, plane=None, norm=None):
+        """Exact percentiles and moments of the positive values of the consumer's Y (plane=None) or of class lane `plane`, computed where the
+        image lies (halo_consumer_stats).  percentiles: up to 16 numbers in [0, 100], numpy's default interpolation; norm: the divisor of the
+        normalised view and of the saturation test (None: the per-pixel intensity, as AutoEv reports it).  Returns a dict with the raw fields
+        (pixel_count, positive_count, saturated_count, sum, sum_sq, max_raw, norm, produced, rank, lo, hi, frac, value — lists in the order
+        asked) and the view the reference's stats tool prints, every value divided by norm: percentiles (a list), mean, std (population, from the
+        exact sums), cv, max, saturation_rate = saturated / positive, non_zero_count.  Without a positive value, or without landed intensity
+        when norm is None, produced is False and the view is all zeros, like the tool's.  Reads the consumer only."""
+        pct = [float(p) for p in percentiles]
+        if len(pct) > abi.STATS_MAX_PERCENTILES:
+            raise ValueError("at most %d percentiles per call" % abi.STATS_MAX_PERCENTILES)
+        spec, r = abi.HaloStatsSpec(), abi.HaloImageStats()
+        spec.plane = abi.STATS_PLANE_Y if plane is None else int(plane)
+        spec.percentile_count = len(pct)
+        for j, p in enumerate(pct):
+            spec.percentiles[j] = p
+        spec.norm = 0.0 if norm is None else float(norm)
+        self._check(self._L.halo_consumer_stats(self._h, C.byref(spec), C.byref(r)))
+        k, n, nm = len(pct), int(r.positive_count), float(r.norm)
+        out = {"pixel_count": int(r.pixel_count), "positive_count": n, "non_zero_count": n, "saturated_count": int(r.saturated_count),
+               "sum": r.sum, "sum_sq": r.sum_sq, "max_raw": r.max, "norm": r.norm, "produced": bool(r.produced),
+               "rank": [int(r.rank[j]) for j in range(k)], "lo": [r.lo[j] for j in range(k)], "hi": [r.hi[j] for j in range(k)],
+               "frac": [r.frac[j] for j in range(k)], "value": [r.value[j] for j in range(k)]}
+        if r.produced:
+            mean = r.sum / n
+            var = max(r.sum_sq / n - mean * mean, 0.0)
+            std = math.sqrt(var) if math.isfinite(var) else float("nan")
+            out.update(percentiles=[r.value[j] / nm for j in range(k)], mean=mean / nm, std=std / nm, cv=std / mean if mean > 0.0 else 0.0,
+                       max=r.max / nm, saturation_rate=r.saturated_count / n)
+        else:
+            out.update(percentiles=[0.0] * k, mean=0.0, std=0.0, cv=0.0, max=0.0, saturation_rate=0.0)
+        return out
 
     def Snapshot(self, intensity_factor=1.0, ray_color=(-1.0, -1.0, -1.0), background=(0.0, 0.0, 0.0), want_xyz=True, auto_ev=False, target_white=135.0):
         """PrepareSnapshot + PostSnapshot: returns (rgb uint8[H,W,3], xyz float32[H,W,3] | None, total_intensity).  auto_ev=True: the image is

@@ -13,7 +13,7 @@ import time
 
 import numpy as np
 
-from . import config
+from . import abi, config
 from .backend import BackendError, BackendUnavailableError, HipTraceBackend
 
 DISPATCH_RAYS = 1 << 26  # rays per TraceLayer call (the reference's GPU dispatch is 2^18, server.cpp:151; we batch far larger)
@@ -145,6 +145,16 @@ def exposure_factor(be, rid, factor, args):
     return factor * 2.0 ** a["ev_auto"]
 
 
+def image_stats_record(be, config_path):
+    """--stats: the per-scene record of the reference's scripts/dump_xyz_stats.py for the consumer's image — Y over the per-pixel intensity,
+    the tool's eleven percentiles, mean / std / cv, max and the saturated share of the positive pixels — computed on the device
+    (HipTraceBackend.ImageStats).  The tool's all-zero record when the image has no positive pixel."""
+    s = be.ImageStats(abi.STATS_TOOL_PERCENTILES)
+    return {"scene": os.path.splitext(os.path.basename(config_path))[0], "config": config_path, "pixel_count": s["pixel_count"],
+            "non_zero_count": s["non_zero_count"], "percentiles": dict(zip(abi.STATS_TOOL_KEYS, s["percentiles"])), "mean": s["mean"], "std": s["std"],
+            "cv": s["cv"], "max": s["max"], "saturation_rate": s["saturation_rate"]}
+
+
 def save_all_renders(job, args):
     """`-f cfg -o dir [--format png] [--quality q]`: what the reference CLI leaves in the output directory (SaveRenderResults /
     SaveCompositeResults, main.cpp:251-315): img_<id>.<fmt> per render entry, img_<id>_components.<fmt> with raypath_color."""
@@ -224,6 +234,10 @@ def main(argv=None):
                     help="expose the mono images of -o and --out-rgb automatically: the config's intensity_factor times 2^ev_auto, the reference GUI's "
                     "Adaptive Brightness computed on the device (P99 of the 8 x 8 box sums of Y against the per-pixel landed intensity, mapped to "
                     "--target-white, clamped to +-6 EV).  The EV chosen is printed per render; the class composite keeps its own P99 anchor")
+    ap.add_argument("--stats", default=None, metavar="FILE",
+                    help="write the statistics of the rendered image as one JSON object with the keys of the reference's scripts/dump_xyz_stats.py "
+                    "(scene, config, pixel_count, non_zero_count, percentiles p50 .. p99_99, mean, std, cv, max, saturation_rate of Y over the "
+                    "per-pixel intensity), computed on the device; with --render or a single render entry, with or without --auto-ev")
     ap.add_argument("--target-white", type=float, default=135.0, help="sRGB level (0, 255] the P99 maps to with --auto-ev (default 135)")
     ap.add_argument("--display-ev", type=float, default=0.0, help="display-time EV of the composite (display_exposure_scale = 2^EV)")
     args = ap.parse_args(argv)
@@ -232,6 +246,9 @@ def main(argv=None):
         return 2
     if not 1 <= args.quality <= 100:
         print("Error: --quality must be between 1 and 100, got %d" % args.quality, file=sys.stderr)
+        return 2
+    if args.stats and args.output_dir is not None and not args.benchmark and args.render is None:
+        print("Error: --stats describes one rendered image: pass --render, not -o alone", file=sys.stderr)
         return 2
     shard = None
     if args.ranks < 1 or (args.ranks > 1 and not args.deterministic):
@@ -285,6 +302,10 @@ def main(argv=None):
     wall = time.perf_counter() - wall0
     if args.deterministic:
         print("xyz sha256: %s" % hashlib.sha256(xyz.tobytes()).hexdigest())
+    if args.stats:
+        with open(args.stats, "w") as f:
+            json.dump(image_stats_record(be, args.config), f, indent=2)
+            f.write("\n")
     if args.out_rgb:
         write_ppm(args.out_rgb, rgb)
     if args.out_xyz:

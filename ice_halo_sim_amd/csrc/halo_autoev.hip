@@ -7,16 +7,13 @@
 //      from kernel to kernel in device memory (AevRecord); the host reads the record once, at the end.
 // Every count is an integer, so the record does not depend on the order of the atomic adds: the stage is bit-reproducible.
 #include "halo_launch.h"
+#include "halo_radix.h"
 
 namespace halo {
 
 namespace {
 
-constexpr int kAevBlock = 1024;            // 16 wave64: the pick scans 2048 bins two per thread
-constexpr uint32_t kAevBins = 2048u;       // the widest digit (11 bits)
-constexpr uint32_t kAevPeel = 4u;          // rounds of wave-level aggregation before the plain LDS add
-__host__ __device__ constexpr uint32_t aev_shift(uint32_t pass) { return pass == 0u ? 21u : (pass == 1u ? 10u : 0u); }
-__host__ __device__ constexpr uint32_t aev_width(uint32_t pass) { return pass == 2u ? 10u : 11u; }
+constexpr uint32_t kAevPeel = 4u;          // rounds of wave-level aggregation before the plain LDS add (the digits themselves: halo_radix.h)
 
 // One wave's adds of 1 to h[bin].  A halo image piles into a handful of exponents, so on the first digit most lanes of a wave name the same
 // bin.  The plain form (AGG = false, the product) leaves that to the LDS: measured on images whose first digit lands in a dozen bins, ds_add_u32

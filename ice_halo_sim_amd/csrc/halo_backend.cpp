@@ -221,6 +221,8 @@ struct HaloBackend {
   DevBuf<uint32_t> aev_ws;
   int aev_agg_hist = 0;                  // option "auto_ev_hist": 1 = wave-aggregated adds in the histogram passes (measured slower: DESIGN 3.5, tools/auto_ev_cost.py)
   int aev_select = -1;                   // option "auto_ev_select": -1 by size (kAevSmallMax), 0 the multi-block select, 1 the one-workgroup select
+  DevBuf<uint32_t> stats_ws;             // halo_consumer_stats: the StatsRecord, then the multi-block form's histograms (its values go to aev_vals)
+  int stats_select = -1;                 // option "stats_select": -1 by size (kStatsSmallMax), 0 the multi-block form, 1 one workgroup
   int cons_w = 0, cons_h = 0;
   double total_intensity = 0.0;
   DevBuf<double> tally;        // kTallyLines x kTallyStride doubles, [kSum*] per line: CUMULATIVE tallies of every kernel this backend ever launched
@@ -643,7 +645,7 @@ int halo_destroy(halo_handle_t b) {
   for (int k = 0; k < 2; k++)
     if (b->cs[k]) (void)hipStreamSynchronize(b->cs[k]);
   release_all(b->acc_own, b->tally, b->mono, b->ovf, b->ovf_flag, b->filter_dev, b->cons_sum, b->cons_comp, b->cons_xyz_out, b->cons_stage, b->cons_rgb, b->comp_rgb,
-              b->lanes_stage, b->comp_hist, b->aev_vals, b->aev_ws, b->counters, b->ring_dev, b->tcache_dev, b->shapes_s[0], b->shapes_s[1], b->cont_cnt, b->cont_mask, b->cont_err, b->cont_base,
+              b->lanes_stage, b->comp_hist, b->aev_vals, b->aev_ws, b->stats_ws, b->counters, b->ring_dev, b->tcache_dev, b->shapes_s[0], b->shapes_s[1], b->cont_cnt, b->cont_mask, b->cont_err, b->cont_base,
               b->cont_tiles, b->lanes, b->fix, b->cont[0], b->cont[1], b->exits, b->host_f, b->host_u);
   for (int k = 0; k < 2; k++) release_all(b->bin_list_s[k], b->bin_cnt_s[k], b->bin_list2_s[k], b->bin_cnt2_s[k]);
   for (int k = 0; k < 2; k++) release_all(b->tile_chunk_s[k], b->tile_cnt_s[k]);
@@ -716,6 +718,7 @@ int halo_set_option(halo_handle_t b, const char* key, int64_t v) {
   else if (k == "defer_fold") b->defer_fold = v ? 1 : 0;
   else if (k == "auto_ev_hist") b->aev_agg_hist = v ? 1 : 0;
   else if (k == "auto_ev_select") b->aev_select = v < 0 ? -1 : (v ? 1 : 0);
+  else if (k == "stats_select") b->stats_select = v < 0 ? -1 : (v ? 1 : 0);
   else if (k == "gen_ahead") b->gen_ahead = v ? 1 : 0;
   else if (k == "close_direct") b->close_direct = v < 0 ? -1 : (v ? 1 : 0);
   else if (k == "lean_events") b->lean_events = v ? 1 : 0;
@@ -2834,6 +2837,80 @@ int halo_consumer_auto_ev(halo_handle_t b, int32_t downsample_factor, float targ
   return HALO_OK;
 }
 
+// ---- image statistics (halo_stats.hip) --------------------------------------------------------------------------
+int halo_host_percentile_rank(double percentile, uint64_t n, uint64_t* rank, double* frac) {
+  return host::PercentileRank(percentile, n, rank, frac) ? HALO_OK : HALO_FATAL;
+}
+int halo_host_binned_sum(const uint64_t* bins, int32_t squares, double* out) {
+  if (!bins || !out) return HALO_FATAL;
+  *out = host::BinnedSum(bins, squares != 0);
+  return HALO_OK;
+}
+
+int halo_consumer_stats(halo_handle_t b, const HaloStatsSpec* spec, HaloImageStats* out) {
+  if (!b) return HALO_FATAL;
+  if (!spec || !out) return fail(b, HALO_FATAL, "consumer_stats: spec or out is NULL");
+  if (spec->percentile_count < 0 || spec->percentile_count > HALO_STATS_MAX_PERCENTILES)
+    return fail(b, HALO_FATAL, "consumer_stats: percentile_count must lie in 0 .. 16");
+  StatsAsk ask{};
+  ask.count = static_cast<uint32_t>(spec->percentile_count);
+  for (uint32_t j = 0; j < ask.count; j++) {
+    if (!(spec->percentiles[j] >= 0.0 && spec->percentiles[j] <= 100.0)) return fail(b, HALO_FATAL, "consumer_stats: a percentile lies outside [0, 100]");
+    ask.q[j] = spec->percentiles[j] / 100.0;
+  }
+  const bool lane = spec->plane >= 0;
+  int w = b->cons_w, h = b->cons_h;
+  if (lane) {
+    if (spec->plane >= static_cast<int>(b->color_classes.size()) || !b->lanes.ptr || b->lanes_w <= 0 || b->lanes_h <= 0)
+      return fail(b, HALO_FATAL, "consumer_stats: no such class lane (halo_set_color's class count; lanes exist after a colour session or halo_consumer_load_lanes)");
+    w = b->lanes_w;
+    h = b->lanes_h;
+  } else if (spec->plane != HALO_STATS_PLANE_Y) {
+    return fail(b, HALO_FATAL, "consumer_stats: plane must be HALO_STATS_PLANE_Y or a lane index");
+  } else if (!b->cons_sum.ptr) {
+    return fail(b, HALO_FATAL, "consumer_stats before consumer_fold");
+  }
+  HIPCHK(b, hipSetDevice(b->device));
+  if (lane)
+    if (int rc = join_aux(b)) return rc;   // (kernels of queued sessions may still be adding to the lanes on the trace / auxiliary streams)
+  const uint32_t npix = static_cast<uint32_t>(w) * static_cast<uint32_t>(h);
+  // GetRawXyzResult (render.cpp:586-587), in float like the reference: the same expression as halo_consumer_auto_ev's
+  const float per_pixel = npix > 0u ? static_cast<float>(b->total_intensity) / (0.08f * static_cast<int>(npix)) : 0.0f;
+  const float norm = spec->norm > 0.0f ? spec->norm : per_pixel;
+  std::memset(out, 0, sizeof(*out));
+  out->pixel_count = npix;
+  out->norm = norm;
+  out->percentile_count = spec->percentile_count;
+  if (!(norm > 0.0f)) return HALO_OK;   // no landed intensity to normalise by: nothing produced
+  HIPCHK(b, b->aev_vals.reserve(npix));
+  HIPCHK(b, b->stats_ws.reserve(kStatsWsWords));
+  const bool one_wg = b->stats_select < 0 ? npix <= kStatsSmallMax : b->stats_select == 1;
+  const double* lane_ptr = lane ? b->lanes.ptr + static_cast<size_t>(spec->plane) * npix : nullptr;
+  hipError_t e = launch_stats(b->cons_sum.ptr, b->cons_comp.ptr, lane_ptr, npix, norm, ask, b->aev_vals.ptr, b->stats_ws.ptr, one_wg, b->cu_count, main_q(b));
+  if (e != hipSuccess) return hip_fail(b, e, "halo_stats kernel launch");
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the record's bins are 64-bit words");
+  auto rec = std::make_unique<StatsRecord>();
+  HIPCHK(b, hipMemcpyAsync(rec.get(), b->stats_ws.ptr, sizeof(StatsRecord), hipMemcpyDeviceToHost, main_q(b)));
+  HIPCHK(b, hipStreamSynchronize(main_q(b)));
+  if (rec->sel.n == 0u) return HALO_OK;
+  out->positive_count = rec->sel.n;
+  out->saturated_count = rec->sat;
+  const uint64_t* bins = reinterpret_cast<const uint64_t*>(rec->bins);
+  out->sum = host::BinnedSum(bins, false);
+  out->sum_sq = host::BinnedSum(bins + kStatsExpBins, true);
+  std::memcpy(&out->max, &rec->max_bits, sizeof(float));
+  out->produced = 1;
+  for (uint32_t j = 0; j < ask.count; j++) {
+    out->rank[j] = rec->rank[j];
+    out->frac[j] = rec->frac[j];
+    std::memcpy(&out->lo[j], &rec->lo_bits[j], sizeof(float));
+    std::memcpy(&out->hi[j], &rec->hi_bits[j], sizeof(float));
+    const double lo = out->lo[j], hi = out->hi[j];
+    out->value[j] = lo + (hi - lo) * out->frac[j];   // (three roundings: this file is built without contraction)
+  }
+  return HALO_OK;
+}
+
 // ---- display-side composite of the class lanes (server/component_compositor.cpp) -------------------------
 int halo_host_parse_composite_mode(const char* mode) {   // ParseCompositeMode, component_compositor.cpp:118-134
   if (mode && std::strcmp(mode, "dominant") == 0) return HALO_COMPOSITE_DOMINANT;
@@ -3078,6 +3155,8 @@ uint64_t halo_abi_sizeof(int which) {
     case 10: return sizeof(HaloRouteInfo);
     case 11: return sizeof(HaloComposite);
     case 12: return sizeof(HaloAutoEv);
+    case 13: return sizeof(HaloStatsSpec);
+    case 14: return sizeof(HaloImageStats);
     default: return 0;
   }
 }

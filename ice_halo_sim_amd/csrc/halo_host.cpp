@@ -881,5 +881,74 @@ std::vector<uint64_t> Partition(const float* prop, int n, uint64_t ray_num, doub
   return out;
 }
 
+// ---- image statistics (halo_consumer_stats): the host halves ------------------------------------------------------------------------------
+bool PercentileRank(double percentile, uint64_t n, uint64_t* rank, double* frac) {
+  if (!(percentile >= 0.0 && percentile <= 100.0) || n == 0 || !rank || !frac) return false;
+  const double q = percentile / 100.0;
+  const double vi = q * static_cast<double>(n - 1);   // (one product: this file is built without contraction)
+  const double fl = std::floor(vi);
+  *rank = static_cast<uint64_t>(fl);
+  *frac = vi - fl;
+  return true;
+}
+
+namespace {
+
+// An unsigned integer of 768 bits: the binned sums need 64 + 24 + 2 * 253 = 594 of them.
+struct Wide {
+  static constexpr int kWords = 12;
+  uint64_t w[kWords] = {};
+  void add_word(int i, uint64_t x) {
+    for (; x != 0 && i < kWords; i++) {
+      const uint64_t s = w[i] + x;
+      x = s < x ? 1u : 0u;
+      w[i] = s;
+    }
+  }
+  void add_shifted(uint64_t x, uint32_t shift) {
+    const int i = static_cast<int>(shift / 64u);
+    const uint32_t b = shift % 64u;
+    add_word(i, x << b);
+    if (b) add_word(i + 1, x >> (64u - b));
+  }
+  bool bit(int p) const { return p >= 0 && ((w[p / 64] >> (p % 64)) & 1u) != 0; }
+  int top() const {   // index of the highest set bit, -1 for zero
+    for (int i = kWords - 1; i >= 0; i--)
+      if (w[i])
+        for (int b = 63; b >= 0; b--)
+          if ((w[i] >> b) & 1u) return i * 64 + b;
+    return -1;
+  }
+};
+
+}  // namespace
+
+double BinnedSum(const uint64_t* bins, bool squares) {
+  // a float of exponent field e and 24-bit significand m (hidden bit included; none at e = 0) is m * 2^(max(e, 1) - 150); its square
+  // (lo + hi * 2^24) * 2^(2 * max(e, 1) - 300) with lo, hi the two 24-bit halves of m * m.  Exponent field 255 with v > 0 is +inf.
+  if (bins[255] || (squares && bins[256 + 255])) return std::numeric_limits<double>::infinity();
+  Wide acc;
+  for (uint32_t e = 0; e < 255u; e++) {
+    const uint32_t s = (e ? e : 1u) - 1u;
+    if (!squares) {
+      acc.add_shifted(bins[e], s);             // units of 2^-149
+    } else {
+      acc.add_shifted(bins[e], 2u * s);        // units of 2^-298
+      acc.add_shifted(bins[256u + e], 2u * s + 24u);
+    }
+  }
+  const int scale = squares ? -298 : -149;
+  const int p = acc.top();
+  if (p < 0) return 0.0;
+  if (p <= 52) return std::ldexp(static_cast<double>(acc.w[0]), scale);   // exact
+  const int sh = p - 52;                       // bits [sh, p] are the 53 kept; round to nearest, ties to even
+  uint64_t mant = 0;
+  for (int i = 52; i >= 0; i--) mant = (mant << 1) | (acc.bit(sh + i) ? 1u : 0u);
+  bool sticky = false;
+  for (int i = sh - 2; i >= 0 && !sticky; i--) sticky = acc.bit(i);
+  if (acc.bit(sh - 1) && (sticky || (mant & 1u))) mant++;   // (2^53 after a carry is still exact in a double)
+  return std::ldexp(static_cast<double>(mant), sh + scale);
+}
+
 }  // namespace host
 }  // namespace halo

@@ -70,6 +70,14 @@ bool BuildEntryFast(const ShapeDev& s, EntryFastDev& out);
 
 uint32_t PcgHash(uint32_t x);
 
+// The host halves of halo_consumer_stats (halo_stats.hip).  PercentileRank: numpy's default ("linear") rule, vi = (percentile / 100) * (n - 1) in
+// float64 with one product, rank = floor(vi), frac = vi - rank; false for a percentile outside [0, 100], n = 0 or a null pointer.
+bool PercentileRank(double percentile, uint64_t n, uint64_t* rank, double* frac);
+// The sum of positive floats (squares = false: bins[256], per exponent field the sum of the 24-bit significands) or of their exact squares
+// (squares = true: bins[512], per exponent field the sums of the low and of the high 24 bits of the squared significands), rounded ONCE, to
+// nearest even, from a fixed-width big integer.  +inf when the top exponent field holds anything.
+double BinnedSum(const uint64_t* bins, bool squares);
+
 }  // namespace host
 }  // namespace halo
 

@@ -73,6 +73,39 @@ constexpr uint32_t kAevSmallMax = 1u << 15;
 hipError_t launch_aev_values(const float* sum, const float* comp, uint32_t width, uint32_t height, uint32_t f, uint32_t wc, uint32_t hc, float* vals, int blocks,
                              hipStream_t stream);
 hipError_t launch_aev_select(const float* vals, uint32_t n, AevRecord* rec, uint32_t* hist, bool one_workgroup, bool aggregate, int blocks, hipStream_t stream);
+// halo_stats.hip — the image-statistics stage: one first sweep (values, first-digit histogram, counts, max, the exponent-binned integer sums of the
+// moments), then a radix select of up to kStatsMaxRanks order statistics at once.  StatsAsk is what the caller wants (q = percentile / 100, divided
+// on the host), StatsSel the select's state as it travels from kernel to kernel: the count of positive values, the K distinct ranks in ascending
+// order — per rank the digits found so far (pref), the rank left inside that prefix and the group it belongs to — and the G distinct prefixes
+// (gpref, ascending), one histogram each in the next pass.  StatsRecord is everything the host reads back, once.
+constexpr uint32_t kStatsMaxQ = 16u, kStatsMaxRanks = 2u * kStatsMaxQ, kStatsExpBins = 256u;
+struct StatsAsk {
+  double q[kStatsMaxQ];
+  uint32_t count, reserved;
+};
+struct StatsSel {
+  uint32_t n, K, G, reserved;
+  uint32_t pref[kStatsMaxRanks], rank[kStatsMaxRanks], group[kStatsMaxRanks], gpref[kStatsMaxRanks];
+};
+struct StatsRecord {
+  StatsSel sel;
+  uint32_t sat, max_bits;                                   // values with v / norm > 1; the largest positive bit pattern
+  uint32_t idx_lo[kStatsMaxQ], idx_hi[kStatsMaxQ];          // percentile j's two ranks among the K distinct ones
+  uint32_t lo_bits[kStatsMaxQ], hi_bits[kStatsMaxQ];        // ... and the order statistics found there
+  uint64_t rank[kStatsMaxQ];                                // floor((n - 1) q)
+  double frac[kStatsMaxQ];                                  // (n - 1) q - rank
+  unsigned long long bins[3u * kStatsExpBins];              // per exponent field: sum of m, of (m * m) & 0xFFFFFF, of (m * m) >> 24 (halo_host_binned_sum)
+};
+constexpr uint32_t kStatsRecWords = sizeof(StatsRecord) / sizeof(uint32_t);
+// the workspace: the record, then the multi-block form's global histograms (first digit; 32 x 2048 second; 32 x 1024 third)
+constexpr uint32_t kStatsWsWords = kStatsRecWords + 2048u + kStatsMaxRanks * (2048u + 1024u);
+// up to this many values one workgroup does the whole call in one launch: measured with the eleven-percentile call, it is 25-30 us ahead of the
+// multi-block form's launches at 1 Ki values, 6-12 us ahead at 8 Ki and 20-33 us behind at 16 Ki (profiles/image_stats_cost.txt) — a quarter
+// of kAevSmallMax, because one workgroup here makes up to nine sweeps where auto-EV's makes three
+constexpr uint32_t kStatsSmallMax = 1u << 13;
+// (lane == nullptr: the values are Y = sum[3 p + 1] + comp[3 p + 1]; else float(lane[p]).  vals: n_pix floats.  ws: kStatsWsWords words)
+hipError_t launch_stats(const float* sum, const float* comp, const double* lane, uint32_t n_pix, float norm, const StatsAsk& ask, float* vals, uint32_t* ws,
+                        bool one_workgroup, int blocks, hipStream_t stream);
 hipError_t launch_cont_reorder(const float* in, uint32_t in_stride, uint32_t region, const uint32_t* cnt, uint32_t max_fill, const uint32_t* mask, uint32_t n_roots,
                                uint32_t* tile_sum, uint32_t* base, float* out, uint32_t out_stride, uint32_t n_cont, uint32_t planes, uint32_t* err, hipStream_t stream);
 

@@ -178,6 +178,14 @@ class HipTraceBackend {
     Check(halo_consumer_auto_ev(h_, downsample, target_white, &r));
     return r;
   }
+  // Exact percentiles and moments of the positive values of the consumer's Y (or of one class lane), computed where the image lies: the numbers of
+  // the reference's doc/xyz-stats-tool.md.  An EV at another anchor than AutoEv's P99 of the box sums is one more call, e.g. for P99.5:
+  // halo_host_ev_auto(float(stats.value[j]), AutoEv().per_pixel_intensity, target_white).  The seam has no counterpart: it is this backend's own.
+  HaloImageStats ImageStats(const HaloStatsSpec& spec) {
+    HaloImageStats r{};
+    Check(halo_consumer_stats(h_, &spec, &r));
+    return r;
+  }
   // trace_backend.hpp:587,625 — real counts of the last session's stochastic draws (never stand-ins)
   size_t GetLastBatchStochasticCrystalSampleCount() const {
     uint64_t c = 0, o = 0;

@@ -572,6 +572,46 @@ int halo_consumer_auto_ev(halo_handle_t h, int32_t downsample_factor, float targ
  * with target_linear the sRGB decoding of target_white / 255.  No GPU needed. */
 float halo_host_ev_auto(float p99_y, float per_pixel_intensity, float target_white);
 
+/* --- image statistics: exact percentiles and moments of the consumer's image, on the device (the numbers of the reference's
+ *     doc/xyz-stats-tool.md / scripts/dump_xyz_stats.py; the stage has no counterpart in the reference's backend seam) --- */
+#define HALO_STATS_MAX_PERCENTILES 16
+enum { HALO_STATS_PLANE_Y = -1 }; /* >= 0: class lane c of halo_set_color */
+typedef struct HaloStatsSpec {
+  int32_t plane;            /* HALO_STATS_PLANE_Y or a lane index */
+  int32_t percentile_count; /* 0 .. 16 */
+  double percentiles[HALO_STATS_MAX_PERCENTILES]; /* each in [0, 100], any order, repeats allowed */
+  float norm;               /* > 0: the divisor of the saturation test; <= 0: the per-pixel intensity (HaloAutoEv::per_pixel_intensity) */
+  int32_t reserved;
+} HaloStatsSpec;
+typedef struct HaloImageStats {
+  uint64_t pixel_count, positive_count, saturated_count;
+  double sum, sum_sq;       /* of the positive values: the exact sums of the floats and of their exact squares, each rounded once */
+  float max, norm;          /* norm: the divisor actually used */
+  int32_t produced;         /* 0: no positive value, or norm == 0 when asked for the intensity */
+  int32_t percentile_count;
+  uint64_t rank[HALO_STATS_MAX_PERCENTILES]; /* lower rank, 0-based */
+  float lo[HALO_STATS_MAX_PERCENTILES], hi[HALO_STATS_MAX_PERCENTILES];      /* order statistics at rank and min(rank + 1, n - 1): raw values, bit-exact */
+  double frac[HALO_STATS_MAX_PERCENTILES], value[HALO_STATS_MAX_PERCENTILES]; /* value = lo + (hi - lo) * frac, evaluated in float64 */
+} HaloImageStats;
+/* Statistics of the values v > 0 (n = positive_count of them; NaN fails the test, +inf passes and orders above every finite value) of the
+ * consumer's snapshot Y = sum + compensation (exactly halo_consumer_snapshot's xyz_out[..., 1] and what halo_consumer_auto_ev's fine path reads)
+ * or of class lane `plane` as it lies.  Percentile p is numpy's default ("linear"): vi = (p / 100.0) * (double)(n - 1) — the quotient first,
+ * then one float64 product — rank = floor(vi), frac = vi - rank, and the two order statistics at rank and min(rank + 1, n - 1), found by ONE
+ * radix select for all ranks with no host wait between its passes.  saturated_count counts v / norm > 1 on the float32 quotient; sum and
+ * sum_sq come from integer sums per exponent and do not depend on the order of any add.  The whole result is bit-reproducible.  With no
+ * positive value — or norm == 0 when the intensity was asked for — only pixel_count, norm and percentile_count are written (the rest is
+ * zero).  Reads the consumer only: image, lanes and total intensity stay as they are.  HALO_FATAL (handle still usable) before any fold /
+ * consume (plane Y) or without lanes / with a lane index outside halo_set_color's class count (plane >= 0), on NULL arguments, on a
+ * percentile outside [0, 100] or a percentile_count outside 0 .. 16. */
+int halo_consumer_stats(halo_handle_t h, const HaloStatsSpec* spec, HaloImageStats* out);
+/* The rank rule above, as the device evaluates it.  HALO_FATAL for a percentile outside [0, 100], n == 0 or a NULL pointer.  No GPU needed. */
+int halo_host_percentile_rank(double percentile, uint64_t n, uint64_t* rank, double* frac);
+/* The exact sum behind HaloImageStats::sum (squares = 0: bins[256], per float exponent field e the sum of the 24-bit significands m, hidden
+ * bit included, none at e = 0; a value is m * 2^(max(e, 1) - 150)) or ::sum_sq (squares = 1: bins[512], per e the sum of (m * m) & 0xFFFFFF,
+ * then per e the sum of (m * m) >> 24), rounded once to the nearest float64, ties to even; +inf when the bins of e = 255 hold anything.  No
+ * GPU needed. */
+int halo_host_binned_sum(const uint64_t* bins, int32_t squares, double* out);
+
 /* --- display-side composite of the raypath-colour class lanes (server/component_compositor.cpp) ------------- */
 /* CompositeMode (component_compositor.hpp:21): how the per-class Y lanes become one colour per pixel. */
 enum { HALO_COMPOSITE_DOMINANT = 0, HALO_COMPOSITE_ADDITIVE = 1, HALO_COMPOSITE_PAINTER = 2 };
@@ -686,7 +726,7 @@ int halo_host_wl_pool(const HaloWl* wl, float* entries5, int cap);
  * different cuts of the share into launches, which must agree (0xFFFFFFFF if they did not).  Parity-test hook, no device needed. */
 uint32_t halo_host_spectrum_entry(uint64_t m, uint32_t count, uint64_t r);
 int halo_abi_version(void);
-/* sizeof() of boundary structs as compiled (0 scene, 1 render, 2 wl, 3 exit record, 4 geom tables, 5 layer stats, 6 entry, 7 colour set, 8 colour class, 9 filter, 10 route info, 11 composite, 12 auto ev). */
+/* sizeof() of boundary structs as compiled (0 scene, 1 render, 2 wl, 3 exit record, 4 geom tables, 5 layer stats, 6 entry, 7 colour set, 8 colour class, 9 filter, 10 route info, 11 composite, 12 auto ev, 13 stats spec, 14 image stats). */
 uint64_t halo_abi_sizeof(int which);
 
 #ifdef __cplusplus
@@ -722,6 +762,8 @@ HALO_STATIC_ASSERT(sizeof(HaloExitRecord) == 40 + HALO_PATH_CAP, "HaloExitRecord
 HALO_STATIC_ASSERT(sizeof(HaloRouteInfo) == 40, "HaloRouteInfo");
 HALO_STATIC_ASSERT(sizeof(HaloDisplay) == 28, "HaloDisplay");
 HALO_STATIC_ASSERT(sizeof(HaloAutoEv) == 28, "HaloAutoEv");
+HALO_STATIC_ASSERT(sizeof(HaloStatsSpec) == 16 + 8 * HALO_STATS_MAX_PERCENTILES, "HaloStatsSpec");
+HALO_STATIC_ASSERT(sizeof(HaloImageStats) == 56 + 32 * HALO_STATS_MAX_PERCENTILES, "HaloImageStats");
 HALO_STATIC_ASSERT(sizeof(HaloCompositeClass) == 24, "HaloCompositeClass");
 HALO_STATIC_ASSERT(sizeof(HaloComposite) == 16 + HALO_COLOR_MAX_CLASSES * 24, "HaloComposite");
 HALO_STATIC_ASSERT(sizeof(HaloGeomTables) == 4 + HALO_MAX_FACES * 20 + 4 + HALO_MAX_TRIS * (36 + 12 + 4 + 4), "HaloGeomTables");

@@ -162,6 +162,12 @@ class HaloImageStats(C.Structure):
                 ("frac", C.c_double * STATS_MAX_PERCENTILES), ("value", C.c_double * STATS_MAX_PERCENTILES)]
 
 
+class HaloViewSpec(C.Structure):
+    """What halo_consumer_view looks through: the view render, the render the consumer's image was accumulated under (has_source = 0: the
+    handle's last session's), the snapshot's display transform."""
+    _fields_ = [("view", HaloRender), ("has_source", C.c_int32), ("source", HaloRender), ("display", HaloDisplay)]
+
+
 COMPOSITE_DOMINANT, COMPOSITE_ADDITIVE, COMPOSITE_PAINTER = 0, 1, 2
 
 

@@ -91,6 +91,8 @@ def load_library():
         "halo_consumer_stats": (C.c_int, [H, C.POINTER(abi.HaloStatsSpec), C.POINTER(abi.HaloImageStats)]),
         "halo_host_percentile_rank": (C.c_int, [C.c_double, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
         "halo_host_binned_sum": (C.c_int, [C.POINTER(C.c_uint64), C.c_int32, C.POINTER(C.c_double)]),
+        "halo_consumer_view": (C.c_int, [H, C.POINTER(abi.HaloViewSpec), C.POINTER(C.c_uint8), f32p, C.POINTER(C.c_int32), f32p]),
+        "halo_host_view_direction": (C.c_int, [C.POINTER(abi.HaloRender), C.c_int32, C.c_int32, f32p]),
         "halo_consumer_composite": (C.c_int, [H, C.POINTER(abi.HaloComposite), f32p, C.POINTER(C.c_uint8), f32p, C.POINTER(C.c_int32)]),
         "halo_consumer_load_lanes": (C.c_int, [H, f32p, C.c_int, C.c_int, C.c_int, C.c_double]),
         "halo_host_parse_composite_mode": (C.c_int, [C.c_char_p]),
@@ -127,6 +129,7 @@ EXPORTED_SYMBOLS = [
     "halo_peek_fixed", "halo_host_fixed_frac_bits", "halo_begin_spectrum", "halo_host_spectrum_entry",
     "halo_consumer_auto_ev", "halo_host_ev_auto",
     "halo_consumer_stats", "halo_host_percentile_rank", "halo_host_binned_sum",
+    "halo_consumer_view", "halo_host_view_direction",
     "halo_set_shard", "halo_host_shard_slice", "halo_export_fixed", "halo_import_fixed",
 ]
 
@@ -456,6 +459,32 @@ class HipTraceBackend:
                                                    xyz.ctypes.data_as(C.POINTER(C.c_float)) if want_xyz else None, C.byref(tot)))
         return rgb, xyz, tot.value
 
+    def View(self, view, source=None, intensity_factor=1.0, ray_color=(-1.0, -1.0, -1.0), background=(0.0, 0.0, 0.0), want=("rgb",)):
+        """The consumer's image through another lens (halo_consumer_view): `view` is a HaloRender (scenes.render) to look through, `source` the
+        render the image was accumulated under (None: this handle's last session's).  Per view pixel the direction of its centre under the view's
+        lens, the source pixel that direction lands on, that pixel's raw XYZ and its display transform — a gather on the device, no ray is traced.
+        want: any of "rgb" (uint8[H,W,3]), "xyz" (float32[H,W,3]), "map" (int32[H,W]: row-major source pixel, -1 for none), "dir"
+        (float32[H,W,3]: world exit direction, zeros for none); returns a dict of the arrays asked for.  The display arguments are Snapshot's
+        (an automatic exposure is the CONSUMER's: intensity_factor * 2 ** AutoEv()["ev_auto"])."""
+        unknown = set(want) - {"rgb", "xyz", "map", "dir"}
+        if unknown:
+            raise ValueError("View: unknown output %r" % sorted(unknown))
+        spec = abi.HaloViewSpec()
+        spec.view = view
+        spec.has_source = 0 if source is None else 1
+        if source is not None:
+            spec.source = source
+        spec.display = abi.HaloDisplay(float(intensity_factor), (C.c_float * 3)(*ray_color), (C.c_float * 3)(*background))
+        h, w = max(int(view.height), 0), max(int(view.width), 0)
+        big = w * h > 1 << 25   # (refused by the library: nothing of that size is allocated here)
+        shapes = {"rgb": ((h, w, 3), np.uint8), "xyz": ((h, w, 3), np.float32), "map": ((h, w), np.int32), "dir": ((h, w, 3), np.float32)}
+        out = {k: np.empty((0,) if big else shapes[k][0], shapes[k][1]) for k in want}
+
+        def ptr(k, t):
+            return out[k].ctypes.data_as(C.POINTER(t)) if k in out else None
+        self._check(self._L.halo_consumer_view(self._h, C.byref(spec), ptr("rgb", C.c_uint8), ptr("xyz", C.c_float), ptr("map", C.c_int32), ptr("dir", C.c_float)))
+        return out
+
     def ResetConsumer(self):
         self._check(self._L.halo_consumer_reset(self._h))
 
@@ -479,6 +508,14 @@ class HipTraceBackend:
         self._check(self._L.halo_consumer_composite(self._h, C.byref(spec), lin.ctypes.data_as(C.POINTER(C.c_float)),
                                                     srgb.ctypes.data_as(C.POINTER(C.c_uint8)) if want_srgb else None, C.byref(p99), C.byref(produced)))
         return bool(produced.value), lin, srgb, p99.value
+
+
+def host_view_direction(view, px, py):
+    """halo_host_view_direction: (has a direction, float32[3]) of pixel (px, py) of the HaloRender `view`, by the view stage's own code on the host
+    (no device needed)."""
+    d = np.zeros(3, np.float32)
+    ok = load_library().halo_host_view_direction(C.byref(view), int(px), int(py), d.ctypes.data_as(C.POINTER(C.c_float)))
+    return bool(ok), d
 
 
 def host_spectrum_entry(m, count, r):

@@ -145,6 +145,30 @@ def exposure_factor(be, rid, factor, args):
     return factor * 2.0 ** a["ev_auto"]
 
 
+def view_render(args, source):
+    """--out-view: the HaloRender to look through.  What is not given keeps the traced render's value (size, view direction, visible range,
+    overlap) or the lens's usual field of view; the lens shift is none."""
+    from . import scenes
+    lens = config.LENS_NAMES[args.view_lens] if args.view_lens else source.lens_type
+    if args.view_size:
+        try:
+            w, h = (int(v) for v in args.view_size.lower().split("x"))
+        except ValueError:
+            raise config.ConfigError("--view-size wants WxH, got %r" % args.view_size)
+    else:
+        w, h = source.width, source.height
+    if args.view_fov is not None:
+        fov = args.view_fov
+    elif lens == source.lens_type:
+        fov = source.fov
+    else:
+        fov = {abi.LENS_LINEAR: 90.0, abi.LENS_GLOBE: 60.0, abi.LENS_RECTANGULAR: 360.0}.get(lens, 180.0)
+    pick = lambda v, d: d if v is None else v
+    return scenes.render(lens, w, h, fov=fov, az=pick(args.view_az, source.view_az), el=pick(args.view_el, source.view_el), ro=pick(args.view_roll, source.view_ro),
+                         visible=config.VISIBLE_NAMES[args.view_visible] if args.view_visible else source.visible,
+                         overlap=pick(args.view_overlap, source.overlap))
+
+
 def image_stats_record(be, config_path):
     """--stats: the per-scene record of the reference's scripts/dump_xyz_stats.py for the consumer's image — Y over the per-pixel intensity,
     the tool's eleven percentiles, mean / std / cv, max and the saturated share of the positive pixels — computed on the device
@@ -207,6 +231,20 @@ def main(argv=None):
     ap.add_argument("--backend", default="hip", help="accepted for the reference's command lines (auto | cpu | metal | cuda | hip); this engine has one backend")
     ap.add_argument("--out-rgb", default=None, help="write the sRGB image as binary PPM")
     ap.add_argument("--out-xyz", default=None, help="write the raw XYZ snapshot as .npy")
+    ap.add_argument("--out-view", default=None, metavar="FILE.ppm",
+                    help="write the traced image seen through another lens as binary PPM: per pixel of the view the traced image is read where that "
+                    "pixel's direction lands (a gather on the device, nearest neighbour; no ray is traced).  Trace into a full-sky equal-area render "
+                    "(dual_fisheye_equal_area) and every view shows radiance.  The --view-* options say what to look through; --auto-ev / "
+                    "--target-white expose it as they expose --out-rgb (the EV is the traced image's)")
+    ap.add_argument("--view-lens", default=None, choices=sorted(config.LENS_NAMES), help="lens of --out-view (default: the traced render's)")
+    ap.add_argument("--view-fov", type=float, default=None, help="field of view of --out-view in degrees (default: the traced render's for the same lens, "
+                    "else 90 linear, 60 globe, 180 fisheye)")
+    ap.add_argument("--view-az", type=float, default=None, help="view azimuth of --out-view in degrees (default: the traced render's)")
+    ap.add_argument("--view-el", type=float, default=None, help="view elevation of --out-view")
+    ap.add_argument("--view-roll", type=float, default=None, help="view roll of --out-view")
+    ap.add_argument("--view-size", default=None, metavar="WxH", help="size of --out-view (default: the traced render's)")
+    ap.add_argument("--view-visible", default=None, choices=sorted(config.VISIBLE_NAMES), help="visible range of --out-view (default: the traced render's)")
+    ap.add_argument("--view-overlap", type=float, default=None, help="dual-fisheye overlap of --out-view (default: the traced render's)")
     ap.add_argument("--out-lanes", default=None, help="raypath_color configs: write the per-class Y lanes (classes, H, W) as .npy")
     ap.add_argument("--out-composite", default=None, help="raypath_color configs: write the class composite (the config's mode: dominant | additive | "
                     "painter; component_compositor.cpp) as binary PPM, composited on the device")
@@ -297,8 +335,9 @@ def main(argv=None):
         leave_ranks()
         return 0
     meta = job.render_meta.get(res["render_id"], {})
-    rgb, xyz, total_intensity = be.Snapshot(intensity_factor=exposure_factor(be, res["render_id"], meta.get("intensity_factor", 1.0), args),
-                                            ray_color=meta.get("ray_color", (-1.0, -1.0, -1.0)), background=meta.get("background", (0.0, 0.0, 0.0)))
+    display = dict(intensity_factor=exposure_factor(be, res["render_id"], meta.get("intensity_factor", 1.0), args),
+                   ray_color=meta.get("ray_color", (-1.0, -1.0, -1.0)), background=meta.get("background", (0.0, 0.0, 0.0)))
+    rgb, xyz, total_intensity = be.Snapshot(**display)
     wall = time.perf_counter() - wall0
     if args.deterministic:
         print("xyz sha256: %s" % hashlib.sha256(xyz.tobytes()).hexdigest())
@@ -310,6 +349,13 @@ def main(argv=None):
         write_ppm(args.out_rgb, rgb)
     if args.out_xyz:
         np.save(args.out_xyz, xyz)
+    if args.out_view:
+        try:
+            write_ppm(args.out_view, be.View(view_render(args, res["render"]), res["render"], **display)["rgb"])
+        except config.ConfigError as e:
+            print("config error: %s" % e, file=sys.stderr)
+            be.close()
+            return 2
     if args.out_composite and job.color_classes:   # before the lanes are drained: the composite reads them where they are
         ok, _, srgb, p99 = be.CompositeColorClasses(job.color_meta, job.color_mode, 2.0 ** args.display_ev, meta.get("intensity_factor", 1.0))
         if ok:

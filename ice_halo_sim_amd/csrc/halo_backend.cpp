@@ -223,6 +223,11 @@ struct HaloBackend {
   int aev_select = -1;                   // option "auto_ev_select": -1 by size (kAevSmallMax), 0 the multi-block select, 1 the one-workgroup select
   DevBuf<uint32_t> stats_ws;             // halo_consumer_stats: the StatsRecord, then the multi-block form's histograms (its values go to aev_vals)
   int stats_select = -1;                 // option "stats_select": -1 by size (kStatsSmallMax), 0 the multi-block form, 1 one workgroup
+  // halo_consumer_view: the view's four outputs before they are copied back
+  DevBuf<uint8_t> view_rgb;
+  DevBuf<float> view_xyz, view_dir;
+  DevBuf<int32_t> view_map;
+  bool had_session = false;              // `render` holds a session's render (halo_consumer_view's default source)
   int cons_w = 0, cons_h = 0;
   double total_intensity = 0.0;
   DevBuf<double> tally;        // kTallyLines x kTallyStride doubles, [kSum*] per line: CUMULATIVE tallies of every kernel this backend ever launched
@@ -645,7 +650,7 @@ int halo_destroy(halo_handle_t b) {
   for (int k = 0; k < 2; k++)
     if (b->cs[k]) (void)hipStreamSynchronize(b->cs[k]);
   release_all(b->acc_own, b->tally, b->mono, b->ovf, b->ovf_flag, b->filter_dev, b->cons_sum, b->cons_comp, b->cons_xyz_out, b->cons_stage, b->cons_rgb, b->comp_rgb,
-              b->lanes_stage, b->comp_hist, b->aev_vals, b->aev_ws, b->stats_ws, b->counters, b->ring_dev, b->tcache_dev, b->shapes_s[0], b->shapes_s[1], b->cont_cnt, b->cont_mask, b->cont_err, b->cont_base,
+              b->lanes_stage, b->comp_hist, b->aev_vals, b->aev_ws, b->stats_ws, b->view_rgb, b->view_xyz, b->view_dir, b->view_map, b->counters, b->ring_dev, b->tcache_dev, b->shapes_s[0], b->shapes_s[1], b->cont_cnt, b->cont_mask, b->cont_err, b->cont_base,
               b->cont_tiles, b->lanes, b->fix, b->cont[0], b->cont[1], b->exits, b->host_f, b->host_u);
   for (int k = 0; k < 2; k++) release_all(b->bin_list_s[k], b->bin_cnt_s[k], b->bin_list2_s[k], b->bin_cnt2_s[k]);
   for (int k = 0; k < 2; k++) release_all(b->tile_chunk_s[k], b->tile_cnt_s[k]);
@@ -884,6 +889,7 @@ static int begin_session(halo_handle_t b, const HaloScene* scene, const HaloRend
   }
   b->scene = *scene;
   b->render = *render;
+  b->had_session = true;
   b->wl = *wl;
   b->proj = host::BuildProj(*render);
   std::vector<WlEntryDev> pool = host::BuildWlPool(*wl);
@@ -2911,6 +2917,50 @@ int halo_consumer_stats(halo_handle_t b, const HaloStatsSpec* spec, HaloImageSta
   return HALO_OK;
 }
 
+// ---- the view stage (halo_view.hip): the consumer's image through another lens -------------------------------
+int halo_host_view_direction(const HaloRender* view, int32_t px, int32_t py, float dir[3]) {
+  if (!view || !dir) return 0;
+  return host::ViewDirection(*view, px, py, dir) ? 1 : 0;
+}
+
+int halo_consumer_view(halo_handle_t b, const HaloViewSpec* spec, uint8_t* rgb_out, float* xyz_out, int32_t* map_out, float* dir_out) {
+  if (!b) return HALO_FATAL;
+  if (!spec) return fail(b, HALO_FATAL, "consumer_view: spec is NULL");
+  if (!b->cons_sum.ptr) return fail(b, HALO_FATAL, "consumer_view before consumer_fold");
+  if (b->in_session) return fail(b, HALO_FATAL, "consumer_view inside a session");
+  if (!rgb_out && !xyz_out && !map_out && !dir_out) return fail(b, HALO_FATAL, "consumer_view: every output is NULL");
+  const HaloRender& view = spec->view;
+  if (view.width <= 0 || view.height <= 0) return fail(b, HALO_FATAL, "consumer_view: empty view");
+  if (static_cast<uint64_t>(view.width) * static_cast<uint64_t>(view.height) > (1ull << 25))
+    return fail(b, HALO_UNAVAILABLE, "consumer_view: a view of more than 2^25 pixels");
+  if (!spec->has_source && !b->had_session) return fail(b, HALO_FATAL, "consumer_view: no source render (has_source = 0 on a handle that has had no session)");
+  const HaloRender& source = spec->has_source ? spec->source : b->render;
+  if (source.width != b->cons_w || source.height != b->cons_h) return fail(b, HALO_FATAL, "consumer_view: the source render's size is not the consumer's");
+  if (view.lens_type < HALO_LENS_LINEAR || view.lens_type > HALO_LENS_GLOBE || source.lens_type < HALO_LENS_LINEAR || source.lens_type > HALO_LENS_GLOBE)
+    return fail(b, HALO_FATAL, "consumer_view: unknown lens type");
+  HIPCHK(b, hipSetDevice(b->device));
+  const uint32_t cons_pix = static_cast<uint32_t>(b->cons_w) * static_cast<uint32_t>(b->cons_h);
+  const size_t npix = static_cast<size_t>(view.width) * static_cast<size_t>(view.height), n = npix * 3;
+  // ExposureScale (render.cpp:96-102) over the CONSUMER's pixels: the expression of halo_consumer_snapshot, so a view pixel is its source pixel's byte
+  const float snapshot_intensity = static_cast<float>(b->total_intensity);
+  const float scale = (cons_pix == 0 || snapshot_intensity <= 0.0f) ? 0.0f : spec->display.intensity_factor * 0.08f * static_cast<float>(cons_pix) / snapshot_intensity;
+  if (rgb_out) HIPCHK(b, b->view_rgb.reserve(n));
+  if (xyz_out) HIPCHK(b, b->view_xyz.reserve(n));
+  if (dir_out) HIPCHK(b, b->view_dir.reserve(n));
+  if (map_out) HIPCHK(b, b->view_map.reserve(npix));
+  hipError_t e = launch_view(b->cons_sum.ptr, b->cons_comp.ptr, host::BuildProj(view), host::BuildProj(source), scale, spec->display.ray_color, spec->display.background,
+                             rgb_out ? b->view_rgb.ptr : nullptr, xyz_out ? b->view_xyz.ptr : nullptr, map_out ? b->view_map.ptr : nullptr,
+                             dir_out ? b->view_dir.ptr : nullptr, b->cu_count * 8, main_q(b));
+  if (e != hipSuccess) return hip_fail(b, e, "halo_view_kernel launch");
+  if (rgb_out) HIPCHK(b, hipMemcpyAsync(rgb_out, b->view_rgb.ptr, n, hipMemcpyDeviceToHost, main_q(b)));
+  if (xyz_out) HIPCHK(b, hipMemcpyAsync(xyz_out, b->view_xyz.ptr, n * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
+  if (map_out) HIPCHK(b, hipMemcpyAsync(map_out, b->view_map.ptr, npix * sizeof(int32_t), hipMemcpyDeviceToHost, main_q(b)));
+  if (dir_out) HIPCHK(b, hipMemcpyAsync(dir_out, b->view_dir.ptr, n * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
+  HIPCHK(b, hipStreamSynchronize(main_q(b)));
+  if (rgb_out && scale == 0.0f) std::memset(rgb_out, 0, n);   // PostSnapshot's early-out, as halo_consumer_snapshot has it
+  return HALO_OK;
+}
+
 // ---- display-side composite of the class lanes (server/component_compositor.cpp) -------------------------
 int halo_host_parse_composite_mode(const char* mode) {   // ParseCompositeMode, component_compositor.cpp:118-134
   if (mode && std::strcmp(mode, "dominant") == 0) return HALO_COMPOSITE_DOMINANT;
@@ -3157,6 +3207,7 @@ uint64_t halo_abi_sizeof(int which) {
     case 12: return sizeof(HaloAutoEv);
     case 13: return sizeof(HaloStatsSpec);
     case 14: return sizeof(HaloImageStats);
+    case 15: return sizeof(HaloViewSpec);
     default: return 0;
   }
 }

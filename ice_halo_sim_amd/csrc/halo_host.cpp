@@ -11,6 +11,7 @@
 
 #include "cie_tables.inc"
 #include "halo_geom.h"
+#include "halo_view.h"
 
 namespace halo {
 namespace host {
@@ -948,6 +949,16 @@ double BinnedSum(const uint64_t* bins, bool squares) {
   for (int i = sh - 2; i >= 0 && !sticky; i--) sticky = acc.bit(i);
   if (acc.bit(sh - 1) && (sticky || (mant & 1u))) mant++;   // (2^53 after a carry is still exact in a double)
   return std::ldexp(static_cast<double>(mant), sh + scale);
+}
+
+// ---- the view stage (halo_consumer_view): the lens inverses on the host ------------------------------------------------------------------
+bool ViewDirection(const HaloRender& view, int px, int py, float dir[3]) {
+  dir[0] = dir[1] = dir[2] = 0.0f;
+  if (view.width <= 0 || view.height <= 0 || px < 0 || py < 0 || px >= view.width || py >= view.height) return false;
+  const ProjDev p = BuildProj(view);
+  float pre[4];
+  view_proj_pre(p, pre);
+  return view_direction(p, pre, px, py, dir);
 }
 
 }  // namespace host

@@ -78,6 +78,10 @@ bool PercentileRank(double percentile, uint64_t n, uint64_t* rank, double* frac)
 // nearest even, from a fixed-width big integer.  +inf when the top exponent field holds anything.
 double BinnedSum(const uint64_t* bins, bool squares);
 
+// The host half of halo_consumer_view: the world exit direction the lens of `view` puts on the centre of pixel (px, py) — halo_view.h
+// view_direction on BuildProj(view), the code halo_view_kernel runs.  false (and zeros) where the pixel has no direction or lies outside the frame.
+bool ViewDirection(const HaloRender& view, int px, int py, float dir[3]);
+
 }  // namespace host
 }  // namespace halo
 

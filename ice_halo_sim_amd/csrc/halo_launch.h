@@ -106,6 +106,11 @@ constexpr uint32_t kStatsSmallMax = 1u << 13;
 // (lane == nullptr: the values are Y = sum[3 p + 1] + comp[3 p + 1]; else float(lane[p]).  vals: n_pix floats.  ws: kStatsWsWords words)
 hipError_t launch_stats(const float* sum, const float* comp, const double* lane, uint32_t n_pix, float norm, const StatsAsk& ask, float* vals, uint32_t* ws,
                         bool one_workgroup, int blocks, hipStream_t stream);
+// halo_view.hip — the view stage: per pixel of the `view` projection the direction of its centre (halo_view.h), the pixel of the `source`
+// projection that direction lands on (project_exit's primary hit; -1 for none), that pixel's sum + comp and its display transform.  Every output
+// may be null: rgb 3 bytes, xyz / dir 3 floats, map one int32 per view pixel.  `blocks` caps the grid; more tiles than that are strided over.
+hipError_t launch_view(const float* sum, const float* comp, const ProjDev& view, const ProjDev& source, float scale, const float ray_color[3], const float background[3],
+                       uint8_t* rgb_out, float* xyz_out, int32_t* map_out, float* dir_out, int blocks, hipStream_t stream);
 hipError_t launch_cont_reorder(const float* in, uint32_t in_stride, uint32_t region, const uint32_t* cnt, uint32_t max_fill, const uint32_t* mask, uint32_t n_roots,
                                uint32_t* tile_sum, uint32_t* base, float* out, uint32_t out_stride, uint32_t n_cont, uint32_t planes, uint32_t* err, hipStream_t stream);
 

@@ -171,6 +171,12 @@ class HipTraceBackend {
     Check(halo_consumer_snapshot(h_, &display, rgb_out, xyz_out, &total));
     return total;
   }
+  // The consumer's image through another lens (halo_consumer_view): per pixel of spec.view the direction of its centre, the pixel of the source
+  // render that direction lands on, its raw XYZ and its display transform — what the reference's preview / export shaders gather from their
+  // full-sky image, here from the image where it lies.  Every output may be null.
+  void View(const HaloViewSpec& spec, uint8_t* rgb_out, float* xyz_out = nullptr, int32_t* map_out = nullptr, float* dir_out = nullptr) {
+    Check(halo_consumer_view(h_, &spec, rgb_out, xyz_out, map_out, dir_out));
+  }
   // The reference GUI's Adaptive Brightness anchor (gui/gui_ev_auto.hpp ComputeP99Y + ComputeEvAuto) on the device consumer: expose a
   // snapshot with display.intensity_factor * exp2(result.ev_auto); result.produced == 0 is the GUI's "auto: no data"
   HaloAutoEv AutoEv(int downsample = 8, float target_white = 135.f) {

@@ -612,6 +612,38 @@ int halo_host_percentile_rank(double percentile, uint64_t n, uint64_t* rank, dou
  * GPU needed. */
 int halo_host_binned_sum(const uint64_t* bins, int32_t squares, double* out);
 
+/* --- view stage: the consumer's image through any lens, gathered on the device (what the reference's preview and export shaders do with
+ *     their one full-sky image: gui/preview_renderer.cpp, gui/export_fbo_renderer.hpp; the stage has no counterpart in the backend seam) --- */
+typedef struct HaloViewSpec {
+  HaloRender view;      /* the lens, fov, size, lens shift, view az / el / roll, visible range and overlap to look through: a session's meaning */
+  int32_t has_source;   /* 0: the image was accumulated under the handle's last session's render; 1: under `source` */
+  HaloRender source;    /* the render the consumer's image was accumulated under (its size must be the consumer's) */
+  HaloDisplay display;  /* halo_consumer_snapshot's display transform */
+} HaloViewSpec;
+/* For every pixel (px, py) of `view`, row-major:
+ *   dir_out  (3 floats) the world-space exit direction w (the trace kernels' convention: the ray's travel direction, sky position -w) that the
+ *            view's lens puts on the pixel's CENTRE — the w for which the trace kernels' projection computes the continuous coordinates (px, py)
+ *            before its floor(. + 0.5).  Zeros where the pixel has no direction: outside a fisheye's image circle (its rim cz = 0 is culled as the
+ *            projection culls it), outside both discs of a dual lens (a disc reaches to the end of its overlap band; the pixel belongs to the
+ *            circle that contains its centre), outside |lon| <= pi, |lat| <= pi/2 of the rectangular lens, past the globe's limb (the unit sphere
+ *            from distance 4), or where the view's own visible range would have culled the direction (single-view lenses, as in the projection).
+ *   map_out  (int32) the row-major index of the source pixel that direction lands on: the projection's PRIMARY hit under `source` (the overlap
+ *            write of a dual source is not read) if it lies inside the source frame, else -1.
+ *   xyz_out  (3 floats) that pixel's raw value sum + compensation, exactly halo_consumer_snapshot's xyz_out there: nearest neighbour, a copy.
+ *            Zeros at -1.
+ *   rgb_out  (3 bytes) halo_consumer_snapshot's display transform of that value: rgb_view[p] == rgb_snapshot[map[p]] byte for byte; at -1 what
+ *            the snapshot gives a zero pixel.
+ * A gather with no Jacobian, like the reference's shader: from an equal-area source (dual fisheye equal area is the reference's choice and the
+ * recommended one) the view shows radiance; from any other source it shows the source pixels' energy as it lies.  No filtering, no class lanes.
+ * Host pointers, any of them NULL to skip that output; runs on the backend's stream with one synchronise; reads the consumer only.
+ * HALO_FATAL (handle still usable) before any fold / consume, inside a session, with every output NULL, with a source render whose size is not
+ * the consumer's, with has_source = 0 on a handle that has had no session, with an empty view or an unknown lens; HALO_UNAVAILABLE for a view of
+ * more than 2^25 pixels. */
+int halo_consumer_view(halo_handle_t h, const HaloViewSpec* spec, uint8_t* rgb_out, float* xyz_out, int32_t* map_out, float* dir_out);
+/* dir_out of one pixel, by the same code on the host: returns 1 and the direction, or 0 and zeros (no direction, a pixel outside the view, NULL
+ * arguments).  No GPU needed. */
+int halo_host_view_direction(const HaloRender* view, int32_t px, int32_t py, float dir[3]);
+
 /* --- display-side composite of the raypath-colour class lanes (server/component_compositor.cpp) ------------- */
 /* CompositeMode (component_compositor.hpp:21): how the per-class Y lanes become one colour per pixel. */
 enum { HALO_COMPOSITE_DOMINANT = 0, HALO_COMPOSITE_ADDITIVE = 1, HALO_COMPOSITE_PAINTER = 2 };
@@ -726,7 +758,7 @@ int halo_host_wl_pool(const HaloWl* wl, float* entries5, int cap);
  * different cuts of the share into launches, which must agree (0xFFFFFFFF if they did not).  Parity-test hook, no device needed. */
 uint32_t halo_host_spectrum_entry(uint64_t m, uint32_t count, uint64_t r);
 int halo_abi_version(void);
-/* sizeof() of boundary structs as compiled (0 scene, 1 render, 2 wl, 3 exit record, 4 geom tables, 5 layer stats, 6 entry, 7 colour set, 8 colour class, 9 filter, 10 route info, 11 composite, 12 auto ev, 13 stats spec, 14 image stats). */
+/* sizeof() of boundary structs as compiled (0 scene, 1 render, 2 wl, 3 exit record, 4 geom tables, 5 layer stats, 6 entry, 7 colour set, 8 colour class, 9 filter, 10 route info, 11 composite, 12 auto ev, 13 stats spec, 14 image stats, 15 view spec). */
 uint64_t halo_abi_sizeof(int which);
 
 #ifdef __cplusplus
@@ -764,6 +796,7 @@ HALO_STATIC_ASSERT(sizeof(HaloDisplay) == 28, "HaloDisplay");
 HALO_STATIC_ASSERT(sizeof(HaloAutoEv) == 28, "HaloAutoEv");
 HALO_STATIC_ASSERT(sizeof(HaloStatsSpec) == 16 + 8 * HALO_STATS_MAX_PERCENTILES, "HaloStatsSpec");
 HALO_STATIC_ASSERT(sizeof(HaloImageStats) == 56 + 32 * HALO_STATS_MAX_PERCENTILES, "HaloImageStats");
+HALO_STATIC_ASSERT(sizeof(HaloViewSpec) == 44 + 4 + 44 + 28, "HaloViewSpec");
 HALO_STATIC_ASSERT(sizeof(HaloCompositeClass) == 24, "HaloCompositeClass");
 HALO_STATIC_ASSERT(sizeof(HaloComposite) == 16 + HALO_COLOR_MAX_CLASSES * 24, "HaloComposite");
 HALO_STATIC_ASSERT(sizeof(HaloGeomTables) == 4 + HALO_MAX_FACES * 20 + 4 + HALO_MAX_TRIS * (36 + 12 + 4 + 4), "HaloGeomTables");

@@ -1,5 +1,7 @@
-// halo_backend.cpp — the C ABI of include/halo_trace.h: session state machine, per-(layer, entry) dispatch,
-// device memory, streams/events.  Host C++ only; kernels live in halo_trace.inl (+ halo_trace_m*.hip) and halo_kernels.hip.
+// halo_backend.cpp — the C ABI of include/halo_trace.h: session state machine, per-(layer, entry) dispatch, device memory, streams/events, the
+// fixed-point import / export and the shards.  Host C++ only; kernels live in halo_trace.inl (+ halo_trace_m*.hip) and halo_kernels.hip.
+// Its neighbours: halo_state.h (the state and the helpers the units share), halo_options.h (the option table halo_set_option asks),
+// halo_consumer.cpp (the consumer stages), halo_host_abi.cpp (every export that takes no handle).
 //
 // State machine (reference trace_backend.hpp:91-116):
 //   halo_begin → (halo_trace_layer → halo_recombine)* → halo_trace_layer → halo_end ; halo_readback_xyz any time.
@@ -13,15 +15,12 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 
-#include "halo_device.h"
-#include "halo_host.hpp"
-#include "halo_launch.h"
+#include "halo_state.h"
 
 #ifndef HALO_XYZ_LOG_MIN_PIX
 #define HALO_XYZ_LOG_MIN_PIX (1u << 19)   // illuminant sessions on images ABOVE this many pixels take the X/Y/Z hit log (below: one scalar plane per pool entry)
@@ -29,322 +28,8 @@
 
 using namespace halo;
 
-namespace {
-
-template <typename T>
-struct DevBuf {
-  T* ptr = nullptr;
-  size_t cap = 0;  // elements
-  hipError_t reserve(size_t n) {
-    if (n <= cap) return hipSuccess;
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&ptr), std::max<size_t>(n, 1) * sizeof(T));
-    if (e == hipSuccess) cap = n;
-    return e;
-  }
-  void release() {
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    cap = 0;
-  }
-};
-template <typename... B>
-void release_all(B&... bufs) { (bufs.release(), ...); }
-
-// "The last work of kind X": an event recorded behind that work, and whether anything has been recorded on it yet (nothing: nobody need wait).
-// (Several markers that fall on one point of one stream share one recorded event: mark_at names an event somebody has just recorded there — a ring
-//  slot's — instead of recording the marker's own.  Should that event be recorded again before the marker is, the marker waits for the later point.)
-struct Marker {
-  hipEvent_t ev = nullptr;
-  hipEvent_t at = nullptr;   // the event that carries the marker now: `ev`, or a shared one
-  bool set = false;
-  hipError_t mark(hipStream_t s) {
-    const hipError_t e = hipEventRecord(ev, s);
-    if (e == hipSuccess) at = ev, set = true;
-    return e;
-  }
-  hipError_t mark_at(hipEvent_t shared) {
-    at = shared, set = true;
-    return hipSuccess;
-  }
-  hipError_t wait_on(hipStream_t s) const { return set ? hipStreamWaitEvent(s, at, 0) : hipSuccess; }
-  void clear() { set = false; }
-};
-
-}  // namespace
-
-struct HaloBackend {
-  int device = 0;
-  uint32_t seed = 1;
-  std::string error;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
-  int cu_count = 256;
-
-  // options
-  int capture = 0;
-  uint32_t geom_clock = 32;  // simulator.hpp:144 (rays per sampled shape)
-  uint64_t chunk = 1ull << 28;   // rays per launch: configs[2]'s 237 M continuations per wavelength run 3.8 % faster as one launch than as four
-  uint64_t stoch_chunk = 0;            // rays per dispatch with device-generated crystal pools (0 = by record size, see chunk_of)
-  uint32_t bin_l1 = 128u;              // coarse lists of the two-level binned route (measured: 512 -> 128 lists 6 % faster, 64 slower)
-  int aggregate = 1;
-  int mono_enabled = 1;
-  int bin = -1;                // binned accumulation: -1 auto (discrete session, full-sky render, launch >= 4 Mi rays), 0 off, 1 on
-  // Two sets of the hit-log / tile-list buffers, taken in turn by the launches that alternate between the two trace streams (<= 2^21 rays):
-  // the one of exactly 2^21 rays that logs may run beside a neighbour.  Launches that fill the chip keep set 0.
-  DevBuf<HitRec> bin_list_s[2], bin_list2_s[2];   // one-level tile lists / coarse lists / log regions; tile lists of the two-level and log routes
-  DevBuf<uint32_t> bin_cnt_s[2], bin_cnt2_s[2];
-  int log_set = 0;                      // the set the next logged launch writes
-  Marker set_free[2];                   // the passes that last read log set s (they may still be running)
-  // Auxiliary stream (round 5): the closing folds are queued here, behind everything the other streams hold, and nobody waits for them until
-  // somebody reads the image or adds to the planes again — a session's fold (20 us) runs under the next session's first kernels instead of
-  // in front of them.  (Two engines side by side on one GPU had measured +10 .. 15 % over one, tools/two_engines_probe.py; what that was,
-  // looked at inside one engine, is the small things between kernels — folds, resets, uploads, the tails — not the trace kernels or their
-  // passes, which gain nothing from running under each other: see queue_passes.)
-  hipStream_t aux = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  bool aux_pending = false;             // work has been queued on `aux` that the main stream has not waited for
-  // Two trace streams: consecutive launches alternate between them, so that launch k+1's workgroups fill the CUs that launch k's last
-  // workgroups leave idle (kernels of ONE stream run one after the other: the tail of every 1.8 ms trace kernel, and the whole of a
-  // latency-bound small launch, went unshared).  Trace kernels of different launches have nothing to order between them: each logs to its own
-  // buffer set or adds with atomics, tallies and continuation appends are atomic.  What they must follow is on the main stream (table
-  // uploads) or the auxiliary one (a fold or per-tile pass before a launch that adds to the planes itself): waited for by events.
-  hipStream_t cs[2] = {nullptr, nullptr};
-  hipEvent_t ev_cs[2] = {nullptr, nullptr}, ev_main = nullptr, ev_aux = nullptr;
-  bool cs_pending[2] = {false, false};
-  int cs_next = 0;
-  bool main_dirty[2] = {true, true};    // the main stream has been given work (main_q) since trace stream i last waited for it
-  int lean_events = 1;                  // option: 1 = one recorded event where several markers fall on one point of a stream, no hop from a main stream
-                                        // that holds nothing new (queue_passes, next_trace_stream); 0 = every marker its own record, every launch the hop
-  uint64_t aux_seq = 0, cs_seen_aux[2] = {0, 0};   // (a trace stream waits for the auxiliary stream only when that holds work it has not waited for yet)
-  int overlap = 1;                      // option: 0 queues the passes and folds on the main stream (round 4 behaviour)
-  int defer_fold = 0;                   // option: 1 = halo_end leaves the fold pending even when the accumulator is the caller's memory; the caller asks for
-                                        // it (halo_sync, or any reader) before it looks at its memory
-  int twin_set = 0;                     // which half of the fp64 twin the open / next session's overflows go to (the other half may still be folding)
-  int lambda_planes = -1;      // illuminant sessions: -1 auto (by batch size), 0 never, 1 always one plane per pool entry
-  int mono_copies = 8;         // power of two; copy = blockIdx & (copies-1)
-  uint32_t mono_s_log2 = 0;    // log2 of the columns per row of the plane (kMonoRows rows; see MonoSlot)
-  int blocks_per_cu = 24;      // cap on workgroups per CU of a launch's STATIC ray loop (five or six resident: several rounds even out the tail; a ticketed
-                               // launch — tile_ticket — runs one resident round instead and evens the tail out wave by wave)
-  int host_shapes = 0;         // 1: stochastic shape pools are built on the host and uploaded (A/B and test path)
-  int gen_serial = 0;          // 1: pyramids are generated one thread per crystal (the serial builder) instead of one team of 32 lanes
-  int small_blocks_per_cu = 0; // experiment knob: workgroups per CU that a small launch may spread over (0 = five, see blocks_of)
-  int blocks_cap = 0;          // experiment knob: absolute cap on the workgroups of one launch (0 = none)
-  int lazy_fold = 1;           // the closing fold of a session waits for the first READER of the image (or a session with other planes) when the accumulator is the backend's own
-  int hit_log = -1;            // hit-log accumulation of cache misses: -1 auto (one-plane sessions, launches >= 2 Mi rays), 0 off, 1 on
-  uint32_t hit_log_cap = 0;    // test knob: records per log region (0 = sized from the launch); the tile lists then get half their even share
-  int hex_fast = 1;            // 1: regular hexagonal prisms of one-shape dispatches run the literal-normal next-face search
-  int entry_fast = 1;          // 1: full prisms of one-shape dispatches take the slab-wise entry pick (EntryFastDev)
-  int filter_fast = 1;         // 1: filtered / colour-tagged dispatches with max_hits <= 16 run the production-shaped kernels (FastTables); 0: the generic ones
-  int async = 0;               // 1: final-layer dispatches are queued without a host sync; stats via halo_collect_stats
-  uint32_t shuffle_chunk_log2 = 5;   // Recombine's shuffle moves chunks of 2^k pool entries (k = 0: per ray, like the reference)
-  int spec_root = 1;           // option (A/B knob): 1 = last-layer plain hit-log launches over a regular prism whose root generation matches a root profile
-                               // (halo_trace.inl kRoot*) run the instantiation that has it as constants; 0 = always the generic root generation
-  // Direct close: a logged launch that is its whole session — one plane, one copy, nothing pending in the planes — has its per-tile
-  // pass add coef x sum to the XYZ image itself (launch_log_route_close): no plane write, no fold on the auxiliary stream, no stream hop in front of
-  // the next session's trace kernel.  The pass is a PLAIN read-modify-write of the image and of the twin's half, on the launch's trace stream: a later
-  // launch on the other trace stream waits for it (close_done), readers and folds join the trace streams as they always do.
-  int close_direct = -1;       // option: -1 auto (launches that fill the chip), 0 never, 1 wherever eligible
-  uint64_t direct_closes = 0;  // launches that closed their session directly, ever (halo_direct_closes)
-  Marker close_done;           // the direct close queued last, on trace stream close_ts
-  int close_ts = 0;
-  bool cnt2_clean[2] = {false, false};   // log set s: the tile-list counters are known to be zero (the closing pass zeroes what it consumed)
-  // Per-tile append: a directly closing launch whose kernel has a kAccTileFinal twin appends its records to per-tile chunks of each
-  // workgroup (halo_trace.inl log_hit_tile) and the closing pass reads the chunks (launch_tile_route_close): the split pass and its tile lists go.
-  int tile_append = -1;        // option: -1 auto (launches that fill the chip), 0 never, 1 wherever eligible
-  uint64_t tile_appends = 0;   // launches that took the route, ever (halo_tile_appends)
-  DevBuf<HitRec> tile_chunk_s[2];   // chunk[tile][workgroup][cap], one set per log set
-  DevBuf<uint32_t> tile_cnt_s[2];   // cnt[tile][workgroup]
-  // Wave tickets: a per-tile-append launch runs ONE resident round of workgroups whose waves draw their passes of the ray loop from a
-  // counter (halo_device.h TicketSize, halo_trace.inl) — no static round's tail, and chunks four times as long for the closing pass.
-  int tile_ticket = -2;        // option: -2 auto (as -1, and the launch's static grid is more than one resident round), -1 auto (launches that take the
-                               // append by tile_append's auto rule), 0 never, 1 every launch that appends per tile
-  uint64_t tile_tickets = 0;   // launches that took tickets, ever (halo_tile_tickets)
-  uint32_t ticket_min = kTicketMin, ticket_max = kTicketMax, ticket_div = kTicketDiv;   // experiment knobs, unsupported: the sweep of profiles/wave_tickets_ab.txt,
-                                                                                        // and the tests' way to guided tickets on launches of a few milliseconds' worth
-  bool ticket_zeroed = false;  // the counters below exist and the one-time memset behind their reserve has completed
-  DevBuf<uint32_t> ticket_cnt; // kTicketGroups counters per log set, kTicketStride words apart: zeroed when reserved, and by every closing pass after
-  HaloRouteInfo route{};       // kernels that served the current / last session (halo_last_route)
-  uint32_t route_root = 0;     // ... and the root profiles among them (halo_last_root_profile): bit kRootProfile* - 1
-
-  // monotone ray counters: seeded once, never reset per session (cuda_trace_backend.cu:3724-3741)
-  uint64_t gen_count = 0, gate_count = 0, transit_count = 0, shape_count = 0;
-  double sess_max_w = 1.0;     // largest initial ray weight of the open session (wavelength-pool spd weights)
-
-  // session
-  bool in_session = false;
-  HaloScene scene{};
-  HaloRender render{};
-  HaloWl wl{};
-  ProjDev proj{};
-  int layer_idx = 0;
-  double carry[HALO_MAX_LAYERS][HALO_MAX_ENTRIES] = {};
-
-  // device state
-  DevBuf<float> acc_own;       // W*H*3 + 4
-  float* acc = nullptr;        // bound accumulator (own or external)
-  uint64_t acc_floats = 0;
-  int acc_w = 0, acc_h = 0;    // image the bound accumulator (own or external) currently holds
-  int own_w = 0, own_h = 0;    // image the OWNED buffer was last sized and zeroed for
-  std::vector<HaloFilter> filters;  // table referenced by HaloEntry::filter_id
-  std::vector<HaloColorSet> color_sets;      // table referenced by HaloEntry::color_id
-  std::vector<HaloColorClass> color_classes; // raypath-colour classes (Y lanes)
-  DevBuf<double> lanes;                      // class_count x W x H, accumulated in fp64 (handed out as float)
-  int lanes_w = 0, lanes_h = 0;
-  DevBuf<FilterDev> filter_dev;
-  std::unique_ptr<FastTables> fast_scratch;  // host staging of a dispatch's fast filter tables (20 KB: not on the stack)
-  DevBuf<float> mono;          // accumulation planes (see MonoSlot): plane_cnt x plane_copies x (kMonoRows << s_log2) floats
-  DevBuf<double> ovf;          // fp64 twin of the planes' copy 0, laid out [plane][slot] (TwinOffset): where full log regions / tile lists overflow to
-  DevBuf<uint32_t> ovf_flag;   // one word: something was written to the twin since the last fold
-  bool mono_session = false;   // kernel variant: true = one scalar per hit (plane 0 or plane wl_idx), false = X,Y,Z planes
-  bool mono_by_wl = false;     // illuminant session with one plane per wavelength-pool entry
-  bool xyz_log = false;        // illuminant session on X, Y, Z planes whose big production launches go through the hit log
-  bool mono_dirty = false;
-  // Two plane SETS for sessions whose every launch goes through the hit log onto one scalar plane (round 6): a fold reads and zeroes the set its
-  // session added to while the passes of the session after it add to the other set — on a discrete spectrum of short sessions the passes of
-  // session k + 1 otherwise wait for the fold of session k, which waits for the passes of session k: one serial chain (bench.py --config 4d).
-  bool mono_two = false;
-  int mono_set = 0;
-  size_t mono_half = 0;                                   // floats per set
-  Marker set_folded[2];                                   // the fold that last zeroed the set
-  uint32_t plane_cnt = 1, plane_copies = 8;
-  std::vector<std::array<float, 3>> plane_coef;  // fold coefficients of the pending planes
-  // consumer (RenderConsumer state, server/render.hpp): Neumaier running image + total landed intensity
-  DevBuf<float> cons_sum, cons_comp, cons_xyz_out, cons_stage;
-  DevBuf<uint8_t> cons_rgb;
-  DevBuf<float> comp_rgb, lanes_stage;   // halo_consumer_composite's linear image, halo_consumer_load_lanes' staging
-  DevBuf<uint32_t> comp_hist;            // radix-select histogram (2048 bins)
-  // halo_consumer_auto_ev: the candidate values, and one block of words — the select's AevRecord, then the multi-block select's histograms
-  DevBuf<float> aev_vals;
-  DevBuf<uint32_t> aev_ws;
-  int aev_agg_hist = 0;                  // option "auto_ev_hist": 1 = wave-aggregated adds in the histogram passes (measured slower: DESIGN 3.5, tools/auto_ev_cost.py)
-  int aev_select = -1;                   // option "auto_ev_select": -1 by size (kAevSmallMax), 0 the multi-block select, 1 the one-workgroup select
-  DevBuf<uint32_t> stats_ws;             // halo_consumer_stats: the StatsRecord, then the multi-block form's histograms (its values go to aev_vals)
-  int stats_select = -1;                 // option "stats_select": -1 by size (kStatsSmallMax), 0 the multi-block form, 1 one workgroup
-  // halo_consumer_view: the view's four outputs before they are copied back
-  DevBuf<uint8_t> view_rgb;
-  DevBuf<float> view_xyz, view_dir;
-  DevBuf<int32_t> view_map;
-  bool had_session = false;              // `render` holds a session's render (halo_consumer_view's default source)
-  int cons_w = 0, cons_h = 0;
-  double total_intensity = 0.0;
-  DevBuf<double> tally;        // kTallyLines x kTallyStride doubles, [kSum*] per line: CUMULATIVE tallies of every kernel this backend ever launched
-  double* tally_host = nullptr;       // hipHostMalloc, one snapshot of `tally`
-  double tally_seen[kSumNum] = {};    // cumulative values already handed on: [kSumLanded] to a readback / take_landed, the rest to the layer statistics
-  bool tally_unread = false;
-  double time_trace_ms = 0.0, time_post_ms = 0.0;   // halo_collect_timing: the last layers' trace kernels' own spans and their passes', since the last call
-  uint64_t time_launches = 0;          // a dispatch has been queued since the statistics were last pulled
-  DevBuf<uint32_t> counters;   // kCntNum
-  // dispatch ring: device slots, pinned host mirrors, pinned tally read-back, per-slot events
-  static constexpr int kRing = 32;
-  DevBuf<DispatchSlot> ring_dev;
-  DispatchSlot* ring_host = nullptr;   // hipHostMalloc
-  hipEvent_t ring_ev0[kRing] = {}, ring_ev1[kRing] = {}, ring_ev2[kRing] = {}, ring_ev3[kRing] = {}, ring_done[kRing] = {};   // ev0..ev1 the trace kernel (main stream), ev2..ev3 its passes (post stream)
-  // (the events that CARRY a slot's "passes begin" and "slot done" for its current launch: ring_ev2 / ring_done themselves, or — option
-  //  lean_events — the neighbour recorded at the same point of the same stream: ring_ev1 where no wait lies between it and the passes, ring_ev3
-  //  behind a direct close)
-  hipEvent_t ring_t2[kRing] = {}, ring_fin[kRing] = {};
-  bool ring_posts[kRing] = {};
-  bool ring_final[kRing] = {};         // the slot's launch belongs to its session's last layer (halo_collect_timing counts those)
-  bool ring_busy[kRing] = {};
-  uint64_t ring_use[kRing] = {};       // how many launches have taken the slot (TableCacheEntry::read_use)
-  int ring_next = 0;
-  // Table cache (round 5): the dispatch-constant tables of a deterministic crystal entry (latitude LUT, wavelength pool, shape, entry-pick
-  // tables, filter / colour tables) stay on the device from one dispatch to the next while scene, wavelength, filters, colour and options
-  // are what they were — a server that sends one wavelength's rays as many equal small sessions (and every chunk of a long layer) then
-  // pays neither the host-side builds (closed-form geometry, LUT, predicate tables) nor the 25-49 KB copy per dispatch.
-  struct TableCacheEntry {
-    bool valid = false;
-    int mode = 0;
-    bool use_filter = false, use_color = false, entry_fast = false, hex_regular = false, has_fast = false;
-    // Two device slots per entry, taken in turn by the uploads: the kernels of the session before (queued on a trace stream, async) may still be
-    // staging their tables out of the slot they were given.  An upload waits (on the stream, not the host) for the last kernel that read ITS
-    // slot — two table sets back, as good as always finished — so consecutive sessions of different wavelengths still overlap.
-    int cur = 0;
-    // the slot's last reader = the dispatch-ring slot of the last launch that was given it (its ring_done event is recorded anyway: no
-    // event of the cache's own, one HIP call less per small session) and that ring slot's use count then: a ring slot that has been taken
-    // again since was harvested first, i.e. that launch is over
-    int read_ring[2] = {-1, -1};
-    uint64_t read_use[2] = {0, 0};
-  };
-  TableCacheEntry tcache[HALO_MAX_LAYERS][HALO_MAX_ENTRIES];
-  DevBuf<DispatchSlot> tcache_dev;     // HALO_MAX_LAYERS x HALO_MAX_ENTRIES x 2 slots, reserved on first use
-  HaloScene tcache_scene{};            // what the valid entries were built for
-  HaloWl tcache_wl{};
-  std::vector<HaloWl> tcache_spec;   // ... and the entry table of a spectrum session (empty otherwise)
-  uint32_t spec_count = 0;           // entries of the open spectrum session (halo_begin_spectrum with count >= 2), 0 = not one
-  int table_cache = 1;                 // option: 0 uploads the tables with every dispatch (round 4 behaviour)
-  std::map<std::string, int64_t> opt_last;   // halo_set_option: the value each key was last set to (an unchanged option keeps the table cache)
-  HaloLayerStats pending{};    // harvested tallies not yet handed to the caller (async mode)
-  HaloLayerStats layer_acc{};  // tallies of the layer being traced
-  std::vector<WlEntryDev> wl_pool_host;
-  uint32_t wl_pool_size = 0;
-  struct LutKey { int32_t type; float center, spread; host::LatLut lut; };
-  std::vector<LutKey> lut_cache;
-  DevBuf<ShapeDev> shapes_s[2];   // sampled-crystal pools: launch k+1's generator must not overwrite what launch k still traces
-  Marker shapes_free[2];                               // the trace kernel that last read the pool
-  hipEvent_t ev_gen = nullptr;                         // the generator of a chip-filling launch, queued on trace stream 1 (see gen_ahead)
-  int shapes_next = 0;
-  // Plane ownership between the two trace streams.  The per-tile sums of a logged (or two-level binned) launch end in PLAIN read-modify-writes of
-  // the planes; everything else that adds to them uses atomics.  So (1) a launch's sums wait for what the OTHER trace stream held when the launch
-  // was queued (ev_gate), and (2) a later launch on the other stream whose trace kernel adds to the planes itself waits for those sums (rmw).
-  // Logged trace kernels touch no plane (their overflow goes to the fp64 twin), so they run beside a neighbour's passes freely.
-  hipEvent_t ev_gate = nullptr;
-  Marker rmw[2];                  // the per-tile sums last queued on trace stream i
-  int log_tiles_log2 = 7;         // option (experiment knob): the scalar hit-log route cuts a plane into up to 2^this tiles (<= 8)
-  int alt_log2 = 25;              // option (experiment knob): launches of up to 2^alt_log2 rays alternate between the two trace streams
-  int rehit_strategy = 1;         // option: 1 [default] the reference's CUDA next-face strategy (the child that leaves through the face it stands on is emitted where it is);
-                                  // 0 its legacy CPU strategy (that child is propagated over all faces with the relaxed accept threshold, optics.cpp:116-155 —
-                                  // SURVEY's stated ground truth): every launch then takes the generic kernels, which carry the re-hit test
-  int pool_entry_fast = 1;        // option (A/B knob): prism pools under the hit log pick a sampled full prism's entry face slab by slab; 0 = the walk over its fan triangles
-  int gen_ahead = 0;              // option (experiment knob): 1 queues the generator of a chip-filling launch on trace stream 1, beside the previous launch's kernels
-  // Deterministic sessions (option "deterministic"): every accumulating launch runs a kAccFixed kernel — 64-bit fixed-point sums from the first add
-  // to the fold, so the plane sums depend on the set of rays alone.  The planes are a buffer of their own, [plane][slot], one copy,
-  // all-zero between folds like the float planes; F and the budget belong to the PENDING plane set (they may span sessions under lazy_fold).
-  int deterministic = 0;                     // the option (not inside a session)
-  bool det_session = false;                  // the open / last session is a deterministic one
-  bool fix_planes = false;                   // the pending planes (mono_dirty) are the fixed-point ones
-  DevBuf<unsigned long long> fix;
-  uint32_t fix_frac = 32, fix_frac_landed = 32;   // F of the pending plane set; F_L of the landed integer (tally slot kSumFixLanded)
-  uint64_t fix_hits = 0;                     // rays traced into the pending plane set since its last fold (<= kFixBudgetHits)
-  unsigned long long fix_landed_seen = 0;    // the cumulative landed integer already handed on (like tally_seen)
-  double landed_carry = 0.0;                 // landed integers converted when F_L had to change before anybody took them
-  // Shards (halo_set_shard): the handle plans every session whole — partition, launches, counters — and launches only the part of each
-  // planned launch that lies in its slice of the launch's crystal entry (shard_slice).  (0, 1), the default, is the whole of everything.
-  uint32_t shard_index = 0, shard_count = 1;
-  int64_t rank_opt = 0;                      // what option "rank" was last set to (0 again after "ray_base"): not to be combined with shards
-  bool fix_imported = false;                 // the pending fixed-point planes came through halo_import_fixed: a whole image, which a sharded handle may fold
-  bool landed_own = false;                   // count > 1: the untaken landed integer holds weight of this shard's own launches (a part, until it is exported)
-  DevBuf<float> cont[2];       // SoA continuation pools, 5 planes
-  uint32_t cont_stride[2] = {0, 0};
-  uint32_t cont_region[2] = {0, 0};          // slots per shard region
-  DevBuf<uint32_t> cont_cnt;                 // kContShards * kContCntStride
-  uint32_t cont_seg[kContShards + 4] = {};   // prefix of the input pool's shard fill counts
-  int cont_out_slot = 0;
-  uint64_t cont_in_n = 0;
-  int cont_shuffle = 1;
-  int cont_order = 0;                        // option: 0 [default] continuations in append order; 1 canonical (root, interaction) order (Recombine sorts the pool)
-  DevBuf<uint32_t> cont_mask;                // cont_order = 1: per root of the layer being traced, the 128-bit mask of its continued exit seqs
-  DevBuf<uint32_t> cont_err;                 // ... the session's error word (kContErr*: appends, scan and scatter), read at the end of every layer
-  DevBuf<uint32_t> cont_base;                // ... each root's first canonical slot, and the scan's tile sums
-  DevBuf<uint32_t> cont_tiles;
-  uint32_t cont_fill_max = 0;                // fullest shard region of the last non-final layer (the scatter's grid)
-  uint64_t cont_roots = 0;                   // roots of the last non-final layer
-  DevBuf<HaloExitRecord> exits;
-  uint64_t exits_pending = 0;
-  DevBuf<float> host_f;        // injected rays: d | p | w
-  DevBuf<uint32_t> host_u;
-  uint64_t sess_crystal_samples = 0, sess_orient_samples = 0;  // this session's stochastic draws (halo_last_sample_counts)
-  // every event made without timing: the one-shot ones, the joins' and the markers' (created in halo_create, destroyed in halo_destroy)
-  std::vector<hipEvent_t*> untimed_events() {
-    return {&ev_cs[0], &ev_cs[1], &ev_main, &ev_aux, &ev_fork, &ev_join, &ev_gen, &ev_gate, &set_free[0].ev, &set_free[1].ev, &shapes_free[0].ev,
-            &shapes_free[1].ev, &rmw[0].ev, &rmw[1].ev, &set_folded[0].ev, &set_folded[1].ev, &close_done.ev};
-  }
-};
-
-namespace {
+// ---- the helpers every unit calls (declared in halo_state.h) ----
+namespace halo {
 
 int fail(HaloBackend* b, int code, const std::string& msg) {
   if (b) b->error = msg;
@@ -353,35 +38,6 @@ int fail(HaloBackend* b, int code, const std::string& msg) {
 int hip_fail(HaloBackend* b, hipError_t e, const char* what) {
   return fail(b, (e == hipErrorNoDevice || e == hipErrorInvalidDevice || e == hipErrorOutOfMemory) ? HALO_UNAVAILABLE : HALO_FATAL,
               std::string(what) + ": " + hipGetErrorString(e));
-}
-#define HIPCHK(b, call)                                   \
-  do {                                                    \
-    hipError_t e__ = (call);                              \
-    if (e__ != hipSuccess) return hip_fail(b, e__, #call); \
-  } while (0)
-
-// The main stream, for whoever queues work on it (or waits for it): the trace streams have not seen that work yet (next_trace_stream).
-inline hipStream_t main_q(HaloBackend* b) {
-  b->main_dirty[0] = b->main_dirty[1] = true;
-  return b->stream;
-}
-// The plane set the open / pending session adds to (HaloBackend::mono_two).
-inline float* planes_of(HaloBackend* b) { return b->mono.ptr + (b->mono_two ? static_cast<size_t>(b->mono_set) * b->mono_half : 0u); }
-// The stream the plane-touching passes of logged launches and the folds are queued on.
-inline hipStream_t post_stream(HaloBackend* b) { return b->overlap ? b->aux : b->stream; }
-// What is queued on the auxiliary stream from here on runs behind everything the main stream and the trace streams hold now.
-int fork_aux(HaloBackend* b) {
-  if (!b->overlap) return HALO_OK;
-  HIPCHK(b, hipEventRecord(b->ev_fork, main_q(b)));
-  HIPCHK(b, hipStreamWaitEvent(b->aux, b->ev_fork, 0));
-  for (int k = 0; k < 2; k++)
-    if (b->cs_pending[k]) {
-      HIPCHK(b, hipEventRecord(b->ev_cs[k], b->cs[k]));
-      HIPCHK(b, hipStreamWaitEvent(b->aux, b->ev_cs[k], 0));
-    }
-  b->aux_pending = true;
-  b->aux_seq++;
-  return HALO_OK;
 }
 // What the main stream is given from here on runs behind everything queued on the auxiliary and the trace streams (no host wait).
 int join_aux(HaloBackend* b) {
@@ -400,9 +56,41 @@ int join_aux(HaloBackend* b) {
     }
   return HALO_OK;
 }
+// Host waits for all streams.
+int sync_all(HaloBackend* b) {
+  if (int rc = join_aux(b)) return rc;
+  HIPCHK(b, hipStreamSynchronize(main_q(b)));
+  return HALO_OK;
+}
+void drop_table_cache(HaloBackend* b) {
+  for (auto& layer : b->tcache)
+    for (auto& e : layer) e.valid = false;
+}
+}  // namespace halo
+
+namespace {
+
+// The plane set the open / pending session adds to (HaloBackend::mono_two).
+inline float* planes_of(HaloBackend* b) { return b->mono.ptr + (b->mono_two ? static_cast<size_t>(b->mono_set) * b->mono_half : 0u); }
+// The stream the plane-touching passes of logged launches and the folds are queued on.
+inline hipStream_t post_stream(HaloBackend* b) { return b->opt.overlap ? b->aux : b->stream; }
+// What is queued on the auxiliary stream from here on runs behind everything the main stream and the trace streams hold now.
+int fork_aux(HaloBackend* b) {
+  if (!b->opt.overlap) return HALO_OK;
+  HIPCHK(b, hipEventRecord(b->ev_fork, main_q(b)));
+  HIPCHK(b, hipStreamWaitEvent(b->aux, b->ev_fork, 0));
+  for (int k = 0; k < 2; k++)
+    if (b->cs_pending[k]) {
+      HIPCHK(b, hipEventRecord(b->ev_cs[k], b->cs[k]));
+      HIPCHK(b, hipStreamWaitEvent(b->aux, b->ev_cs[k], 0));
+    }
+  b->aux_pending = true;
+  b->aux_seq++;
+  return HALO_OK;
+}
 // Trace stream i goes on behind what the auxiliary stream holds now (a closing fold: it reads and zeroes the planes).
 int wait_for_aux(HaloBackend* b, int i) {
-  if (b->overlap && b->aux_pending && b->cs_seen_aux[i] != b->aux_seq) {
+  if (b->opt.overlap && b->aux_pending && b->cs_seen_aux[i] != b->aux_seq) {
     HIPCHK(b, hipEventRecord(b->ev_aux, b->aux));
     HIPCHK(b, hipStreamWaitEvent(b->cs[i], b->ev_aux, 0));
     b->cs_seen_aux[i] = b->aux_seq;
@@ -412,7 +100,7 @@ int wait_for_aux(HaloBackend* b, int i) {
 // The stream the next trace kernel goes to: behind what the main stream holds now (table uploads, counter resets) and — for a launch that
 // adds to the planes itself — behind what the auxiliary stream holds (folds, per-tile passes).
 int next_trace_stream(HaloBackend* b, bool touches_planes, bool alternate, hipStream_t* out, int* which) {
-  if (!b->overlap) {
+  if (!b->opt.overlap) {
     *out = b->stream;
     *which = 0;
     return HALO_OK;
@@ -424,7 +112,7 @@ int next_trace_stream(HaloBackend* b, bool touches_planes, bool alternate, hipSt
   if (alternate) b->cs_next ^= 1;
   // (the hop is for what the main stream has been given since this trace stream last waited for it — table uploads, counter resets: main_q.  With
   //  nothing new there it orders nothing, and option lean_events leaves it out.  A caller's stream may hold work this backend never saw: always hopped.)
-  if (!b->lean_events || b->main_dirty[i] || b->stream != b->own_stream) {
+  if (!b->opt.lean_events || b->main_dirty[i] || b->stream != b->own_stream) {
     HIPCHK(b, hipEventRecord(b->ev_main, b->stream));
     HIPCHK(b, hipStreamWaitEvent(b->cs[i], b->ev_main, 0));
     b->main_dirty[i] = false;
@@ -441,30 +129,8 @@ int next_trace_stream(HaloBackend* b, bool touches_planes, bool alternate, hipSt
 // full-sky render lands every exit (5-6 per root: 0.8 M roots = 4.4 M atomics = 210 us against 102 us of logged trace kernel, bench.py --config 4d),
 // a lens that sees part of the sky 1-2 per root.
 inline uint64_t log_min_rays(int visible) { return visible == HALO_VISIBLE_FULL ? (1ull << 19) : (2ull << 20); }
-// Host waits for all streams.
-int sync_all(HaloBackend* b) {
-  if (int rc = join_aux(b)) return rc;
-  HIPCHK(b, hipStreamSynchronize(main_q(b)));
-  return HALO_OK;
-}
-// DevBuf::reserve frees the old allocation when it grows: nothing on either stream may still be using it.
-template <typename T>
-int reserve_idle(HaloBackend* b, DevBuf<T>& buf, size_t n, hipError_t* err = nullptr) {
-  if (n > buf.cap) {
-    if (int rc = sync_all(b)) return rc;
-  }
-  const hipError_t e = buf.reserve(n);
-  if (err) {
-    *err = e;
-    return HALO_OK;
-  }
-  HIPCHK(b, e);
-  return HALO_OK;
-}
-
 // The cumulative landed tally up to here belongs to the OWNED image that is being left (re-sized: its light is discarded with it): whoever
 // reads the new image must not be handed weight that landed in the old one and was never taken.
-int take_landed_delta(HaloBackend* b, double* landed);
 int forget_landed(HaloBackend* b) {
   if (!b->tally.ptr) return HALO_OK;
   if (int rc = join_aux(b)) return rc;
@@ -521,19 +187,19 @@ void harvest_slot(HaloBackend* b, int k) {
 }
 // Snapshot of the cumulative tallies (one 1 KB D2H copy + a stream sync): the sum over the lines, per tally.
 int read_tally(HaloBackend* b, double out[kSumNum], unsigned long long* fix_landed = nullptr) {
-  HIPCHK(b, hipMemcpyAsync(b->tally_host, b->tally.ptr, kTallyLines * kTallyStride * sizeof(double), hipMemcpyDeviceToHost, main_q(b)));
+  HIPCHK(b, hipMemcpyAsync(b->tally_host.ptr, b->tally.ptr, kTallyLines * kTallyStride * sizeof(double), hipMemcpyDeviceToHost, main_q(b)));
   HIPCHK(b, hipStreamSynchronize(main_q(b)));
   if (fix_landed) {   // the lines' integer slot (deterministic sessions), summed modulo 2^64
     *fix_landed = 0ull;
     for (uint32_t l = 0; l < kTallyLines; l++) {
       unsigned long long v;
-      std::memcpy(&v, &b->tally_host[l * kTallyStride + kSumFixLanded], sizeof(v));
+      std::memcpy(&v, &b->tally_host.ptr[l * kTallyStride + kSumFixLanded], sizeof(v));
       *fix_landed += v;
     }
   }
   for (int t = 0; t < kSumNum; t++) {
     double v = 0.0;
-    for (uint32_t l = 0; l < kTallyLines; l++) v += b->tally_host[l * kTallyStride + static_cast<uint32_t>(t)];
+    for (uint32_t l = 0; l < kTallyLines; l++) v += b->tally_host.ptr[l * kTallyStride + static_cast<uint32_t>(t)];
     out[t] = v;
   }
   return HALO_OK;
@@ -551,6 +217,9 @@ int pull_tally(HaloBackend* b) {
   b->tally_unread = false;
   return HALO_OK;
 }
+}  // namespace
+
+namespace halo {
 // The landed weight since the last taker (readback, take_landed, consumer fold).
 int take_landed_delta(HaloBackend* b, double* landed) {
   double now[kSumNum];
@@ -564,6 +233,10 @@ int take_landed_delta(HaloBackend* b, double* landed) {
   b->landed_carry = 0.0;
   return HALO_OK;
 }
+}  // namespace halo
+
+namespace {
+
 void harvest_all(HaloBackend* b) {
   for (int k = 0; k < HaloBackend::kRing; k++) harvest_slot(b, k);
 }
@@ -576,10 +249,6 @@ void add_stats(HaloLayerStats& dst, const HaloLayerStats& src) {
   dst.pixel_hits += src.pixel_hits;
   dst.launches += src.launches;
 }
-void drop_table_cache(HaloBackend* b) {
-  for (auto& layer : b->tcache)
-    for (auto& e : layer) e.valid = false;
-}
 const host::LatLut& cached_lut(HaloBackend* b, const HaloDist& d) {
   for (const auto& e : b->lut_cache)
     if (e.type == d.type && e.center == d.center && e.spread == d.spread) return e.lut;
@@ -590,11 +259,9 @@ const host::LatLut& cached_lut(HaloBackend* b, const HaloDist& d) {
 
 }  // namespace
 
-extern "C" {
-
-static int fold_if_dirty(HaloBackend* b);
 static int fold_queue(HaloBackend* b);
-int halo_abi_version(void) { return HALO_ABI_VERSION; }
+
+extern "C" {
 
 int halo_device_count(void) {
   int n = 0;
@@ -622,8 +289,7 @@ int halo_create(int device_ordinal, uint32_t seed, halo_handle_t* out) {
                 hipStreamCreateWithFlags(&b->cs[1], hipStreamNonBlocking) == hipSuccess;
   for (hipEvent_t* ev : b->untimed_events()) aux_ok = aux_ok && hipEventCreateWithFlags(ev, hipEventDisableTiming) == hipSuccess;
   bool ring_ok = aux_ok && b->ring_dev.reserve(HaloBackend::kRing) == hipSuccess &&
-                 hipHostMalloc(reinterpret_cast<void**>(&b->ring_host), HaloBackend::kRing * sizeof(DispatchSlot), hipHostMallocDefault) == hipSuccess &&
-                 hipHostMalloc(reinterpret_cast<void**>(&b->tally_host), kTallyLines * kTallyStride * sizeof(double), hipHostMallocDefault) == hipSuccess;
+                 b->ring_host.alloc(HaloBackend::kRing) == hipSuccess && b->tally_host.alloc(kTallyLines * kTallyStride) == hipSuccess;
   for (int k = 0; ring_ok && k < HaloBackend::kRing; k++)
     ring_ok = hipEventCreate(&b->ring_ev0[k]) == hipSuccess && hipEventCreate(&b->ring_ev1[k]) == hipSuccess && hipEventCreate(&b->ring_ev2[k]) == hipSuccess && hipEventCreate(&b->ring_ev3[k]) == hipSuccess &&
               hipEventCreateWithFlags(&b->ring_done[k], hipEventDisableTiming) == hipSuccess;
@@ -633,7 +299,7 @@ int halo_create(int device_ordinal, uint32_t seed, halo_handle_t* out) {
   }
   b->stream = b->own_stream;
   if (b->tally.reserve(kTallyLines * kTallyStride) != hipSuccess || b->counters.reserve(kCntNum) != hipSuccess) {
-    halo_destroy(b);  // releases the stream, the ring, the pinned mirrors and the events as well
+    halo_destroy(b);  // the streams and the events; the ring and the pinned mirrors go with the handle
     return HALO_UNAVAILABLE;
   }
   (void)hipMemsetAsync(b->tally.ptr, 0, kTallyLines * kTallyStride * sizeof(double), main_q(b));
@@ -649,14 +315,6 @@ int halo_destroy(halo_handle_t b) {
   if (b->aux) (void)hipStreamSynchronize(b->aux);
   for (int k = 0; k < 2; k++)
     if (b->cs[k]) (void)hipStreamSynchronize(b->cs[k]);
-  release_all(b->acc_own, b->tally, b->mono, b->ovf, b->ovf_flag, b->filter_dev, b->cons_sum, b->cons_comp, b->cons_xyz_out, b->cons_stage, b->cons_rgb, b->comp_rgb,
-              b->lanes_stage, b->comp_hist, b->aev_vals, b->aev_ws, b->stats_ws, b->view_rgb, b->view_xyz, b->view_dir, b->view_map, b->counters, b->ring_dev, b->tcache_dev, b->shapes_s[0], b->shapes_s[1], b->cont_cnt, b->cont_mask, b->cont_err, b->cont_base,
-              b->cont_tiles, b->lanes, b->fix, b->cont[0], b->cont[1], b->exits, b->host_f, b->host_u);
-  for (int k = 0; k < 2; k++) release_all(b->bin_list_s[k], b->bin_cnt_s[k], b->bin_list2_s[k], b->bin_cnt2_s[k]);
-  for (int k = 0; k < 2; k++) release_all(b->tile_chunk_s[k], b->tile_cnt_s[k]);
-  release_all(b->ticket_cnt);
-  if (b->ring_host) (void)hipHostFree(b->ring_host);
-  if (b->tally_host) (void)hipHostFree(b->tally_host);
   for (int k = 0; k < HaloBackend::kRing; k++)
     for (hipEvent_t ev : {b->ring_ev0[k], b->ring_ev1[k], b->ring_ev2[k], b->ring_ev3[k], b->ring_done[k]})
       if (ev) (void)hipEventDestroy(ev);
@@ -666,123 +324,29 @@ int halo_destroy(halo_handle_t b) {
   for (int k = 0; k < 2; k++)
     if (b->cs[k]) (void)hipStreamDestroy(b->cs[k]);
   if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
-  delete b;
+  delete b;   // every buffer frees itself (DevBuf, PinnedBuf): the streams were synchronised above
   return HALO_OK;
 }
 
 const char* halo_last_error(halo_handle_t b) { return b ? b->error.c_str() : "null handle"; }
 
+// The rules — keys, value rules, refusals, what counts as a change — are halo_options.h set_option's, which needs no device; here its verdict is
+// carried out: the effects first, and only then the value.  A refused set leaves nothing behind.
 int halo_set_option(halo_handle_t b, const char* key, int64_t v) {
   if (!b || !key) return HALO_FATAL;
-  const std::string k(key);
-  {  // most options shape the tables or the kernels that read them: a CHANGED option drops the table cache.  A caller that sets its options before
-     // every session (the Lumice glue does) sets them to what they are: the cache stays.  Counter / seed options always act (they move state).
-    auto it = b->opt_last.find(k);
-    const bool same = it != b->opt_last.end() && it->second == v && k != "rank" && k != "ray_base" && k != "seed";
-    if (!same) drop_table_cache(b);
-    b->opt_last[k] = v;
-  }
-  // the session's plane layout (privatised copies, hit-log eligibility) was decided at halo_begin from these two: changing them with a session
-  // open would send direct atomics to a layout made for another route
-  if ((k == "capture_exits" || k == "filter_fast") && b->in_session) return fail(b, HALO_FATAL, k + " cannot change inside a session");
-  if (k == "capture_exits") b->capture = v ? 1 : 0;
-  else if (k == "geom_clock") b->geom_clock = static_cast<uint32_t>(v > 0 ? v : 32);
-  else if (k == "chunk") {  // the kernels' grid-stride index is 32-bit: n_rays + one stride of workgroups must stay below 2^32
-    const uint64_t top = (1ull << 32) - (static_cast<uint64_t>(b->cu_count) * 64ull * kBlock) - kBlock;
-    b->chunk = std::min<uint64_t>(static_cast<uint64_t>(v > 0 ? v : (1ll << 28)), top);
-  }
-  else if (k == "bin_l1") {  // the kernels index the coarse lists with `& (lists - 1)`: a power of two in [8, 512]
-    if (v < 8 || v > 512 || (v & (v - 1)) != 0) return fail(b, HALO_FATAL, "bin_l1 must be a power of two in [8, 512]");
-    b->bin_l1 = static_cast<uint32_t>(v);
-  }
-  else if (k == "stoch_chunk") b->stoch_chunk = static_cast<uint64_t>(v > 0 ? v : 0);
-  else if (k == "aggregate") b->aggregate = static_cast<int>(v);
-  else if (k == "mono") b->mono_enabled = v ? 1 : 0;
-  else if (k == "async") b->async = v ? 1 : 0;
-  else if (k == "lambda_planes") b->lambda_planes = static_cast<int>(v);
-  else if (k == "bin") b->bin = static_cast<int>(v);
-  else if (k == "host_shapes") b->host_shapes = v ? 1 : 0;
-  else if (k == "entry_fast") b->entry_fast = v ? 1 : 0;
-  else if (k == "hex_fast") b->hex_fast = v ? 1 : 0;
-  else if (k == "filter_fast") b->filter_fast = v ? 1 : 0;
-  else if (k == "spec_root") b->spec_root = v ? 1 : 0;
-  else if (k == "hit_log") b->hit_log = static_cast<int>(v);
-  else if (k == "hit_log_cap") b->hit_log_cap = static_cast<uint32_t>(std::max<int64_t>(v, 0));
-  else if (k == "gen_serial") b->gen_serial = v ? 1 : 0;
-  else if (k == "shuffle_chunk") {
-    if (v < 1 || v > 64 || (v & (v - 1)) != 0) return fail(b, HALO_FATAL, "shuffle_chunk must be a power of two in [1, 64]");
-    b->shuffle_chunk_log2 = 0;
-    while ((1ll << b->shuffle_chunk_log2) < v) b->shuffle_chunk_log2++;
-  }
-  else if (k == "lazy_fold") b->lazy_fold = v ? 1 : 0;
-  else if (k == "table_cache") b->table_cache = v ? 1 : 0;
-  else if (k == "overlap") {
-    if (int rc = sync_all(b)) return rc;
-    b->overlap = v ? 1 : 0;
-  }
-  else if (k == "defer_fold") b->defer_fold = v ? 1 : 0;
-  else if (k == "auto_ev_hist") b->aev_agg_hist = v ? 1 : 0;
-  else if (k == "auto_ev_select") b->aev_select = v < 0 ? -1 : (v ? 1 : 0);
-  else if (k == "stats_select") b->stats_select = v < 0 ? -1 : (v ? 1 : 0);
-  else if (k == "gen_ahead") b->gen_ahead = v ? 1 : 0;
-  else if (k == "close_direct") b->close_direct = v < 0 ? -1 : (v ? 1 : 0);
-  else if (k == "lean_events") b->lean_events = v ? 1 : 0;
-  else if (k == "tile_append") b->tile_append = v < 0 ? -1 : (v ? 1 : 0);
-  else if (k == "tile_ticket") b->tile_ticket = v < -1 ? -2 : v < 0 ? -1 : (v ? 1 : 0);
-  else if (k == "ticket_min") b->ticket_min = static_cast<uint32_t>(std::min<int64_t>(std::max<int64_t>(v, 1), 1024));
-  else if (k == "ticket_max") b->ticket_max = static_cast<uint32_t>(std::min<int64_t>(std::max<int64_t>(v, 1), 1024));
-  else if (k == "ticket_div") b->ticket_div = static_cast<uint32_t>(std::min<int64_t>(std::max<int64_t>(v, 1), 64));
-  else if (k == "pool_entry_fast") b->pool_entry_fast = v ? 1 : 0;
-  else if (k == "rehit_strategy") {
-    if (b->in_session) return fail(b, HALO_FATAL, "rehit_strategy cannot change inside a session");
-    b->rehit_strategy = v ? 1 : 0;
-  }
-  else if (k == "cont_order") {
-    if (b->in_session) return fail(b, HALO_FATAL, "cont_order cannot change inside a session");
-    if (v != 0 && v != 1) return fail(b, HALO_FATAL, "cont_order must be 0 (append order) or 1 (canonical order)");
-    b->cont_order = static_cast<int>(v);
-  }
-  else if (k == "deterministic") {
-    if (b->in_session) return fail(b, HALO_FATAL, "deterministic cannot change inside a session");
-    if (v != 0 && v != 1) return fail(b, HALO_FATAL, "deterministic must be 0 (float accumulation) or 1 (fixed-point accumulation)");
-    b->deterministic = static_cast<int>(v);
-  }
-  else if (k == "log_tiles_log2") b->log_tiles_log2 = static_cast<int>(std::min<int64_t>(std::max<int64_t>(v, 0), 8));
-  else if (k == "alt_log2") b->alt_log2 = static_cast<int>(std::min<int64_t>(std::max<int64_t>(v, 10), 28));
-  else if (k == "small_blocks_per_cu") b->small_blocks_per_cu = static_cast<int>(std::max<int64_t>(v, 0));
-  else if (k == "blocks_cap") b->blocks_cap = static_cast<int>(std::max<int64_t>(v, 0));
-  else if (k == "mono_copies") {
-    if (b->in_session) return fail(b, HALO_FATAL, "mono_copies cannot change while a session's plane is pending");
+  // (the kernels' grid-stride index is 32-bit: n_rays + one stride of workgroups must stay below 2^32)
+  const uint64_t chunk_top = (1ull << 32) - (static_cast<uint64_t>(b->cu_count) * 64ull * kBlock) - kBlock;
+  const OptionSet set = set_option(b->opt, b->in_session, b->shard_count, chunk_top, key, v);
+  if (set.status == OptionSet::kRefused) return fail(b, HALO_FATAL, set.message);
+  if (set.effects & kFxFoldPlanes)
     if (int rc = fold_if_dirty(b)) return rc;   // planes of ended sessions may still wait for their fold (lazy_fold)
-    int c = 1;
-    while (c < v && c < 64) c <<= 1;
-    if (c != b->mono_copies) {
-      if (int rc = sync_all(b)) return rc;       // (nothing may still be reading what is freed)
-      b->mono.release();
-    }
-    b->mono_copies = c;
-  }
-  else if (k == "blocks_per_cu") b->blocks_per_cu = static_cast<int>(std::min<int64_t>(std::max<int64_t>(v, 1), 64));
-  else if ((k == "rank" || k == "ray_base") && b->in_session) {
-    // the layers of an open session draw their gate / transit / shape streams at indices that follow on from the first layer's
-    return fail(b, HALO_FATAL, k + " cannot change inside a session");
-  }
-  else if (k == "rank") {
-    if (v != 0 && b->shard_count > 1) return fail(b, HALO_FATAL, "rank: not with halo_set_shard count > 1 (shards trace the one-rank run's rays: they share its counter range)");
-    b->rank_opt = v;
-    // disjoint 64-bit counter ranges per shard: the hi word feeds pcg_seed_with_high, so ranks never share a stream
-    const uint64_t base = static_cast<uint64_t>(v) << 40;
-    b->gen_count = b->gate_count = b->transit_count = b->shape_count = base;
-  } else if (k == "seed") {
-    // re-seed between sessions (the reference's backends take their seed from the first non-zero SessionSpec::seed, cpu_trace_backend.cpp:252)
-    if (b->in_session) return fail(b, HALO_FATAL, "seed cannot change inside a session");
-    b->seed = static_cast<uint32_t>(v) ? static_cast<uint32_t>(v) : 1u;
-  } else if (k == "ray_base") {
-    // the session's first 64-bit ray index (SplitPcgRayBase, trace_backend.hpp:184: lo feeds the stream index, hi pcg_seed_with_high)
-    const uint64_t base = static_cast<uint64_t>(v);
-    b->gen_count = b->gate_count = b->transit_count = b->shape_count = base;
-    b->rank_opt = 0;
-  } else return fail(b, HALO_FATAL, "unknown option: " + k);
+  if (set.effects & kFxSync)
+    if (int rc = sync_all(b)) return rc;        // (nothing may still be reading what is freed, or be queued by the other overlap rule)
+  if (set.effects & kFxReleasePlanes) b->mono.release();
+  if (set.effects & kFxDropCache) drop_table_cache(b);
+  if (set.effects & kFxCounters) b->gen_count = b->gate_count = b->transit_count = b->shape_count = set.counter_base;
+  if (set.effects & kFxSeed) b->seed = static_cast<uint32_t>(set.value);
+  set.commit(b->opt);
   return HALO_OK;
 }
 
@@ -839,7 +403,7 @@ static int begin_session(halo_handle_t b, const HaloScene* scene, const HaloRend
   if (scene->layer_count < 1 || scene->layer_count > HALO_MAX_LAYERS) return fail(b, HALO_FATAL, "layer_count out of range");
   if (scene->max_hits < 1 || scene->max_hits > HALO_MAX_HITS) return fail(b, HALO_FATAL, "max_hits out of range");
   if (render->width <= 0 || render->height <= 0) return fail(b, HALO_FATAL, "bad resolution");
-  bool plain_scene = !b->capture;   // no filter, raypath colour or capture anywhere: every launch runs the production kernels
+  bool plain_scene = !b->opt.capture;   // no filter, raypath colour or capture anywhere: every launch runs the production kernels
   for (int l = 0; l < scene->layer_count; l++) {
     if (scene->layers[l].entry_count < 1 || scene->layers[l].entry_count > HALO_MAX_ENTRIES)
       return fail(b, HALO_FATAL, "entry_count out of range");
@@ -855,15 +419,15 @@ static int begin_session(halo_handle_t b, const HaloScene* scene, const HaloRend
   }
   if (b->shard_count > 1 && scene->layer_count > 1)
     return fail(b, HALO_FATAL, "halo_set_shard count > 1: a multi-layer scene is not supported (the next layer's pool order and shuffle are global over all roots; shards do not exchange continuation pools)");
-  const bool det = b->deterministic != 0;
+  const bool det = b->opt.deterministic != 0;
   if (det) {
     // A deterministic session runs the kAccFixed kernels or nothing: what they do not cover is refused here, by name, before any state changes —
     // never run on a float route in silence.
-    if (scene->layer_count > 1 && !b->cont_order)
+    if (scene->layer_count > 1 && !b->opt.cont_order)
       return fail(b, HALO_FATAL, "deterministic = 1: a multi-layer session needs cont_order = 1 (the continuation pool's append order decides which rays the next layer traces)");
     if (!b->color_classes.empty() || !b->color_sets.empty()) return fail(b, HALO_FATAL, "deterministic = 1: raypath-colour tables are set (the class lanes are fp64 atomics)");
-    if (b->capture) return fail(b, HALO_FATAL, "deterministic = 1: capture_exits = 1 is not supported (the capture kernels have no fixed-point route)");
-    if (b->rehit_strategy == 0) return fail(b, HALO_FATAL, "deterministic = 1: rehit_strategy = 0 is not supported (the legacy strategy lives in the generic kernels)");
+    if (b->opt.capture) return fail(b, HALO_FATAL, "deterministic = 1: capture_exits = 1 is not supported (the capture kernels have no fixed-point route)");
+    if (b->opt.rehit_strategy == 0) return fail(b, HALO_FATAL, "deterministic = 1: rehit_strategy = 0 is not supported (the legacy strategy lives in the generic kernels)");
     for (int l = 0; l < scene->layer_count; l++)
       for (int e = 0; e < scene->layers[l].entry_count; e++) {
         const HaloEntry& E = scene->layers[l].entries[e];
@@ -872,7 +436,7 @@ static int begin_session(halo_handle_t b, const HaloScene* scene, const HaloRend
         if (!(fd.is_complex || fd.terms[0].type != HALO_FILTER_NONE || fd.action != 0)) continue;   // a filter that passes everything: the plain kernels
         std::unique_ptr<FastTables> ft(new FastTables());
         std::memset(ft.get(), 0, sizeof(FastTables));
-        if (!b->filter_fast || scene->max_hits > 16 ||
+        if (!b->opt.filter_fast || scene->max_hits > 16 ||
             !host::BuildFastTables(&b->filters[static_cast<size_t>(E.filter_id - 1)], nullptr, E.axis, static_cast<uint32_t>(E.crystal_config_id), *ft))
           return fail(b, HALO_FATAL, "deterministic = 1: a filter of this scene needs the generic filter kernels (filter_fast = 0, max_hits > 16, or tables that do not fit the fast form)");
       }
@@ -924,9 +488,9 @@ static int begin_session(halo_handle_t b, const HaloScene* scene, const HaloRend
   // (one plane per pool entry + binned lists; privatised copies for the direct atomics).
   const bool log_xyz_fits = s_log2 <= 11u, log_mono_fits = s_log2 <= 12u;
   // (the layout is worked out in locals first: whether the planes of earlier sessions must be folded before this one starts depends on it)
-  const bool xyz_log_n = !det && b->mono_enabled && !discrete && b->lambda_planes < 0 && b->hit_log != 0 && ray_num >= (2ull << 20) && npix > HALO_XYZ_LOG_MIN_PIX && log_xyz_fits;
-  const bool mono_by_wl_n = !det && b->mono_enabled && !discrete && !xyz_log_n && npix <= (1u << 23) && (b->lambda_planes < 0 ? ray_num >= (8ull << 20) : b->lambda_planes != 0);
-  const bool mono_session_n = b->mono_enabled && (discrete || mono_by_wl_n);
+  const bool xyz_log_n = !det && b->opt.mono_enabled && !discrete && b->opt.lambda_planes < 0 && b->opt.hit_log != 0 && ray_num >= (2ull << 20) && npix > HALO_XYZ_LOG_MIN_PIX && log_xyz_fits;
+  const bool mono_by_wl_n = !det && b->opt.mono_enabled && !discrete && !xyz_log_n && npix <= (1u << 23) && (b->opt.lambda_planes < 0 ? ray_num >= (8ull << 20) : b->opt.lambda_planes != 0);
+  const bool mono_session_n = b->opt.mono_enabled && (discrete || mono_by_wl_n);
   const uint32_t plane_cnt_n = mono_by_wl_n ? static_cast<uint32_t>(pool.size()) : (mono_session_n ? 1u : 3u);
   // privatised copies spread the direct atomics of hot pixels; per-entry planes spread them already, and a session whose
   // launches all go through the hit log (copy 0 only) would just make the closing fold read seven empty copies
@@ -935,12 +499,12 @@ static int begin_session(halo_handle_t b, const HaloScene* scene, const HaloRend
   // threshold, a last chunk or a thin continuation layer, is little work by definition)
   bool one_entry_layers = true;
   for (int l = 0; l < scene->layer_count; l++) one_entry_layers = one_entry_layers && scene->layers[l].entry_count == 1;
-  const bool fast_scene = b->rehit_strategy != 0 && (plain_scene || (!b->capture && b->filter_fast && scene->max_hits <= 16));   // (a dispatch whose tables do not fit the fast form still adds directly: copy 0 only, correct, slower)
-  const bool all_logged = !det && fast_scene && one_entry_layers && b->hit_log < 0 && b->aggregate == 1 && ray_num >= (discrete ? log_min_rays(render->visible) : (2ull << 20)) &&
+  const bool fast_scene = b->opt.rehit_strategy != 0 && (plain_scene || (!b->opt.capture && b->opt.filter_fast && scene->max_hits <= 16));   // (a dispatch whose tables do not fit the fast form still adds directly: copy 0 only, correct, slower)
+  const bool all_logged = !det && fast_scene && one_entry_layers && b->opt.hit_log < 0 && b->opt.aggregate == 1 && ray_num >= (discrete ? log_min_rays(render->visible) : (2ull << 20)) &&
                           (discrete ? log_mono_fits : xyz_log_n) && (mono_session_n || xyz_log_n);
   // (a deterministic session: one scalar plane or X, Y, Z, one copy — integer atomics onto HaloBackend::fix; hit_log, bin, lambda_planes and mono_copies do not apply)
-  const uint32_t plane_copies_n = (mono_by_wl_n || all_logged || det) ? 1u : static_cast<uint32_t>(b->mono_copies);
-  const bool two_sets_n = all_logged && discrete && mono_session_n && !mono_by_wl_n && b->overlap != 0;   // (see HaloBackend::mono_two)
+  const uint32_t plane_copies_n = (mono_by_wl_n || all_logged || det) ? 1u : static_cast<uint32_t>(b->opt.mono_copies);
+  const bool two_sets_n = all_logged && discrete && mono_session_n && !mono_by_wl_n && b->opt.overlap != 0;   // (see HaloBackend::mono_two)
   std::vector<std::array<float, 3>> coef_n;
   for (uint32_t m = 0; m < plane_cnt_n; m++) {
     if (mono_session_n) coef_n.push_back({pool[m].cmf_x, pool[m].cmf_y, pool[m].cmf_z});
@@ -952,7 +516,7 @@ static int begin_session(halo_handle_t b, const HaloScene* scene, const HaloRend
     // sessions (Lumice's CUDA-route dispatch is 2^18 rays, server.cpp:151) then pays one fold per readback instead of one per session (22 us
     // of a 0.15 ms session at 1920x1080 x 8 copies).  Anything else — another wavelength, image size, plane count or copy count — is folded
     // now, with the members still describing the old planes.
-    const bool same_planes = b->mono_dirty && b->lazy_fold && b->acc != nullptr && b->acc == b->acc_own.ptr && b->acc_w == render->width &&
+    const bool same_planes = b->mono_dirty && b->opt.lazy_fold && b->acc != nullptr && b->acc == b->acc_own.ptr && b->acc_w == render->width &&
                              b->acc_h == render->height && b->mono_s_log2 == s_log2 && b->plane_cnt == plane_cnt_n && b->plane_copies == plane_copies_n &&
                              b->mono_two == two_sets_n && b->plane_coef == coef_n && b->fix_planes == det;
     if (!same_planes) {
@@ -961,7 +525,7 @@ static int begin_session(halo_handle_t b, const HaloScene* scene, const HaloRend
       // this fold, or with two plane sets for the one that last zeroed theirs (LaunchPlan::under_fold).  The twin's two halves keep the fold and the open session apart)
       int rc = fold_queue(b);  // also: a session that was never ended still owes its plane to the accumulator (old layout)
       if (rc != HALO_OK) return rc;
-      const bool caller_reads = b->acc != nullptr && b->acc != b->acc_own.ptr && !b->defer_fold;   // the caller's memory, read in stream order: the fold must be in that order too
+      const bool caller_reads = b->acc != nullptr && b->acc != b->acc_own.ptr && !b->opt.defer_fold;   // the caller's memory, read in stream order: the fold must be in that order too
       const bool layout_changes = b->mono_s_log2 != s_log2 || b->plane_cnt != plane_cnt_n || b->plane_copies != plane_copies_n || b->mono_two != two_sets_n;   // the twin's halves (and the plane sets) move
       if (caller_reads || layout_changes) {
         rc = join_aux(b);
@@ -1032,7 +596,7 @@ static int begin_session(halo_handle_t b, const HaloScene* scene, const HaloRend
   b->route_root = 0u;
   b->route.plane_cnt = b->plane_cnt;
   b->route.plane_copies = b->plane_copies;
-  b->route.shuffle_chunk = 1u << b->shuffle_chunk_log2;
+  b->route.shuffle_chunk = 1u << b->opt.shuffle_chunk_log2;
   b->in_session = true;
   b->layer_idx = 0;
   b->cont_in_n = 0;
@@ -1058,32 +622,7 @@ int halo_begin_spectrum(halo_handle_t b, const HaloScene* scene, const HaloRende
   return begin_session(b, scene, render, entries, entries, count, ray_num);
 }
 
-uint32_t halo_host_spectrum_entry(uint64_t m, uint32_t count, uint64_t r) {
-  // The kernels' own function, given what the host would hand a launch that holds ray r — two ways: the launch that starts as late as a 32-bit
-  // thread index allows (a long way into the launch, across many block edges), and one that starts at a multiple of 65521 rays (an offset in the
-  // middle of a block).  They must agree; 0xFFFFFFFF says they did not.
-  const uint64_t reach = 0xFFFFFFFEull, off_a = r > reach ? r - reach : 0ull, off_b = r - r % 65521ull;
-  const SpectrumChunkDev a = SpectrumChunk(m, count, off_a), c = SpectrumChunk(m, count, off_b);
-  const uint32_t ka = SpectrumEntry(a.per, a.k0, a.rem, a.last, static_cast<uint32_t>(r - off_a));
-  const uint32_t kb = SpectrumEntry(c.per, c.k0, c.rem, c.last, static_cast<uint32_t>(r - off_b));
-  return ka == kb ? ka : 0xFFFFFFFFu;
-}
-
-// Fractional bits of the per-tile fixed-point sums for a launch of `m` rays whose weights are at most `max_w`: the largest F <= 32 with
-// 4 * max_w * m * 2^F < 2^62 (see halo_kernels.hip FixQ for the factor 4).
-// The deterministic route applies the same bound to the rays a plane set may take before it is folded (kFixBudgetHits) and to the landed integer
-// (kFixLandedHits): halo_host_fixed_frac_bits exports the rule.
-static uint32_t fix_frac_bits(double max_w, uint64_t m) {
-  const double bound = 4.0 * std::max(max_w, 1e-30) * static_cast<double>(std::max<uint64_t>(m, 1));
-  int e = 0;
-  (void)std::frexp(bound, &e);   // bound < 2^e
-  return static_cast<uint32_t>(std::min(32, std::max(0, 62 - e)));
-}
-
-// Rays one unfolded fixed-point plane set takes (F = 29 for weights up to 1: a hit is quantised to 1.9e-9): a constant, because F must not depend
-// on how a run is cut into launches or sessions.  The landed integer's scale allows for the 2^32 rays of the largest layer.
-constexpr uint64_t kFixBudgetHits = 1ull << 30, kFixLandedHits = 1ull << 32;
-uint32_t halo_host_fixed_frac_bits(double max_w, uint64_t hits) { return fix_frac_bits(max_w, hits); }
+}  // extern "C"
 
 // The twin half a session of the current layout uses: valid only when the buffer holds two halves of this layout.
 static double* twin_of(HaloBackend* b, int set) {
@@ -1137,10 +676,12 @@ static int fold_queue(HaloBackend* b) {
   return HALO_OK;
 }
 // ... and with the main stream waiting for it: for readers of the image and for whoever hands the image to somebody else.
-static int fold_if_dirty(HaloBackend* b) {
+int halo::fold_if_dirty(HaloBackend* b) {
   if (int rc = fold_queue(b)) return rc;
   return join_aux(b);
 }
+
+extern "C" {
 
 int halo_end(halo_handle_t b) {
   if (!b) return HALO_FATAL;
@@ -1149,7 +690,7 @@ int halo_end(halo_handle_t b) {
   // first) or a session with other planes begins
   int rc = HALO_OK;
   const bool own = b->acc != nullptr && b->acc == b->acc_own.ptr;
-  if (!((b->lazy_fold && own) || (b->defer_fold && !own))) rc = fold_if_dirty(b);
+  if (!((b->opt.lazy_fold && own) || (b->opt.defer_fold && !own))) rc = fold_if_dirty(b);
   b->in_session = false;
   return rc;
 }
@@ -1164,16 +705,6 @@ static int cont_order_fail(HaloBackend* b, uint32_t err) {
 // ---- The steps of halo_trace_layer: plan (no HIP call) -> entry tables -> parameters -> route buffers -> launch + passes -> route record -> close ----
 namespace {
 
-// Shard `index` of `count` takes rays [first, first + n) of a crystal entry's share: the share is cut in units of `clock` rays (the rays of one
-// sampled shape; 1 for a fixed one), u = ceil(share / clock) of them, and the shard gets units [floor(index * u / count), floor((index + 1) * u / count)) —
-// the last unit may be short.  Every shard gets a part of every entry, the parts differ by at most one unit, no unit is cut.
-void shard_slice(uint64_t share, uint32_t clock, uint32_t index, uint32_t count, uint64_t* first, uint64_t* n) {
-  typedef unsigned __int128 u128;
-  const u128 c = clock ? clock : 1u, u = (static_cast<u128>(share) + c - 1u) / c;
-  const u128 lo = std::min<u128>(c * (static_cast<u128>(index) * u / count), share), hi = std::min<u128>(c * ((static_cast<u128>(index) + 1u) * u / count), share);
-  *first = static_cast<uint64_t>(lo);
-  *n = static_cast<uint64_t>(hi - lo);
-}
 
 // What the launches of one halo_trace_layer call share.
 struct LayerCtx {
@@ -1228,14 +759,14 @@ struct EntryTables {
 };
 // launch plan: chunking bounds the host-built shape pool for stochastic geometry and keeps n_rays < 2^32
 uint64_t chunk_of(const HaloBackend& b, uint64_t left, const HaloCrystal& crystal, bool host_crystal) {
-  uint64_t m = std::min<uint64_t>(left, b.chunk);
+  uint64_t m = std::min<uint64_t>(left, b.opt.chunk);
   if (b.det_session) m = std::min<uint64_t>(m, kFixBudgetHits);   // a launch fits the budget of one fixed-point plane set
   // stochastic geometry: one pool record per geom_clock rays.  Device-generated prisms are 1360 B records (2.9 GB per
   // 64 Mi rays), other device-generated shapes 4.1 KB (2 GB per 16 Mi rays); host-built pools (pageable staging + H2D)
   // stay at 4 Mi rays
   if (!host::IsDeterministic(crystal) && !host_crystal) {
-    const uint64_t dev = b.stoch_chunk ? b.stoch_chunk : (1ull << 26);   // records: 2.9 GB (prism) / 8.6 GB (general) per 64 Mi rays
-    m = std::min<uint64_t>(m, b.host_shapes ? (1ull << 22) : dev);
+    const uint64_t dev = b.opt.stoch_chunk ? b.opt.stoch_chunk : (1ull << 26);   // records: 2.9 GB (prism) / 8.6 GB (general) per 64 Mi rays
+    m = std::min<uint64_t>(m, b.opt.host_shapes ? (1ull << 22) : dev);
   }
   return m;
 }
@@ -1258,11 +789,11 @@ int blocks_of(const HaloBackend& b, uint64_t m, bool pool) {
   const uint64_t want = m / (static_cast<uint64_t>(kBlock) * 32u);
   // (shape-pool kernels hold four workgroups a CU, not six, and every workgroup of a logged launch is a region for the split pass: three per CU
   //  there — bench.py --config 4d, 0.8 M rays per session, ms per step at 1 / 2 / 3 / 4 / 5 / 6 / 8 per CU: 7.26 / 5.99 / 5.73 / 5.77 / 5.86 / 6.14 / 6.39)
-  const int small_k = b.small_blocks_per_cu > 0 ? b.small_blocks_per_cu : pool ? 3 : 5;
-  const uint64_t lo_cap = static_cast<uint64_t>(b.cu_count) * static_cast<uint64_t>(std::min(b.blocks_per_cu, small_k));
-  const uint64_t cap = std::min<uint64_t>(static_cast<uint64_t>(b.cu_count * b.blocks_per_cu), std::max<uint64_t>(lo_cap, want));
+  const int small_k = b.opt.small_blocks_per_cu > 0 ? b.opt.small_blocks_per_cu : pool ? 3 : 5;
+  const uint64_t lo_cap = static_cast<uint64_t>(b.cu_count) * static_cast<uint64_t>(std::min(b.opt.blocks_per_cu, small_k));
+  const uint64_t cap = std::min<uint64_t>(static_cast<uint64_t>(b.cu_count * b.opt.blocks_per_cu), std::max<uint64_t>(lo_cap, want));
   uint64_t nb = std::min<uint64_t>((m + kBlock - 1) / kBlock, cap);
-  if (b.blocks_cap > 0) nb = std::min<uint64_t>(nb, static_cast<uint64_t>(b.blocks_cap));
+  if (b.opt.blocks_cap > 0) nb = std::min<uint64_t>(nb, static_cast<uint64_t>(b.opt.blocks_cap));
   return static_cast<int>(nb);
 }
 // The chunking part of a launch's plan: the next launch of entry `ci`, `left` of whose rays are still to be traced (`first_ci` = the entry's first ray).
@@ -1272,14 +803,14 @@ LaunchPlan plan_launch(const HaloBackend& b, const LayerCtx& c, int ci, uint64_t
   p.ci = ci, p.off = off, p.first = first_ci + off, p.share = off + left;
   p.m = chunk_of(b, left, crystal, c.host_crystal);
   p.deterministic = c.host_crystal || host::IsDeterministic(crystal);
-  p.shape_cnt = p.deterministic ? 1u : static_cast<uint32_t>((p.m + b.geom_clock - 1) / b.geom_clock);
-  p.host_pool = !p.deterministic && b.host_shapes;
+  p.shape_cnt = p.deterministic ? 1u : static_cast<uint32_t>((p.m + b.opt.geom_clock - 1) / b.opt.geom_clock);
+  p.host_pool = !p.deterministic && b.opt.host_shapes;
   p.geom = p.deterministic ? 0 : ((crystal.kind == HALO_CRYSTAL_PRISM && !p.host_pool) ? 2 : 1);
   p.blocks = blocks_of(b, p.m, !p.deterministic);
   // Launches of <= 2^21 rays alternate between the two trace streams (next_trace_stream); only those can meet a neighbour that still reads
   // or writes a buffer set, so only those take the sets in turn — a launch that fills the chip keeps stream 0 and set 0 (a second set
   // allocated in the middle of a run is a host sync and a multi-gigabyte hipMalloc: 1.2 s in configs[4]'s first timed step)
-  p.alternate = p.m <= (1ull << b.alt_log2);
+  p.alternate = p.m <= (1ull << b.opt.alt_log2);
   return p;
 }
 // The accumulation route of a planned launch (direct / binned one- or two-level / hit log scalar / hit log X/Y/Z / none) and the buffer sizes it asks for.
@@ -1296,7 +827,7 @@ void plan_route(const HaloBackend& b, const LayerCtx& c, bool fast_mode, LaunchP
   // up to 512 tiles: one level (interleaved tiles).  More (per-wavelength planes of a large image): two levels — the
   // trace kernel fills coarse lists of `fan` consecutive tiles each, a split pass deals them out to the tiles.
   p.fan_log2 = 0u;
-  while (((p.bin_tiles + (1u << p.fan_log2) - 1u) >> p.fan_log2) > b.bin_l1) p.fan_log2++;
+  while (((p.bin_tiles + (1u << p.fan_log2) - 1u) >> p.fan_log2) > b.opt.bin_l1) p.fan_log2++;
   p.two_level = p.bin_tiles > 512u;
   const bool bin_shape_ok = p.two_level ? (p.fan_log2 <= 8u && (bin_slots & 16383ull) == 0ull)
                                         : (p.bin_tiles >= 8u && (p.bin_tiles & (p.bin_tiles - 1u)) == 0u);
@@ -1304,15 +835,15 @@ void plan_route(const HaloBackend& b, const LayerCtx& c, bool fast_mode, LaunchP
   // 2^t interleaved tiles of <= 16 Ki slots, and the split pass feeds at most 512 lists — 64 planes up to 128 Ki pixels, 32 up to 256 Ki.
   const uint32_t wl_t_log2 = s_log2 >= 4u ? s_log2 - 4u : 0u;
   const bool log_planes_ok = b.mono_by_wl && (static_cast<uint64_t>(b.plane_cnt) << wl_t_log2) <= 512ull &&
-                             (static_cast<uint64_t>(b.plane_cnt) << (s_log2 + 10u)) <= (1ull << 31) && b.hit_log != 0 && b.bin <= 0;
+                             (static_cast<uint64_t>(b.plane_cnt) << (s_log2 + 10u)) <= (1ull << 31) && b.opt.hit_log != 0 && b.opt.bin <= 0;
   // (a layer before the last under canonical continuation order takes direct accumulation: only those kernels have CANON twins)
-  p.canon = b.cont_order && !c.final_layer;
+  p.canon = b.opt.cont_order && !c.final_layer;
   p.fixed = b.det_session;   // every accumulating launch of a deterministic session adds integers: directly, or through the hit log's integer twins — never lists
   const bool fixed_xyz = p.fixed && !b.mono_session;   // ... on X, Y, Z planes (a deterministic session has no plane per pool entry)
-  p.use_bin = !p.fixed && !p.canon && b.mono_session && b.aggregate == 1 && !b.capture && bin_shape_ok && bin_slots <= (1ull << 31) &&
+  p.use_bin = !p.fixed && !p.canon && b.mono_session && b.opt.aggregate == 1 && !b.opt.capture && bin_shape_ok && bin_slots <= (1ull << 31) &&
               // own choice: only where the hit log cannot go (one plane per pool entry on a larger image) — the log beats the binned route
               // on every launch measured (tools/bin_vs_log_probe.py: dual fisheye 50 M rays 5.13 -> 4.42 ms)
-              (b.bin < 0 ? (b.mono_by_wl && !log_planes_ok && bin_geom_ok && full_sky && m >= (2ull << 20)) : b.bin != 0);
+              (b.opt.bin < 0 ? (b.mono_by_wl && !log_planes_ok && bin_geom_ok && full_sky && m >= (2ull << 20)) : b.opt.bin != 0);
   p.lists1 = p.two_level ? ((p.bin_tiles + (1u << p.fan_log2) - 1u) >> p.fan_log2) : p.bin_tiles;
   // Hit log (halo_trace.inl log_hit): global fp32 atomics retire memory-side at 21 G/s on this part, which bounded every big
   // launch once its trace was fast enough (configs[1]: 2.4 ms of trace, 2.8 ms of atomics).  A production-mode launch on one
@@ -1322,22 +853,22 @@ void plan_route(const HaloBackend& b, const LayerCtx& c, bool fast_mode, LaunchP
   // 256 and at most 16 Ki slots (X/Y/Z: 4 Ki) of ONE plane: 512 for X/Y/Z; for a scalar plane 128 where that keeps them within
   // 16 Ki slots (longer runs in the split pass: 0.23 vs 0.25 ms at configs[1]).
   // (a small launch takes 256 tiles: its per-tile pass is one workgroup per tile, and 128 of them leave half the chip idle — config 4d 2.85 -> 3.18 G rays/s; big launches keep 128 for the split's longer runs)
-  const uint32_t asked_t_log2 = static_cast<uint32_t>(m < (4ull << 20) ? std::max(b.log_tiles_log2, 8) : b.log_tiles_log2);
+  const uint32_t asked_t_log2 = static_cast<uint32_t>(m < (4ull << 20) ? std::max(b.opt.log_tiles_log2, 8) : b.opt.log_tiles_log2);
   const uint32_t scalar_t_log2 = std::max<uint32_t>(wl_t_log2, std::min<uint32_t>(asked_t_log2, s_log2 + 2u));   // tiles of 256 .. 16 Ki slots
   p.log_t_log2 = log_planes_ok ? wl_t_log2 : (b.xyz_log || fixed_xyz) ? std::min<uint32_t>(9u, s_log2 + 2u) : scalar_t_log2;
   p.log_planes = log_planes_ok ? b.plane_cnt : 1u;
   p.log_tiles = p.log_planes << p.log_t_log2;   // lists the split pass feeds
   const bool log_layout_ok = (b.xyz_log || fixed_xyz) ? (s_log2 <= 11u) : (b.mono_session && (log_planes_ok || (!b.mono_by_wl && s_log2 <= 12u)));
   // (aggregate = 0 under a forced log — every hit a record — exists in deterministic sessions only, where the cache is a run-time branch of accumulate_fixed)
-  const bool log_agg_ok = b.aggregate == 1 || (p.fixed && b.aggregate == 0 && b.hit_log > 0);
+  const bool log_agg_ok = b.opt.aggregate == 1 || (p.fixed && b.opt.aggregate == 0 && b.opt.hit_log > 0);
   p.use_log = !p.canon && !p.use_bin && log_layout_ok && log_agg_ok && fast_mode &&
               (L.prob < 1.0f || c.final_layer) &&   // a layer whose every exit continues puts nothing on the image
               // (own choice in a deterministic session: from 2 Mi rays on either plane layout and whatever the visible range — the float route's
               //  512 Ki for full-sky scalar sessions buys nothing there: the integer log neither starts under the previous fold nor has two plane
               //  sets, and bench.py --config 4d measured 10.96 ms per step logged against 10.79 direct)
-              (b.hit_log < 0 ? m >= (p.fixed ? (2ull << 20) : (b.mono_session && !b.mono_by_wl) ? log_min_rays(b.render.visible) : (2ull << 20)) : b.hit_log != 0);
+              (b.opt.hit_log < 0 ? m >= (p.fixed ? (2ull << 20) : (b.mono_session && !b.mono_by_wl) ? log_min_rays(b.render.visible) : (2ull << 20)) : b.opt.hit_log != 0);
   p.use_log_xyz = p.use_log && (b.xyz_log || fixed_xyz);
-  p.no_land = L.prob >= 1.0f && !c.final_layer && fast_mode && b.aggregate == 1;
+  p.no_land = L.prob >= 1.0f && !c.final_layer && fast_mode && b.opt.aggregate == 1;
   if (p.use_log) {
     // a region takes 4 records per ray of its workgroup (configs[1]: 1.2 logged per ray), 8 for full-sky renders (5-6 per ray),
     // and a tile list twice its even share of that; what runs over falls back to direct atomics
@@ -1352,8 +883,8 @@ void plan_route(const HaloBackend& b, const LayerCtx& c, bool fast_mode, LaunchP
     // even shares and its pixel read 5.6e-4 high with 2x)
     p.cap2 = std::max<uint64_t>(kListSlack * ((p.use_log_xyz || full_sky) ? 8ull : 4ull) * m / p.log_tiles, 1ull << 14);
     p.cap2 = std::min<uint64_t>(p.cap2, (8ull << 30) / (8ull * p.log_tiles));
-    if (b.hit_log_cap) {   // tests: run both overflow fallbacks
-      p.cap1 = b.hit_log_cap;
+    if (b.opt.hit_log_cap) {   // tests: run both overflow fallbacks
+      p.cap1 = b.opt.hit_log_cap;
       p.cap2 = std::max<uint64_t>(p.cap1 * blocks / (2ull * p.log_tiles), 64ull);
     }
   } else if (p.use_bin) {
@@ -1384,7 +915,7 @@ int reserve_log_buffers(HaloBackend* b, LaunchPlan& p, int ls) {
   if (int rc = reserve_idle(b, b->bin_list_s[ls], p.cap1 * blocks, &e1)) return rc;
   if (e1 == hipSuccess)
     if (int rc = reserve_idle(b, b->bin_list2_s[ls], p.cap2 * p.log_tiles, &e2)) return rc;
-  if (b->overlap && p.alternate && e1 == hipSuccess && e2 == hipSuccess) {
+  if (b->opt.overlap && p.alternate && e1 == hipSuccess && e2 == hipSuccess) {
     // the other set with it: the next launch would otherwise stop the queue (a host sync and a multi-gigabyte hipMalloc) for it.  A speed
     // matter only — if there is no room, the launch that finds the set short shrinks its log as above.
     hipError_t e3 = hipSuccess, e4 = hipSuccess;
@@ -1405,7 +936,7 @@ void prepare_entry_tables(HaloBackend* b, const LayerCtx& c, int ci, EntryTables
   const bool deterministic = c.host_crystal || host::IsDeterministic(E.crystal);
   T = EntryTables{};
   // the entry's tables may still be on the device from an earlier dispatch (table cache, see HaloBackend::TableCacheEntry)
-  T.ce = (b->table_cache && deterministic && !c.host_crystal && c.source != kSrcTransit) ? &b->tcache[c.layer][ci] : nullptr;
+  T.ce = (b->opt.table_cache && deterministic && !c.host_crystal && c.source != kSrcTransit) ? &b->tcache[c.layer][ci] : nullptr;
   if (T.ce && !b->tcache_dev.ptr) {
     if (b->tcache_dev.reserve(static_cast<size_t>(HALO_MAX_LAYERS) * HALO_MAX_ENTRIES * 2u) != hipSuccess) {
       (void)hipGetLastError();
@@ -1448,11 +979,11 @@ void prepare_entry_tables(HaloBackend* b, const LayerCtx& c, int ci, EntryTables
 
   // Which kernels: capture (tests) > filter / colour in their fast form (paths <= 16 faces, tables fit) > the generic filter kernels > plain
   if (T.cached) T.mode = T.ce->mode;
-  else if (b->capture) T.mode = 2;
-  else if (b->rehit_strategy == 0) T.mode = 3;   // the legacy next-face strategy lives in the generic kernels only
+  else if (b->opt.capture) T.mode = 2;
+  else if (b->opt.rehit_strategy == 0) T.mode = 3;   // the legacy next-face strategy lives in the generic kernels only
   else if (T.use_filter || T.use_color) {
     T.mode = 3;
-    if (b->filter_fast && b->scene.max_hits <= 16) {
+    if (b->opt.filter_fast && b->scene.max_hits <= 16) {
       b->fast_scratch.reset(new FastTables());
       std::memset(b->fast_scratch.get(), 0, sizeof(FastTables));
       const HaloColorSet* cs = (T.use_color && E.color_id > 0) ? &b->color_sets[static_cast<size_t>(E.color_id - 1)] : nullptr;
@@ -1476,7 +1007,7 @@ void prepare_entry_tables(HaloBackend* b, const LayerCtx& c, int ci, EntryTables
 int upload_tables(HaloBackend* b, const LayerCtx& c, const LaunchPlan& p, const HaloEntry& E, uint32_t lat_path, const ShapeDev* shape, int k, EntryTables& T,
                   DispatchSlot** out) {
   HaloBackend::TableCacheEntry* ce = T.ce;
-  DispatchSlot& hs = b->ring_host[k];
+  DispatchSlot& hs = b->ring_host.ptr[k];
   if (ce && !T.cached) ce->cur ^= 1;   // an upload takes the entry's other slot
   DispatchSlot* ds = *out = ce ? T.ce_dev + ce->cur : b->ring_dev.ptr + k;
   if (T.cached) return HALO_OK;   // (T describes the slot already: from the cache entry, or from this entry's previous upload)
@@ -1489,7 +1020,7 @@ int upload_tables(HaloBackend* b, const LayerCtx& c, const LaunchPlan& p, const 
   std::copy(b->wl_pool_host.begin(), b->wl_pool_host.end(), hs.wl);
   if (p.deterministic) {
     hs.shape = *shape;
-    T.entry_fast = b->entry_fast && host::BuildEntryFast(*shape, hs.efast);
+    T.entry_fast = b->opt.entry_fast && host::BuildEntryFast(*shape, hs.efast);
     T.hex_regular = T.entry_fast && hs.efast.hex_regular;
   }
   if (T.use_filter) hs.filter = T.fd;
@@ -1536,13 +1067,13 @@ DispatchParams fill_params(HaloBackend* b, const LayerCtx& c, int ci) {
   P.max_hits = static_cast<uint32_t>(b->scene.max_hits);
   P.prob = L.prob;
   P.crystal_id = static_cast<uint32_t>(E.crystal_config_id);
-  P.capture = static_cast<uint32_t>(b->capture);
+  P.capture = static_cast<uint32_t>(b->opt.capture);
   P.gen_seed = b->seed ^ kNonceGen;
   P.gate_seed = b->seed ^ kNonceGate;
   P.transit_seed = b->seed ^ kNonceTransit;
   P.shuffle = static_cast<uint32_t>(b->cont_shuffle);
   P.shuffle_seed = (b->seed ^ kNonceShuffle) ^ static_cast<uint32_t>(c.layer);  // cuda_trace_backend.cu:4541
-  P.shuffle_chunk_log2 = b->shuffle_chunk_log2;
+  P.shuffle_chunk_log2 = b->opt.shuffle_chunk_log2;
   // orientation wire params (BuildTransitGpParams cuda_trace_backend.cu:342-383)
   P.lat_path = host::SelectLatPath(E.axis);
   P.lat_mean_rad = E.axis.latitude.center * host::kDegToRad;
@@ -1574,7 +1105,7 @@ DispatchParams fill_params(HaloBackend* b, const LayerCtx& c, int ci) {
   P.cont_out_cap = c.out_cap;
   P.cont_in_region = b->cont_region[c.out_slot ^ 1];
   P.cont_cnt = b->cont_cnt.ptr;
-  P.cont_mask = (b->cont_order && !c.final_layer) ? b->cont_mask.ptr : nullptr;
+  P.cont_mask = (b->opt.cont_order && !c.final_layer) ? b->cont_mask.ptr : nullptr;
   P.cont_err = c.canon_check ? b->cont_err.ptr : nullptr;
   P.counters = b->counters.ptr;
   P.mono = planes_of(b);
@@ -1582,16 +1113,16 @@ DispatchParams fill_params(HaloBackend* b, const LayerCtx& c, int ci) {
   P.ovf = twin_of(b, b->twin_set);
   P.ovf_copies_log2 = static_cast<uint32_t>(__builtin_ctz(b->plane_copies));
   P.ovf_flag = P.ovf ? b->ovf_flag.ptr + b->twin_set : nullptr;
-  P.pool_entry_fast = b->pool_entry_fast ? 1u : 0u;
-  P.rehit_legacy = b->rehit_strategy == 0 ? 1u : 0u;
+  P.pool_entry_fast = b->opt.pool_entry_fast ? 1u : 0u;
+  P.rehit_legacy = b->opt.rehit_strategy == 0 ? 1u : 0u;
   P.tally = b->tally.ptr;
   P.exits = b->exits.ptr;
   P.exit_cap = static_cast<uint32_t>(std::min<uint64_t>(b->exits.cap, 0xFFFFFFFFull));
-  P.aggregate = static_cast<uint32_t>(b->aggregate);
-  P.geom_clock = b->geom_clock;
+  P.aggregate = static_cast<uint32_t>(b->opt.aggregate);
+  P.geom_clock = b->opt.geom_clock;
   P.lanes = b->lanes.ptr;
   P.lane_stride = static_cast<uint32_t>(b->acc_w) * static_cast<uint32_t>(b->acc_h);
-  P.root_profile = (b->spec_root && b->spec_count == 0u) ? root_profile_of(P) : kRootProfileNone;   // (a spectrum session picks its entry in the generic root generation)
+  P.root_profile = (b->opt.spec_root && b->spec_count == 0u) ? root_profile_of(P) : kRootProfileNone;   // (a spectrum session picks its entry in the generic root generation)
   P.fix = b->det_session ? b->fix.ptr : nullptr;   // (fix_frac, fix_frac_landed: trace_launch, once fix_prepare has settled them)
   return P;
 }
@@ -1627,7 +1158,7 @@ int bind_route(HaloBackend* b, LaunchPlan& p, int ls, DispatchParams& P) {
   P.mono_copy_mask = lists ? 0u : b->plane_copies - 1u;   // logged / staged hits and their fallbacks address copy 0
   if (lists) {
     P.bin_cap = static_cast<uint32_t>(p.cap1);
-    P.bin_tiles = p.use_log ? p.log_tiles : p.two_level ? b->bin_l1 : p.bin_tiles;
+    P.bin_tiles = p.use_log ? p.log_tiles : p.two_level ? b->opt.bin_l1 : p.bin_tiles;
     P.bin_shift = (p.use_bin && p.two_level) ? 14u + p.fan_log2 : 0u;
     P.bin_cnt = bin_cnt.ptr;   // (log: one fill count per region, written by the trace kernel)
   }
@@ -1635,21 +1166,21 @@ int bind_route(HaloBackend* b, LaunchPlan& p, int ls, DispatchParams& P) {
   P.no_land = p.no_land ? 1u : 0u;
   return HALO_OK;
 }
-// Whether a planned, bound launch closes its session in its per-tile pass (HaloBackend::close_direct).  What is checked: it is the only launch of
+// Whether a planned, bound launch closes its session in its per-tile pass (Options::close_direct).  What is checked: it is the only launch of
 // its halo_trace_layer call (one crystal entry, one chunk), on the last layer, with nothing pending in the planes — an earlier layer that put light
 // on them, or an unfolded session under lazy_fold, has left mono_dirty set — on the float hit log's contiguous-tile scalar route, one plane in one
 // copy, with the twin to overflow to.  (halo_begin's ray count is not consulted: a caller that traces a last layer in several calls gets a direct
 // close per call, each adding its own sums to the image — the planes stay clean in between, so that is the same image.)
 bool close_direct_ok(const HaloBackend& b, const LaunchPlan& p, const DispatchParams& P) {
-  if (b.close_direct == 0 || !p.only || p.fixed || !p.use_log || p.use_log_xyz || p.log_planes != 1u || b.mono_by_wl) return false;
+  if (b.opt.close_direct == 0 || !p.only || p.fixed || !p.use_log || p.use_log_xyz || p.log_planes != 1u || b.mono_by_wl) return false;
   if (b.plane_cnt != 1u || b.plane_copies != 1u || b.render.visible == HALO_VISIBLE_FULL) return false;   // (full sky: interleaved tiles)
   if ((1u << p.log_t_log2) > 256u || b.mono_s_log2 + 10u - p.log_t_log2 > kBinTileLog2) return false;
   if (P.ovf == nullptr || P.ovf_flag == nullptr || b.mono_dirty || b.acc == nullptr) return false;
-  return b.close_direct > 0 || !p.alternate;   // auto: the hit log's own threshold chose the log; launches that fill the chip only
+  return b.opt.close_direct > 0 || !p.alternate;   // auto: the hit log's own threshold chose the log; launches that fill the chip only
 }
 // a one-shape dispatch of a regular hexagonal prism takes the literal-normal instantiation (kGeomOneHex = 3)
-int launch_geom_of(const HaloBackend& b, const LaunchPlan& p, const EntryTables& T) { return (p.geom == 0 && T.entry_fast && b.hex_fast && T.hex_regular) ? kGeomOneHex : p.geom; }
-// The per-tile append of a launch that closes directly (HaloBackend::tile_append): taken where the launch's kernel has a kAccTileFinal twin — the
+int launch_geom_of(const HaloBackend& b, const LaunchPlan& p, const EntryTables& T) { return (p.geom == 0 && T.entry_fast && b.opt.hex_fast && T.hex_regular) ? kGeomOneHex : p.geom; }
+// The per-tile append of a launch that closes directly (Options::tile_append): taken where the launch's kernel has a kAccTileFinal twin — the
 // selector is asked (halo_select.h: plain mode, one regular prism, scalar plane, last layer with a closed gate, one of the lenses that are
 // template constants, the upper sky) — and the chunk buffers of log set `ls` can be reserved.  Tiles: the close's own contiguous ones, at most
 // kTileAppendMax (a small launch's 256 become 128: the kernel holds one LDS counter per tile).  A chunk holds kListSlack (8) x its even share of the
@@ -1661,7 +1192,7 @@ int bind_tile_append(HaloBackend* b, LaunchPlan& p, const EntryTables& T, int ls
   p.tile = p.ticket = false;
   // auto: launches that fill the chip, over generated roots.  (A last layer over the continuation pool — configs[2]: five times the records per
   // launch, hot tiles past their chunks — measured slower with the append, profiles/tile_append_ab.txt: 1 takes it, auto does not.)
-  if (!p.close || b->tile_append == 0 || (b->tile_append < 0 && (p.alternate || P.source != kSrcGen))) return HALO_OK;
+  if (!p.close || b->opt.tile_append == 0 || (b->opt.tile_append < 0 && (p.alternate || P.source != kSrcGen))) return HALO_OK;
   const KernelRequest req = make_request(P, T.mode, launch_geom_of(*b, p, T), b->mono_session);
   if (select_kernel(tile_request(req, false)).err != 0) return HALO_OK;   // this launch's kernel has no kAccTileFinal twin
   const uint32_t t_log2 = std::min<uint32_t>(p.log_t_log2, static_cast<uint32_t>(__builtin_ctz(kTileAppendMax)));
@@ -1672,8 +1203,8 @@ int bind_tile_append(HaloBackend* b, LaunchPlan& p, const EntryTables& T, int ls
   // (Only where the twin has a ticketed form: halo_select.h kernel_exists.)
   // The default (-2) asks for more: a static grid of more than one resident round — a launch that fits into one round has no rounds to even out,
   // and its landed tally stays the static loop's to the last digit (tests/test_gpu_tile_append_sessions.py compares it at 1e-12).
-  const int round = (b->tile_ticket != 0 && select_kernel(tile_request(req, true)).err == 0) ? tile_ticket_resident_per_cu() * b->cu_count : 0;
-  const bool want_ticket = round > 0 && (b->tile_ticket > 0 || (!p.alternate && P.source == kSrcGen && (b->tile_ticket == -1 || p.blocks > round)));
+  const int round = (b->opt.tile_ticket != 0 && select_kernel(tile_request(req, true)).err == 0) ? tile_ticket_resident_per_cu() * b->cu_count : 0;
+  const bool want_ticket = round > 0 && (b->opt.tile_ticket > 0 || (!p.alternate && P.source == kSrcGen && (b->opt.tile_ticket == -1 || p.blocks > round)));
   const int resident = want_ticket ? round : 0;
   uint32_t* ticket = nullptr;
   if (resident > 0) {
@@ -1694,7 +1225,7 @@ int bind_tile_append(HaloBackend* b, LaunchPlan& p, const EntryTables& T, int ls
   const uint64_t per_wg = (p.m + blocks - 1u) / blocks;
   uint64_t cap = std::max<uint64_t>(8ull * 4ull * per_wg / tiles, 16ull);
   cap = std::min<uint64_t>(cap, (1ull << 30) / chunks);
-  if (b->hit_log_cap) cap = std::max<uint64_t>(b->hit_log_cap / tiles, 2ull);   // tests: chunks that overflow
+  if (b->opt.hit_log_cap) cap = std::max<uint64_t>(b->opt.hit_log_cap / tiles, 2ull);   // tests: chunks that overflow
   size_t free_b = 0, total_b = 0;
   const uint64_t have = b->tile_chunk_s[ls].cap * sizeof(HitRec), need = cap * chunks * sizeof(HitRec);
   if (need > have && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need - have > free_b / 2u)
@@ -1713,7 +1244,7 @@ int bind_tile_append(HaloBackend* b, LaunchPlan& p, const EntryTables& T, int ls
     p.blocks = blocks_was;
     return HALO_OK;
   }
-  if (b->overlap && p.alternate) {   // the other set with it, as reserve_log_buffers does (a speed matter only)
+  if (b->opt.overlap && p.alternate) {   // the other set with it, as reserve_log_buffers does (a speed matter only)
     hipError_t e3 = hipSuccess, e4 = hipSuccess;
     if (int rc = reserve_idle(b, b->tile_chunk_s[ls ^ 1], cap * chunks, &e3)) return rc;
     if (e3 == hipSuccess)
@@ -1723,8 +1254,8 @@ int bind_tile_append(HaloBackend* b, LaunchPlan& p, const EntryTables& T, int ls
   p.tile = true;
   p.ticket = ticket != nullptr;
   P.ticket = ticket;
-  P.ticket_waves = std::max<uint32_t>(static_cast<uint32_t>(p.blocks) * static_cast<uint32_t>(kBlock / 64) * b->ticket_div / kTicketGroups, 1u);
-  P.ticket_min = b->ticket_min, P.ticket_max = b->ticket_max;
+  P.ticket_waves = std::max<uint32_t>(static_cast<uint32_t>(p.blocks) * static_cast<uint32_t>(kBlock / 64) * b->opt.ticket_div / kTicketGroups, 1u);
+  P.ticket_min = b->opt.ticket_min, P.ticket_max = b->opt.ticket_max;
   P.tile_chunk = b->tile_chunk_s[ls].ptr, P.tile_cnt = b->tile_cnt_s[ls].ptr;
   P.tile_cap = static_cast<uint32_t>(cap), P.tile_tiles = static_cast<uint32_t>(tiles), P.tile_log2 = b->mono_s_log2 + 10u - t_log2;
   return HALO_OK;
@@ -1763,7 +1294,7 @@ int queue_passes(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, c
                                                          p.bin_tiles, p.fan_log2, frac_bits, P.ovf, P.ovf_flag, ts, before_sums)
                                   : launch_bin_accumulate(P.mono, bin_list.ptr, P.bin_cap, bin_cnt.ptr, p.bin_tiles, frac_bits, ts);
       if (be != hipSuccess) return hip_fail(b, be, "halo_bin_accumulate_kernel launch");
-      if (b->overlap && p.two_level) HIPCHK(b, b->rmw[ts_i].mark(ts));
+      if (b->opt.overlap && p.two_level) HIPCHK(b, b->rmw[ts_i].mark(ts));
     }
     HIPCHK(b, hipEventRecord(b->ring_ev1[k], ts));
     b->ring_posts[k] = false;
@@ -1782,7 +1313,7 @@ int queue_passes(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, c
     } else if (int rc = wait_for_aux(b, ts_i)) return rc;
   }
   // (nothing between ev1 and here unless the passes wait for a fold: one record serves as both, the spans stay the trace kernel's and the passes')
-  if (b->lean_events && !p.under_fold()) b->ring_t2[k] = b->ring_ev1[k];
+  if (b->opt.lean_events && !p.under_fold()) b->ring_t2[k] = b->ring_ev1[k];
   else {
     HIPCHK(b, hipEventRecord(b->ring_ev2[k], ps));
     b->ring_t2[k] = b->ring_ev2[k];
@@ -1792,7 +1323,7 @@ int queue_passes(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, c
   auto close_marks = [&]() -> hipError_t {
     hipError_t e = hipEventRecord(b->ring_ev3[k], ps);
     if (e != hipSuccess) return e;
-    if (b->lean_events) {
+    if (b->opt.lean_events) {
       (void)b->close_done.mark_at(b->ring_ev3[k]);
       (void)b->set_free[S.ls].mark_at(b->ring_ev3[k]);
       b->ring_fin[k] = b->ring_ev3[k];
@@ -1825,7 +1356,7 @@ int queue_passes(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, c
     }
     HIPCHK(b, close_marks());
     b->close_ts = ts_i;
-    if (b->overlap && p.alternate) b->log_set ^= 1;
+    if (b->opt.overlap && p.alternate) b->log_set ^= 1;
     b->ring_posts[k] = true;
     return HALO_OK;
   }
@@ -1842,7 +1373,7 @@ int queue_passes(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, c
     b->direct_closes++;
     HIPCHK(b, close_marks());
     b->close_ts = ts_i;
-    if (b->overlap && p.alternate) b->log_set ^= 1;
+    if (b->opt.overlap && p.alternate) b->log_set ^= 1;
     b->ring_posts[k] = true;
     return HALO_OK;
   }
@@ -1860,10 +1391,10 @@ int queue_passes(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, c
                                                    bin_cnt2.ptr, 1u << p.log_t_log2, p.log_planes, b->mono_s_log2, b->render.visible == HALO_VISIBLE_FULL, frac_bits,
                                                    P.ovf, P.ovf_flag, P.ovf_copies_log2, ps, before_sums);
   if (be != hipSuccess) return hip_fail(b, be, "halo_split_kernel launch");
-  if (b->overlap && !p.fixed) HIPCHK(b, b->rmw[ts_i].mark(ps));
+  if (b->opt.overlap && !p.fixed) HIPCHK(b, b->rmw[ts_i].mark(ps));
   HIPCHK(b, hipEventRecord(b->ring_ev3[k], ps));
   HIPCHK(b, b->set_free[S.ls].mark(ps));
-  if (b->overlap && p.alternate) b->log_set ^= 1;
+  if (b->opt.overlap && p.alternate) b->log_set ^= 1;
   b->ring_posts[k] = true;
   HIPCHK(b, hipEventRecord(b->ring_done[k], ps));
   b->ring_fin[k] = b->ring_done[k];
@@ -1882,9 +1413,9 @@ int queue_launch(HaloBackend* b, const LaunchPlan& p, const HaloEntry& E, EntryT
     HIPCHK(b, b->close_done.wait_on(ts));
   hipEvent_t before_sums = nullptr;   // rule (1), for the routes whose sums write the planes plainly
 #ifndef HALO_NO_PLANE_GATES   // (defined only to see tests/test_gpu_production_routes.py's two-stream test fail without the gates)
-  if (b->overlap && !p.use_log)   // this trace kernel adds to the planes itself: behind the other stream's sums
+  if (b->opt.overlap && !p.use_log)   // this trace kernel adds to the planes itself: behind the other stream's sums
     HIPCHK(b, b->rmw[ts_i ^ 1].wait_on(ts));
-  if (b->overlap && ((p.use_log && !p.fixed) || (p.use_bin && p.two_level)) && b->cs_pending[ts_i ^ 1]) {
+  if (b->opt.overlap && ((p.use_log && !p.fixed) || (p.use_bin && p.two_level)) && b->cs_pending[ts_i ^ 1]) {
     HIPCHK(b, hipEventRecord(b->ev_gate, b->cs[ts_i ^ 1]));
     before_sums = b->ev_gate;
   }
@@ -1894,10 +1425,10 @@ int queue_launch(HaloBackend* b, const LaunchPlan& p, const HaloEntry& E, EntryT
     // launch that fills the chip on trace stream 1 instead, beside the previous launch's trace kernel and passes (it needs nothing of
     // them, only its pool back from the launch before that one).  Measured (25 M rays per launch): prism pools 4.43 -> 4.55 ms per launch,
     // pyramid pools 7.78 -> 7.70: both kernels are VALU-bound, so sharing the chip conserves the work.  Off by default.
-    const bool ahead = b->overlap && b->gen_ahead && !p.alternate;
+    const bool ahead = b->opt.overlap && b->opt.gen_ahead && !p.alternate;
     hipStream_t gs = ahead ? b->cs[1] : ts;
     HIPCHK(b, b->shapes_free[S.shape_set].wait_on(gs));
-    hipError_t ge = launch_shapegen(const_cast<ShapeDev*>(P.shapes), p.geom == 2, p.shape_cnt, b->seed, host::MakeRecipe(E.crystal), S.first_shape, gs, b->gen_serial != 0);
+    hipError_t ge = launch_shapegen(const_cast<ShapeDev*>(P.shapes), p.geom == 2, p.shape_cnt, b->seed, host::MakeRecipe(E.crystal), S.first_shape, gs, b->opt.gen_serial != 0);
     if (ge != hipSuccess) return hip_fail(b, ge, "halo_shapegen_kernel launch");
     if (ahead) {
       HIPCHK(b, hipEventRecord(b->ev_gen, gs));
@@ -1990,7 +1521,7 @@ int trace_launch(HaloBackend* b, const LayerCtx& c, LaunchPlan& p, EntryTables& 
   } else {
     // Two pools, taken in turn by the launches that may run beside a neighbour: the records of launch k+1 are written while launch k still
     // traces out of the other one.
-    const bool turn = b->overlap && (p.alternate || b->gen_ahead);   // (a launch that fills the chip runs alone on stream 0: pool 0)
+    const bool turn = b->opt.overlap && (p.alternate || b->opt.gen_ahead);   // (a launch that fills the chip runs alone on stream 0: pool 0)
     S.shape_set = turn ? b->shapes_next : 0;
     if (turn) b->shapes_next ^= 1;
     DevBuf<ShapeDev>& shapes = b->shapes_s[S.shape_set];
@@ -2029,7 +1560,7 @@ int trace_launch(HaloBackend* b, const LayerCtx& c, LaunchPlan& p, EntryTables& 
     P.fix_frac = b->fix_frac;
     P.fix_frac_landed = b->fix_frac_landed;
   }
-  S.ls = (b->overlap && p.alternate) ? b->log_set : 0;   // the buffer set of this launch
+  S.ls = (b->opt.overlap && p.alternate) ? b->log_set : 0;   // the buffer set of this launch
   if (int rc = bind_route(b, p, S.ls, P)) return rc;
   p.close = close_direct_ok(*b, p, P);
   if (int rc = bind_tile_append(b, p, T, S.ls, P)) return rc;
@@ -2048,7 +1579,7 @@ int trace_launch(HaloBackend* b, const LayerCtx& c, LaunchPlan& p, EntryTables& 
 // launches start at multiples of the chunk — a sampled entry whose launches do not start on shapes is refused, before anything is queued.
 int trace_shard(HaloBackend* b, LayerCtx& c, std::vector<LaunchPlan>& plans, const std::vector<uint64_t>& per_ci) {
   for (const LaunchPlan& p : plans)
-    if (!p.deterministic && p.off % b->geom_clock != 0u)
+    if (!p.deterministic && p.off % b->opt.geom_clock != 0u)
       return fail(b, HALO_FATAL, "halo_set_shard count > 1: a sampled crystal entry is cut into launches (chunk, stoch_chunk) that are not multiples of geom_clock; a shard cannot start inside a sampled shape");
   // (checked here, before a counter has moved; fix_prepare holds the same line for every launch)
   if (b->det_session && b->landed_own && fix_frac_bits(b->sess_max_w, kFixLandedHits) != b->fix_frac_landed)
@@ -2060,7 +1591,7 @@ int trace_shard(HaloBackend* b, LayerCtx& c, std::vector<LaunchPlan>& plans, con
   c.traced = 0;
   for (const LaunchPlan& whole : plans) {
     uint64_t s0 = 0, sn = 0;
-    shard_slice(per_ci[static_cast<size_t>(whole.ci)], whole.deterministic ? 1u : b->geom_clock, b->shard_index, b->shard_count, &s0, &sn);
+    shard_slice(per_ci[static_cast<size_t>(whole.ci)], whole.deterministic ? 1u : b->opt.geom_clock, b->shard_index, b->shard_count, &s0, &sn);
     const uint64_t lo = std::max(whole.off, s0), hi = std::min(whole.off + whole.m, s0 + sn);
     const uint64_t gen0 = b->gen_count, gate0 = b->gate_count, shape0 = b->shape_count;
     if (lo < hi) {
@@ -2068,7 +1599,7 @@ int trace_shard(HaloBackend* b, LayerCtx& c, std::vector<LaunchPlan>& plans, con
       p.share = whole.share;
       b->gen_count = gen0 + (lo - whole.off);
       b->gate_count = gate0 + (lo - whole.off);
-      if (!whole.deterministic) b->shape_count = shape0 + (lo - whole.off) / b->geom_clock;
+      if (!whole.deterministic) b->shape_count = shape0 + (lo - whole.off) / b->opt.geom_clock;
       if (p.ci != cur) {
         cur = p.ci;
         prepare_entry_tables(b, c, cur, T);
@@ -2128,7 +1659,7 @@ int close_layer(HaloBackend* b, const LayerCtx& c, bool defer, HaloLayerStats* s
     for (int sI = 0; sI < kContShards; sI++) {
       const uint32_t cs = fill[static_cast<size_t>(sI) * kContCntStride];
       // (canonical order included: a pool that lost records would be handed on with holes in its order — never, the session fails)
-      if (cs > c.out_cap) return fail(b, HALO_FATAL, b->cont_order ? "continuation pool overflow (cont_order = 1: the canonical pool would be incomplete)" : "continuation pool overflow");
+      if (cs > c.out_cap) return fail(b, HALO_FATAL, b->opt.cont_order ? "continuation pool overflow (cont_order = 1: the canonical pool would be incomplete)" : "continuation pool overflow");
       b->cont_seg[sI] = static_cast<uint32_t>(n_cont);
       n_cont += cs;
       b->cont_fill_max = std::max(b->cont_fill_max, cs);
@@ -2173,7 +1704,7 @@ int halo_trace_layer(halo_handle_t b, uint64_t count, const HaloHostRays* rays, 
   c.host_crystal = rays != nullptr && rays->crystal != nullptr && layer == 0;
   c.out_slot = b->cont_out_slot;
   // canonical order over several layers: every layer ends with the error-word check (the appends of this layer, the reorder in front of it)
-  c.canon_check = b->cont_order && b->scene.layer_count > 1;
+  c.canon_check = b->opt.cont_order && b->scene.layer_count > 1;
   float props[HALO_MAX_ENTRIES];
   for (int ci = 0; ci < L.entry_count; ci++) props[ci] = L.entries[ci].proportion;
   std::vector<uint64_t> per_ci = host::Partition(props, L.entry_count, n, b->carry[layer]);
@@ -2199,16 +1730,16 @@ int halo_trace_layer(halo_handle_t b, uint64_t count, const HaloHostRays* rays, 
     const uint64_t stride = region * kContShards;
     if (stride > 0xFFFFFFF0ull) return fail(b, HALO_FATAL, "continuation pool would exceed 2^32 rays; split the batch");
     // + mask lo/hi planes with raypath colour; canonical order: + root and interaction planes (kContPlaneRoot, kContPlaneBit)
-    const uint64_t planes = b->cont_order ? kContPlanesCanonical : (b->color_classes.empty() ? 5 : 7);
-    if (b->cont_order && stride * planes > 0xFFFFFFFFull) return fail(b, HALO_FATAL, "canonical continuation pool planes would exceed 2^32 floats; split the batch");
+    const uint64_t planes = b->opt.cont_order ? kContPlanesCanonical : (b->color_classes.empty() ? 5 : 7);
+    if (b->opt.cont_order && stride * planes > 0xFFFFFFFFull) return fail(b, HALO_FATAL, "canonical continuation pool planes would exceed 2^32 floats; split the batch");
     if (int rc = reserve_idle(b, b->cont[c.out_slot], stride * planes)) return rc;
     b->cont_stride[c.out_slot] = static_cast<uint32_t>(stride);
     b->cont_region[c.out_slot] = static_cast<uint32_t>(region);
     c.out_cap = static_cast<uint32_t>(region);
     HIPCHK(b, b->cont_cnt.reserve(kContShards * kContCntStride));
     HIPCHK(b, hipMemsetAsync(b->cont_cnt.ptr, 0, kContShards * kContCntStride * sizeof(uint32_t), main_q(b)));
-    if (b->cont_order) {   // the roots' masks start empty: queued on the stream, behind the scatter that read the previous layer's
-      if (b->rehit_strategy == 0) return fail(b, HALO_FATAL, "cont_order = 1 needs rehit_strategy = 1 (the legacy strategy can emit twice at one interaction)");
+    if (b->opt.cont_order) {   // the roots' masks start empty: queued on the stream, behind the scatter that read the previous layer's
+      if (b->opt.rehit_strategy == 0) return fail(b, HALO_FATAL, "cont_order = 1 needs rehit_strategy = 1 (the legacy strategy can emit twice at one interaction)");
       if (int rc = reserve_idle(b, b->cont_mask, kContMaskWords * std::max<uint64_t>(c.n, 1))) return rc;
       HIPCHK(b, hipMemsetAsync(b->cont_mask.ptr, 0, kContMaskWords * c.n * sizeof(uint32_t), main_q(b)));
       if (c.layer == 0) {   // a session starts with a clean error word (a session that set one was refused)
@@ -2217,14 +1748,14 @@ int halo_trace_layer(halo_handle_t b, uint64_t count, const HaloHostRays* rays, 
       }
     }
   }
-  const bool defer = b->async && c.final_layer && !b->capture && !c.canon_check;  // nothing the caller needs before the next call
+  const bool defer = b->opt.async && c.final_layer && !b->opt.capture && !c.canon_check;  // nothing the caller needs before the next call
   if (!defer) {  // earlier queued dispatches go to `pending`, so layer_acc ends up holding this layer alone
     harvest_all(b);
     if (int rc = pull_tally(b)) return rc;   // (a copy + sync only when something was queued and never collected)
     add_stats(b->pending, b->layer_acc);
     b->layer_acc = HaloLayerStats{};
   }
-  if (b->capture) {
+  if (b->opt.capture) {
     const uint64_t need = b->exits_pending + n * static_cast<uint64_t>(b->scene.max_hits + 1);
     if (need > b->exits.cap) {
       DevBuf<HaloExitRecord> bigger;
@@ -2232,8 +1763,7 @@ int halo_trace_layer(halo_handle_t b, uint64_t count, const HaloHostRays* rays, 
       if (b->exits_pending)
         HIPCHK(b, hipMemcpyAsync(bigger.ptr, b->exits.ptr, b->exits_pending * sizeof(HaloExitRecord), hipMemcpyDeviceToDevice, main_q(b)));
       if (int rc = sync_all(b)) return rc;
-      b->exits.release();
-      b->exits = bigger;
+      b->exits.swap(bigger);   // (the old buffer goes with `bigger`)
     }
   }
   if (rays && layer == 0) {   // host rays bring their own weights (and hand them on to the layers behind)
@@ -2278,7 +1808,7 @@ int halo_generate_shapes(halo_handle_t b, const HaloCrystal* crystal, uint64_t f
     DevBuf<ShapePrism> dev;
     HIPCHK(b, dev.reserve(n));
     std::vector<ShapePrism> recs(n);
-    hipError_t ge = launch_shapegen(dev.ptr, true, n, b->seed, host::MakeRecipe(*crystal), first_index, b->stream, b->gen_serial != 0);
+    hipError_t ge = launch_shapegen(dev.ptr, true, n, b->seed, host::MakeRecipe(*crystal), first_index, b->stream, b->opt.gen_serial != 0);
     if (ge == hipSuccess) ge = hipMemcpyAsync(recs.data(), dev.ptr, static_cast<size_t>(n) * sizeof(ShapePrism), hipMemcpyDeviceToHost, main_q(b));
     if (ge == hipSuccess) ge = hipStreamSynchronize(main_q(b));
     dev.release();
@@ -2300,7 +1830,7 @@ int halo_generate_shapes(halo_handle_t b, const HaloCrystal* crystal, uint64_t f
     HIPCHK(b, hipSetDevice(b->device));
     DevBuf<ShapeDev> dev;
     HIPCHK(b, dev.reserve(n));
-    hipError_t ge = launch_shapegen(dev.ptr, false, n, b->seed, host::MakeRecipe(*crystal), first_index, b->stream, b->gen_serial != 0);
+    hipError_t ge = launch_shapegen(dev.ptr, false, n, b->seed, host::MakeRecipe(*crystal), first_index, b->stream, b->opt.gen_serial != 0);
     if (ge == hipSuccess) ge = hipMemcpyAsync(pool.data(), dev.ptr, static_cast<size_t>(n) * sizeof(ShapeDev), hipMemcpyDeviceToHost, main_q(b));
     if (ge == hipSuccess) ge = hipStreamSynchronize(main_q(b));
     dev.release();
@@ -2328,23 +1858,6 @@ int halo_set_color(halo_handle_t b, const HaloColorSet* sets, int n_sets, const 
   b->color_sets.assign(sets, sets + n_sets);
   b->color_classes.assign(classes, classes + n_classes);
   drop_table_cache(b);
-  return HALO_OK;
-}
-
-int halo_readback_class_lanes(halo_handle_t b, float* lanes, int width, int height, int class_count) {
-  if (!b || !lanes) return HALO_FATAL;
-  if (class_count != static_cast<int>(b->color_classes.size()) || width != b->lanes_w || height != b->lanes_h || !b->lanes.ptr)
-    return fail(b, HALO_FATAL, "class lanes: size does not match the session (classes x width x height)");
-  HIPCHK(b, hipSetDevice(b->device));
-  if (int rc = join_aux(b)) return rc;   // (kernels of queued sessions may still be running on the trace / auxiliary streams)
-  const size_t n = static_cast<size_t>(class_count) * width * height;
-  // the lanes are summed in fp64 on the device (hot pixels), the seam hands out floats (trace_backend.hpp:471-493): narrowed and drained by
-  // one kernel into the staging buffer, so half the bytes cross the bus and no host pass follows
-  HIPCHK(b, b->lanes_stage.reserve(n));
-  hipError_t e = launch_lanes_drain(b->lanes.ptr, b->lanes_stage.ptr, n, b->cu_count * 8, main_q(b));
-  if (e != hipSuccess) return hip_fail(b, e, "halo_lanes_drain_kernel launch");
-  HIPCHK(b, hipMemcpyAsync(lanes, b->lanes_stage.ptr, n * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
-  HIPCHK(b, hipStreamSynchronize(main_q(b)));
   return HALO_OK;
 }
 
@@ -2378,17 +1891,6 @@ int halo_tile_tickets(halo_handle_t b, uint64_t* out) {
   *out = b->tile_tickets;
   return HALO_OK;
 }
-
-// The ticket rule the ticketed kernels apply (halo_device.h TicketSize), for tests/test_ticket_size.py: no device needed.
-uint32_t halo_host_ticket_size(uint32_t total, uint32_t seen, uint32_t waves, uint32_t lo, uint32_t hi) { return TicketSize(total, seen, waves, lo, hi); }
-// ... and the ranges of a launch's passes with a counter each, and the range a wave turns to (TicketRangeOf, TicketNextRange)
-uint32_t halo_host_ticket_groups(void) { return kTicketGroups; }
-void halo_host_ticket_range(uint32_t all, uint32_t g, uint32_t* first, uint32_t* n) {
-  const TicketRange r = TicketRangeOf(all, g);
-  if (first) *first = r.first;
-  if (n) *n = r.n;
-}
-uint32_t halo_host_ticket_next(uint64_t open, uint32_t home) { return open ? TicketNextRange(open, home) : kTicketGroups; }
 
 int halo_last_root_profile(halo_handle_t b, uint32_t* out) {
   if (!b || !out) return HALO_FATAL;
@@ -2453,7 +1955,7 @@ int halo_recombine(halo_handle_t b, int shuffle, uint64_t* continuation_count) {
   if (!b->in_session) return fail(b, HALO_FATAL, "Recombine outside a session");
   // No data moves: the pools swap roles and the Feistel permutation (shuffle_cont_kernel, cu:1633-1657) is
   // applied as a gather index by the next layer's kernel.
-  if (b->cont_order) {
+  if (b->opt.cont_order) {
     // Canonical order: the sharded pool is sorted by (root, interaction) into the pool the layer just traced has read (free now: its kernels were
     // joined and waited for at the end of TraceLayer), as ONE region; the next layer appends to the sharded pool again.  Queued on the session's
     // stream behind every launch of the layer, no host wait; the next layer's mask clear and counter reset queue behind it.
@@ -2535,7 +2037,7 @@ int halo_sync(halo_handle_t b) {
   if (!b) return HALO_FATAL;
   HIPCHK(b, hipSetDevice(b->device));
   // with option defer_fold a caller-bound accumulator is brought up to date HERE (and by every reader): the closing folds of the ended sessions
-  if (b->defer_fold && !b->in_session)
+  if (b->opt.defer_fold && !b->in_session)
     if (int rc = fold_if_dirty(b)) return rc;
   return sync_all(b);
 }
@@ -2580,15 +2082,9 @@ int halo_set_shard(halo_handle_t b, uint32_t index, uint32_t count) {
   if (!b) return HALO_FATAL;
   if (b->in_session) return fail(b, HALO_FATAL, "halo_set_shard inside a session");
   if (count == 0u || index >= count) return fail(b, HALO_FATAL, "halo_set_shard: index " + std::to_string(index) + " outside count " + std::to_string(count) + " (needs count >= 1 and index < count)");
-  if (count > 1u && b->rank_opt != 0) return fail(b, HALO_FATAL, "halo_set_shard count > 1: option rank is set (shards trace the one-rank run's rays: they share its counter range)");
+  if (count > 1u && b->opt.rank != 0) return fail(b, HALO_FATAL, "halo_set_shard count > 1: option rank is set (shards trace the one-rank run's rays: they share its counter range)");
   b->shard_index = index;
   b->shard_count = count;
-  return HALO_OK;
-}
-
-int halo_host_shard_slice(uint64_t share, uint32_t clock, uint32_t index, uint32_t count, uint64_t* first, uint64_t* n) {
-  if (!first || !n || clock == 0u || count == 0u || index >= count) return HALO_FATAL;
-  shard_slice(share, clock, index, count, first, n);
   return HALO_OK;
 }
 
@@ -2686,530 +2182,5 @@ int halo_readback_xyz(halo_handle_t b, float* xyz, int width, int height, float*
   return rc;
 }
 
-// ---- consumer on device ------------------------------------------------------------------------------------
-int halo_consumer_reset(halo_handle_t b) {
-  if (!b) return HALO_FATAL;
-  HIPCHK(b, hipSetDevice(b->device));
-  if (int rc = join_aux(b)) return rc;   // (kernels of queued sessions may still be running on the trace / auxiliary streams)
-  if (b->cons_sum.ptr) {
-    const size_t n = static_cast<size_t>(b->cons_w) * b->cons_h * 3;
-    HIPCHK(b, hipMemsetAsync(b->cons_sum.ptr, 0, n * sizeof(float), main_q(b)));
-    HIPCHK(b, hipMemsetAsync(b->cons_comp.ptr, 0, n * sizeof(float), main_q(b)));
-  }
-  if (b->lanes.ptr) HIPCHK(b, hipMemsetAsync(b->lanes.ptr, 0, b->lanes.cap * sizeof(double), main_q(b)));   // RenderConsumer::Reset clears the class lanes too (render.cpp:598-612)
-  b->total_intensity = 0.0;
-  return HALO_OK;
-}
-
-int halo_consumer_fold(halo_handle_t b) {
-  if (!b) return HALO_FATAL;
-  if (!b->acc || b->acc_w <= 0) return fail(b, HALO_FATAL, "consumer_fold before any session");
-  HIPCHK(b, hipSetDevice(b->device));
-  int rc = fold_if_dirty(b);
-  if (rc != HALO_OK) return rc;
-  const size_t n = static_cast<size_t>(b->acc_w) * b->acc_h * 3;
-  if (b->cons_w != b->acc_w || b->cons_h != b->acc_h || !b->cons_sum.ptr) {
-    HIPCHK(b, b->cons_sum.reserve(n));
-    HIPCHK(b, b->cons_comp.reserve(n));
-    b->cons_w = b->acc_w;
-    b->cons_h = b->acc_h;
-    HIPCHK(b, hipMemsetAsync(b->cons_sum.ptr, 0, n * sizeof(float), main_q(b)));
-    HIPCHK(b, hipMemsetAsync(b->cons_comp.ptr, 0, n * sizeof(float), main_q(b)));
-    b->total_intensity = 0.0;
-  }
-  hipError_t e = launch_consumer_fold(b->acc, b->cons_sum.ptr, b->cons_comp.ptr, static_cast<uint32_t>(n), b->cu_count * 8, main_q(b));
-  if (e != hipSuccess) return hip_fail(b, e, "halo_consumer_fold_kernel launch");
-  double landed = 0.0;
-  if (int rc = take_landed_delta(b, &landed)) return rc;
-  b->total_intensity += landed;  // total_intensity_ += xyz_landed_weight_ (render.cpp:149)
-  return HALO_OK;
-}
-
-int halo_consumer_consume(halo_handle_t b, const float* xyz, int width, int height, float landed, const float* lanes, int class_count) {
-  if (!b || !xyz) return HALO_FATAL;
-  if (b->in_session) return fail(b, HALO_FATAL, "consumer_consume inside a session");
-  if (width <= 0 || height <= 0) return fail(b, HALO_FATAL, "consumer_consume: empty image");
-  if (static_cast<uint64_t>(width) * static_cast<uint64_t>(height) > (1ull << 25)) return fail(b, HALO_UNAVAILABLE, "more than 2^25 pixels");
-  if (b->cons_sum.ptr && (b->cons_w != width || b->cons_h != height)) return fail(b, HALO_FATAL, "consumer_consume: image size differs from the consumer's (halo_consumer_reset first)");
-  HIPCHK(b, hipSetDevice(b->device));
-  if (int rc = join_aux(b)) return rc;   // (kernels of queued sessions may still be running on the trace / auxiliary streams)
-  const size_t n = static_cast<size_t>(width) * height * 3;
-  if (!b->cons_sum.ptr) {
-    HIPCHK(b, b->cons_sum.reserve(n));
-    HIPCHK(b, b->cons_comp.reserve(n));
-    b->cons_w = width;
-    b->cons_h = height;
-    HIPCHK(b, hipMemsetAsync(b->cons_sum.ptr, 0, n * sizeof(float), main_q(b)));
-    HIPCHK(b, hipMemsetAsync(b->cons_comp.ptr, 0, n * sizeof(float), main_q(b)));
-    b->total_intensity = 0.0;
-  }
-  // the caller's image goes through the staging buffer and the same Neumaier fold kernel the device accumulator takes (the kernel zeroes
-  // what it folds: the staging buffer here)
-  HIPCHK(b, b->cons_stage.reserve(n));
-  HIPCHK(b, hipMemcpyAsync(b->cons_stage.ptr, xyz, n * sizeof(float), hipMemcpyHostToDevice, main_q(b)));
-  hipError_t e = launch_consumer_fold(b->cons_stage.ptr, b->cons_sum.ptr, b->cons_comp.ptr, static_cast<uint32_t>(n), b->cu_count * 8, main_q(b));
-  if (e != hipSuccess) return hip_fail(b, e, "halo_consumer_fold_kernel launch");
-  if (lanes != nullptr && class_count > 0) {   // lane_pixel_data_: dst[p] += src[p] per class (render.cpp:176-185)
-    if (class_count != static_cast<int>(b->color_classes.size())) return fail(b, HALO_FATAL, "consumer_consume: class count must equal halo_set_color's");
-    const size_t nl = static_cast<size_t>(class_count) * width * height;
-    if (!b->lanes.ptr || b->lanes_w != width || b->lanes_h != height) {
-      HIPCHK(b, b->lanes.reserve(nl));
-      HIPCHK(b, hipMemsetAsync(b->lanes.ptr, 0, b->lanes.cap * sizeof(double), main_q(b)));
-      b->lanes_w = width;
-      b->lanes_h = height;
-    }
-    HIPCHK(b, b->lanes_stage.reserve(nl));
-    HIPCHK(b, hipMemcpyAsync(b->lanes_stage.ptr, lanes, nl * sizeof(float), hipMemcpyHostToDevice, main_q(b)));
-    e = launch_lanes_add(b->lanes_stage.ptr, b->lanes.ptr, nl, b->cu_count * 8, main_q(b));
-    if (e != hipSuccess) return hip_fail(b, e, "halo_lanes_add_kernel launch");
-  }
-  HIPCHK(b, hipStreamSynchronize(main_q(b)));   // `xyz` / `lanes` are the caller's (pageable) memory
-  b->total_intensity += static_cast<double>(landed);   // total_intensity_ += xyz_landed_weight_ (render.cpp:149)
-  return HALO_OK;
-}
-
-int halo_consumer_snapshot(halo_handle_t b, const HaloDisplay* dsp, uint8_t* rgb_out, float* xyz_out, double* total_intensity) {
-  if (!b || !dsp) return HALO_FATAL;
-  if (!b->cons_sum.ptr) return fail(b, HALO_FATAL, "consumer_snapshot before consumer_fold");
-  HIPCHK(b, hipSetDevice(b->device));
-  const uint32_t npix = static_cast<uint32_t>(b->cons_w) * static_cast<uint32_t>(b->cons_h);
-  const size_t n = static_cast<size_t>(npix) * 3;
-  // ExposureScale (render.cpp:96-102), evaluated in float like the reference
-  const float snapshot_intensity = static_cast<float>(b->total_intensity);
-  const float scale = (npix == 0 || snapshot_intensity <= 0.0f) ? 0.0f : dsp->intensity_factor * 0.08f * static_cast<float>(npix) / snapshot_intensity;
-  if (rgb_out) HIPCHK(b, b->cons_rgb.reserve(n));
-  if (xyz_out) HIPCHK(b, b->cons_xyz_out.reserve(n));
-  hipError_t e = launch_post_snapshot(b->cons_sum.ptr, b->cons_comp.ptr, rgb_out ? b->cons_rgb.ptr : nullptr,
-                                      xyz_out ? b->cons_xyz_out.ptr : nullptr, npix, scale, dsp->ray_color, dsp->background,
-                                      b->cu_count * 8, main_q(b));
-  if (e != hipSuccess) return hip_fail(b, e, "halo_post_snapshot_kernel launch");
-  if (rgb_out) HIPCHK(b, hipMemcpyAsync(rgb_out, b->cons_rgb.ptr, n, hipMemcpyDeviceToHost, main_q(b)));
-  if (xyz_out) HIPCHK(b, hipMemcpyAsync(xyz_out, b->cons_xyz_out.ptr, n * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
-  HIPCHK(b, hipStreamSynchronize(main_q(b)));
-  if (rgb_out && scale == 0.0f) std::memset(rgb_out, 0, n);  // PostSnapshot early-out (render.cpp:515-518)
-  if (total_intensity) *total_intensity = b->total_intensity;
-  return HALO_OK;
-}
-
-// ---- auto exposure (gui/gui_ev_auto.hpp) ---------------------------------------------------------------------
-float halo_host_ev_auto(float p99_y, float per_pixel_intensity, float target_white) {   // ComputeEvAuto, gui_ev_auto.hpp:143-155
-  if (per_pixel_intensity <= 0.0f || p99_y <= 0.0f) return 0.0f;
-  const float p99_norm = p99_y / per_pixel_intensity;
-  const float t = target_white / 255.0f;
-  const float target_linear = t <= 0.04045f ? t / 12.92f : std::pow((t + 0.055f) / 1.055f, 2.4f);
-  if (target_linear <= 0.0f || p99_norm <= 0.0f) return 0.0f;
-  const float ev = std::log2f(target_linear / p99_norm);
-  return std::min(std::max(ev, -6.0f), 6.0f);
-}
-
-int halo_consumer_auto_ev(halo_handle_t b, int32_t downsample_factor, float target_white, HaloAutoEv* out) {
-  if (!b) return HALO_FATAL;
-  if (!out) return fail(b, HALO_FATAL, "consumer_auto_ev: out is NULL");
-  if (!b->cons_sum.ptr) return fail(b, HALO_FATAL, "consumer_auto_ev before consumer_fold");
-  if (!(target_white > 0.0f && target_white <= 255.0f)) return fail(b, HALO_FATAL, "consumer_auto_ev: target_white must lie in (0, 255]");
-  HIPCHK(b, hipSetDevice(b->device));
-  const uint32_t w = static_cast<uint32_t>(b->cons_w), h = static_cast<uint32_t>(b->cons_h), npix = w * h;
-  // ComputeP99Y's fallback order (:80-86): the coarse path only for f > 1 and a grid that does not collapse
-  const uint32_t f = downsample_factor > 1 ? static_cast<uint32_t>(downsample_factor) : 1u;
-  const bool coarse = f > 1u && w / f > 0u && h / f > 0u;
-  const uint32_t wc = coarse ? w / f : 0u, hc = coarse ? h / f : 0u;
-  const uint32_t n_vals = coarse ? wc * hc : npix;
-  HIPCHK(b, b->aev_vals.reserve(n_vals));
-  constexpr size_t kRecWords = sizeof(AevRecord) / sizeof(uint32_t);
-  HIPCHK(b, b->aev_ws.reserve(kRecWords + kAevHistWords));
-  AevRecord* rec_dev = reinterpret_cast<AevRecord*>(b->aev_ws.ptr);
-  hipError_t e = launch_aev_values(b->cons_sum.ptr, b->cons_comp.ptr, w, h, f, wc, hc, b->aev_vals.ptr, b->cu_count * 8, main_q(b));
-  if (e != hipSuccess) return hip_fail(b, e, "halo_aev value kernel launch");
-  const bool one_wg = b->aev_select < 0 ? n_vals <= kAevSmallMax : b->aev_select == 1;
-  e = launch_aev_select(b->aev_vals.ptr, n_vals, rec_dev, b->aev_ws.ptr + kRecWords, one_wg, b->aev_agg_hist != 0, b->cu_count, main_q(b));
-  if (e != hipSuccess) return hip_fail(b, e, "halo_aev select kernel launch");
-  AevRecord rec{};
-  HIPCHK(b, hipMemcpyAsync(&rec, rec_dev, sizeof(rec), hipMemcpyDeviceToHost, main_q(b)));
-  HIPCHK(b, hipStreamSynchronize(main_q(b)));
-  float p99 = 0.0f;
-  if (rec.count) std::memcpy(&p99, &rec.p99_bits, sizeof(float));
-  if (coarse) p99 = p99 / (static_cast<float>(f) * static_cast<float>(f));   // the fine-equivalent P99 (:112-113)
-  // GetRawXyzResult (render.cpp:586-587), in float like the reference
-  const float snapshot_intensity = static_cast<float>(b->total_intensity);
-  const int total_pix = b->cons_w * b->cons_h;
-  const float per_pixel = total_pix > 0 ? snapshot_intensity / (0.08f * total_pix) : 0.0f;
-  out->p99_y = p99;
-  out->per_pixel_intensity = per_pixel;
-  out->ev_auto = halo_host_ev_auto(p99, per_pixel, target_white);
-  out->produced = (p99 > 0.0f && per_pixel > 0.0f) ? 1 : 0;
-  out->value_count = rec.count;
-  out->coarse_w = static_cast<int32_t>(wc);
-  out->coarse_h = static_cast<int32_t>(hc);
-  return HALO_OK;
-}
-
-// ---- image statistics (halo_stats.hip) --------------------------------------------------------------------------
-int halo_host_percentile_rank(double percentile, uint64_t n, uint64_t* rank, double* frac) {
-  return host::PercentileRank(percentile, n, rank, frac) ? HALO_OK : HALO_FATAL;
-}
-int halo_host_binned_sum(const uint64_t* bins, int32_t squares, double* out) {
-  if (!bins || !out) return HALO_FATAL;
-  *out = host::BinnedSum(bins, squares != 0);
-  return HALO_OK;
-}
-
-int halo_consumer_stats(halo_handle_t b, const HaloStatsSpec* spec, HaloImageStats* out) {
-  if (!b) return HALO_FATAL;
-  if (!spec || !out) return fail(b, HALO_FATAL, "consumer_stats: spec or out is NULL");
-  if (spec->percentile_count < 0 || spec->percentile_count > HALO_STATS_MAX_PERCENTILES)
-    return fail(b, HALO_FATAL, "consumer_stats: percentile_count must lie in 0 .. 16");
-  StatsAsk ask{};
-  ask.count = static_cast<uint32_t>(spec->percentile_count);
-  for (uint32_t j = 0; j < ask.count; j++) {
-    if (!(spec->percentiles[j] >= 0.0 && spec->percentiles[j] <= 100.0)) return fail(b, HALO_FATAL, "consumer_stats: a percentile lies outside [0, 100]");
-    ask.q[j] = spec->percentiles[j] / 100.0;
-  }
-  const bool lane = spec->plane >= 0;
-  int w = b->cons_w, h = b->cons_h;
-  if (lane) {
-    if (spec->plane >= static_cast<int>(b->color_classes.size()) || !b->lanes.ptr || b->lanes_w <= 0 || b->lanes_h <= 0)
-      return fail(b, HALO_FATAL, "consumer_stats: no such class lane (halo_set_color's class count; lanes exist after a colour session or halo_consumer_load_lanes)");
-    w = b->lanes_w;
-    h = b->lanes_h;
-  } else if (spec->plane != HALO_STATS_PLANE_Y) {
-    return fail(b, HALO_FATAL, "consumer_stats: plane must be HALO_STATS_PLANE_Y or a lane index");
-  } else if (!b->cons_sum.ptr) {
-    return fail(b, HALO_FATAL, "consumer_stats before consumer_fold");
-  }
-  HIPCHK(b, hipSetDevice(b->device));
-  if (lane)
-    if (int rc = join_aux(b)) return rc;   // (kernels of queued sessions may still be adding to the lanes on the trace / auxiliary streams)
-  const uint32_t npix = static_cast<uint32_t>(w) * static_cast<uint32_t>(h);
-  // GetRawXyzResult (render.cpp:586-587), in float like the reference: the same expression as halo_consumer_auto_ev's
-  const float per_pixel = npix > 0u ? static_cast<float>(b->total_intensity) / (0.08f * static_cast<int>(npix)) : 0.0f;
-  const float norm = spec->norm > 0.0f ? spec->norm : per_pixel;
-  std::memset(out, 0, sizeof(*out));
-  out->pixel_count = npix;
-  out->norm = norm;
-  out->percentile_count = spec->percentile_count;
-  if (!(norm > 0.0f)) return HALO_OK;   // no landed intensity to normalise by: nothing produced
-  HIPCHK(b, b->aev_vals.reserve(npix));
-  HIPCHK(b, b->stats_ws.reserve(kStatsWsWords));
-  const bool one_wg = b->stats_select < 0 ? npix <= kStatsSmallMax : b->stats_select == 1;
-  const double* lane_ptr = lane ? b->lanes.ptr + static_cast<size_t>(spec->plane) * npix : nullptr;
-  hipError_t e = launch_stats(b->cons_sum.ptr, b->cons_comp.ptr, lane_ptr, npix, norm, ask, b->aev_vals.ptr, b->stats_ws.ptr, one_wg, b->cu_count, main_q(b));
-  if (e != hipSuccess) return hip_fail(b, e, "halo_stats kernel launch");
-  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the record's bins are 64-bit words");
-  auto rec = std::make_unique<StatsRecord>();
-  HIPCHK(b, hipMemcpyAsync(rec.get(), b->stats_ws.ptr, sizeof(StatsRecord), hipMemcpyDeviceToHost, main_q(b)));
-  HIPCHK(b, hipStreamSynchronize(main_q(b)));
-  if (rec->sel.n == 0u) return HALO_OK;
-  out->positive_count = rec->sel.n;
-  out->saturated_count = rec->sat;
-  const uint64_t* bins = reinterpret_cast<const uint64_t*>(rec->bins);
-  out->sum = host::BinnedSum(bins, false);
-  out->sum_sq = host::BinnedSum(bins + kStatsExpBins, true);
-  std::memcpy(&out->max, &rec->max_bits, sizeof(float));
-  out->produced = 1;
-  for (uint32_t j = 0; j < ask.count; j++) {
-    out->rank[j] = rec->rank[j];
-    out->frac[j] = rec->frac[j];
-    std::memcpy(&out->lo[j], &rec->lo_bits[j], sizeof(float));
-    std::memcpy(&out->hi[j], &rec->hi_bits[j], sizeof(float));
-    const double lo = out->lo[j], hi = out->hi[j];
-    out->value[j] = lo + (hi - lo) * out->frac[j];   // (three roundings: this file is built without contraction)
-  }
-  return HALO_OK;
-}
-
-// ---- the view stage (halo_view.hip): the consumer's image through another lens -------------------------------
-int halo_host_view_direction(const HaloRender* view, int32_t px, int32_t py, float dir[3]) {
-  if (!view || !dir) return 0;
-  return host::ViewDirection(*view, px, py, dir) ? 1 : 0;
-}
-
-int halo_consumer_view(halo_handle_t b, const HaloViewSpec* spec, uint8_t* rgb_out, float* xyz_out, int32_t* map_out, float* dir_out) {
-  if (!b) return HALO_FATAL;
-  if (!spec) return fail(b, HALO_FATAL, "consumer_view: spec is NULL");
-  if (!b->cons_sum.ptr) return fail(b, HALO_FATAL, "consumer_view before consumer_fold");
-  if (b->in_session) return fail(b, HALO_FATAL, "consumer_view inside a session");
-  if (!rgb_out && !xyz_out && !map_out && !dir_out) return fail(b, HALO_FATAL, "consumer_view: every output is NULL");
-  const HaloRender& view = spec->view;
-  if (view.width <= 0 || view.height <= 0) return fail(b, HALO_FATAL, "consumer_view: empty view");
-  if (static_cast<uint64_t>(view.width) * static_cast<uint64_t>(view.height) > (1ull << 25))
-    return fail(b, HALO_UNAVAILABLE, "consumer_view: a view of more than 2^25 pixels");
-  if (!spec->has_source && !b->had_session) return fail(b, HALO_FATAL, "consumer_view: no source render (has_source = 0 on a handle that has had no session)");
-  const HaloRender& source = spec->has_source ? spec->source : b->render;
-  if (source.width != b->cons_w || source.height != b->cons_h) return fail(b, HALO_FATAL, "consumer_view: the source render's size is not the consumer's");
-  if (view.lens_type < HALO_LENS_LINEAR || view.lens_type > HALO_LENS_GLOBE || source.lens_type < HALO_LENS_LINEAR || source.lens_type > HALO_LENS_GLOBE)
-    return fail(b, HALO_FATAL, "consumer_view: unknown lens type");
-  HIPCHK(b, hipSetDevice(b->device));
-  const uint32_t cons_pix = static_cast<uint32_t>(b->cons_w) * static_cast<uint32_t>(b->cons_h);
-  const size_t npix = static_cast<size_t>(view.width) * static_cast<size_t>(view.height), n = npix * 3;
-  // ExposureScale (render.cpp:96-102) over the CONSUMER's pixels: the expression of halo_consumer_snapshot, so a view pixel is its source pixel's byte
-  const float snapshot_intensity = static_cast<float>(b->total_intensity);
-  const float scale = (cons_pix == 0 || snapshot_intensity <= 0.0f) ? 0.0f : spec->display.intensity_factor * 0.08f * static_cast<float>(cons_pix) / snapshot_intensity;
-  if (rgb_out) HIPCHK(b, b->view_rgb.reserve(n));
-  if (xyz_out) HIPCHK(b, b->view_xyz.reserve(n));
-  if (dir_out) HIPCHK(b, b->view_dir.reserve(n));
-  if (map_out) HIPCHK(b, b->view_map.reserve(npix));
-  hipError_t e = launch_view(b->cons_sum.ptr, b->cons_comp.ptr, host::BuildProj(view), host::BuildProj(source), scale, spec->display.ray_color, spec->display.background,
-                             rgb_out ? b->view_rgb.ptr : nullptr, xyz_out ? b->view_xyz.ptr : nullptr, map_out ? b->view_map.ptr : nullptr,
-                             dir_out ? b->view_dir.ptr : nullptr, b->cu_count * 8, main_q(b));
-  if (e != hipSuccess) return hip_fail(b, e, "halo_view_kernel launch");
-  if (rgb_out) HIPCHK(b, hipMemcpyAsync(rgb_out, b->view_rgb.ptr, n, hipMemcpyDeviceToHost, main_q(b)));
-  if (xyz_out) HIPCHK(b, hipMemcpyAsync(xyz_out, b->view_xyz.ptr, n * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
-  if (map_out) HIPCHK(b, hipMemcpyAsync(map_out, b->view_map.ptr, npix * sizeof(int32_t), hipMemcpyDeviceToHost, main_q(b)));
-  if (dir_out) HIPCHK(b, hipMemcpyAsync(dir_out, b->view_dir.ptr, n * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
-  HIPCHK(b, hipStreamSynchronize(main_q(b)));
-  if (rgb_out && scale == 0.0f) std::memset(rgb_out, 0, n);   // PostSnapshot's early-out, as halo_consumer_snapshot has it
-  return HALO_OK;
-}
-
-// ---- display-side composite of the class lanes (server/component_compositor.cpp) -------------------------
-int halo_host_parse_composite_mode(const char* mode) {   // ParseCompositeMode, component_compositor.cpp:118-134
-  if (mode && std::strcmp(mode, "dominant") == 0) return HALO_COMPOSITE_DOMINANT;
-  if (mode && std::strcmp(mode, "additive") == 0) return HALO_COMPOSITE_ADDITIVE;
-  return HALO_COMPOSITE_PAINTER;
-}
-
-int halo_consumer_load_lanes(halo_handle_t b, const float* lanes, int width, int height, int class_count, double total_intensity) {
-  if (!b || !lanes) return HALO_FATAL;
-  if (b->in_session) return fail(b, HALO_FATAL, "consumer_load_lanes inside a session");
-  if (width <= 0 || height <= 0 || class_count <= 0 || class_count != static_cast<int>(b->color_classes.size()))
-    return fail(b, HALO_FATAL, "consumer_load_lanes: class count must equal halo_set_color's, image must not be empty");
-  if (static_cast<uint64_t>(width) * static_cast<uint64_t>(height) > (1ull << 25)) return fail(b, HALO_UNAVAILABLE, "more than 2^25 pixels");
-  HIPCHK(b, hipSetDevice(b->device));
-  if (int rc = join_aux(b)) return rc;   // (kernels of queued sessions may still be running on the trace / auxiliary streams)
-  const size_t n = static_cast<size_t>(class_count) * width * height;
-  HIPCHK(b, b->lanes.reserve(n));
-  b->lanes_w = width;
-  b->lanes_h = height;
-  HIPCHK(b, b->lanes_stage.reserve(n));
-  HIPCHK(b, hipMemcpyAsync(b->lanes_stage.ptr, lanes, n * sizeof(float), hipMemcpyHostToDevice, main_q(b)));
-  hipError_t e = launch_lanes_load(b->lanes_stage.ptr, b->lanes.ptr, n, b->cu_count * 8, main_q(b));
-  if (e != hipSuccess) return hip_fail(b, e, "halo_lanes_load_kernel launch");
-  HIPCHK(b, hipStreamSynchronize(main_q(b)));   // `lanes` is the caller's (pageable) memory
-  if (total_intensity >= 0.0) b->total_intensity = total_intensity;
-  return HALO_OK;
-}
-
-int halo_consumer_composite(halo_handle_t b, const HaloComposite* spec, float* linear_rgb_out, uint8_t* srgb_out, float* participating_p99_y, int32_t* produced) {
-  if (!b || !spec || !produced) return HALO_FATAL;
-  *produced = 0;
-  if (spec->mode < HALO_COMPOSITE_DOMINANT || spec->mode > HALO_COMPOSITE_PAINTER) return fail(b, HALO_FATAL, "consumer_composite: unknown mode");
-  uint64_t referenced = 0;   // ColorClassTable::referenced_mask_ = OR of the classes' member bits (color_class_table.hpp:38-43)
-  for (const HaloColorClass& c : b->color_classes) referenced |= c.bits;
-  if (referenced == 0) return HALO_OK;   // component_compositor.cpp:183-185: nothing is touched
-  if (spec->class_count != static_cast<int>(b->color_classes.size())) return fail(b, HALO_FATAL, "consumer_composite: class_count differs from halo_set_color's");
-  if (!b->lanes.ptr || b->lanes_w <= 0 || b->lanes_h <= 0) return fail(b, HALO_FATAL, "consumer_composite before any colour session (no lanes)");
-  HIPCHK(b, hipSetDevice(b->device));
-  if (int rc = join_aux(b)) return rc;   // (kernels of queued sessions may still be running on the trace / auxiliary streams)
-  const uint32_t npix = static_cast<uint32_t>(b->lanes_w) * static_cast<uint32_t>(b->lanes_h);
-  const size_t n3 = static_cast<size_t>(npix) * 3u;
-  // GatherActiveClasses (component_compositor.cpp:24-54): solo beats visible; stable sort by z_order; lane binding by class index
-  bool any_solo = false;
-  for (int c = 0; c < spec->class_count; c++) any_solo = any_solo || spec->classes[c].solo != 0;
-  std::vector<int> order(static_cast<size_t>(spec->class_count));
-  for (int c = 0; c < spec->class_count; c++) order[static_cast<size_t>(c)] = c;
-  std::stable_sort(order.begin(), order.end(), [spec](int x, int y) { return spec->classes[x].z_order < spec->classes[y].z_order; });
-  CompositeDev cd{};
-  cd.mode = static_cast<uint32_t>(spec->mode);
-  for (int c : order) {
-    const HaloCompositeClass& k = spec->classes[c];
-    if (!(any_solo ? k.solo != 0 : k.visible != 0)) continue;
-    cd.lane[cd.n_active] = static_cast<uint32_t>(c);
-    for (int j = 0; j < 3; j++) cd.color[cd.n_active][j] = k.color[j];
-    cd.n_active++;
-  }
-  auto deliver_black = [&]() -> int {   // "nothing visible -> all-black, still a valid composite" (:201-206)
-    if (linear_rgb_out) std::memset(linear_rgb_out, 0, n3 * sizeof(float));
-    if (srgb_out) std::memset(srgb_out, 0, n3);
-    if (participating_p99_y) *participating_p99_y = 0.0f;
-    *produced = 1;
-    return HALO_OK;
-  };
-  if (cd.n_active == 0) return deliver_black();
-  // ComputeParticipatingP99Y (:138-163) as a radix select: 11 + 11 + 10 bits of the float pattern, one histogram pass each
-  HIPCHK(b, b->comp_hist.reserve(2048));
-  std::vector<uint32_t> hist(2048);
-  const int blocks = b->cu_count * 8;
-  float p99 = 0.0f;
-  {
-    uint32_t prefix = 0u;
-    uint64_t rank = 0;   // 0-based rank wanted among the values that share `prefix`
-    const uint32_t shifts[3] = {21u, 10u, 0u}, widths[3] = {11u, 11u, 10u};
-    bool empty = false;
-    for (int pass = 0; pass < 3 && !empty; pass++) {
-      const uint32_t nb = 1u << widths[pass];
-      HIPCHK(b, hipMemsetAsync(b->comp_hist.ptr, 0, nb * sizeof(uint32_t), main_q(b)));
-      hipError_t e = launch_lane_hist(b->lanes.ptr, npix, cd, shifts[pass], widths[pass], prefix, b->comp_hist.ptr, blocks, main_q(b));
-      if (e != hipSuccess) return hip_fail(b, e, "halo_lane_hist_kernel launch");
-      HIPCHK(b, hipMemcpyAsync(hist.data(), b->comp_hist.ptr, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, main_q(b)));
-      HIPCHK(b, hipStreamSynchronize(main_q(b)));
-      if (pass == 0) {
-        uint64_t count = 0;
-        for (uint32_t i = 0; i < nb; i++) count += hist[i];
-        if (count == 0) {
-          empty = true;
-          break;
-        }
-        // idx = size * 0.99f in float, clamped (:156-159)
-        uint64_t idx = static_cast<uint64_t>(static_cast<float>(count) * 0.99f);
-        if (idx >= count) idx = count - 1;
-        rank = idx;
-      }
-      uint32_t bin = 0;
-      for (; bin < nb; bin++) {
-        if (rank < hist[bin]) break;
-        rank -= hist[bin];
-      }
-      if (bin >= nb) return fail(b, HALO_FATAL, "consumer_composite: lanes changed under the P99 select");
-      prefix = (prefix << widths[pass]) | bin;
-    }
-    if (!empty) std::memcpy(&p99, &prefix, sizeof(float));
-  }
-  // ParticipatingExposureScale (render.cpp:120-135), in float like the reference
-  const float snapshot_intensity = static_cast<float>(b->total_intensity);
-  float A = 0.0f;
-  if (p99 > 0.0f && snapshot_intensity > 0.0f) {
-    const float target_srgb = 135.0f / 255.0f;
-    const float target_linear = target_srgb <= 0.04045f ? target_srgb / 12.92f : std::pow((target_srgb + 0.055f) / 1.055f, 2.4f);
-    A = spec->intensity_factor * target_linear / p99;
-  }
-  if (participating_p99_y) *participating_p99_y = p99;
-  if (!(A > 0.0f)) {   // :209-214: P99 published, no composite; the linear buffer was already assigned zeros (:189)
-    if (linear_rgb_out) std::memset(linear_rgb_out, 0, n3 * sizeof(float));
-    return HALO_OK;
-  }
-  cd.a = A;
-  cd.s = A * spec->display_exposure_scale;
-  cd.display = spec->display_exposure_scale;
-  if (linear_rgb_out) HIPCHK(b, b->comp_rgb.reserve(n3));
-  if (srgb_out) HIPCHK(b, b->cons_rgb.reserve(n3));
-  if (linear_rgb_out || srgb_out) {
-    hipError_t e = launch_composite(b->lanes.ptr, npix, cd, linear_rgb_out ? b->comp_rgb.ptr : nullptr, srgb_out ? b->cons_rgb.ptr : nullptr, blocks, main_q(b));
-    if (e != hipSuccess) return hip_fail(b, e, "halo_composite_kernel launch");
-    if (linear_rgb_out) HIPCHK(b, hipMemcpyAsync(linear_rgb_out, b->comp_rgb.ptr, n3 * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
-    if (srgb_out) HIPCHK(b, hipMemcpyAsync(srgb_out, b->cons_rgb.ptr, n3, hipMemcpyDeviceToHost, main_q(b)));
-    HIPCHK(b, hipStreamSynchronize(main_q(b)));
-  }
-  *produced = 1;
-  return HALO_OK;
-}
-
-// ---- host-side pieces, exported for parity tests -------------------------------------------------------
-int halo_host_prism_geometry(float h, const float dist[6], HaloGeomTables* out) {
-  if (!out || !dist) return HALO_FATAL;
-  host::BuildPrism(h, dist, *out);
-  return HALO_OK;
-}
-int halo_host_pyramid_geometry(float wu, float wl, float h1, float h2, float h3, const float dist[6], HaloGeomTables* out) {
-  if (!out || !dist) return HALO_FATAL;
-  return host::BuildPyramid(wu, wl, h1, h2, h3, dist, *out) ? HALO_OK : HALO_UNAVAILABLE;
-}
-int halo_host_shape_scalars(const HaloCrystal* crystal, uint32_t seed, uint64_t shape_index, int via_plan, float out9[9]) {
-  if (!crystal || !out9) return HALO_FATAL;
-  const geom::CrystalRecipe rc = host::MakeRecipe(*crystal);
-  if (via_plan) {
-    for (int q = 0; q < 9; q++) out9[q] = geom::DrawShapeScalarOne(seed, rc, shape_index, q);
-  } else {
-    geom::DrawShapeScalars(seed, rc, shape_index, out9);
-  }
-  return HALO_OK;
-}
-int halo_host_build_lat_lut(const HaloDist* lat, float* theta, float* cdf, float* flip) {
-  if (!lat || !theta || !cdf || !flip) return HALO_FATAL;
-  host::LatLut l = host::BuildLatLut(*lat);
-  std::copy(l.theta.begin(), l.theta.end(), theta);
-  std::copy(l.cdf.begin(), l.cdf.end(), cdf);
-  std::copy(l.flip.begin(), l.flip.end(), flip);
-  return HALO_OK;
-}
-int halo_host_build_proj_params(const HaloRender* render, void* out76) {
-  if (!render || !out76) return HALO_FATAL;
-  ProjDev p = host::BuildProj(*render);
-  static_assert(sizeof(ProjDev) == 76, "ProjDev mirrors lm_proj::ProjParams");
-  std::memcpy(out76, &p, sizeof(p));
-  return HALO_OK;
-}
-int halo_host_partition(const float* prop, int n, uint64_t ray_num, double* carry, uint64_t* out) {
-  if (!prop || !carry || !out || n < 0) return HALO_FATAL;
-  std::vector<uint64_t> v = host::Partition(prop, n, ray_num, carry);
-  std::copy(v.begin(), v.end(), out);
-  return HALO_OK;
-}
-int halo_host_reduce_raypath(const uint8_t* rp, int32_t n, int32_t symmetry, int32_t sigma_a, int32_t d_applicable, uint8_t* out) {
-  if (!rp || !out || n < 0 || n > HALO_MAX_HITS) return HALO_FATAL;
-  std::vector<uint8_t> v = host::ReduceRaypath(std::vector<uint8_t>(rp, rp + n), static_cast<uint8_t>(symmetry), sigma_a, d_applicable != 0);
-  std::copy(v.begin(), v.end(), out);
-  return HALO_OK;
-}
-int halo_host_filter_fast_check(const HaloFilter* f, const HaloAxis* axis, const uint8_t* path, int32_t n, const float dir[3], int32_t crystal_id, int32_t* pass) {
-  if (!f || !axis || !pass || n < 0 || n > 16 || (n && !path) || !dir) return HALO_FATAL;
-  // the tables of the (filter, axis) asked about last are kept: the tests sweep thousands of paths per filter
-  struct Cache {
-    HaloFilter f;
-    HaloAxis axis;
-    int32_t crystal_id = 0;
-    bool valid = false, fits = false;
-    FastTables tables;
-  };
-  static thread_local std::unique_ptr<Cache> cache;
-  if (!cache) cache.reset(new Cache());
-  if (!cache->valid || std::memcmp(&cache->f, f, sizeof(HaloFilter)) != 0 || std::memcmp(&cache->axis, axis, sizeof(HaloAxis)) != 0 || cache->crystal_id != crystal_id) {
-    std::memset(&cache->tables, 0, sizeof(FastTables));
-    cache->f = *f;
-    cache->axis = *axis;
-    cache->crystal_id = crystal_id;
-    cache->fits = host::BuildFastTables(f, nullptr, *axis, static_cast<uint32_t>(crystal_id), cache->tables);
-    cache->valid = true;
-  }
-  if (!cache->fits) return HALO_FATAL;
-  *pass = host::FastFilterCheck(cache->tables, path, static_cast<uint32_t>(n), dir, static_cast<uint32_t>(crystal_id)) ? 1 : 0;
-  return HALO_OK;
-}
-int halo_host_color_fast_mask(const HaloColorSet* colors, const HaloAxis* axis, const uint8_t* path, int32_t n, const float dir[3], int32_t crystal_id, uint64_t carried,
-                              uint64_t* mask) {
-  if (!colors || !axis || !mask || n < 0 || n > 16 || (n && !path) || !dir) return HALO_FATAL;
-  std::unique_ptr<FastTables> tables(new FastTables());
-  std::memset(tables.get(), 0, sizeof(FastTables));
-  if (!host::BuildFastTables(nullptr, colors, *axis, static_cast<uint32_t>(crystal_id), *tables)) return HALO_FATAL;
-  *mask = host::FastColorMask(*tables, carried, path, static_cast<uint32_t>(n), dir, static_cast<uint32_t>(crystal_id));
-  return HALO_OK;
-}
-double halo_host_refractive_index(double wl) { return host::IceRefractiveIndex(wl); }
-float halo_host_illuminant_spd(int illuminant, float wl) { return host::IlluminantSpd(illuminant, wl); }
-int halo_host_wl_pool(const HaloWl* wl, float* entries5, int cap) {
-  if (!wl || !entries5 || cap < 0) return 0;
-  const std::vector<WlEntryDev> pool = host::BuildWlPool(*wl);
-  for (size_t m = 0; m < pool.size() && static_cast<int>(m) < cap; m++) {
-    float* e = entries5 + 5 * m;
-    e[0] = pool[m].n_idx;
-    e[1] = pool[m].spd_weight;
-    e[2] = pool[m].cmf_x;
-    e[3] = pool[m].cmf_y;
-    e[4] = pool[m].cmf_z;
-  }
-  return static_cast<int>(pool.size());
-}
-
-// sizes of the boundary structs, for the Python layout check
-uint64_t halo_abi_sizeof(int which) {
-  switch (which) {
-    case 0: return sizeof(HaloScene);
-    case 1: return sizeof(HaloRender);
-    case 2: return sizeof(HaloWl);
-    case 3: return sizeof(HaloExitRecord);
-    case 4: return sizeof(HaloGeomTables);
-    case 5: return sizeof(HaloLayerStats);
-    case 6: return sizeof(HaloEntry);
-    case 7: return sizeof(HaloColorSet);
-    case 8: return sizeof(HaloColorClass);
-    case 9: return sizeof(HaloFilter);
-    case 10: return sizeof(HaloRouteInfo);
-    case 11: return sizeof(HaloComposite);
-    case 12: return sizeof(HaloAutoEv);
-    case 13: return sizeof(HaloStatsSpec);
-    case 14: return sizeof(HaloImageStats);
-    case 15: return sizeof(HaloViewSpec);
-    default: return 0;
-  }
-}
 
 }  // extern "C"

@@ -3,7 +3,9 @@
 #ifndef HALO_HOST_HPP_
 #define HALO_HOST_HPP_
 
+#include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <vector>
 
@@ -83,6 +85,35 @@ double BinnedSum(const uint64_t* bins, bool squares);
 bool ViewDirection(const HaloRender& view, int px, int py, float dir[3]);
 
 }  // namespace host
+
+// ---- rules the backend applies and halo_host_abi.cpp exports for the tests: one definition ----
+
+// Fractional bits of the per-tile fixed-point sums for a launch of `m` rays whose weights are at most `max_w`: the largest F <= 32 with
+// 4 * max_w * m * 2^F < 2^62 (see halo_kernels.hip FixQ for the factor 4).
+// The deterministic route applies the same bound to the rays a plane set may take before it is folded (kFixBudgetHits) and to the landed integer
+// (kFixLandedHits): halo_host_fixed_frac_bits exports the rule.
+inline uint32_t fix_frac_bits(double max_w, uint64_t m) {
+  const double bound = 4.0 * std::max(max_w, 1e-30) * static_cast<double>(std::max<uint64_t>(m, 1));
+  int e = 0;
+  (void)std::frexp(bound, &e);   // bound < 2^e
+  return static_cast<uint32_t>(std::min(32, std::max(0, 62 - e)));
+}
+
+// Rays one unfolded fixed-point plane set takes (F = 29 for weights up to 1: a hit is quantised to 1.9e-9): a constant, because F must not depend
+// on how a run is cut into launches or sessions.  The landed integer's scale allows for the 2^32 rays of the largest layer.
+constexpr uint64_t kFixBudgetHits = 1ull << 30, kFixLandedHits = 1ull << 32;
+
+// Shard `index` of `count` takes rays [first, first + n) of a crystal entry's share: the share is cut in units of `clock` rays (the rays of one
+// sampled shape; 1 for a fixed one), u = ceil(share / clock) of them, and the shard gets units [floor(index * u / count), floor((index + 1) * u / count)) —
+// the last unit may be short.  Every shard gets a part of every entry, the parts differ by at most one unit, no unit is cut.
+inline void shard_slice(uint64_t share, uint32_t clock, uint32_t index, uint32_t count, uint64_t* first, uint64_t* n) {
+  typedef unsigned __int128 u128;
+  const u128 c = clock ? clock : 1u, u = (static_cast<u128>(share) + c - 1u) / c;
+  const u128 lo = std::min<u128>(c * (static_cast<u128>(index) * u / count), share), hi = std::min<u128>(c * ((static_cast<u128>(index) + 1u) * u / count), share);
+  *first = static_cast<uint64_t>(lo);
+  *n = static_cast<uint64_t>(hi - lo);
+}
+
 }  // namespace halo
 
 #endif

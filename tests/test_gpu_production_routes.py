@@ -1019,3 +1019,44 @@ def test_options_that_shape_an_open_session_are_refused_inside_it():
     for key, val in (("seed", 5), ("ray_base", 1 << 33), ("rank", 2), ("capture_exits", 0), ("filter_fast", 1), ("mono_copies", 8)):
         hb.set_option(key, val)
     hb.close()
+
+
+@pytest.mark.gpu
+def test_a_refused_option_is_not_remembered_by_the_table_cache():
+    """A set that is refused leaves nothing behind (halo_options.h set_option).  capture_exits = 1 is refused inside session A, which traces with
+    the plain kernels and leaves its entry's tables in the table cache (one deterministic prism entry, table_cache at its default).  The same set
+    between the sessions is legal and is a change: it must drop the cache, so session B's launch runs the capture kernels and DrainExits hands
+    back one record per exit — as many as a handle that had capture_exits = 1 from the start gets for the same two sessions.  (Had the refused
+    value been remembered, the legal set would count as unchanged, the cached entry would keep the plain kernel mode and B would capture nothing.)
+    Every ray leaves at most max_hits + 1 records and the backend sizes the capture buffer for that, so the drain holds them all.
+    (Run once on the library of the commit before the option table: session B drained 0 records of 19678 exits there; 19678 of 19678 here.)"""
+    from ice_halo_sim_amd.backend import BackendError, HipTraceBackend
+    n, max_hits = 4096, 7
+    full = {"type": "uniform", "mean": 0.0, "std": 360.0}
+    sc = scenes.scene([(0.0, [scenes.entry(scenes.prism_crystal(1.0), scenes.axis(zenith=full, azimuth=full, roll=full), 1.0, 1)])], max_hits=max_hits, sun_altitude=20.0)
+    rd, wl = scenes.config2_render(64, 32), scenes.wl_discrete(550.0)
+
+    def session(hb, refuse=False):
+        hb.BeginSession(sc, rd, wl, n)
+        if refuse:
+            with pytest.raises(BackendError):
+                hb.set_option("capture_exits", 1)
+        st = hb.TraceLayer(n)
+        hb.EndSession()
+        return st, hb.DrainExits()
+
+    hb = HipTraceBackend(device=0, seed=11)
+    st_a, exits_a = session(hb, refuse=True)
+    assert st_a.exit_count > 0 and len(exits_a) == 0
+    hb.set_option("capture_exits", 1)
+    st_b, exits_b = session(hb)
+    hb.close()
+    ref = HipTraceBackend(device=0, seed=11, capture_exits=1)
+    ref_a, _ = session(ref)
+    ref_b, ref_exits_b = session(ref)
+    ref.close()
+    print("session B: exit_count", int(st_b.exit_count), "drained", len(exits_b), "| from the start: exit_count", int(ref_b.exit_count), "drained", len(ref_exits_b))
+    assert int(ref_a.exit_count) == int(st_a.exit_count)
+    assert 0 < len(exits_b) <= n * (max_hits + 1)
+    assert len(exits_b) == int(st_b.exit_count)
+    assert len(exits_b) == len(ref_exits_b) and int(st_b.exit_count) == int(ref_b.exit_count)

@@ -72,10 +72,10 @@ def _same_rays_same_image(on, off, what):
 
 
 def test_spec_root_is_a_known_option_and_defaults_to_on():
-    """No GPU needed: the option is handled by halo_set_option, the backend starts with it on, and the header documents both."""
-    src = open(os.path.join(ROOT, "ice_halo_sim_amd", "csrc", "halo_backend.cpp")).read()
-    body = src[src.index("int halo_set_option("):src.index("int halo_set_stream(")]
-    assert re.search(r'k == "spec_root"\) b->spec_root = v \? 1 : 0;', body)
+    """No GPU needed: the option is a row of the option table that stores a boolean, the options start with it on, and the header documents both.
+    (tests/test_cpp_options.py checks the first two by running the table: the key is accepted, 0 / 1 / 7 / -3 store 0 / 1 / 1 / 1, the default is 1.)"""
+    src = open(os.path.join(ROOT, "ice_halo_sim_amd", "csrc", "halo_options.h")).read()
+    assert re.search(r'^\s*\{"spec_root", &Options::spec_root, kOptBool, 0, ', src, re.M)
     assert re.search(r"^\s*int spec_root = 1;", src, re.M)
     header = open(os.path.join(ROOT, "include", "halo_trace.h")).read()
     assert '"spec_root" (1 [default]' in header

@@ -8,6 +8,12 @@ TIR or not, which pixel) can flip for rays sitting on a boundary.  Stated tolera
   image                   ||A - B||_2 / ||B||_2 <= 2e-3 on 8x8 block means; landed weight rel 1e-4
 (the north_star's "image L2 < 1e-3 at 50 M rays" is a Monte-Carlo bound between independent samples; with
 shared streams we hold a tighter, deterministic one at test sizes).
+
+The fractional bar is what random rays allow; it cannot tell "ill-conditioned" from "wrong at an edge".  The edges of the interaction
+loop — grazing entries, critical angles, edges and vertices of the next face, faces a ray skims, entry points off their plane, the hit
+budget, the path register's 16 faces — are held with NO fractional bar in tests/test_gpu_hit_loop.py, against the float64 model of
+tests/_hit_model.py (margins and bars measured on the host: tests/test_hit_model.py); the lens projection likewise in
+tests/test_gpu_lens_edges.py.
 """
 import os
 

@@ -1,6 +1,7 @@
 // halo_backend.cpp — the C ABI of include/halo_trace.h: session state machine, per-(layer, entry) dispatch, device memory, streams/events, the
 // fixed-point import / export and the shards.  Host C++ only; kernels live in halo_trace.inl (+ halo_trace_m*.hip) and halo_kernels.hip.
 // Its neighbours: halo_state.h (the state and the helpers the units share), halo_options.h (the option table halo_set_option asks),
+// halo_order.h (the streams and everything that orders them: b->ord),
 // halo_consumer.cpp (the consumer stages), halo_host_abi.cpp (every export that takes no handle).
 //
 // State machine (reference trace_backend.hpp:91-116):
@@ -39,29 +40,6 @@ int hip_fail(HaloBackend* b, hipError_t e, const char* what) {
   return fail(b, (e == hipErrorNoDevice || e == hipErrorInvalidDevice || e == hipErrorOutOfMemory) ? HALO_UNAVAILABLE : HALO_FATAL,
               std::string(what) + ": " + hipGetErrorString(e));
 }
-// What the main stream is given from here on runs behind everything queued on the auxiliary and the trace streams (no host wait).
-int join_aux(HaloBackend* b) {
-  if (b->aux_pending) {
-    HIPCHK(b, hipEventRecord(b->ev_join, b->aux));
-    HIPCHK(b, hipStreamWaitEvent(main_q(b), b->ev_join, 0));   // (main_q: the trace streams reach this wait through their next hop)
-    b->aux_pending = false;
-  }
-  for (int k = 0; k < 2; k++)
-    if (b->cs_pending[k]) {
-      HIPCHK(b, hipEventRecord(b->ev_cs[k], b->cs[k]));
-      HIPCHK(b, hipStreamWaitEvent(main_q(b), b->ev_cs[k], 0));
-      b->cs_pending[k] = false;
-      b->rmw[k].clear();   // (every later launch waits for the main stream, which now waits for these sums)
-      if (b->close_ts == k) b->close_done.clear();   // ... and for this direct close
-    }
-  return HALO_OK;
-}
-// Host waits for all streams.
-int sync_all(HaloBackend* b) {
-  if (int rc = join_aux(b)) return rc;
-  HIPCHK(b, hipStreamSynchronize(main_q(b)));
-  return HALO_OK;
-}
 void drop_table_cache(HaloBackend* b) {
   for (auto& layer : b->tcache)
     for (auto& e : layer) e.valid = false;
@@ -72,58 +50,6 @@ namespace {
 
 // The plane set the open / pending session adds to (HaloBackend::mono_two).
 inline float* planes_of(HaloBackend* b) { return b->mono.ptr + (b->mono_two ? static_cast<size_t>(b->mono_set) * b->mono_half : 0u); }
-// The stream the plane-touching passes of logged launches and the folds are queued on.
-inline hipStream_t post_stream(HaloBackend* b) { return b->opt.overlap ? b->aux : b->stream; }
-// What is queued on the auxiliary stream from here on runs behind everything the main stream and the trace streams hold now.
-int fork_aux(HaloBackend* b) {
-  if (!b->opt.overlap) return HALO_OK;
-  HIPCHK(b, hipEventRecord(b->ev_fork, main_q(b)));
-  HIPCHK(b, hipStreamWaitEvent(b->aux, b->ev_fork, 0));
-  for (int k = 0; k < 2; k++)
-    if (b->cs_pending[k]) {
-      HIPCHK(b, hipEventRecord(b->ev_cs[k], b->cs[k]));
-      HIPCHK(b, hipStreamWaitEvent(b->aux, b->ev_cs[k], 0));
-    }
-  b->aux_pending = true;
-  b->aux_seq++;
-  return HALO_OK;
-}
-// Trace stream i goes on behind what the auxiliary stream holds now (a closing fold: it reads and zeroes the planes).
-int wait_for_aux(HaloBackend* b, int i) {
-  if (b->opt.overlap && b->aux_pending && b->cs_seen_aux[i] != b->aux_seq) {
-    HIPCHK(b, hipEventRecord(b->ev_aux, b->aux));
-    HIPCHK(b, hipStreamWaitEvent(b->cs[i], b->ev_aux, 0));
-    b->cs_seen_aux[i] = b->aux_seq;
-  }
-  return HALO_OK;
-}
-// The stream the next trace kernel goes to: behind what the main stream holds now (table uploads, counter resets) and — for a launch that
-// adds to the planes itself — behind what the auxiliary stream holds (folds, per-tile passes).
-int next_trace_stream(HaloBackend* b, bool touches_planes, bool alternate, hipStream_t* out, int* which) {
-  if (!b->opt.overlap) {
-    *out = b->stream;
-    *which = 0;
-    return HALO_OK;
-  }
-  // Launches alternate streams only while they are latency-bound (up to 2^21 rays: tools/dispatch_probe.cpp, us per session with / without,
-  // 2^16 18.8 / 30.6, 2^18 25.2 / 44.0, 2^20 65.5 / 110, 2^22 264 / 250, 2^24 817 / 820); a launch that fills the chip by itself gains nothing
-  // from a neighbour and keeps stream 0, where its HIP events time it undisturbed.
-  const int i = alternate ? b->cs_next : 0;
-  if (alternate) b->cs_next ^= 1;
-  // (the hop is for what the main stream has been given since this trace stream last waited for it — table uploads, counter resets: main_q.  With
-  //  nothing new there it orders nothing, and option lean_events leaves it out.  A caller's stream may hold work this backend never saw: always hopped.)
-  if (!b->opt.lean_events || b->main_dirty[i] || b->stream != b->own_stream) {
-    HIPCHK(b, hipEventRecord(b->ev_main, b->stream));
-    HIPCHK(b, hipStreamWaitEvent(b->cs[i], b->ev_main, 0));
-    b->main_dirty[i] = false;
-  }
-  if (touches_planes)
-    if (int rc = wait_for_aux(b, i)) return rc;
-  b->cs_pending[i] = true;
-  *out = b->cs[i];
-  *which = i;
-  return HALO_OK;
-}
 // Smallest launch the hit log takes by itself (option hit_log = -1).  Direct atomics retire memory-side at ~21 G/s whatever they hit; the log's
 // passes cost a fixed ~75 us per launch plus ~10 ps per record, and on a small launch they run beside the next session's trace kernel.  A
 // full-sky render lands every exit (5-6 per root: 0.8 M roots = 4.4 M atomics = 210 us against 102 us of logged trace kernel, bench.py --config 4d),
@@ -165,25 +91,25 @@ int ensure_accumulator(HaloBackend* b, int w, int h) {
 }
 
 // take the timing of one finished ring slot (the tallies are cumulative device counters: pull_tally)
-void harvest_slot(HaloBackend* b, int k) {
-  if (!b->ring_busy[k]) return;
-  (void)hipEventSynchronize(b->ring_fin[k]);
+void harvest_slot(HaloBackend* b, Order::RingSlot& r) {
+  if (!r.busy) return;
+  (void)hipEventSynchronize(r.fin);
   float ms = 0.0f, ms2 = 0.0f;
-  (void)hipEventElapsedTime(&ms, b->ring_ev0[k], b->ring_ev1[k]);
-  if (b->ring_posts[k]) (void)hipEventElapsedTime(&ms2, b->ring_t2[k], b->ring_ev3[k]);   // the passes' own span
+  (void)hipEventElapsedTime(&ms, r.ev0, r.ev1);
+  if (r.posts) (void)hipEventElapsedTime(&ms2, r.t2, r.ev3);   // the passes' own span
   static const bool debug_timing = std::getenv("HALO_DEBUG_TIMING") != nullptr;
-  if (debug_timing) std::fprintf(stderr, "[halo timing] slot %d final %d posts %d trace %.4f ms passes %.4f ms\n", k, int(b->ring_final[k]), int(b->ring_posts[k]), ms, ms2);
+  if (debug_timing) std::fprintf(stderr, "[halo timing] slot %d final %d posts %d trace %.4f ms passes %.4f ms\n", int(&r - b->ord.ring), int(r.final), int(r.posts), ms, ms2);
   // An event pair that reads backwards (seen once: two twelve-launch runs of one bench process summed to -10 ms; the rocprofv3 trace of the same
   // command had every kernel in order) is a measurement that did not happen: it is left out of the timing sums and of their launch count.
   const bool timed = ms >= 0.0f && ms2 >= 0.0f;
   if (timed) b->layer_acc.kernel_ms += ms + ms2;
-  if (b->ring_final[k] && timed) {
+  if (r.final && timed) {
     b->time_trace_ms += ms;
     b->time_post_ms += ms2;
     b->time_launches += 1;
   }
   b->layer_acc.launches += 1;
-  b->ring_busy[k] = false;
+  r.busy = false;
 }
 // Snapshot of the cumulative tallies (one 1 KB D2H copy + a stream sync): the sum over the lines, per tally.
 int read_tally(HaloBackend* b, double out[kSumNum], unsigned long long* fix_landed = nullptr) {
@@ -238,7 +164,7 @@ int take_landed_delta(HaloBackend* b, double* landed) {
 namespace {
 
 void harvest_all(HaloBackend* b) {
-  for (int k = 0; k < HaloBackend::kRing; k++) harvest_slot(b, k);
+  for (Order::RingSlot& r : b->ord.ring) harvest_slot(b, r);
 }
 void add_stats(HaloLayerStats& dst, const HaloLayerStats& src) {
   dst.root_count += src.root_count;
@@ -281,25 +207,11 @@ int halo_create(int device_ordinal, uint32_t seed, halo_handle_t* out) {
   b->device = device_ordinal;
   b->seed = seed ? seed : 1u;
   b->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  if (hipSetDevice(device_ordinal) != hipSuccess || hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking) != hipSuccess) {
-    delete b;
-    return HALO_UNAVAILABLE;
-  }
-  bool aux_ok = hipStreamCreateWithFlags(&b->aux, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&b->cs[0], hipStreamNonBlocking) == hipSuccess &&
-                hipStreamCreateWithFlags(&b->cs[1], hipStreamNonBlocking) == hipSuccess;
-  for (hipEvent_t* ev : b->untimed_events()) aux_ok = aux_ok && hipEventCreateWithFlags(ev, hipEventDisableTiming) == hipSuccess;
-  bool ring_ok = aux_ok && b->ring_dev.reserve(HaloBackend::kRing) == hipSuccess &&
-                 b->ring_host.alloc(HaloBackend::kRing) == hipSuccess && b->tally_host.alloc(kTallyLines * kTallyStride) == hipSuccess;
-  for (int k = 0; ring_ok && k < HaloBackend::kRing; k++)
-    ring_ok = hipEventCreate(&b->ring_ev0[k]) == hipSuccess && hipEventCreate(&b->ring_ev1[k]) == hipSuccess && hipEventCreate(&b->ring_ev2[k]) == hipSuccess && hipEventCreate(&b->ring_ev3[k]) == hipSuccess &&
-              hipEventCreateWithFlags(&b->ring_done[k], hipEventDisableTiming) == hipSuccess;
-  if (!ring_ok) {
+  // (whatever exists when a step fails goes in halo_destroy: the streams and the events with b->ord, the ring and the pinned mirrors with the handle)
+  if (hipSetDevice(device_ordinal) != hipSuccess || b->ord.create() != hipSuccess || b->slots_dev.reserve(Order::kRing) != hipSuccess ||
+      b->slots_host.alloc(Order::kRing) != hipSuccess || b->tally_host.alloc(kTallyLines * kTallyStride) != hipSuccess ||
+      b->tally.reserve(kTallyLines * kTallyStride) != hipSuccess || b->counters.reserve(kCntNum) != hipSuccess) {
     halo_destroy(b);
-    return HALO_UNAVAILABLE;
-  }
-  b->stream = b->own_stream;
-  if (b->tally.reserve(kTallyLines * kTallyStride) != hipSuccess || b->counters.reserve(kCntNum) != hipSuccess) {
-    halo_destroy(b);  // the streams and the events; the ring and the pinned mirrors go with the handle
     return HALO_UNAVAILABLE;
   }
   (void)hipMemsetAsync(b->tally.ptr, 0, kTallyLines * kTallyStride * sizeof(double), main_q(b));
@@ -311,19 +223,7 @@ int halo_create(int device_ordinal, uint32_t seed, halo_handle_t* out) {
 int halo_destroy(halo_handle_t b) {
   if (!b) return HALO_OK;
   (void)hipSetDevice(b->device);
-  (void)hipStreamSynchronize(main_q(b));
-  if (b->aux) (void)hipStreamSynchronize(b->aux);
-  for (int k = 0; k < 2; k++)
-    if (b->cs[k]) (void)hipStreamSynchronize(b->cs[k]);
-  for (int k = 0; k < HaloBackend::kRing; k++)
-    for (hipEvent_t ev : {b->ring_ev0[k], b->ring_ev1[k], b->ring_ev2[k], b->ring_ev3[k], b->ring_done[k]})
-      if (ev) (void)hipEventDestroy(ev);
-  for (hipEvent_t* ev : b->untimed_events())
-    if (*ev) (void)hipEventDestroy(*ev);
-  if (b->aux) (void)hipStreamDestroy(b->aux);
-  for (int k = 0; k < 2; k++)
-    if (b->cs[k]) (void)hipStreamDestroy(b->cs[k]);
-  if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
+  b->ord.destroy();   // the streams are synchronised, then the events go, then the streams
   delete b;   // every buffer frees itself (DevBuf, PinnedBuf): the streams were synchronised above
   return HALO_OK;
 }
@@ -352,9 +252,7 @@ int halo_set_option(halo_handle_t b, const char* key, int64_t v) {
 
 int halo_set_stream(halo_handle_t b, void* s) {
   if (!b) return HALO_FATAL;
-  (void)sync_all(b);
-  b->stream = s ? static_cast<hipStream_t>(s) : b->own_stream;
-  b->main_dirty[0] = b->main_dirty[1] = true;   // another main stream: the trace streams have seen nothing of it
+  b->ord.set_main(static_cast<hipStream_t>(s));   // (host waits for all streams first; no stream: the handle's own again)
   return HALO_OK;
 }
 
@@ -639,8 +537,8 @@ static int fold_queue(HaloBackend* b) {
     return fail(b, HALO_FATAL, "shard " + std::to_string(b->shard_index) + " of " + std::to_string(b->shard_count) +
                                    ": the pending fixed-point planes hold a part of the image; move them out with halo_export_fixed (and fold what halo_import_fixed brings in)");
   HIPCHK(b, hipSetDevice(b->device));
-  if (int rc = fork_aux(b)) return rc;
-  hipStream_t ps = post_stream(b);
+  HIPCHK(b, b->ord.fork_aux());
+  hipStream_t ps = b->ord.post_stream();
   const uint32_t npix = static_cast<uint32_t>(b->acc_w) * static_cast<uint32_t>(b->acc_h);
   if (b->fix_planes) {   // a deterministic session's planes: integers in, float32(double(S) * 2^-F) out, then the same chain (no copies, no twin)
     FoldCoef coef{};
@@ -669,7 +567,7 @@ static int fold_queue(HaloBackend* b) {
   if (flag) HIPCHK(b, hipMemsetAsync(flag, 0, sizeof(uint32_t), ps));   // every group has seen it; the fold zeroed what it took
   b->twin_set ^= 1;   // what traces from here on overflows into the other half
   if (b->mono_two) {    // ... and adds to the other plane set, once the fold that last zeroed THAT one is through (set_folded)
-    HIPCHK(b, b->set_folded[b->mono_set].mark(ps));
+    HIPCHK(b, b->ord.set_folded[b->mono_set].mark(ps));
     b->mono_set ^= 1;
   }
   b->mono_dirty = false;
@@ -742,6 +640,7 @@ struct LaunchPlan {
   // (A deterministic logged launch flushes its integer cache onto the planes from the trace kernel itself: it waits for the fold, as a direct one does.)
   // (A directly closing launch writes the image and the twin's half in its passes: it is queued behind the auxiliary stream like a launch that fills the chip.)
   bool under_fold() const { return use_log && alternate && !fixed && !close; }
+  bool sums_plain() const { return (use_log && !fixed) || (use_bin && two_level); }   // the per-tile sums end in plain read-modify-writes of the planes (Order: plane ownership)
 };
 // What a launch was given when it was queued: its dispatch-ring slot, log buffer set, shape pool and the first index of its shape stream.
 struct LaunchSlots { int k = 0, ls = 0, shape_set = 0; uint64_t first_shape = 0; };
@@ -1007,9 +906,9 @@ void prepare_entry_tables(HaloBackend* b, const LayerCtx& c, int ci, EntryTables
 int upload_tables(HaloBackend* b, const LayerCtx& c, const LaunchPlan& p, const HaloEntry& E, uint32_t lat_path, const ShapeDev* shape, int k, EntryTables& T,
                   DispatchSlot** out) {
   HaloBackend::TableCacheEntry* ce = T.ce;
-  DispatchSlot& hs = b->ring_host.ptr[k];
+  DispatchSlot& hs = b->slots_host.ptr[k];
   if (ce && !T.cached) ce->cur ^= 1;   // an upload takes the entry's other slot
-  DispatchSlot* ds = *out = ce ? T.ce_dev + ce->cur : b->ring_dev.ptr + k;
+  DispatchSlot* ds = *out = ce ? T.ce_dev + ce->cur : b->slots_dev.ptr + k;
   if (T.cached) return HALO_OK;   // (T describes the slot already: from the cache entry, or from this entry's previous upload)
   if (lat_path == kLatLut) {
     const host::LatLut& lut = cached_lut(b, E.axis.latitude);
@@ -1033,13 +932,7 @@ int upload_tables(HaloBackend* b, const LayerCtx& c, const LaunchPlan& p, const 
   // tables out of it on a trace stream.  The upload goes behind the last launch that read this slot (no host wait; ring slots are
   // protected by harvest_slot).  Without this the earlier kernel's late workgroups could pick up THIS session's wavelength pool or
   // shape (tests/test_gpu_production_routes.py::test_async_sessions_alternating_wavelengths).
-  if (ce && ce->read_ring[ce->cur] >= 0) {
-    const int rk = ce->read_ring[ce->cur];
-    if (b->ring_busy[rk] && b->ring_use[rk] == ce->read_use[ce->cur]) {
-      HIPCHK(b, hipStreamWaitEvent(b->stream, b->ring_fin[rk], 0));
-      b->main_dirty[0] = b->main_dirty[1] = true;
-    }
-  }
+  if (ce && ce->read_ring[ce->cur] >= 0) HIPCHK(b, b->ord.behind_reader(ce->read_ring[ce->cur], ce->read_use[ce->cur]));
   HIPCHK(b, hipMemcpyAsync(ds, &hs, T.fast_host ? sizeof(DispatchSlot) : offsetof(DispatchSlot, fast), hipMemcpyHostToDevice, main_q(b)));
   if (ce) {   // the next dispatch of this entry — the layer's next chunk, the next equal session — finds the tables in place
     ce->valid = true, ce->mode = T.mode, ce->use_filter = T.use_filter, ce->use_color = T.use_color;
@@ -1138,7 +1031,7 @@ int bind_route(HaloBackend* b, LaunchPlan& p, int ls, DispatchParams& P) {
   if (p.use_log) {
     if (int rc = reserve_idle(b, bin_cnt, std::max<size_t>(static_cast<size_t>(p.blocks), static_cast<size_t>(512) * 16u))) return rc;
     if (int rc = reserve_idle(b, bin_cnt2, static_cast<size_t>(512) * 16u)) return rc;
-    HIPCHK(b, b->set_free[ls].wait_on(main_q(b)));   // the passes of the launch that last wrote this set
+    HIPCHK(b, b->ord.set_free[ls].wait_on(main_q(b)));   // the passes of the launch that last wrote this set
   } else if (p.use_bin) {
     if (int rc = reserve_idle(b, bin_cnt, static_cast<size_t>(512) * 16u)) return rc;
     HIPCHK(b, hipMemsetAsync(bin_cnt.ptr, 0, static_cast<size_t>(p.two_level ? 512u : p.bin_tiles) * 16u * sizeof(uint32_t), main_q(b)));
@@ -1282,7 +1175,8 @@ void record_route(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, 
 }
 // The accumulation passes of a launch, behind its trace kernel on trace stream `ts` (index ts_i), and the ring slot's closing events.
 int queue_passes(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, const LaunchSlots& S, hipStream_t ts, int ts_i, hipEvent_t before_sums) {
-  const int k = S.k;
+  Order& ord = b->ord;
+  Order::RingSlot& r = ord.ring[S.k];
   DevBuf<HitRec>&bin_list = b->bin_list_s[S.ls], &bin_list2 = b->bin_list2_s[S.ls];
   DevBuf<uint32_t>&bin_cnt = b->bin_cnt_s[S.ls], &bin_cnt2 = b->bin_cnt2_s[S.ls];
   // fixed-point scale of the per-tile sums (halo_kernels.hip FixQ): no slot of this launch can sum to more than 4 x max weight x rays
@@ -1294,46 +1188,25 @@ int queue_passes(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, c
                                                          p.bin_tiles, p.fan_log2, frac_bits, P.ovf, P.ovf_flag, ts, before_sums)
                                   : launch_bin_accumulate(P.mono, bin_list.ptr, P.bin_cap, bin_cnt.ptr, p.bin_tiles, frac_bits, ts);
       if (be != hipSuccess) return hip_fail(b, be, "halo_bin_accumulate_kernel launch");
-      if (b->opt.overlap && p.two_level) HIPCHK(b, b->rmw[ts_i].mark(ts));
+      HIPCHK(b, ord.sums_queued(ts, ts_i, p.sums_plain()));
     }
-    HIPCHK(b, hipEventRecord(b->ring_ev1[k], ts));
-    b->ring_posts[k] = false;
-    HIPCHK(b, hipEventRecord(b->ring_done[k], ts));
-    b->ring_fin[k] = b->ring_done[k];
+    HIPCHK(b, hipEventRecord(r.ev1, ts));
+    r.posts = false;
+    HIPCHK(b, ord.slot_done(r, ts));
     return HALO_OK;
   }
   // the accumulation passes of this launch: behind the trace kernel on its stream.  (Round 5 tried them on the auxiliary stream, under the
   // next launch's trace kernel: configs[1] + 1.2 %, the trace kernel itself 5 % slower for the CUs the 134 KB split workgroups take, the
   // passes' spans stretched sevenfold — profiles that no longer say what a kernel costs, for one percent.  Not kept.)
-  HIPCHK(b, hipEventRecord(b->ring_ev1[k], ts));          // the trace kernel alone: ev0 .. ev1
+  HIPCHK(b, hipEventRecord(r.ev1, ts));          // the trace kernel alone: ev0 .. ev1
   hipStream_t ps = ts;
   if (p.under_fold()) {   // the passes add to the planes: behind the fold that last touched THEIR planes
     if (b->mono_two) {   // two plane sets: that is the fold of two sessions ago (it zeroed this set), not the one the trace kernel started under
-      HIPCHK(b, b->set_folded[b->mono_set].wait_on(ps));
-    } else if (int rc = wait_for_aux(b, ts_i)) return rc;
+      HIPCHK(b, ord.set_folded[b->mono_set].wait_on(ps));
+    } else HIPCHK(b, ord.wait_for_aux(ts_i));
   }
   // (nothing between ev1 and here unless the passes wait for a fold: one record serves as both, the spans stay the trace kernel's and the passes')
-  if (b->opt.lean_events && !p.under_fold()) b->ring_t2[k] = b->ring_ev1[k];
-  else {
-    HIPCHK(b, hipEventRecord(b->ring_ev2[k], ps));
-    b->ring_t2[k] = b->ring_ev2[k];
-  }
-  // behind a direct close four markers fall on one point of the stream — the close, the end of the passes' span, the log set free again, the slot
-  // done: one record, ring_ev3, and the others name it
-  auto close_marks = [&]() -> hipError_t {
-    hipError_t e = hipEventRecord(b->ring_ev3[k], ps);
-    if (e != hipSuccess) return e;
-    if (b->opt.lean_events) {
-      (void)b->close_done.mark_at(b->ring_ev3[k]);
-      (void)b->set_free[S.ls].mark_at(b->ring_ev3[k]);
-      b->ring_fin[k] = b->ring_ev3[k];
-      return hipSuccess;
-    }
-    if ((e = b->close_done.mark(ps)) != hipSuccess) return e;
-    if ((e = b->set_free[S.ls].mark(ps)) != hipSuccess) return e;
-    b->ring_fin[k] = b->ring_done[k];
-    return hipEventRecord(b->ring_done[k], ps);
-  };
+  HIPCHK(b, ord.passes_begin(r, ps, !p.under_fold()));
   if (p.close && p.tile) {
     // the closing pass over the chunks the trace kernel filled: no split, no list counters; the twin's flag is cleared behind the pass as below
     const float coef[3] = {b->plane_coef[0][0], b->plane_coef[0][1], b->plane_coef[0][2]};
@@ -1354,10 +1227,9 @@ int queue_passes(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, c
                    P.tile_cap, cnt.size(), static_cast<unsigned long long>(met), static_cast<double>(met) / static_cast<double>(cnt.size()), static_cast<unsigned long long>(most),
                    static_cast<unsigned long long>(empty), static_cast<unsigned long long>(over));
     }
-    HIPCHK(b, close_marks());
-    b->close_ts = ts_i;
+    HIPCHK(b, ord.close_marks(r, ps, ts_i, S.ls));   // (the close, the passes' span, the log set free, the slot done: Order::close_marks)
     if (b->opt.overlap && p.alternate) b->log_set ^= 1;
-    b->ring_posts[k] = true;
+    r.posts = true;
     return HALO_OK;
   }
   if (p.close) {
@@ -1371,10 +1243,9 @@ int queue_passes(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, c
     if (ce != hipSuccess) return hip_fail(b, ce, "halo_split_kernel launch (direct close)");
     b->cnt2_clean[S.ls] = true;
     b->direct_closes++;
-    HIPCHK(b, close_marks());
-    b->close_ts = ts_i;
+    HIPCHK(b, ord.close_marks(r, ps, ts_i, S.ls));   // (the close, the passes' span, the log set free, the slot done: Order::close_marks)
     if (b->opt.overlap && p.alternate) b->log_set ^= 1;
-    b->ring_posts[k] = true;
+    r.posts = true;
     return HALO_OK;
   }
   HIPCHK(b, hipMemsetAsync(bin_cnt2.ptr, 0, static_cast<size_t>(p.log_tiles) * 16u * sizeof(uint32_t), ps));
@@ -1391,34 +1262,29 @@ int queue_passes(HaloBackend* b, const LaunchPlan& p, const DispatchParams& P, c
                                                    bin_cnt2.ptr, 1u << p.log_t_log2, p.log_planes, b->mono_s_log2, b->render.visible == HALO_VISIBLE_FULL, frac_bits,
                                                    P.ovf, P.ovf_flag, P.ovf_copies_log2, ps, before_sums);
   if (be != hipSuccess) return hip_fail(b, be, "halo_split_kernel launch");
-  if (b->opt.overlap && !p.fixed) HIPCHK(b, b->rmw[ts_i].mark(ps));
-  HIPCHK(b, hipEventRecord(b->ring_ev3[k], ps));
-  HIPCHK(b, b->set_free[S.ls].mark(ps));
+  HIPCHK(b, ord.sums_queued(ps, ts_i, p.sums_plain()));
+  HIPCHK(b, hipEventRecord(r.ev3, ps));
+  HIPCHK(b, ord.set_free[S.ls].mark(ps));
   if (b->opt.overlap && p.alternate) b->log_set ^= 1;
-  b->ring_posts[k] = true;
-  HIPCHK(b, hipEventRecord(b->ring_done[k], ps));
-  b->ring_fin[k] = b->ring_done[k];
+  r.posts = true;
+  HIPCHK(b, ord.slot_done(r, ps));
   return HALO_OK;
 }
 // Stream choice, plane gates, generator, trace kernel, route record and passes of one launch whose tables, shapes and buffers are in place.
 int queue_launch(HaloBackend* b, const LaunchPlan& p, const HaloEntry& E, EntryTables& T, const DispatchParams& P, const LaunchSlots& S) {
-  const int k = S.k;
+  Order& ord = b->ord;
+  Order::RingSlot& r = ord.ring[S.k];
   // The launch's trace stream (alternating for small launches), behind whatever the auxiliary stream still does to the planes (a closing
   // fold): the launch adds to them — from the trace kernel itself (direct atomics, staged lists) or in its passes, which follow it on
   // the same stream.  (A small logged launch starts under that fold: LaunchPlan::under_fold.)
   hipStream_t ts = nullptr;
   int ts_i = 0;
-  if (int rc = next_trace_stream(b, !p.under_fold(), p.alternate, &ts, &ts_i)) return rc;
-  if (b->close_done.set && b->close_ts != ts_i)   // a direct close on the other trace stream: it writes the image and the twin's half plainly
-    HIPCHK(b, b->close_done.wait_on(ts));
+  HIPCHK(b, ord.next_trace_stream(!p.under_fold(), p.alternate, &ts, &ts_i));
+  HIPCHK(b, ord.behind_other_close(ts, ts_i));   // a direct close on the other trace stream: it writes the image and the twin's half plainly
   hipEvent_t before_sums = nullptr;   // rule (1), for the routes whose sums write the planes plainly
 #ifndef HALO_NO_PLANE_GATES   // (defined only to see tests/test_gpu_production_routes.py's two-stream test fail without the gates)
-  if (b->opt.overlap && !p.use_log)   // this trace kernel adds to the planes itself: behind the other stream's sums
-    HIPCHK(b, b->rmw[ts_i ^ 1].wait_on(ts));
-  if (b->opt.overlap && ((p.use_log && !p.fixed) || (p.use_bin && p.two_level)) && b->cs_pending[ts_i ^ 1]) {
-    HIPCHK(b, hipEventRecord(b->ev_gate, b->cs[ts_i ^ 1]));
-    before_sums = b->ev_gate;
-  }
+  if (!p.use_log) HIPCHK(b, ord.behind_other_sums(ts, ts_i));   // this trace kernel adds to the planes itself: behind the other stream's sums
+  if (p.sums_plain()) HIPCHK(b, ord.gate_sums(ts_i, &before_sums));
 #endif
   if (!p.deterministic && !p.host_pool) {
     // Device generator: one team per sampled crystal, in front of the trace kernel on its stream.  Option "gen_ahead" puts the one of a
@@ -1426,24 +1292,20 @@ int queue_launch(HaloBackend* b, const LaunchPlan& p, const HaloEntry& E, EntryT
     // them, only its pool back from the launch before that one).  Measured (25 M rays per launch): prism pools 4.43 -> 4.55 ms per launch,
     // pyramid pools 7.78 -> 7.70: both kernels are VALU-bound, so sharing the chip conserves the work.  Off by default.
     const bool ahead = b->opt.overlap && b->opt.gen_ahead && !p.alternate;
-    hipStream_t gs = ahead ? b->cs[1] : ts;
-    HIPCHK(b, b->shapes_free[S.shape_set].wait_on(gs));
+    hipStream_t gs = ahead ? ord.gen_ahead_stream() : ts;
+    HIPCHK(b, ord.shapes_free[S.shape_set].wait_on(gs));
     hipError_t ge = launch_shapegen(const_cast<ShapeDev*>(P.shapes), p.geom == 2, p.shape_cnt, b->seed, host::MakeRecipe(E.crystal), S.first_shape, gs, b->opt.gen_serial != 0);
     if (ge != hipSuccess) return hip_fail(b, ge, "halo_shapegen_kernel launch");
-    if (ahead) {
-      HIPCHK(b, hipEventRecord(b->ev_gen, gs));
-      HIPCHK(b, hipStreamWaitEvent(ts, b->ev_gen, 0));
-      b->cs_pending[1] = true;
-    }
+    if (ahead) HIPCHK(b, ord.behind_generator(ts));
   }
-  HIPCHK(b, hipEventRecord(b->ring_ev0[k], ts));  // HIP events on the launch stream bracket the kernel alone
-  b->ring_final[k] = P.final_layer != 0u;
+  HIPCHK(b, hipEventRecord(r.ev0, ts));  // HIP events on the launch stream bracket the kernel alone
+  r.final = P.final_layer != 0u;
   const int launch_geom = launch_geom_of(*b, p, T);
   KernelId launched;
   hipError_t le = launch_trace(P, p.blocks, ts, T.mode, launch_geom, b->mono_session, &launched);
-  if (T.ce) {   // the slot's last reader (see TableCacheEntry): this launch, whose ring_done event is recorded below
-    T.ce->read_ring[T.ce->cur] = k;
-    T.ce->read_use[T.ce->cur] = b->ring_use[k];
+  if (T.ce) {   // the slot's last reader (see TableCacheEntry): this launch, whose slot-done event is recorded below
+    T.ce->read_ring[T.ce->cur] = S.k;
+    T.ce->read_use[T.ce->cur] = r.use;
   }
   // (a launch that closes its session itself leaves the planes as it found them; so does one of the no-accumulation kernels — no_land on one shape,
   // halo_select.h select_kernel: kAccNone has no cache, no exit queue and no code that touches a plane, the log or the twin.  The latter holds for
@@ -1452,10 +1314,10 @@ int queue_launch(HaloBackend* b, const LaunchPlan& p, const HaloEntry& E, EntryT
   b->fix_planes = b->det_session;
   if (le != hipSuccess) return hip_fail(b, le, "halo_trace_kernel launch");   // (nothing ran: no route to record)
   record_route(b, p, P, launched);
-  if (!p.deterministic) HIPCHK(b, b->shapes_free[S.shape_set].mark(ts));
+  if (!p.deterministic) HIPCHK(b, ord.shapes_free[S.shape_set].mark(ts));
   if (int rc = queue_passes(b, p, P, S, ts, ts_i, before_sums)) return rc;
   b->tally_unread = true;
-  b->ring_busy[k] = true;
+  r.busy = true;
   return HALO_OK;
 }
 // Before a deterministic launch of `m` rays: the scales it adds with.  All adds into one unfolded plane set share one F, so the pending planes are
@@ -1503,10 +1365,9 @@ int trace_launch(HaloBackend* b, const LayerCtx& c, LaunchPlan& p, EntryTables& 
   }
   if (c.rays == nullptr && (E.axis.azimuth.type != HALO_DIST_NONE || E.axis.latitude.type != HALO_DIST_NONE || E.axis.roll.type != HALO_DIST_NONE))
     b->sess_orient_samples += m;   // AxisDistribution::IsAxisDeterministic is false: one orientation per ray
-  S.k = b->ring_next;
-  b->ring_next = (S.k + 1) % HaloBackend::kRing;
-  harvest_slot(b, S.k);  // blocks only if the ring has wrapped onto a dispatch still in flight
-  b->ring_use[S.k]++;
+  bool wrapped = false;
+  S.k = b->ord.take(&wrapped);
+  if (wrapped) harvest_slot(b, b->ord.ring[S.k]);  // blocks only if the ring has wrapped onto a dispatch still in flight
   DispatchSlot* ds = nullptr;
   if (int rc = upload_tables(b, c, p, E, P.lat_path, pool.empty() ? nullptr : pool.data(), S.k, T, &ds)) return rc;
   P.lut = ds->lut;
@@ -1529,7 +1390,7 @@ int trace_launch(HaloBackend* b, const LayerCtx& c, LaunchPlan& p, EntryTables& 
     if (turn)   // (its twin with it, for the same reason as the log's second buffer set)
       if (int rc = reserve_idle(b, b->shapes_s[S.shape_set ^ 1], p.shape_cnt)) return rc;
     if (p.host_pool) {
-      HIPCHK(b, b->shapes_free[S.shape_set].wait_on(main_q(b)));
+      HIPCHK(b, b->ord.shapes_free[S.shape_set].wait_on(main_q(b)));
       HIPCHK(b, hipMemcpyAsync(shapes.ptr, pool.data(), pool.size() * sizeof(ShapeDev), hipMemcpyHostToDevice, main_q(b)));
     }
     // (device generator: queued by queue_launch on the launch's trace stream, in front of the trace kernel)
@@ -1808,7 +1669,7 @@ int halo_generate_shapes(halo_handle_t b, const HaloCrystal* crystal, uint64_t f
     DevBuf<ShapePrism> dev;
     HIPCHK(b, dev.reserve(n));
     std::vector<ShapePrism> recs(n);
-    hipError_t ge = launch_shapegen(dev.ptr, true, n, b->seed, host::MakeRecipe(*crystal), first_index, b->stream, b->opt.gen_serial != 0);
+    hipError_t ge = launch_shapegen(dev.ptr, true, n, b->seed, host::MakeRecipe(*crystal), first_index, main_q(b), b->opt.gen_serial != 0);
     if (ge == hipSuccess) ge = hipMemcpyAsync(recs.data(), dev.ptr, static_cast<size_t>(n) * sizeof(ShapePrism), hipMemcpyDeviceToHost, main_q(b));
     if (ge == hipSuccess) ge = hipStreamSynchronize(main_q(b));
     dev.release();
@@ -1830,7 +1691,7 @@ int halo_generate_shapes(halo_handle_t b, const HaloCrystal* crystal, uint64_t f
     HIPCHK(b, hipSetDevice(b->device));
     DevBuf<ShapeDev> dev;
     HIPCHK(b, dev.reserve(n));
-    hipError_t ge = launch_shapegen(dev.ptr, false, n, b->seed, host::MakeRecipe(*crystal), first_index, b->stream, b->opt.gen_serial != 0);
+    hipError_t ge = launch_shapegen(dev.ptr, false, n, b->seed, host::MakeRecipe(*crystal), first_index, main_q(b), b->opt.gen_serial != 0);
     if (ge == hipSuccess) ge = hipMemcpyAsync(pool.data(), dev.ptr, static_cast<size_t>(n) * sizeof(ShapeDev), hipMemcpyDeviceToHost, main_q(b));
     if (ge == hipSuccess) ge = hipStreamSynchronize(main_q(b));
     dev.release();

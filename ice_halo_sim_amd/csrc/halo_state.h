@@ -1,6 +1,6 @@
 // halo_state.h — what the host units of the library share (halo_backend.cpp: sessions, trace path, fixed-point import / export, shards;
-// halo_consumer.cpp: the consumer stages): the owning device and pinned buffers, the stream markers, the backend's state and the helpers that more than
-// one unit calls.  Internal: not installed, not part of include/halo_trace.h.
+// halo_consumer.cpp: the consumer stages): the owning device and pinned buffers, the stream order over the real HIP calls (halo_order.h), the backend's
+// state and the helpers that more than one unit calls.  Internal: not installed, not part of include/halo_trace.h.
 #ifndef HALO_STATE_H_
 #define HALO_STATE_H_
 
@@ -18,6 +18,7 @@
 #include "halo_host.hpp"
 #include "halo_launch.h"
 #include "halo_options.h"
+#include "halo_order.h"
 
 namespace halo {
 
@@ -62,25 +63,21 @@ struct PinnedBuf {
   hipError_t alloc(size_t n) { return hipHostMalloc(reinterpret_cast<void**>(&ptr), n * sizeof(T), hipHostMallocDefault); }
 };
 
-// "The last work of kind X": an event recorded behind that work, and whether anything has been recorded on it yet (nothing: nobody need wait).
-// (Several markers that fall on one point of one stream share one recorded event: mark_at names an event somebody has just recorded there — a ring
-//  slot's — instead of recording the marker's own.  Should that event be recorded again before the marker is, the marker waits for the later point.)
-struct Marker {
-  hipEvent_t ev = nullptr;
-  hipEvent_t at = nullptr;   // the event that carries the marker now: `ev`, or a shared one
-  bool set = false;
-  hipError_t mark(hipStream_t s) {
-    const hipError_t e = hipEventRecord(ev, s);
-    if (e == hipSuccess) at = ev, set = true;
-    return e;
-  }
-  hipError_t mark_at(hipEvent_t shared) {
-    at = shared, set = true;
-    return hipSuccess;
-  }
-  hipError_t wait_on(hipStream_t s) const { return set ? hipStreamWaitEvent(s, at, 0) : hipSuccess; }
-  void clear() { set = false; }
+// The stream order (halo_order.h) over the real calls: streams that do not join the null stream, events timed (the ring's spans) or not.
+struct HipOrderApi {
+  using Stream = hipStream_t;
+  using Event = hipEvent_t;
+  using Error = hipError_t;
+  static constexpr Error kOk = hipSuccess;
+  static Error record(Event e, Stream s) { return hipEventRecord(e, s); }
+  static Error wait(Stream s, Event e) { return hipStreamWaitEvent(s, e, 0); }
+  static Error sync(Stream s) { return hipStreamSynchronize(s); }
+  static Error create_stream(Stream* s) { return hipStreamCreateWithFlags(s, hipStreamNonBlocking); }
+  static Error destroy_stream(Stream s) { return hipStreamDestroy(s); }
+  static Error create_event(Event* e, bool timed) { return timed ? hipEventCreate(e) : hipEventCreateWithFlags(e, hipEventDisableTiming); }
+  static Error destroy_event(Event e) { return hipEventDestroy(e); }
 };
+using Order = StreamOrder<HipOrderApi>;
 
 // The consumer stages' own state (halo_consumer.cpp; RenderConsumer, server/render.hpp): Neumaier running image + total landed intensity, and the
 // device buffers each stage stages its results in.  (The class lanes themselves are written by trace sessions: BackendState::lanes.)
@@ -106,45 +103,21 @@ struct BackendState {
   int device = 0;
   uint32_t seed = 1;
   std::string error;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
   int cu_count = 256;
 
   Options opt;                 // every knob of halo_set_option (halo_options.h)
+  Order ord{&opt};             // the streams, every event that orders them, the markers and the dispatch ring (halo_order.h)
   // Two sets of the hit-log / tile-list buffers, taken in turn by the launches that alternate between the two trace streams (<= 2^21 rays):
   // the one of exactly 2^21 rays that logs may run beside a neighbour.  Launches that fill the chip keep set 0.
   DevBuf<HitRec> bin_list_s[2], bin_list2_s[2];   // one-level tile lists / coarse lists / log regions; tile lists of the two-level and log routes
   DevBuf<uint32_t> bin_cnt_s[2], bin_cnt2_s[2];
   int log_set = 0;                      // the set the next logged launch writes
-  Marker set_free[2];                   // the passes that last read log set s (they may still be running)
-  // Auxiliary stream (round 5): the closing folds are queued here, behind everything the other streams hold, and nobody waits for them until
-  // somebody reads the image or adds to the planes again — a session's fold (20 us) runs under the next session's first kernels instead of
-  // in front of them.  (Two engines side by side on one GPU had measured +10 .. 15 % over one, tools/two_engines_probe.py; what that was,
-  // looked at inside one engine, is the small things between kernels — folds, resets, uploads, the tails — not the trace kernels or their
-  // passes, which gain nothing from running under each other: see queue_passes.)
-  hipStream_t aux = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  bool aux_pending = false;             // work has been queued on `aux` that the main stream has not waited for
-  // Two trace streams: consecutive launches alternate between them, so that launch k+1's workgroups fill the CUs that launch k's last
-  // workgroups leave idle (kernels of ONE stream run one after the other: the tail of every 1.8 ms trace kernel, and the whole of a
-  // latency-bound small launch, went unshared).  Trace kernels of different launches have nothing to order between them: each logs to its own
-  // buffer set or adds with atomics, tallies and continuation appends are atomic.  What they must follow is on the main stream (table
-  // uploads) or the auxiliary one (a fold or per-tile pass before a launch that adds to the planes itself): waited for by events.
-  hipStream_t cs[2] = {nullptr, nullptr};
-  hipEvent_t ev_cs[2] = {nullptr, nullptr}, ev_main = nullptr, ev_aux = nullptr;
-  bool cs_pending[2] = {false, false};
-  int cs_next = 0;
-  bool main_dirty[2] = {true, true};    // the main stream has been given work (main_q) since trace stream i last waited for it
-  uint64_t aux_seq = 0, cs_seen_aux[2] = {0, 0};   // (a trace stream waits for the auxiliary stream only when that holds work it has not waited for yet)
   int twin_set = 0;                     // which half of the fp64 twin the open / next session's overflows go to (the other half may still be folding)
   uint32_t mono_s_log2 = 0;    // log2 of the columns per row of the plane (kMonoRows rows; see MonoSlot)
   // Direct close: a logged launch that is its whole session — one plane, one copy, nothing pending in the planes — has its per-tile
   // pass add coef x sum to the XYZ image itself (launch_log_route_close): no plane write, no fold on the auxiliary stream, no stream hop in front of
-  // the next session's trace kernel.  The pass is a PLAIN read-modify-write of the image and of the twin's half, on the launch's trace stream: a later
-  // launch on the other trace stream waits for it (close_done), readers and folds join the trace streams as they always do.
+  // the next session's trace kernel.  (What a later launch on the other trace stream owes such a pass: Order::close_done.)
   uint64_t direct_closes = 0;  // launches that closed their session directly, ever (halo_direct_closes)
-  Marker close_done;           // the direct close queued last, on trace stream close_ts
-  int close_ts = 0;
   bool cnt2_clean[2] = {false, false};   // log set s: the tile-list counters are known to be zero (the closing pass zeroes what it consumed)
   // Per-tile append: a directly closing launch whose kernel has a kAccTileFinal twin appends its records to per-tile chunks of each
   // workgroup (halo_trace.inl log_hit_tile) and the closing pass reads the chunks (launch_tile_route_close): the split pass and its tile lists go.
@@ -198,7 +171,6 @@ struct BackendState {
   bool mono_two = false;
   int mono_set = 0;
   size_t mono_half = 0;                                   // floats per set
-  Marker set_folded[2];                                   // the fold that last zeroed the set
   uint32_t plane_cnt = 1, plane_copies = 8;
   std::vector<std::array<float, 3>> plane_coef;  // fold coefficients of the pending planes
   Consumer cons;               // the consumer stages' state (halo_consumer.cpp)
@@ -210,20 +182,9 @@ struct BackendState {
   double time_trace_ms = 0.0, time_post_ms = 0.0;   // halo_collect_timing: the last layers' trace kernels' own spans and their passes', since the last call
   uint64_t time_launches = 0;          // a dispatch has been queued since the statistics were last pulled
   DevBuf<uint32_t> counters;   // kCntNum
-  // dispatch ring: device slots, pinned host mirrors, pinned tally read-back, per-slot events
-  static constexpr int kRing = 32;
-  DevBuf<DispatchSlot> ring_dev;
-  PinnedBuf<DispatchSlot> ring_host;
-  hipEvent_t ring_ev0[kRing] = {}, ring_ev1[kRing] = {}, ring_ev2[kRing] = {}, ring_ev3[kRing] = {}, ring_done[kRing] = {};   // ev0..ev1 the trace kernel (main stream), ev2..ev3 its passes (post stream)
-  // (the events that CARRY a slot's "passes begin" and "slot done" for its current launch: ring_ev2 / ring_done themselves, or — option
-  //  lean_events — the neighbour recorded at the same point of the same stream: ring_ev1 where no wait lies between it and the passes, ring_ev3
-  //  behind a direct close)
-  hipEvent_t ring_t2[kRing] = {}, ring_fin[kRing] = {};
-  bool ring_posts[kRing] = {};
-  bool ring_final[kRing] = {};         // the slot's launch belongs to its session's last layer (halo_collect_timing counts those)
-  bool ring_busy[kRing] = {};
-  uint64_t ring_use[kRing] = {};       // how many launches have taken the slot (TableCacheEntry::read_use)
-  int ring_next = 0;
+  // dispatch ring (Order::ring holds each slot's events and use count): device slots and their pinned host mirrors
+  DevBuf<DispatchSlot> slots_dev;
+  PinnedBuf<DispatchSlot> slots_host;
   // Table cache (round 5): the dispatch-constant tables of a deterministic crystal entry (latitude LUT, wavelength pool, shape, entry-pick
   // tables, filter / colour tables) stay on the device from one dispatch to the next while scene, wavelength, filters, colour and options
   // are what they were — a server that sends one wavelength's rays as many equal small sessions (and every chunk of a long layer) then
@@ -236,7 +197,7 @@ struct BackendState {
     // staging their tables out of the slot they were given.  An upload waits (on the stream, not the host) for the last kernel that read ITS
     // slot — two table sets back, as good as always finished — so consecutive sessions of different wavelengths still overlap.
     int cur = 0;
-    // the slot's last reader = the dispatch-ring slot of the last launch that was given it (its ring_done event is recorded anyway: no
+    // the slot's last reader = the dispatch-ring slot of the last launch that was given it (its slot-done event is recorded anyway: no
     // event of the cache's own, one HIP call less per small session) and that ring slot's use count then: a ring slot that has been taken
     // again since was harvested first, i.e. that launch is over
     int read_ring[2] = {-1, -1};
@@ -255,15 +216,7 @@ struct BackendState {
   struct LutKey { int32_t type; float center, spread; host::LatLut lut; };
   std::vector<LutKey> lut_cache;
   DevBuf<ShapeDev> shapes_s[2];   // sampled-crystal pools: launch k+1's generator must not overwrite what launch k still traces
-  Marker shapes_free[2];                               // the trace kernel that last read the pool
-  hipEvent_t ev_gen = nullptr;                         // the generator of a chip-filling launch, queued on trace stream 1 (see gen_ahead)
   int shapes_next = 0;
-  // Plane ownership between the two trace streams.  The per-tile sums of a logged (or two-level binned) launch end in PLAIN read-modify-writes of
-  // the planes; everything else that adds to them uses atomics.  So (1) a launch's sums wait for what the OTHER trace stream held when the launch
-  // was queued (ev_gate), and (2) a later launch on the other stream whose trace kernel adds to the planes itself waits for those sums (rmw).
-  // Logged trace kernels touch no plane (their overflow goes to the fp64 twin), so they run beside a neighbour's passes freely.
-  hipEvent_t ev_gate = nullptr;
-  Marker rmw[2];                  // the per-tile sums last queued on trace stream i
   // Deterministic sessions (option "deterministic"): every accumulating launch runs a kAccFixed kernel — 64-bit fixed-point sums from the first add
   // to the fold, so the plane sums depend on the set of rays alone.  The planes are a buffer of their own, [plane][slot], one copy,
   // all-zero between folds like the float planes; F and the budget belong to the PENDING plane set (they may span sessions under lazy_fold).
@@ -298,11 +251,6 @@ struct BackendState {
   DevBuf<float> host_f;        // injected rays: d | p | w
   DevBuf<uint32_t> host_u;
   uint64_t sess_crystal_samples = 0, sess_orient_samples = 0;  // this session's stochastic draws (halo_last_sample_counts)
-  // every event made without timing: the one-shot ones, the joins' and the markers' (created in halo_create, destroyed in halo_destroy)
-  std::vector<hipEvent_t*> untimed_events() {
-    return {&ev_cs[0], &ev_cs[1], &ev_main, &ev_aux, &ev_fork, &ev_join, &ev_gen, &ev_gate, &set_free[0].ev, &set_free[1].ev, &shapes_free[0].ev,
-            &shapes_free[1].ev, &rmw[0].ev, &rmw[1].ev, &set_folded[0].ev, &set_folded[1].ev, &close_done.ev};
-  }
 };
 
 }  // namespace halo
@@ -321,14 +269,17 @@ int hip_fail(HaloBackend* b, hipError_t e, const char* what);
   } while (0)
 
 // The main stream, for whoever queues work on it (or waits for it): the trace streams have not seen that work yet (next_trace_stream).
-inline hipStream_t main_q(HaloBackend* b) {
-  b->main_dirty[0] = b->main_dirty[1] = true;
-  return b->stream;
-}
+inline hipStream_t main_q(HaloBackend* b) { return b->ord.main_q(); }
 // What the main stream is given from here on runs behind everything queued on the auxiliary and the trace streams (no host wait).
-int join_aux(HaloBackend* b);
+inline int join_aux(HaloBackend* b) {
+  HIPCHK(b, b->ord.join());
+  return HALO_OK;
+}
 // Host waits for all streams.
-int sync_all(HaloBackend* b);
+inline int sync_all(HaloBackend* b) {
+  HIPCHK(b, b->ord.sync_all());
+  return HALO_OK;
+}
 // DevBuf::reserve frees the old allocation when it grows: nothing on either stream may still be using it.
 template <typename T>
 int reserve_idle(HaloBackend* b, DevBuf<T>& buf, size_t n, hipError_t* err = nullptr) {

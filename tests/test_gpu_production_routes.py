@@ -815,7 +815,7 @@ def test_equal_small_sessions_equal_one_large_session():
 def test_mixed_session_sizes_on_two_streams_equal_one_stream():
     """Sessions of mixed sizes queued back to back take the two trace streams in turn (<= 2^25 rays), and their routes differ in HOW they add to
     the planes: logged launches (>= 2^21 rays) end in plain read-modify-writes by their per-tile sums, smaller ones add with atomics from the
-    trace kernel.  Events keep a plain write-out from running beside any other writer of the same planes (halo_backend.cpp: ev_gate / ev_rmw).
+    trace kernel.  Events keep a plain write-out from running beside any other writer of the same planes (halo_order.h: gate_sums / rmw).
     What this test can show is that the two-stream run of such a mix gives the one-stream run's image pixel by pixel (a lost update would be
     a pixel missing a whole tile sum, tens of per cent; float-order differences are ~1e-5 of a pixel) and its tallies exactly.  It is NOT a race
     detector: a build without the gates (-DHALO_NO_PLANE_GATES) passes it too, the window being a few nanoseconds per slot — the ordering

@@ -168,6 +168,15 @@ class HaloViewSpec(C.Structure):
     _fields_ = [("view", HaloRender), ("has_source", C.c_int32), ("source", HaloRender), ("display", HaloDisplay)]
 
 
+VIEW_NEAREST, VIEW_BILINEAR = 0, 1
+VIEW_FILTERS = {"nearest": VIEW_NEAREST, "bilinear": VIEW_BILINEAR}
+
+
+class HaloViewFilter(C.Structure):
+    """halo_consumer_view_filtered's filter: VIEW_NEAREST | VIEW_BILINEAR, blend 0 | 1 (a dual-fisheye source's overlap band), two zero words."""
+    _fields_ = [("filter", C.c_int32), ("blend", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 COMPOSITE_DOMINANT, COMPOSITE_ADDITIVE, COMPOSITE_PAINTER = 0, 1, 2
 
 

@@ -93,6 +93,8 @@ def load_library():
         "halo_host_binned_sum": (C.c_int, [C.POINTER(C.c_uint64), C.c_int32, C.POINTER(C.c_double)]),
         "halo_consumer_view": (C.c_int, [H, C.POINTER(abi.HaloViewSpec), C.POINTER(C.c_uint8), f32p, C.POINTER(C.c_int32), f32p]),
         "halo_host_view_direction": (C.c_int, [C.POINTER(abi.HaloRender), C.c_int32, C.c_int32, f32p]),
+        "halo_consumer_view_filtered": (C.c_int, [H, C.POINTER(abi.HaloViewSpec), C.POINTER(abi.HaloViewFilter), C.POINTER(C.c_uint8), f32p, C.POINTER(C.c_int32), f32p, f32p]),
+        "halo_host_view_source_pos": (C.c_int, [C.POINTER(abi.HaloRender), f32p, f32p]),
         "halo_consumer_composite": (C.c_int, [H, C.POINTER(abi.HaloComposite), f32p, C.POINTER(C.c_uint8), f32p, C.POINTER(C.c_int32)]),
         "halo_consumer_load_lanes": (C.c_int, [H, f32p, C.c_int, C.c_int, C.c_int, C.c_double]),
         "halo_host_parse_composite_mode": (C.c_int, [C.c_char_p]),
@@ -129,7 +131,7 @@ EXPORTED_SYMBOLS = [
     "halo_peek_fixed", "halo_host_fixed_frac_bits", "halo_begin_spectrum", "halo_host_spectrum_entry",
     "halo_consumer_auto_ev", "halo_host_ev_auto",
     "halo_consumer_stats", "halo_host_percentile_rank", "halo_host_binned_sum",
-    "halo_consumer_view", "halo_host_view_direction",
+    "halo_consumer_view", "halo_host_view_direction", "halo_consumer_view_filtered", "halo_host_view_source_pos",
     "halo_set_shard", "halo_host_shard_slice", "halo_export_fixed", "halo_import_fixed",
 ]
 
@@ -459,16 +461,22 @@ class HipTraceBackend:
                                                    xyz.ctypes.data_as(C.POINTER(C.c_float)) if want_xyz else None, C.byref(tot)))
         return rgb, xyz, tot.value
 
-    def View(self, view, source=None, intensity_factor=1.0, ray_color=(-1.0, -1.0, -1.0), background=(0.0, 0.0, 0.0), want=("rgb",)):
+    def View(self, view, source=None, intensity_factor=1.0, ray_color=(-1.0, -1.0, -1.0), background=(0.0, 0.0, 0.0), want=("rgb",), filter="nearest", blend=False):
         """The consumer's image through another lens (halo_consumer_view): `view` is a HaloRender (scenes.render) to look through, `source` the
         render the image was accumulated under (None: this handle's last session's).  Per view pixel the direction of its centre under the view's
         lens, the source pixel that direction lands on, that pixel's raw XYZ and its display transform — a gather on the device, no ray is traced.
         want: any of "rgb" (uint8[H,W,3]), "xyz" (float32[H,W,3]), "map" (int32[H,W]: row-major source pixel, -1 for none), "dir"
         (float32[H,W,3]: world exit direction, zeros for none); returns a dict of the arrays asked for.  The display arguments are Snapshot's
-        (an automatic exposure is the CONSUMER's: intensity_factor * 2 ** AutoEv()["ev_auto"])."""
-        unknown = set(want) - {"rgb", "xyz", "map", "dir"}
+        (an automatic exposure is the CONSUMER's: intensity_factor * 2 ** AutoEv()["ev_auto"]).
+        filter="bilinear": four taps around the continuous source position instead of the copy; blend=True: a dual-fisheye source's overlap band is
+        cross-faded in as the reference's preview does; want may then name "tap" (float32[H,W,5]: fx0, fy0, fx1, fy1, t — what the values were
+        made from).  Any of the three makes the call halo_consumer_view_filtered; the defaults are halo_consumer_view and its bytes."""
+        unknown = set(want) - {"rgb", "xyz", "map", "dir", "tap"}
         if unknown:
             raise ValueError("View: unknown output %r" % sorted(unknown))
+        if filter not in abi.VIEW_FILTERS:
+            raise ValueError("View: unknown filter %r (nearest | bilinear)" % (filter,))
+        filtered = filter != "nearest" or bool(blend) or "tap" in want
         spec = abi.HaloViewSpec()
         spec.view = view
         spec.has_source = 0 if source is None else 1
@@ -477,12 +485,18 @@ class HipTraceBackend:
         spec.display = abi.HaloDisplay(float(intensity_factor), (C.c_float * 3)(*ray_color), (C.c_float * 3)(*background))
         h, w = max(int(view.height), 0), max(int(view.width), 0)
         big = w * h > 1 << 25   # (refused by the library: nothing of that size is allocated here)
-        shapes = {"rgb": ((h, w, 3), np.uint8), "xyz": ((h, w, 3), np.float32), "map": ((h, w), np.int32), "dir": ((h, w, 3), np.float32)}
+        shapes = {"rgb": ((h, w, 3), np.uint8), "xyz": ((h, w, 3), np.float32), "map": ((h, w), np.int32), "dir": ((h, w, 3), np.float32),
+                  "tap": ((h, w, 5), np.float32)}
         out = {k: np.empty((0,) if big else shapes[k][0], shapes[k][1]) for k in want}
 
         def ptr(k, t):
             return out[k].ctypes.data_as(C.POINTER(t)) if k in out else None
-        self._check(self._L.halo_consumer_view(self._h, C.byref(spec), ptr("rgb", C.c_uint8), ptr("xyz", C.c_float), ptr("map", C.c_int32), ptr("dir", C.c_float)))
+        if filtered:
+            f = abi.HaloViewFilter(abi.VIEW_FILTERS[filter], 1 if blend else 0)
+            self._check(self._L.halo_consumer_view_filtered(self._h, C.byref(spec), C.byref(f), ptr("rgb", C.c_uint8), ptr("xyz", C.c_float), ptr("map", C.c_int32),
+                                                            ptr("dir", C.c_float), ptr("tap", C.c_float)))
+        else:
+            self._check(self._L.halo_consumer_view(self._h, C.byref(spec), ptr("rgb", C.c_uint8), ptr("xyz", C.c_float), ptr("map", C.c_int32), ptr("dir", C.c_float)))
         return out
 
     def ResetConsumer(self):
@@ -571,3 +585,12 @@ EXIT_DTYPE = np.dtype([("dir", np.float32, 3), ("weight", np.float32), ("root", 
                        ("layer", np.uint8), ("path_len", np.uint8), ("path", np.uint8, abi.PATH_CAP),
                        ("pixel", np.int32), ("crystal_id", np.uint16), ("wl_idx", np.uint16), ("color_mask", np.uint64)])
 assert EXIT_DTYPE.itemsize == C.sizeof(abi.HaloExitRecord)
+
+
+def host_view_source_pos(source, direction):
+    """halo_host_view_source_pos: (hit count, float32[5] = fx0, fy0, fx1, fy1, t) of the exit direction `direction` under the HaloRender `source`,
+    by the filtered view's own code on the host (no device needed)."""
+    d = np.ascontiguousarray(direction, np.float32)
+    pos = np.zeros(5, np.float32)
+    n = load_library().halo_host_view_source_pos(C.byref(source), d.ctypes.data_as(C.POINTER(C.c_float)), pos.ctypes.data_as(C.POINTER(C.c_float)))
+    return int(n), pos

@@ -245,6 +245,12 @@ def main(argv=None):
     ap.add_argument("--view-size", default=None, metavar="WxH", help="size of --out-view (default: the traced render's)")
     ap.add_argument("--view-visible", default=None, choices=sorted(config.VISIBLE_NAMES), help="visible range of --out-view (default: the traced render's)")
     ap.add_argument("--view-overlap", type=float, default=None, help="dual-fisheye overlap of --out-view (default: the traced render's)")
+    ap.add_argument("--view-filter", default="nearest", choices=("nearest", "bilinear"),
+                    help="how --out-view reads the traced image: nearest copies the source pixel under each view pixel (default); bilinear weighs the four "
+                    "around the exact spot, as the reference's preview does — for views that magnify the traced image")
+    ap.add_argument("--view-blend", action="store_true",
+                    help="--out-view of a dual-fisheye render traced with an overlap: cross-fade the two hemispheres across the overlap band, as the "
+                    "reference's preview does, so that no seam shows at the horizon (changes nothing without an overlap)")
     ap.add_argument("--out-lanes", default=None, help="raypath_color configs: write the per-class Y lanes (classes, H, W) as .npy")
     ap.add_argument("--out-composite", default=None, help="raypath_color configs: write the class composite (the config's mode: dominant | additive | "
                     "painter; component_compositor.cpp) as binary PPM, composited on the device")
@@ -351,7 +357,7 @@ def main(argv=None):
         np.save(args.out_xyz, xyz)
     if args.out_view:
         try:
-            write_ppm(args.out_view, be.View(view_render(args, res["render"]), res["render"], **display)["rgb"])
+            write_ppm(args.out_view, be.View(view_render(args, res["render"]), res["render"], filter=args.view_filter, blend=args.view_blend, **display)["rgb"])
         except config.ConfigError as e:
             print("config error: %s" % e, file=sys.stderr)
             be.close()

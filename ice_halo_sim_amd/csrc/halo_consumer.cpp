@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstring>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "halo_state.h"
@@ -37,6 +38,57 @@ int start_image(HaloBackend* b, int w, int h) {
   HIPCHK(b, hipMemsetAsync(b->cons.sum.ptr, 0, n * sizeof(float), main_q(b)));
   HIPCHK(b, hipMemsetAsync(b->cons.comp.ptr, 0, n * sizeof(float), main_q(b)));
   b->cons.total_intensity = 0.0;
+  return HALO_OK;
+}
+
+// halo_consumer_view and halo_consumer_view_filtered (`filter` != nullptr: its kernel and its fifth output): the argument checks, the launch, the
+// copy-back.  `who` names the call in the messages.
+int view_call(HaloBackend* b, const char* who, const HaloViewSpec* spec, const HaloViewFilter* filter, uint8_t* rgb_out, float* xyz_out, int32_t* map_out, float* dir_out,
+              float* tap_out) {
+  if (!b) return HALO_FATAL;
+  const std::string name(who);
+  if (!spec) return fail(b, HALO_FATAL, name + ": spec is NULL");
+  if (!b->cons.sum.ptr) return fail(b, HALO_FATAL, name + " before consumer_fold");
+  if (b->in_session) return fail(b, HALO_FATAL, name + " inside a session");
+  if (!rgb_out && !xyz_out && !map_out && !dir_out && !tap_out) return fail(b, HALO_FATAL, name + ": every output is NULL");
+  const HaloRender& view = spec->view;
+  if (view.width <= 0 || view.height <= 0) return fail(b, HALO_FATAL, name + ": empty view");
+  if (static_cast<uint64_t>(view.width) * static_cast<uint64_t>(view.height) > (1ull << 25))
+    return fail(b, HALO_UNAVAILABLE, name + ": a view of more than 2^25 pixels");
+  if (!spec->has_source && !b->had_session) return fail(b, HALO_FATAL, name + ": no source render (has_source = 0 on a handle that has had no session)");
+  const HaloRender& source = spec->has_source ? spec->source : b->render;
+  if (source.width != b->cons.w || source.height != b->cons.h) return fail(b, HALO_FATAL, name + ": the source render's size is not the consumer's");
+  if (view.lens_type < HALO_LENS_LINEAR || view.lens_type > HALO_LENS_GLOBE || source.lens_type < HALO_LENS_LINEAR || source.lens_type > HALO_LENS_GLOBE)
+    return fail(b, HALO_FATAL, name + ": unknown lens type");
+  HIPCHK(b, hipSetDevice(b->device));
+  const uint32_t cons_pix = static_cast<uint32_t>(b->cons.w) * static_cast<uint32_t>(b->cons.h);
+  const size_t npix = static_cast<size_t>(view.width) * static_cast<size_t>(view.height), n = npix * 3;
+  const float scale = exposure_scale(b, spec->display.intensity_factor, cons_pix);   // over the CONSUMER's pixels, as halo_consumer_snapshot: a view pixel is its source pixel's byte
+  if (rgb_out) HIPCHK(b, b->cons.view_rgb.reserve(n));
+  if (xyz_out) HIPCHK(b, b->cons.view_xyz.reserve(n));
+  if (dir_out) HIPCHK(b, b->cons.view_dir.reserve(n));
+  if (map_out) HIPCHK(b, b->cons.view_map.reserve(npix));
+  if (tap_out) HIPCHK(b, b->cons.view_tap.reserve(npix * 5));
+  uint8_t* rgb_dev = rgb_out ? b->cons.view_rgb.ptr : nullptr;
+  float* xyz_dev = xyz_out ? b->cons.view_xyz.ptr : nullptr;
+  int32_t* map_dev = map_out ? b->cons.view_map.ptr : nullptr;
+  float* dir_dev = dir_out ? b->cons.view_dir.ptr : nullptr;
+  hipError_t e;
+  if (filter)
+    e = launch_view_filtered(b->cons.sum.ptr, b->cons.comp.ptr, host::BuildProj(view), host::BuildProj(source), scale, spec->display.ray_color, spec->display.background,
+                             filter->filter == HALO_VIEW_BILINEAR, filter->blend != 0, rgb_dev, xyz_dev, map_dev, dir_dev, tap_out ? b->cons.view_tap.ptr : nullptr,
+                             b->cu_count * 8, main_q(b));
+  else
+    e = launch_view(b->cons.sum.ptr, b->cons.comp.ptr, host::BuildProj(view), host::BuildProj(source), scale, spec->display.ray_color, spec->display.background, rgb_dev,
+                    xyz_dev, map_dev, dir_dev, b->cu_count * 8, main_q(b));
+  if (e != hipSuccess) return hip_fail(b, e, filter ? "halo_view_filtered_kernel launch" : "halo_view_kernel launch");
+  if (rgb_out) HIPCHK(b, hipMemcpyAsync(rgb_out, b->cons.view_rgb.ptr, n, hipMemcpyDeviceToHost, main_q(b)));
+  if (xyz_out) HIPCHK(b, hipMemcpyAsync(xyz_out, b->cons.view_xyz.ptr, n * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
+  if (map_out) HIPCHK(b, hipMemcpyAsync(map_out, b->cons.view_map.ptr, npix * sizeof(int32_t), hipMemcpyDeviceToHost, main_q(b)));
+  if (dir_out) HIPCHK(b, hipMemcpyAsync(dir_out, b->cons.view_dir.ptr, n * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
+  if (tap_out) HIPCHK(b, hipMemcpyAsync(tap_out, b->cons.view_tap.ptr, npix * 5 * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
+  HIPCHK(b, hipStreamSynchronize(main_q(b)));
+  if (rgb_out && scale == 0.0f) std::memset(rgb_out, 0, n);   // PostSnapshot's early-out, as halo_consumer_snapshot has it
   return HALO_OK;
 }
 
@@ -237,39 +289,17 @@ int halo_consumer_stats(halo_handle_t b, const HaloStatsSpec* spec, HaloImageSta
 
 // ---- the view stage (halo_view.hip): the consumer's image through another lens -------------------------------
 int halo_consumer_view(halo_handle_t b, const HaloViewSpec* spec, uint8_t* rgb_out, float* xyz_out, int32_t* map_out, float* dir_out) {
+  return view_call(b, "consumer_view", spec, nullptr, rgb_out, xyz_out, map_out, dir_out, nullptr);
+}
+
+int halo_consumer_view_filtered(halo_handle_t b, const HaloViewSpec* spec, const HaloViewFilter* filter, uint8_t* rgb_out, float* xyz_out, int32_t* map_out, float* dir_out,
+                                float* tap_out) {
   if (!b) return HALO_FATAL;
-  if (!spec) return fail(b, HALO_FATAL, "consumer_view: spec is NULL");
-  if (!b->cons.sum.ptr) return fail(b, HALO_FATAL, "consumer_view before consumer_fold");
-  if (b->in_session) return fail(b, HALO_FATAL, "consumer_view inside a session");
-  if (!rgb_out && !xyz_out && !map_out && !dir_out) return fail(b, HALO_FATAL, "consumer_view: every output is NULL");
-  const HaloRender& view = spec->view;
-  if (view.width <= 0 || view.height <= 0) return fail(b, HALO_FATAL, "consumer_view: empty view");
-  if (static_cast<uint64_t>(view.width) * static_cast<uint64_t>(view.height) > (1ull << 25))
-    return fail(b, HALO_UNAVAILABLE, "consumer_view: a view of more than 2^25 pixels");
-  if (!spec->has_source && !b->had_session) return fail(b, HALO_FATAL, "consumer_view: no source render (has_source = 0 on a handle that has had no session)");
-  const HaloRender& source = spec->has_source ? spec->source : b->render;
-  if (source.width != b->cons.w || source.height != b->cons.h) return fail(b, HALO_FATAL, "consumer_view: the source render's size is not the consumer's");
-  if (view.lens_type < HALO_LENS_LINEAR || view.lens_type > HALO_LENS_GLOBE || source.lens_type < HALO_LENS_LINEAR || source.lens_type > HALO_LENS_GLOBE)
-    return fail(b, HALO_FATAL, "consumer_view: unknown lens type");
-  HIPCHK(b, hipSetDevice(b->device));
-  const uint32_t cons_pix = static_cast<uint32_t>(b->cons.w) * static_cast<uint32_t>(b->cons.h);
-  const size_t npix = static_cast<size_t>(view.width) * static_cast<size_t>(view.height), n = npix * 3;
-  const float scale = exposure_scale(b, spec->display.intensity_factor, cons_pix);   // over the CONSUMER's pixels, as halo_consumer_snapshot: a view pixel is its source pixel's byte
-  if (rgb_out) HIPCHK(b, b->cons.view_rgb.reserve(n));
-  if (xyz_out) HIPCHK(b, b->cons.view_xyz.reserve(n));
-  if (dir_out) HIPCHK(b, b->cons.view_dir.reserve(n));
-  if (map_out) HIPCHK(b, b->cons.view_map.reserve(npix));
-  hipError_t e = launch_view(b->cons.sum.ptr, b->cons.comp.ptr, host::BuildProj(view), host::BuildProj(source), scale, spec->display.ray_color, spec->display.background,
-                             rgb_out ? b->cons.view_rgb.ptr : nullptr, xyz_out ? b->cons.view_xyz.ptr : nullptr, map_out ? b->cons.view_map.ptr : nullptr,
-                             dir_out ? b->cons.view_dir.ptr : nullptr, b->cu_count * 8, main_q(b));
-  if (e != hipSuccess) return hip_fail(b, e, "halo_view_kernel launch");
-  if (rgb_out) HIPCHK(b, hipMemcpyAsync(rgb_out, b->cons.view_rgb.ptr, n, hipMemcpyDeviceToHost, main_q(b)));
-  if (xyz_out) HIPCHK(b, hipMemcpyAsync(xyz_out, b->cons.view_xyz.ptr, n * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
-  if (map_out) HIPCHK(b, hipMemcpyAsync(map_out, b->cons.view_map.ptr, npix * sizeof(int32_t), hipMemcpyDeviceToHost, main_q(b)));
-  if (dir_out) HIPCHK(b, hipMemcpyAsync(dir_out, b->cons.view_dir.ptr, n * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
-  HIPCHK(b, hipStreamSynchronize(main_q(b)));
-  if (rgb_out && scale == 0.0f) std::memset(rgb_out, 0, n);   // PostSnapshot's early-out, as halo_consumer_snapshot has it
-  return HALO_OK;
+  if (!filter) return fail(b, HALO_FATAL, "consumer_view_filtered: filter is NULL");
+  if (filter->filter != HALO_VIEW_NEAREST && filter->filter != HALO_VIEW_BILINEAR) return fail(b, HALO_FATAL, "consumer_view_filtered: unknown filter");
+  if (filter->blend != 0 && filter->blend != 1) return fail(b, HALO_FATAL, "consumer_view_filtered: blend must be 0 or 1");
+  if (filter->reserved[0] != 0 || filter->reserved[1] != 0) return fail(b, HALO_FATAL, "consumer_view_filtered: reserved words must be zero");
+  return view_call(b, "consumer_view_filtered", spec, filter, rgb_out, xyz_out, map_out, dir_out, tap_out);
 }
 
 // ---- display-side composite of the class lanes (server/component_compositor.cpp) -------------------------

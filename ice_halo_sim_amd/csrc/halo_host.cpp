@@ -961,5 +961,14 @@ bool ViewDirection(const HaloRender& view, int px, int py, float dir[3]) {
   return view_direction(p, pre, px, py, dir);
 }
 
+int ViewSourcePos(const HaloRender& source, const float dir[3], float pos[5]) {
+  pos[0] = pos[1] = pos[2] = pos[3] = pos[4] = 0.0f;
+  if (source.lens_type < HALO_LENS_LINEAR || source.lens_type > HALO_LENS_GLOBE) return 0;
+  const ProjDev p = BuildProj(source);
+  float pre[4];
+  view_proj_pre(p, pre);
+  return view_source_pos(p, pre, dir[0], dir[1], dir[2], pos);
+}
+
 }  // namespace host
 }  // namespace halo

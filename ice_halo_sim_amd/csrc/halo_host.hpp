@@ -83,6 +83,9 @@ double BinnedSum(const uint64_t* bins, bool squares);
 // The host half of halo_consumer_view: the world exit direction the lens of `view` puts on the centre of pixel (px, py) — halo_view.h
 // view_direction on BuildProj(view), the code halo_view_kernel runs.  false (and zeros) where the pixel has no direction or lies outside the frame.
 bool ViewDirection(const HaloRender& view, int px, int py, float dir[3]);
+// ... and of halo_consumer_view_filtered: where the exit direction `dir` lands under `source`, continuous — halo_view.h view_source_pos on
+// BuildProj(source): {fx0, fy0, fx1, fy1, t}, the hit count returned (0 and zeros: culled, or an unknown lens).
+int ViewSourcePos(const HaloRender& source, const float dir[3], float pos[5]);
 
 }  // namespace host
 

@@ -72,6 +72,11 @@ int halo_host_view_direction(const HaloRender* view, int32_t px, int32_t py, flo
   if (!view || !dir) return 0;
   return host::ViewDirection(*view, px, py, dir) ? 1 : 0;
 }
+int halo_host_view_source_pos(const HaloRender* source, const float dir[3], float pos[5]) {
+  if (pos) pos[0] = pos[1] = pos[2] = pos[3] = pos[4] = 0.0f;
+  if (!source || !dir || !pos) return 0;
+  return host::ViewSourcePos(*source, dir, pos);
+}
 
 // ---- display-side composite of the class lanes (server/component_compositor.cpp) -------------------------
 int halo_host_parse_composite_mode(const char* mode) {   // ParseCompositeMode, component_compositor.cpp:118-134
@@ -195,6 +200,7 @@ uint64_t halo_abi_sizeof(int which) {
     case 13: return sizeof(HaloStatsSpec);
     case 14: return sizeof(HaloImageStats);
     case 15: return sizeof(HaloViewSpec);
+    case 16: return sizeof(HaloViewFilter);
     default: return 0;
   }
 }

@@ -111,6 +111,12 @@ hipError_t launch_stats(const float* sum, const float* comp, const double* lane,
 // may be null: rgb 3 bytes, xyz / dir 3 floats, map one int32 per view pixel.  `blocks` caps the grid; more tiles than that are strided over.
 hipError_t launch_view(const float* sum, const float* comp, const ProjDev& view, const ProjDev& source, float scale, const float ray_color[3], const float background[3],
                        uint8_t* rgb_out, float* xyz_out, int32_t* map_out, float* dir_out, int blocks, hipStream_t stream);
+// ... and its filtered form (halo_consumer_view_filtered): the sample is bilinear (`bilinear`; else the copy above) at the continuous position
+// halo_view.h view_source_pos gives, a dual source's overlap write is cross-faded in with the reference's tent weight (`blend`), and `tap_out`
+// (may be null) takes the five floats {fx0, fy0, fx1, fy1, t} per view pixel the values were made from.  A kernel of its own: launch_view's stays.
+hipError_t launch_view_filtered(const float* sum, const float* comp, const ProjDev& view, const ProjDev& source, float scale, const float ray_color[3],
+                                const float background[3], bool bilinear, bool blend, uint8_t* rgb_out, float* xyz_out, int32_t* map_out, float* dir_out, float* tap_out,
+                                int blocks, hipStream_t stream);
 hipError_t launch_cont_reorder(const float* in, uint32_t in_stride, uint32_t region, const uint32_t* cnt, uint32_t max_fill, const uint32_t* mask, uint32_t n_roots,
                                uint32_t* tile_sum, uint32_t* base, float* out, uint32_t out_stride, uint32_t n_cont, uint32_t planes, uint32_t* err, hipStream_t stream);
 

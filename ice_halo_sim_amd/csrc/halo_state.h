@@ -92,7 +92,7 @@ struct Consumer {
   DevBuf<uint32_t> stats_ws;             // halo_consumer_stats: the StatsRecord, then the multi-block form's histograms (its values go to aev_vals)
   // halo_consumer_view: the view's four outputs before they are copied back
   DevBuf<uint8_t> view_rgb;
-  DevBuf<float> view_xyz, view_dir;
+  DevBuf<float> view_xyz, view_dir, view_tap;   // (view_tap: halo_consumer_view_filtered's fifth)
   DevBuf<int32_t> view_map;
   int w = 0, h = 0;
   double total_intensity = 0.0;

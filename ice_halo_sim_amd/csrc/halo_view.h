@@ -162,6 +162,111 @@ HALO_VIEW_HD bool view_direction(const ProjDev& p, const float pre[4], int px, i
   return true;
 }
 
+// ---- the forward half, continuous: where a direction lands in the source, before the floor ------------------------------------------------
+// view_source_pos is project_exit's sibling (halo_trace.inl, which every trace kernel includes and which stays as it is): the same culls, the same
+// expressions spelled as the same HALO_FMA chains, the same four floats behind the ProjDev (`pre`), up to — not including — floorf(. + 0.5f).
+//   pos[0..1]  the primary hit (fx0, fy0): floorf(fx0 + 0.5f), floorf(fy0 + 0.5f) is project_exit's (px0, py0) — for the rectangular lens before
+//              its wrap modulo the width (fx0 is the unwrapped x).  Pixel n's centre is n.  The single-view lenses and the globe add their 0.5
+//              BEFORE the lens shift, g = fma(x, scale, w / 2) + 0.5f + shift: their coordinate is g - 0.5f, which is exact for 0.5 <= g < 2^23,
+//              so fx0 + 0.5f is g again and the floor is project_exit's on every hit in the frame.
+//   pos[2..3]  a dual source's overlap write (fx1, fy1), pos[4] the tent weight t = (max_abs_dz - |sz|) / (2 max_abs_dz) of the reference's
+//              sampleDualFisheye (gui/preview_renderer.cpp:152-180) — one difference, one product, one quotient in fp32.  Zeros without a second hit.
+// Returns the hit count (0: culled; pos is zeros).  Host and device differ by libm and by the equal-area form's reciprocal square root
+// (v_rsq_f32 on the device, as project_exit has it; 1 / sqrtf on the host).  The body is built without contraction beyond what is spelled.
+HALO_VIEW_HD float view_rsq(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_rsqf(x);
+#else
+  return 1.0f / sqrtf(x);
+#endif
+}
+
+// the four fisheye forms of project_exit's dual_forward / fisheye_*: false = the form culls the direction (orthographic, dz < 0; x = y = 0 then)
+HALO_VIEW_HD bool view_form_forward(int form, float dx, float dy, float dz, float rs, float& x, float& y) {
+#pragma clang fp contract(off)
+  x = y = 0.0f;
+  if (form == 0) {
+    const float k = rs * view_rsq(1.0f + fminf(fmaxf(dz, -1.0f + 1e-6f), 1.0f));
+    x = k * dx, y = k * dy;
+    return true;
+  }
+  if (form == 3) {
+    if (dz < 0.0f) return false;
+    x = rs * dx, y = rs * dy;
+    return true;
+  }
+  const float rho = sqrtf(HALO_FMA(dx, dx, dy * dy));
+  if (rho < 1e-10f) return true;
+  const float theta = acosf(fminf(fmaxf(dz, -1.0f), 1.0f));
+  const float sc = form == 1 ? rs * theta / (kViewPi2F * rho) : rs * tanf(theta / 2.0f) / rho;
+  x = sc * dx, y = sc * dy;
+  return true;
+}
+
+HALO_VIEW_HD int view_source_pos(const ProjDev& src, const float pre[4], float wx, float wy, float wz, float pos[5]) {
+#pragma clang fp contract(off)
+  pos[0] = pos[1] = pos[2] = pos[3] = pos[4] = 0.0f;
+  const int t = src.proj_type;
+  const int fam = view_family(t);
+  if (fam == kViewSingle) {
+    if ((src.visible_range == HALO_VISIBLE_UPPER && wz > 0.0f) || (src.visible_range == HALO_VISIBLE_LOWER && wz < 0.0f)) return 0;
+    const float cx = HALO_FMA(src.rot[6], -wz, HALO_FMA(src.rot[3], -wy, src.rot[0] * (-wx)));
+    const float cy = HALO_FMA(src.rot[7], -wz, HALO_FMA(src.rot[4], -wy, src.rot[1] * (-wx)));
+    const float cz = HALO_FMA(src.rot[8], -wz, HALO_FMA(src.rot[5], -wy, src.rot[2] * (-wx)));
+    if (cz <= 0.0f) return 0;
+    float x, y;
+    if (t == HALO_LENS_LINEAR) {
+      x = cx / cz, y = cy / cz;
+    } else if (!view_form_forward(view_form_of(t), cx, cy, cz, 1.0f, x, y)) {
+      return 0;
+    }
+    x = -x;
+    pos[0] = (HALO_FMA(x, src.scale, pre[0]) + 0.5f + pre[2]) - 0.5f;
+    pos[1] = (HALO_FMA(y, src.scale, pre[1]) + 0.5f + pre[3]) - 0.5f;
+    return 1;
+  }
+  if (fam == kViewRect) {
+    float lon = atan2f(-wy, -wx) - src.az0;
+    const float lat = asinf(fminf(fmaxf(-wz, -1.0f), 1.0f));
+    while (lon < -kViewPiF) lon += 2.0f * kViewPiF;
+    while (lon > kViewPiF) lon -= 2.0f * kViewPiF;
+    pos[0] = HALO_FMA(lon, src.scale, static_cast<float>(src.img_w) / 2.0f);
+    pos[1] = HALO_FMA(-lat, src.scale, static_cast<float>(src.img_h) / 2.0f);
+    return 1;
+  }
+  if (fam == kViewDual) {
+    const float sx = -wx, sy = -wy, sz = -wz;
+    const bool upper = sz >= 0.0f;
+    const float z_hemi = upper ? sz : -sz;
+    // dual_to_pixel's layout
+    const int half_w = src.img_w / 2;
+    const int short_res = half_w < src.img_h ? half_w : src.img_h;
+    const float r = static_cast<float>(short_res) / 2.0f;
+    const float cy = static_cast<float>(src.img_h) / 2.0f;
+    const float cxu = static_cast<float>(src.img_w) / 2.0f - r, cxl = static_cast<float>(src.img_w) / 2.0f + r;
+    const int form = view_form_of(t);
+    float x, y;
+    view_form_forward(form, sx, sy, z_hemi, src.r_scale, x, y);   // (project_exit lands a dual form's (0, 0) where the form culls)
+    pos[0] = HALO_FMA(upper ? -y : y, r, upper ? cxu : cxl);
+    pos[1] = HALO_FMA(x, r, cy);
+    if (!(src.max_abs_dz > 0.0f && fabsf(sz) < src.max_abs_dz)) return 1;
+    view_form_forward(form, sx, sy, -z_hemi, src.r_scale, x, y);
+    pos[2] = HALO_FMA(upper ? y : -y, r, upper ? cxl : cxu);
+    pos[3] = HALO_FMA(x, r, cy);
+    pos[4] = (src.max_abs_dz - fabsf(sz)) / (2.0f * src.max_abs_dz);
+    return 2;
+  }
+  // globe
+  const float cx = HALO_FMA(src.rot[6], -wz, HALO_FMA(src.rot[3], -wy, src.rot[0] * (-wx)));
+  const float cy = HALO_FMA(src.rot[7], -wz, HALO_FMA(src.rot[4], -wy, src.rot[1] * (-wx)));
+  const float cz = HALO_FMA(src.rot[8], -wz, HALO_FMA(src.rot[5], -wy, src.rot[2] * (-wx)));
+  if (cz >= -1.0f / kViewGlobeD) return 0;
+  const float denom = kViewGlobeD + cz;
+  pos[0] = (HALO_FMA(-cx / denom, src.scale, static_cast<float>(src.img_w) / 2.0f) + 0.5f + static_cast<float>(src.lens_shift_x)) - 0.5f;
+  pos[1] = (HALO_FMA(cy / denom, src.scale, static_cast<float>(src.img_h) / 2.0f) + 0.5f + static_cast<float>(src.lens_shift_y)) - 0.5f;
+  return 1;
+}
+
 }  // namespace halo
 
 #endif

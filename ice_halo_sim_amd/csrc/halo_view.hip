@@ -61,6 +61,164 @@ __global__ void __launch_bounds__(kBlock) halo_view_kernel(const float* __restri
   }
 }
 
+// ---- the filtered view (halo_consumer_view_filtered): bilinear taps and the overlap-band blend ----------------------------------------------
+// What the reference's preview shader does with its GL_LINEAR, clamp-to-edge XYZ texture (gui/preview_renderer.cpp:554-557) and its
+// sampleDualFisheye (:152-180).  A kernel of its own beside halo_view_kernel, whose instantiations keep their code.
+namespace {
+
+// one tap: the snapshot's xyz_out of source pixel (ix, iy), both inside the frame
+__device__ __forceinline__ void view_tap(const float* __restrict__ sum, const float* __restrict__ comp, int w, int ix, int iy, float v[3]) {
+  const uint32_t at = 3u * (static_cast<uint32_t>(iy) * static_cast<uint32_t>(w) + static_cast<uint32_t>(ix));
+#pragma unroll
+  for (int j = 0; j < 3; j++) v[j] = __fadd_rn(sum[at + j], comp[at + j]);
+}
+
+__device__ __forceinline__ int view_clamp_index(float f, int n) {   // (the float first: whatever f is, the cast is defined)
+  return static_cast<int>(fminf(fmaxf(f, 0.0f), static_cast<float>(n - 1)));
+}
+
+// The sample at the continuous position (fx, fy), pixel n's centre at n.  Bilinear: columns floor(fx) and floor(fx) + 1 clamped to the frame — or
+// taken modulo the width, the rectangular lens's own wrap — rows clamped; three lerps per channel, each one subtraction and one fma, each a
+// single fp32 rounding.  Nearest: the pixel floor(f + 0.5), clamped (wrapped) alike.  Every index is inside the frame whatever (fx, fy) is.
+__device__ __forceinline__ void view_sample(const float* __restrict__ sum, const float* __restrict__ comp, int w, int h, bool wrap, bool bilinear, float fx, float fy,
+                                            float c[3]) {
+#pragma clang fp contract(off)
+  const float bx = floorf(bilinear ? fx : fx + 0.5f), by = floorf(bilinear ? fy : fy + 0.5f);
+  int x0, x1;
+  if (wrap) {
+    const int raw = static_cast<int>(fminf(fmaxf(bx, -1073741824.0f), 1073741824.0f));
+    x0 = ((raw % w) + w) % w;
+    x1 = x0 + 1 == w ? 0 : x0 + 1;
+  } else {
+    x0 = view_clamp_index(bx, w);
+    x1 = view_clamp_index(bx + 1.0f, w);
+  }
+  const int y0 = view_clamp_index(by, h), y1 = view_clamp_index(by + 1.0f, h);
+  float v00[3];
+  view_tap(sum, comp, w, x0, y0, v00);
+  if (!bilinear) {
+#pragma unroll
+    for (int j = 0; j < 3; j++) c[j] = v00[j];
+    return;
+  }
+  const float ax = fx - bx, ay = fy - by;   // (exact: a float less its own floor)
+  float v10[3], v01[3], v11[3];
+  view_tap(sum, comp, w, x1, y0, v10);
+  view_tap(sum, comp, w, x0, y1, v01);
+  view_tap(sum, comp, w, x1, y1, v11);
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    const float top = fmaf(ax, v10[j] - v00[j], v00[j]);
+    const float bot = fmaf(ax, v11[j] - v01[j], v01[j]);
+    c[j] = fmaf(ay, bot - top, top);
+  }
+}
+
+}  // namespace
+
+// FAM: the view's lens family.  DUAL_SRC: the source is a dual fisheye — the only source with a second hit: the second sample and the blend are
+// compiled for it alone.  `bilinear` and `blend` are kernel arguments, like the projections: scalar branches.
+template <int FAM, bool DUAL_SRC>
+__global__ void __launch_bounds__(kBlock) halo_view_filtered_kernel(const float* __restrict__ sum, const float* __restrict__ comp, ProjLds view, ProjLds src, DisplayDev dsp,
+                                                                     int bilinear, int blend, uint8_t* __restrict__ rgb_out, float* __restrict__ xyz_out,
+                                                                     int32_t* __restrict__ map_out, float* __restrict__ dir_out, float* __restrict__ tap_out, uint32_t tiles_x,
+                                                                     uint32_t n_tiles) {
+#pragma clang fp contract(off)
+  const uint32_t tx = threadIdx.x & (kViewTile - 1u), ty = threadIdx.x / kViewTile;
+  const uint32_t vw = static_cast<uint32_t>(view.p.img_w), vh = static_cast<uint32_t>(view.p.img_h);
+  const int sw = src.p.img_w, sh = src.p.img_h;
+  const bool wrap = !DUAL_SRC && src.p.proj_type == HALO_LENS_RECTANGULAR;
+  for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {   // (workgroup-uniform)
+    const uint32_t x = (tile % tiles_x) * kViewTile + tx, y = (tile / tiles_x) * kViewTile + ty;
+    if (x >= vw || y >= vh) continue;
+    const size_t p = static_cast<size_t>(y) * vw + x;
+    float w[3];
+    const bool has_dir = view_direction(view.p, &view.half_w, static_cast<int>(x), static_cast<int>(y), w, FAM);
+    int32_t from = -1;
+    if (has_dir) {   // a pixel has a source iff the nearest call gives it one: project_exit's primary hit, inside the frame
+      const Hits h = project_exit(src.p, w[0], w[1], w[2]);
+      if (h.count > 0 && h.px0 >= 0 && h.px0 < sw && h.py0 >= 0 && h.py0 < sh) from = h.py0 * sw + h.px0;
+    }
+    float pos[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    int hits = 0;
+    if (from >= 0) hits = view_source_pos(src.p, &src.half_w, w[0], w[1], w[2], pos);
+    if (dir_out) {
+#pragma unroll
+      for (int j = 0; j < 3; j++) dir_out[3u * p + j] = w[j];
+    }
+    if (map_out) map_out[p] = from;
+    if (tap_out) {
+#pragma unroll
+      for (int j = 0; j < 5; j++) tap_out[5u * p + j] = pos[j];
+    }
+    if (xyz_out == nullptr && rgb_out == nullptr) continue;
+    float raw[3] = {0.0f, 0.0f, 0.0f};
+    if (from >= 0) {
+      if (bilinear) {
+        view_sample(sum, comp, sw, sh, wrap, true, pos[0], pos[1], raw);
+      } else {   // the copy halo_view_kernel makes
+#pragma unroll
+        for (int j = 0; j < 3; j++) raw[j] = __fadd_rn(sum[3u * static_cast<uint32_t>(from) + j], comp[3u * static_cast<uint32_t>(from) + j]);
+      }
+      if (DUAL_SRC && blend && hits == 2) {
+        float c2[3];
+        view_sample(sum, comp, sw, sh, false, bilinear != 0, pos[2], pos[3], c2);
+#pragma unroll
+        for (int j = 0; j < 3; j++) raw[j] = fmaf(pos[4], c2[j] - raw[j], raw[j]);
+      }
+    }
+    if (xyz_out) {
+#pragma unroll
+      for (int j = 0; j < 3; j++) xyz_out[3u * p + j] = raw[j];
+    }
+    if (rgb_out == nullptr) continue;
+    uint8_t px[3];
+    display_pixel(raw, dsp, px);
+#pragma unroll
+    for (int j = 0; j < 3; j++) rgb_out[3u * p + j] = px[j];
+  }
+}
+
+template <int FAM>
+static void launch_view_filtered_family(bool dual_src, uint32_t grid, hipStream_t stream, const float* sum, const float* comp, const ProjLds& v, const ProjLds& s,
+                                        const DisplayDev& d, int bilinear, int blend, uint8_t* rgb_out, float* xyz_out, int32_t* map_out, float* dir_out, float* tap_out,
+                                        uint32_t tiles_x, uint32_t n_tiles) {
+  if (dual_src)
+    hipLaunchKernelGGL((halo_view_filtered_kernel<FAM, true>), dim3(grid), dim3(kBlock), 0, stream, sum, comp, v, s, d, bilinear, blend, rgb_out, xyz_out, map_out, dir_out,
+                       tap_out, tiles_x, n_tiles);
+  else
+    hipLaunchKernelGGL((halo_view_filtered_kernel<FAM, false>), dim3(grid), dim3(kBlock), 0, stream, sum, comp, v, s, d, bilinear, blend, rgb_out, xyz_out, map_out, dir_out,
+                       tap_out, tiles_x, n_tiles);
+}
+
+hipError_t launch_view_filtered(const float* sum, const float* comp, const ProjDev& view, const ProjDev& source, float scale, const float ray_color[3],
+                                const float background[3], bool bilinear, bool blend, uint8_t* rgb_out, float* xyz_out, int32_t* map_out, float* dir_out, float* tap_out,
+                                int blocks, hipStream_t stream) {
+  ProjLds v, s;
+  v.p = view;
+  s.p = source;
+  view_proj_pre(view, &v.half_w);
+  view_proj_pre(source, &s.half_w);
+  DisplayDev d;
+  d.scale = scale;
+  for (int j = 0; j < 3; j++) {
+    d.ray_color[j] = ray_color[j];
+    d.background[j] = background[j];
+  }
+  const uint32_t tiles_x = (static_cast<uint32_t>(view.img_w) + kViewTile - 1u) / kViewTile, tiles_y = (static_cast<uint32_t>(view.img_h) + kViewTile - 1u) / kViewTile;
+  const uint32_t n_tiles = tiles_x * tiles_y;
+  const uint32_t grid = n_tiles < static_cast<uint32_t>(blocks) ? n_tiles : static_cast<uint32_t>(blocks);
+  const bool dual_src = view_family(source.proj_type) == kViewDual;
+  const int bi = bilinear ? 1 : 0, bl = blend ? 1 : 0;
+  switch (view_family(view.proj_type)) {
+    case kViewSingle: launch_view_filtered_family<kViewSingle>(dual_src, grid, stream, sum, comp, v, s, d, bi, bl, rgb_out, xyz_out, map_out, dir_out, tap_out, tiles_x, n_tiles); break;
+    case kViewDual: launch_view_filtered_family<kViewDual>(dual_src, grid, stream, sum, comp, v, s, d, bi, bl, rgb_out, xyz_out, map_out, dir_out, tap_out, tiles_x, n_tiles); break;
+    case kViewRect: launch_view_filtered_family<kViewRect>(dual_src, grid, stream, sum, comp, v, s, d, bi, bl, rgb_out, xyz_out, map_out, dir_out, tap_out, tiles_x, n_tiles); break;
+    default: launch_view_filtered_family<kViewGlobe>(dual_src, grid, stream, sum, comp, v, s, d, bi, bl, rgb_out, xyz_out, map_out, dir_out, tap_out, tiles_x, n_tiles); break;
+  }
+  return hipGetLastError();
+}
+
 hipError_t launch_view(const float* sum, const float* comp, const ProjDev& view, const ProjDev& source, float scale, const float ray_color[3], const float background[3],
                        uint8_t* rgb_out, float* xyz_out, int32_t* map_out, float* dir_out, int blocks, hipStream_t stream) {
   ProjLds v, s;

@@ -177,6 +177,12 @@ class HipTraceBackend {
   void View(const HaloViewSpec& spec, uint8_t* rgb_out, float* xyz_out = nullptr, int32_t* map_out = nullptr, float* dir_out = nullptr) {
     Check(halo_consumer_view(h_, &spec, rgb_out, xyz_out, map_out, dir_out));
   }
+  // ... with a filter (halo_consumer_view_filtered): bilinear taps around the continuous source position, a dual source's overlap band cross-faded
+  // as the reference's sampleDualFisheye does; tap_out takes {fx0, fy0, fx1, fy1, t} per pixel.  {HALO_VIEW_NEAREST, 0} is the call above.
+  void View(const HaloViewSpec& spec, const HaloViewFilter& filter, uint8_t* rgb_out, float* xyz_out = nullptr, int32_t* map_out = nullptr, float* dir_out = nullptr,
+            float* tap_out = nullptr) {
+    Check(halo_consumer_view_filtered(h_, &spec, &filter, rgb_out, xyz_out, map_out, dir_out, tap_out));
+  }
   // The reference GUI's Adaptive Brightness anchor (gui/gui_ev_auto.hpp ComputeP99Y + ComputeEvAuto) on the device consumer: expose a
   // snapshot with display.intensity_factor * exp2(result.ev_auto); result.produced == 0 is the GUI's "auto: no data"
   HaloAutoEv AutoEv(int downsample = 8, float target_white = 135.f) {

@@ -644,6 +644,37 @@ int halo_consumer_view(halo_handle_t h, const HaloViewSpec* spec, uint8_t* rgb_o
  * arguments).  No GPU needed. */
 int halo_host_view_direction(const HaloRender* view, int32_t px, int32_t py, float dir[3]);
 
+/* --- the filtered view: what the reference's shaders do on top of the gather — GL_LINEAR, clamp to edge (gui/preview_renderer.cpp:554-557), and
+ *     the cross-fade of a dual fisheye's overlap band (sampleDualFisheye, :152-180) --- */
+enum { HALO_VIEW_NEAREST = 0, HALO_VIEW_BILINEAR = 1 };
+typedef struct HaloViewFilter {
+  int32_t filter;      /* HALO_VIEW_NEAREST: the copy of the view call above; HALO_VIEW_BILINEAR: four taps around the continuous source position */
+  int32_t blend;       /* 1: where a dual-fisheye source holds an overlap write for the direction, cross-fade it in; 0: the primary hit alone */
+  int32_t reserved[2]; /* zero */
+} HaloViewFilter;
+/* The view call above with a filter.  dir_out and map_out are that call's: a pixel has a source iff map_out >= 0.  Per pixel that has one:
+ *   tap_out  (5 floats) {fx0, fy0, fx1, fy1, t}: the continuous source coordinates of the projection's primary hit — the projection's own fp32
+ *            expressions before its floor(. + 0.5): pixel n's centre is n, and floor(fx0 + 0.5), floor(fy0 + 0.5) is map_out's pixel (the rectangular
+ *            lens gives the unwrapped column) — and, where the source is a dual fisheye with overlap > 0 and the sky direction has |sz| < max_abs_dz,
+ *            those of its overlap write and the tent weight t = (max_abs_dz - |sz|) / (2 max_abs_dz), in fp32; else fx1 = fy1 = t = 0.  Zeros
+ *            where map_out is -1.
+ *   xyz_out  (3 floats) the sample at (fx0, fy0).  Bilinear: with x0 = floor(fx), ax = fx - x0 (and so for y), taps v = sum + compensation at
+ *            columns x0, x0 + 1 and rows y0, y0 + 1 — clamped to the frame; the columns of a rectangular source wrap modulo its width instead —
+ *            top = fma(ax, v10 - v00, v00), bot = fma(ax, v11 - v01, v01), c = fma(ay, bot - top, top): every difference and every fma one fp32
+ *            rounding.  Nearest: map_out's pixel, a copy.  With blend = 1 and a second hit, c = fma(t, c2 - c, c) with c2 the same sample at
+ *            (fx1, fy1) (nearest: the pixel floor(f + 0.5), clamped to the frame).  No source pixel is masked: what no exit was landed on is zero,
+ *            and a disc's rim fades into it as the reference's does.  Zeros at -1.
+ *   rgb_out  (3 bytes) the snapshot's display transform of xyz_out: it runs on the filtered value, as the shader's does.
+ * filter = nearest, blend = 0 gives the view call's bytes.  blend = 1 on a source without an overlap band changes nothing.  No area filter for
+ * minified views, no Jacobian, no class lanes.  Refusals are the view call's (every output NULL counts tap_out), plus HALO_FATAL — the handle
+ * stays usable — for a NULL filter, an unknown filter, a blend other than 0 or 1, non-zero reserved words. */
+int halo_consumer_view_filtered(halo_handle_t h, const HaloViewSpec* spec, const HaloViewFilter* filter, uint8_t* rgb_out, float* xyz_out, int32_t* map_out,
+                                float* dir_out, float* tap_out);
+/* tap_out of one direction under `source`, by the same code on the host: returns the hit count (0: the projection culls the direction, or NULL
+ * arguments / an unknown lens; pos is zeros then) and pos = {fx0, fy0, fx1, fy1, t}.  The frame is not consulted: a hit outside it is returned
+ * as it lies.  No GPU needed. */
+int halo_host_view_source_pos(const HaloRender* source, const float dir[3], float pos[5]);
+
 /* --- display-side composite of the raypath-colour class lanes (server/component_compositor.cpp) ------------- */
 /* CompositeMode (component_compositor.hpp:21): how the per-class Y lanes become one colour per pixel. */
 enum { HALO_COMPOSITE_DOMINANT = 0, HALO_COMPOSITE_ADDITIVE = 1, HALO_COMPOSITE_PAINTER = 2 };
@@ -797,6 +828,7 @@ HALO_STATIC_ASSERT(sizeof(HaloAutoEv) == 28, "HaloAutoEv");
 HALO_STATIC_ASSERT(sizeof(HaloStatsSpec) == 16 + 8 * HALO_STATS_MAX_PERCENTILES, "HaloStatsSpec");
 HALO_STATIC_ASSERT(sizeof(HaloImageStats) == 56 + 32 * HALO_STATS_MAX_PERCENTILES, "HaloImageStats");
 HALO_STATIC_ASSERT(sizeof(HaloViewSpec) == 44 + 4 + 44 + 28, "HaloViewSpec");
+HALO_STATIC_ASSERT(sizeof(HaloViewFilter) == 16, "HaloViewFilter");
 HALO_STATIC_ASSERT(sizeof(HaloCompositeClass) == 24, "HaloCompositeClass");
 HALO_STATIC_ASSERT(sizeof(HaloComposite) == 16 + HALO_COLOR_MAX_CLASSES * 24, "HaloComposite");
 HALO_STATIC_ASSERT(sizeof(HaloGeomTables) == 4 + HALO_MAX_FACES * 20 + 4 + HALO_MAX_TRIS * (36 + 12 + 4 + 4), "HaloGeomTables");

@@ -98,6 +98,9 @@ def load_library():
         "halo_consumer_composite": (C.c_int, [H, C.POINTER(abi.HaloComposite), f32p, C.POINTER(C.c_uint8), f32p, C.POINTER(C.c_int32)]),
         "halo_consumer_load_lanes": (C.c_int, [H, f32p, C.c_int, C.c_int, C.c_int, C.c_double]),
         "halo_host_parse_composite_mode": (C.c_int, [C.c_char_p]),
+        "halo_consumer_view_composite": (C.c_int, [H, C.POINTER(abi.HaloViewSpec), C.POINTER(abi.HaloViewFilter), C.POINTER(abi.HaloComposite), C.POINTER(C.c_uint8), f32p,
+                                                   C.POINTER(C.c_int32), f32p, f32p, C.POINTER(C.c_int32)]),
+        "halo_consumer_view_lanes": (C.c_int, [H, C.POINTER(abi.HaloViewSpec), C.POINTER(abi.HaloViewFilter), f32p, C.POINTER(C.c_int32), f32p]),
         "halo_host_prism_geometry": (C.c_int, [C.c_float, f32p, C.POINTER(abi.HaloGeomTables)]),
         "halo_host_pyramid_geometry": (C.c_int, [C.c_float] * 5 + [f32p, C.POINTER(abi.HaloGeomTables)]),
         "halo_host_shape_scalars": (C.c_int, [C.POINTER(abi.HaloCrystal), C.c_uint32, C.c_uint64, C.c_int, f32p]),
@@ -132,6 +135,7 @@ EXPORTED_SYMBOLS = [
     "halo_consumer_auto_ev", "halo_host_ev_auto",
     "halo_consumer_stats", "halo_host_percentile_rank", "halo_host_binned_sum",
     "halo_consumer_view", "halo_host_view_direction", "halo_consumer_view_filtered", "halo_host_view_source_pos",
+    "halo_consumer_view_composite", "halo_consumer_view_lanes",
     "halo_set_shard", "halo_host_shard_slice", "halo_export_fixed", "halo_import_fixed",
 ]
 
@@ -522,6 +526,59 @@ class HipTraceBackend:
         self._check(self._L.halo_consumer_composite(self._h, C.byref(spec), lin.ctypes.data_as(C.POINTER(C.c_float)),
                                                     srgb.ctypes.data_as(C.POINTER(C.c_uint8)) if want_srgb else None, C.byref(p99), C.byref(produced)))
         return bool(produced.value), lin, srgb, p99.value
+
+    def _lane_view_spec(self, who, view, source, filter, want, known):
+        unknown = set(want) - set(known)
+        if unknown:
+            raise ValueError("%s: unknown output %r" % (who, sorted(unknown)))
+        if filter not in abi.VIEW_FILTERS:
+            raise ValueError("%s: unknown filter %r (nearest | bilinear)" % (who, filter))
+        spec = abi.HaloViewSpec()
+        spec.view = view
+        spec.has_source = 0 if source is None else 1
+        if source is not None:
+            spec.source = source
+        h, w = max(int(view.height), 0), max(int(view.width), 0)
+        return spec, h, w
+
+    def ViewComposite(self, view, classes, mode="painter", display_exposure_scale=1.0, intensity_factor=1.0, source=None, filter="nearest", blend=False, want=("srgb",)):
+        """The class composite through another lens (halo_consumer_view_composite): CompositeColorClasses' image of the device lanes — `classes`,
+        `mode` and the two factors are its arguments — gathered as View gathers the consumer's image, the way the reference's preview shows it in
+        RGB mode.  `source` is the render the LANES lie under (None: this handle's last session's).  want: any of "srgb" (uint8[H,W,3]), "value"
+        (float32[H,W,3]: the sampled value in byte units, srgb = floor(value + 0.5)), "map" (int32[H,W]) and "tap" (float32[H,W,5]), View's.
+        Returns a dict of the arrays asked for plus "produced" (bool) and "p99" (float), CompositeColorClasses' two: with produced False "srgb" is
+        None (no composite) and "value" is zeros.  The lanes stay as they are."""
+        spec, h, w = self._lane_view_spec("ViewComposite", view, source, filter, want, ("srgb", "value", "map", "tap"))
+        comp = abi.composite(classes, mode, display_exposure_scale, intensity_factor)
+        big = w * h > 1 << 25   # (refused by the library: nothing of that size is allocated here)
+        shapes = {"srgb": ((h, w, 3), np.uint8), "value": ((h, w, 3), np.float32), "map": ((h, w), np.int32), "tap": ((h, w, 5), np.float32)}
+        out = {k: np.zeros((0,) if big else shapes[k][0], shapes[k][1]) for k in want}
+
+        def ptr(k, t):
+            return out[k].ctypes.data_as(C.POINTER(t)) if k in out else None
+        f = abi.HaloViewFilter(abi.VIEW_FILTERS[filter], 1 if blend else 0)
+        p99, produced = C.c_float(0.0), C.c_int32(0)
+        self._check(self._L.halo_consumer_view_composite(self._h, C.byref(spec), C.byref(f), C.byref(comp), ptr("srgb", C.c_uint8), ptr("value", C.c_float),
+                                                         ptr("map", C.c_int32), ptr("tap", C.c_float), C.byref(p99), C.byref(produced)))
+        if not produced.value and "srgb" in out:
+            out["srgb"] = None
+        out["produced"], out["p99"] = bool(produced.value), p99.value
+        return out
+
+    def ViewLanes(self, view, source=None, filter="nearest", blend=False, want=("lanes",)):
+        """The class lanes through another lens (halo_consumer_view_lanes): "lanes" float32[classes, H, W] — per class the same sample of the raw
+        lane, no exposure, no composite — "map" and "tap" as ViewComposite's.  Returns a dict of the arrays asked for.  The lanes stay."""
+        spec, h, w = self._lane_view_spec("ViewLanes", view, source, filter, want, ("lanes", "map", "tap"))
+        n = getattr(self, "_n_classes", 0)   # (set_color's: the library's lane count)
+        big = w * h > 1 << 25 or n * w * h > 1 << 27
+        shapes = {"lanes": ((n, h, w), np.float32), "map": ((h, w), np.int32), "tap": ((h, w, 5), np.float32)}
+        out = {k: np.zeros((0,) if big else shapes[k][0], shapes[k][1]) for k in want}
+
+        def ptr(k, t):
+            return out[k].ctypes.data_as(C.POINTER(t)) if k in out else None
+        f = abi.HaloViewFilter(abi.VIEW_FILTERS[filter], 1 if blend else 0)
+        self._check(self._L.halo_consumer_view_lanes(self._h, C.byref(spec), C.byref(f), ptr("lanes", C.c_float), ptr("map", C.c_int32), ptr("tap", C.c_float)))
+        return out
 
 
 def host_view_direction(view, px, py):

@@ -254,6 +254,10 @@ def main(argv=None):
     ap.add_argument("--out-lanes", default=None, help="raypath_color configs: write the per-class Y lanes (classes, H, W) as .npy")
     ap.add_argument("--out-composite", default=None, help="raypath_color configs: write the class composite (the config's mode: dominant | additive | "
                     "painter; component_compositor.cpp) as binary PPM, composited on the device")
+    ap.add_argument("--out-view-composite", default=None, metavar="FILE.ppm",
+                    help="raypath_color configs: write the class composite seen through another lens as binary PPM — --out-composite's image gathered "
+                    "on the device the way --out-view gathers the traced one (the --view-* arguments, --view-filter and --view-blend apply; "
+                    "--display-ev is the composite's)")
     ap.add_argument("--canonical-order", action="store_true",
                     help="multi-scattering configs: hand every layer's continuing rays to the next layer in canonical (root ray, interaction) "
                     "order, so a fixed --seed traces the same second- and third-layer rays on every run (option cont_order = 1; costs a sort of the "
@@ -368,6 +372,18 @@ def main(argv=None):
             write_ppm(args.out_composite, srgb)
         else:
             print("no composite: the participating classes hold no energy (P99 %.3g)" % p99, file=sys.stderr)
+    if args.out_view_composite and job.color_classes:   # ... and so does its view
+        try:
+            out = be.ViewComposite(view_render(args, res["render"]), job.color_meta, job.color_mode, 2.0 ** args.display_ev, meta.get("intensity_factor", 1.0),
+                                   source=res["render"], filter=args.view_filter, blend=args.view_blend)
+        except config.ConfigError as e:
+            print("config error: %s" % e, file=sys.stderr)
+            be.close()
+            return 2
+        if out["produced"]:
+            write_ppm(args.out_view_composite, out["srgb"])
+        else:
+            print("no composite: the participating classes hold no energy (P99 %.3g)" % out["p99"], file=sys.stderr)
     if args.out_lanes and job.color_classes:
         np.save(args.out_lanes, be.ReadbackClassLanes())
     if args.benchmark:

@@ -1,6 +1,6 @@
 // halo_consumer.cpp — the consumer stages of the C ABI (RenderConsumer, server/render.hpp, on the device): the Neumaier running image and its
 // total landed intensity (reset, fold, consume), and what is made of them — snapshot, auto exposure, image statistics, the view through another
-// lens — and of the class lanes: load, composite, read-back.  Their state is HaloBackend::cons (halo_state.h Consumer); the lanes themselves are
+// lens — and of the class lanes: load, composite, composite and lanes through another lens, read-back.  Their state is HaloBackend::cons (halo_state.h Consumer); the lanes themselves are
 // written by trace sessions and stay with the session state.  Host C++ only; built without FMA contraction like every host unit: the float
 // expressions below are the reference's, operand for operand.
 #include <hip/hip_runtime.h>
@@ -89,6 +89,137 @@ int view_call(HaloBackend* b, const char* who, const HaloViewSpec* spec, const H
   if (tap_out) HIPCHK(b, hipMemcpyAsync(tap_out, b->cons.view_tap.ptr, npix * 5 * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
   HIPCHK(b, hipStreamSynchronize(main_q(b)));
   if (rgb_out && scale == 0.0f) std::memset(rgb_out, 0, n);   // PostSnapshot's early-out, as halo_consumer_snapshot has it
+  return HALO_OK;
+}
+
+// What comes before halo_composite_kernel, for halo_consumer_composite and halo_consumer_view_composite alike: the argument checks (`who` names the
+// call in the messages), GatherActiveClasses, the participating P99 by three histogram passes — the host waits for each — and
+// ParticipatingExposureScale.  `state` says how far the reference's function gets:
+enum {
+  kCompositeNothing = 0,   // no class references a raypath bit: the reference returns false and touches nothing
+  kCompositeBlack = 1,     // no active class: an all-black composite, still a valid one (P99 0)
+  kCompositeNoScale = 2,   // the exposure scale is not positive: P99 published, no composite
+  kCompositeReady = 3,     // cd is what halo_composite_kernel takes
+};
+struct CompositePlan {
+  CompositeDev cd{};
+  float p99 = 0.0f;
+  uint32_t npix = 0;   // of the lanes
+  int state = kCompositeNothing;
+};
+int composite_prepare(HaloBackend* b, const char* who, const HaloComposite* spec, CompositePlan* plan) {
+  const std::string name(who);
+  if (spec->mode < HALO_COMPOSITE_DOMINANT || spec->mode > HALO_COMPOSITE_PAINTER) return fail(b, HALO_FATAL, name + ": unknown mode");
+  uint64_t referenced = 0;   // ColorClassTable::referenced_mask_ = OR of the classes' member bits (color_class_table.hpp:38-43)
+  for (const HaloColorClass& c : b->color_classes) referenced |= c.bits;
+  if (referenced == 0) return HALO_OK;   // component_compositor.cpp:183-185
+  if (spec->class_count != static_cast<int>(b->color_classes.size())) return fail(b, HALO_FATAL, name + ": class_count differs from halo_set_color's");
+  if (!b->lanes.ptr || b->lanes_w <= 0 || b->lanes_h <= 0) return fail(b, HALO_FATAL, name + " before any colour session (no lanes)");
+  HIPCHK(b, hipSetDevice(b->device));
+  if (int rc = join_aux(b)) return rc;   // (kernels of queued sessions may still be running on the trace / auxiliary streams)
+  const uint32_t npix = static_cast<uint32_t>(b->lanes_w) * static_cast<uint32_t>(b->lanes_h);
+  plan->npix = npix;
+  // GatherActiveClasses (component_compositor.cpp:24-54): solo beats visible; stable sort by z_order; lane binding by class index
+  bool any_solo = false;
+  for (int c = 0; c < spec->class_count; c++) any_solo = any_solo || spec->classes[c].solo != 0;
+  std::vector<int> order(static_cast<size_t>(spec->class_count));
+  for (int c = 0; c < spec->class_count; c++) order[static_cast<size_t>(c)] = c;
+  std::stable_sort(order.begin(), order.end(), [spec](int x, int y) { return spec->classes[x].z_order < spec->classes[y].z_order; });
+  CompositeDev& cd = plan->cd;
+  cd.mode = static_cast<uint32_t>(spec->mode);
+  for (int c : order) {
+    const HaloCompositeClass& k = spec->classes[c];
+    if (!(any_solo ? k.solo != 0 : k.visible != 0)) continue;
+    cd.lane[cd.n_active] = static_cast<uint32_t>(c);
+    for (int j = 0; j < 3; j++) cd.color[cd.n_active][j] = k.color[j];
+    cd.n_active++;
+  }
+  if (cd.n_active == 0) {
+    plan->state = kCompositeBlack;
+    return HALO_OK;
+  }
+  // ComputeParticipatingP99Y (:138-163) as a radix select: 11 + 11 + 10 bits of the float pattern, one histogram pass each
+  HIPCHK(b, b->cons.comp_hist.reserve(2048));
+  std::vector<uint32_t> hist(2048);
+  const int blocks = b->cu_count * 8;
+  float p99 = 0.0f;
+  {
+    uint32_t prefix = 0u;
+    uint64_t rank = 0;   // 0-based rank wanted among the values that share `prefix`
+    const uint32_t shifts[3] = {21u, 10u, 0u}, widths[3] = {11u, 11u, 10u};
+    bool empty = false;
+    for (int pass = 0; pass < 3 && !empty; pass++) {
+      const uint32_t nb = 1u << widths[pass];
+      HIPCHK(b, hipMemsetAsync(b->cons.comp_hist.ptr, 0, nb * sizeof(uint32_t), main_q(b)));
+      hipError_t e = launch_lane_hist(b->lanes.ptr, npix, cd, shifts[pass], widths[pass], prefix, b->cons.comp_hist.ptr, blocks, main_q(b));
+      if (e != hipSuccess) return hip_fail(b, e, "halo_lane_hist_kernel launch");
+      HIPCHK(b, hipMemcpyAsync(hist.data(), b->cons.comp_hist.ptr, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, main_q(b)));
+      HIPCHK(b, hipStreamSynchronize(main_q(b)));
+      if (pass == 0) {
+        uint64_t count = 0;
+        for (uint32_t i = 0; i < nb; i++) count += hist[i];
+        if (count == 0) {
+          empty = true;
+          break;
+        }
+        // idx = size * 0.99f in float, clamped (:156-159)
+        uint64_t idx = static_cast<uint64_t>(static_cast<float>(count) * 0.99f);
+        if (idx >= count) idx = count - 1;
+        rank = idx;
+      }
+      uint32_t bin = 0;
+      for (; bin < nb; bin++) {
+        if (rank < hist[bin]) break;
+        rank -= hist[bin];
+      }
+      if (bin >= nb) return fail(b, HALO_FATAL, name + ": lanes changed under the P99 select");
+      prefix = (prefix << widths[pass]) | bin;
+    }
+    if (!empty) std::memcpy(&p99, &prefix, sizeof(float));
+  }
+  plan->p99 = p99;
+  // ParticipatingExposureScale (render.cpp:120-135), in float like the reference
+  const float snapshot_intensity = static_cast<float>(b->cons.total_intensity);
+  float A = 0.0f;
+  if (p99 > 0.0f && snapshot_intensity > 0.0f) {
+    const float target_srgb = 135.0f / 255.0f;
+    const float target_linear = target_srgb <= 0.04045f ? target_srgb / 12.92f : std::pow((target_srgb + 0.055f) / 1.055f, 2.4f);
+    A = spec->intensity_factor * target_linear / p99;
+  }
+  if (!(A > 0.0f)) {
+    plan->state = kCompositeNoScale;
+    return HALO_OK;
+  }
+  cd.a = A;
+  cd.s = A * spec->display_exposure_scale;
+  cd.display = spec->display_exposure_scale;
+  plan->state = kCompositeReady;
+  return HALO_OK;
+}
+
+// halo_consumer_view_composite and halo_consumer_view_lanes: what both refuse, in one place.  On HALO_OK `*source` is the render the lanes lie under.
+int lane_view_checks(HaloBackend* b, const std::string& name, const HaloViewSpec* spec, const HaloViewFilter* filter, bool any_output, const HaloRender** source) {
+  if (!spec) return fail(b, HALO_FATAL, name + ": spec is NULL");
+  if (b->in_session) return fail(b, HALO_FATAL, name + " inside a session");
+  if (!any_output) return fail(b, HALO_FATAL, name + ": every output is NULL");
+  if (filter) {
+    if (filter->filter != HALO_VIEW_NEAREST && filter->filter != HALO_VIEW_BILINEAR) return fail(b, HALO_FATAL, name + ": unknown filter");
+    if (filter->blend != 0 && filter->blend != 1) return fail(b, HALO_FATAL, name + ": blend must be 0 or 1");
+    if (filter->reserved[0] != 0 || filter->reserved[1] != 0) return fail(b, HALO_FATAL, name + ": reserved words must be zero");
+  }
+  // (the second test: classes set after the lanes were made, for which no lane exists yet)
+  if (!b->lanes.ptr || b->lanes_w <= 0 || b->lanes_h <= 0 || b->color_classes.size() * static_cast<size_t>(b->lanes_w) * static_cast<size_t>(b->lanes_h) > b->lanes.cap)
+    return fail(b, HALO_FATAL, name + " before any colour session or consumer_load_lanes (no lanes)");
+  const HaloRender& view = spec->view;
+  if (view.width <= 0 || view.height <= 0) return fail(b, HALO_FATAL, name + ": empty view");
+  if (static_cast<uint64_t>(view.width) * static_cast<uint64_t>(view.height) > (1ull << 25))
+    return fail(b, HALO_UNAVAILABLE, name + ": a view of more than 2^25 pixels");
+  if (!spec->has_source && !b->had_session) return fail(b, HALO_FATAL, name + ": no source render (has_source = 0 on a handle that has had no session)");
+  const HaloRender& src = spec->has_source ? spec->source : b->render;
+  if (src.width != b->lanes_w || src.height != b->lanes_h) return fail(b, HALO_FATAL, name + ": the source render's size is not the lanes'");
+  if (view.lens_type < HALO_LENS_LINEAR || view.lens_type > HALO_LENS_GLOBE || src.lens_type < HALO_LENS_LINEAR || src.lens_type > HALO_LENS_GLOBE)
+    return fail(b, HALO_FATAL, name + ": unknown lens type");
+  *source = &src;
   return HALO_OK;
 }
 
@@ -327,104 +458,120 @@ int halo_consumer_load_lanes(halo_handle_t b, const float* lanes, int width, int
 int halo_consumer_composite(halo_handle_t b, const HaloComposite* spec, float* linear_rgb_out, uint8_t* srgb_out, float* participating_p99_y, int32_t* produced) {
   if (!b || !spec || !produced) return HALO_FATAL;
   *produced = 0;
-  if (spec->mode < HALO_COMPOSITE_DOMINANT || spec->mode > HALO_COMPOSITE_PAINTER) return fail(b, HALO_FATAL, "consumer_composite: unknown mode");
-  uint64_t referenced = 0;   // ColorClassTable::referenced_mask_ = OR of the classes' member bits (color_class_table.hpp:38-43)
-  for (const HaloColorClass& c : b->color_classes) referenced |= c.bits;
-  if (referenced == 0) return HALO_OK;   // component_compositor.cpp:183-185: nothing is touched
-  if (spec->class_count != static_cast<int>(b->color_classes.size())) return fail(b, HALO_FATAL, "consumer_composite: class_count differs from halo_set_color's");
-  if (!b->lanes.ptr || b->lanes_w <= 0 || b->lanes_h <= 0) return fail(b, HALO_FATAL, "consumer_composite before any colour session (no lanes)");
-  HIPCHK(b, hipSetDevice(b->device));
-  if (int rc = join_aux(b)) return rc;   // (kernels of queued sessions may still be running on the trace / auxiliary streams)
-  const uint32_t npix = static_cast<uint32_t>(b->lanes_w) * static_cast<uint32_t>(b->lanes_h);
-  const size_t n3 = static_cast<size_t>(npix) * 3u;
-  // GatherActiveClasses (component_compositor.cpp:24-54): solo beats visible; stable sort by z_order; lane binding by class index
-  bool any_solo = false;
-  for (int c = 0; c < spec->class_count; c++) any_solo = any_solo || spec->classes[c].solo != 0;
-  std::vector<int> order(static_cast<size_t>(spec->class_count));
-  for (int c = 0; c < spec->class_count; c++) order[static_cast<size_t>(c)] = c;
-  std::stable_sort(order.begin(), order.end(), [spec](int x, int y) { return spec->classes[x].z_order < spec->classes[y].z_order; });
-  CompositeDev cd{};
-  cd.mode = static_cast<uint32_t>(spec->mode);
-  for (int c : order) {
-    const HaloCompositeClass& k = spec->classes[c];
-    if (!(any_solo ? k.solo != 0 : k.visible != 0)) continue;
-    cd.lane[cd.n_active] = static_cast<uint32_t>(c);
-    for (int j = 0; j < 3; j++) cd.color[cd.n_active][j] = k.color[j];
-    cd.n_active++;
-  }
-  auto deliver_black = [&]() -> int {   // "nothing visible -> all-black, still a valid composite" (:201-206)
+  CompositePlan plan;
+  if (int rc = composite_prepare(b, "consumer_composite", spec, &plan)) return rc;
+  if (plan.state == kCompositeNothing) return HALO_OK;   // component_compositor.cpp:183-185: nothing is touched
+  const size_t n3 = static_cast<size_t>(plan.npix) * 3u;
+  if (plan.state == kCompositeBlack) {   // "nothing visible -> all-black, still a valid composite" (:201-206)
     if (linear_rgb_out) std::memset(linear_rgb_out, 0, n3 * sizeof(float));
     if (srgb_out) std::memset(srgb_out, 0, n3);
     if (participating_p99_y) *participating_p99_y = 0.0f;
     *produced = 1;
     return HALO_OK;
-  };
-  if (cd.n_active == 0) return deliver_black();
-  // ComputeParticipatingP99Y (:138-163) as a radix select: 11 + 11 + 10 bits of the float pattern, one histogram pass each
-  HIPCHK(b, b->cons.comp_hist.reserve(2048));
-  std::vector<uint32_t> hist(2048);
-  const int blocks = b->cu_count * 8;
-  float p99 = 0.0f;
-  {
-    uint32_t prefix = 0u;
-    uint64_t rank = 0;   // 0-based rank wanted among the values that share `prefix`
-    const uint32_t shifts[3] = {21u, 10u, 0u}, widths[3] = {11u, 11u, 10u};
-    bool empty = false;
-    for (int pass = 0; pass < 3 && !empty; pass++) {
-      const uint32_t nb = 1u << widths[pass];
-      HIPCHK(b, hipMemsetAsync(b->cons.comp_hist.ptr, 0, nb * sizeof(uint32_t), main_q(b)));
-      hipError_t e = launch_lane_hist(b->lanes.ptr, npix, cd, shifts[pass], widths[pass], prefix, b->cons.comp_hist.ptr, blocks, main_q(b));
-      if (e != hipSuccess) return hip_fail(b, e, "halo_lane_hist_kernel launch");
-      HIPCHK(b, hipMemcpyAsync(hist.data(), b->cons.comp_hist.ptr, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, main_q(b)));
-      HIPCHK(b, hipStreamSynchronize(main_q(b)));
-      if (pass == 0) {
-        uint64_t count = 0;
-        for (uint32_t i = 0; i < nb; i++) count += hist[i];
-        if (count == 0) {
-          empty = true;
-          break;
-        }
-        // idx = size * 0.99f in float, clamped (:156-159)
-        uint64_t idx = static_cast<uint64_t>(static_cast<float>(count) * 0.99f);
-        if (idx >= count) idx = count - 1;
-        rank = idx;
-      }
-      uint32_t bin = 0;
-      for (; bin < nb; bin++) {
-        if (rank < hist[bin]) break;
-        rank -= hist[bin];
-      }
-      if (bin >= nb) return fail(b, HALO_FATAL, "consumer_composite: lanes changed under the P99 select");
-      prefix = (prefix << widths[pass]) | bin;
-    }
-    if (!empty) std::memcpy(&p99, &prefix, sizeof(float));
   }
-  // ParticipatingExposureScale (render.cpp:120-135), in float like the reference
-  const float snapshot_intensity = static_cast<float>(b->cons.total_intensity);
-  float A = 0.0f;
-  if (p99 > 0.0f && snapshot_intensity > 0.0f) {
-    const float target_srgb = 135.0f / 255.0f;
-    const float target_linear = target_srgb <= 0.04045f ? target_srgb / 12.92f : std::pow((target_srgb + 0.055f) / 1.055f, 2.4f);
-    A = spec->intensity_factor * target_linear / p99;
-  }
-  if (participating_p99_y) *participating_p99_y = p99;
-  if (!(A > 0.0f)) {   // :209-214: P99 published, no composite; the linear buffer was already assigned zeros (:189)
+  if (participating_p99_y) *participating_p99_y = plan.p99;
+  if (plan.state == kCompositeNoScale) {   // :209-214: P99 published, no composite; the linear buffer was already assigned zeros (:189)
     if (linear_rgb_out) std::memset(linear_rgb_out, 0, n3 * sizeof(float));
     return HALO_OK;
   }
-  cd.a = A;
-  cd.s = A * spec->display_exposure_scale;
-  cd.display = spec->display_exposure_scale;
   if (linear_rgb_out) HIPCHK(b, b->cons.comp_rgb.reserve(n3));
   if (srgb_out) HIPCHK(b, b->cons.rgb.reserve(n3));
   if (linear_rgb_out || srgb_out) {
-    hipError_t e = launch_composite(b->lanes.ptr, npix, cd, linear_rgb_out ? b->cons.comp_rgb.ptr : nullptr, srgb_out ? b->cons.rgb.ptr : nullptr, blocks, main_q(b));
+    hipError_t e = launch_composite(b->lanes.ptr, plan.npix, plan.cd, linear_rgb_out ? b->cons.comp_rgb.ptr : nullptr, srgb_out ? b->cons.rgb.ptr : nullptr, b->cu_count * 8,
+                                    main_q(b));
     if (e != hipSuccess) return hip_fail(b, e, "halo_composite_kernel launch");
     if (linear_rgb_out) HIPCHK(b, hipMemcpyAsync(linear_rgb_out, b->cons.comp_rgb.ptr, n3 * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
     if (srgb_out) HIPCHK(b, hipMemcpyAsync(srgb_out, b->cons.rgb.ptr, n3, hipMemcpyDeviceToHost, main_q(b)));
     HIPCHK(b, hipStreamSynchronize(main_q(b)));
   }
   *produced = 1;
+  return HALO_OK;
+}
+
+// ---- the raypath-colour images through another lens (halo_view_composite.hip) -------------------------------------
+// The reference's preview in RGB mode (gui/preview_renderer.cpp:458-464, 660-678): stage 1 is halo_consumer_composite's source image, by its code,
+// into a device buffer that stays there; stage 2 gathers the view from its bytes.
+int halo_consumer_view_composite(halo_handle_t b, const HaloViewSpec* spec, const HaloViewFilter* filter, const HaloComposite* composite, uint8_t* srgb_out,
+                                 float* value_out, int32_t* map_out, float* tap_out, float* participating_p99_y, int32_t* produced) {
+  if (!b) return HALO_FATAL;
+  const std::string name("consumer_view_composite");
+  if (!produced) return fail(b, HALO_FATAL, name + ": produced is NULL");
+  *produced = 0;
+  const HaloRender* source = nullptr;
+  if (int rc = lane_view_checks(b, name, spec, filter, srgb_out || value_out || map_out || tap_out, &source)) return rc;
+  if (!composite) return fail(b, HALO_FATAL, name + ": composite is NULL");
+  if (composite->mode < HALO_COMPOSITE_DOMINANT || composite->mode > HALO_COMPOSITE_PAINTER) return fail(b, HALO_FATAL, name + ": unknown mode");
+  if (composite->class_count != static_cast<int>(b->color_classes.size())) return fail(b, HALO_FATAL, name + ": class_count differs from halo_set_color's");
+  HIPCHK(b, hipSetDevice(b->device));
+  if (int rc = join_aux(b)) return rc;   // (kernels of queued sessions may still be adding to the lanes on the trace / auxiliary streams)
+  CompositePlan plan;
+  if (int rc = composite_prepare(b, name.c_str(), composite, &plan)) return rc;
+  const HaloRender& view = spec->view;
+  const size_t npix = static_cast<size_t>(view.width) * static_cast<size_t>(view.height), n = npix * 3;
+  const bool ready = plan.state == kCompositeReady;
+  const uint8_t* src_dev = nullptr;
+  if (ready && (srgb_out || value_out)) {
+    HIPCHK(b, b->cons.view_comp_src.reserve(static_cast<size_t>(plan.npix) * 3u));
+    hipError_t e = launch_composite(b->lanes.ptr, plan.npix, plan.cd, nullptr, b->cons.view_comp_src.ptr, b->cu_count * 8, main_q(b));
+    if (e != hipSuccess) return hip_fail(b, e, "halo_composite_kernel launch");
+    src_dev = b->cons.view_comp_src.ptr;
+  }
+  if (src_dev || map_out || tap_out) {
+    if (src_dev && srgb_out) HIPCHK(b, b->cons.view_rgb.reserve(n));
+    if (src_dev && value_out) HIPCHK(b, b->cons.view_xyz.reserve(n));
+    if (map_out) HIPCHK(b, b->cons.view_map.reserve(npix));
+    if (tap_out) HIPCHK(b, b->cons.view_tap.reserve(npix * 5));
+    hipError_t e = launch_view_composite(src_dev, host::BuildProj(view), host::BuildProj(*source), filter && filter->filter == HALO_VIEW_BILINEAR, filter && filter->blend != 0,
+                                         src_dev && srgb_out ? b->cons.view_rgb.ptr : nullptr, src_dev && value_out ? b->cons.view_xyz.ptr : nullptr,
+                                         map_out ? b->cons.view_map.ptr : nullptr, tap_out ? b->cons.view_tap.ptr : nullptr, b->cu_count * 8, main_q(b));
+    if (e != hipSuccess) return hip_fail(b, e, "halo_view_composite_kernel launch");
+    if (src_dev && srgb_out) HIPCHK(b, hipMemcpyAsync(srgb_out, b->cons.view_rgb.ptr, n, hipMemcpyDeviceToHost, main_q(b)));
+    if (src_dev && value_out) HIPCHK(b, hipMemcpyAsync(value_out, b->cons.view_xyz.ptr, n * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
+    if (map_out) HIPCHK(b, hipMemcpyAsync(map_out, b->cons.view_map.ptr, npix * sizeof(int32_t), hipMemcpyDeviceToHost, main_q(b)));
+    if (tap_out) HIPCHK(b, hipMemcpyAsync(tap_out, b->cons.view_tap.ptr, npix * 5 * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
+    HIPCHK(b, hipStreamSynchronize(main_q(b)));
+  }
+  // the cases that stop before a composite, as halo_consumer_composite has them
+  if (plan.state == kCompositeNothing) return HALO_OK;   // neither image is written
+  if (plan.state == kCompositeBlack) {
+    if (srgb_out) std::memset(srgb_out, 0, n);
+    if (value_out) std::memset(value_out, 0, n * sizeof(float));
+    if (participating_p99_y) *participating_p99_y = 0.0f;
+    *produced = 1;
+    return HALO_OK;
+  }
+  if (participating_p99_y) *participating_p99_y = plan.p99;
+  if (plan.state == kCompositeNoScale) {   // the bytes stay untouched; the value image is the zeros the reference assigns its linear buffer
+    if (value_out) std::memset(value_out, 0, n * sizeof(float));
+    return HALO_OK;
+  }
+  *produced = 1;
+  return HALO_OK;
+}
+
+int halo_consumer_view_lanes(halo_handle_t b, const HaloViewSpec* spec, const HaloViewFilter* filter, float* lanes_out, int32_t* map_out, float* tap_out) {
+  if (!b) return HALO_FATAL;
+  const std::string name("consumer_view_lanes");
+  const HaloRender* source = nullptr;
+  if (int rc = lane_view_checks(b, name, spec, filter, lanes_out || map_out || tap_out, &source)) return rc;
+  const HaloRender& view = spec->view;
+  const size_t npix = static_cast<size_t>(view.width) * static_cast<size_t>(view.height);
+  const size_t classes = b->color_classes.size();
+  if (classes == 0) return fail(b, HALO_FATAL, name + ": no classes (halo_set_color)");
+  if (static_cast<uint64_t>(classes) * npix > (1ull << 27)) return fail(b, HALO_UNAVAILABLE, name + ": class_count x view pixels of more than 2^27 floats");
+  HIPCHK(b, hipSetDevice(b->device));
+  if (int rc = join_aux(b)) return rc;   // (kernels of queued sessions may still be adding to the lanes on the trace / auxiliary streams)
+  if (lanes_out) HIPCHK(b, b->cons.view_lanes.reserve(classes * npix));
+  if (map_out) HIPCHK(b, b->cons.view_map.reserve(npix));
+  if (tap_out) HIPCHK(b, b->cons.view_tap.reserve(npix * 5));
+  hipError_t e = launch_view_lanes(b->lanes.ptr, static_cast<uint32_t>(classes), host::BuildProj(view), host::BuildProj(*source), filter && filter->filter == HALO_VIEW_BILINEAR,
+                                   filter && filter->blend != 0, lanes_out ? b->cons.view_lanes.ptr : nullptr, map_out ? b->cons.view_map.ptr : nullptr,
+                                   tap_out ? b->cons.view_tap.ptr : nullptr, b->cu_count * 8, main_q(b));
+  if (e != hipSuccess) return hip_fail(b, e, "halo_view_lanes_kernel launch");
+  if (lanes_out) HIPCHK(b, hipMemcpyAsync(lanes_out, b->cons.view_lanes.ptr, classes * npix * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
+  if (map_out) HIPCHK(b, hipMemcpyAsync(map_out, b->cons.view_map.ptr, npix * sizeof(int32_t), hipMemcpyDeviceToHost, main_q(b)));
+  if (tap_out) HIPCHK(b, hipMemcpyAsync(tap_out, b->cons.view_tap.ptr, npix * 5 * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
+  HIPCHK(b, hipStreamSynchronize(main_q(b)));
   return HALO_OK;
 }
 

@@ -117,6 +117,15 @@ hipError_t launch_view(const float* sum, const float* comp, const ProjDev& view,
 hipError_t launch_view_filtered(const float* sum, const float* comp, const ProjDev& view, const ProjDev& source, float scale, const float ray_color[3],
                                 const float background[3], bool bilinear, bool blend, uint8_t* rgb_out, float* xyz_out, int32_t* map_out, float* dir_out, float* tap_out,
                                 int blocks, hipStream_t stream);
+// halo_view_composite.hip — the same view of the raypath-colour images.  launch_view_composite: `srgb_src` is halo_composite_kernel's srgb_out
+// of the source render (3 bytes per source pixel; null: no composite, only map_out / tap_out are written); a tap is its byte triple as floats in
+// byte units, value_out (3 floats) the sampled and blended value, srgb_out (3 bytes) uint8(floorf(value + 0.5f)); zeros where map is -1.
+// launch_view_lanes: `lanes` are the fp64 class lanes of the source render, class c at lanes[c * source pixels]; a tap is float(lane);
+// lanes_out[c * view pixels + p] (null: the geometry alone).  map_out / tap_out are launch_view_filtered's, bit for bit; any output may be null.
+hipError_t launch_view_composite(const uint8_t* srgb_src, const ProjDev& view, const ProjDev& source, bool bilinear, bool blend, uint8_t* srgb_out, float* value_out,
+                                 int32_t* map_out, float* tap_out, int blocks, hipStream_t stream);
+hipError_t launch_view_lanes(const double* lanes, uint32_t class_count, const ProjDev& view, const ProjDev& source, bool bilinear, bool blend, float* lanes_out,
+                             int32_t* map_out, float* tap_out, int blocks, hipStream_t stream);
 hipError_t launch_cont_reorder(const float* in, uint32_t in_stride, uint32_t region, const uint32_t* cnt, uint32_t max_fill, const uint32_t* mask, uint32_t n_roots,
                                uint32_t* tile_sum, uint32_t* base, float* out, uint32_t out_stride, uint32_t n_cont, uint32_t planes, uint32_t* err, hipStream_t stream);
 

@@ -94,6 +94,9 @@ struct Consumer {
   DevBuf<uint8_t> view_rgb;
   DevBuf<float> view_xyz, view_dir, view_tap;   // (view_tap: halo_consumer_view_filtered's fifth)
   DevBuf<int32_t> view_map;
+  // halo_consumer_view_composite: the source-sized composite its gather reads (never copied back); halo_consumer_view_lanes: the class planes of the view
+  DevBuf<uint8_t> view_comp_src;
+  DevBuf<float> view_lanes;
   int w = 0, h = 0;
   double total_intensity = 0.0;
 };

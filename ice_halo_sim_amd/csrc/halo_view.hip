@@ -13,13 +13,9 @@
 #include "halo_display.h"
 #include "halo_launch.h"
 #include "halo_view.h"
+#include "halo_view_sample.h"
 
 namespace halo {
-
-namespace {
-constexpr uint32_t kViewTile = 16u;
-static_assert(kViewTile * kViewTile == kBlock, "one thread per pixel of a tile");
-}  // namespace
 
 template <int FAM>
 __global__ void __launch_bounds__(kBlock) halo_view_kernel(const float* __restrict__ sum, const float* __restrict__ comp, ProjLds view, ProjLds src, DisplayDev dsp,
@@ -66,53 +62,18 @@ __global__ void __launch_bounds__(kBlock) halo_view_kernel(const float* __restri
 // sampleDualFisheye (:152-180).  A kernel of its own beside halo_view_kernel, whose instantiations keep their code.
 namespace {
 
-// one tap: the snapshot's xyz_out of source pixel (ix, iy), both inside the frame
-__device__ __forceinline__ void view_tap(const float* __restrict__ sum, const float* __restrict__ comp, int w, int ix, int iy, float v[3]) {
-  const uint32_t at = 3u * (static_cast<uint32_t>(iy) * static_cast<uint32_t>(w) + static_cast<uint32_t>(ix));
+// one tap of halo_view_sample.h's view_sample: the snapshot's xyz_out of source pixel (ix, iy), both inside the frame
+struct XyzTap {
+  static constexpr int kN = 3;
+  const float* __restrict__ sum;
+  const float* __restrict__ comp;
+  int w;
+  __device__ __forceinline__ void at(uint32_t pixel, float v[3]) const {
 #pragma unroll
-  for (int j = 0; j < 3; j++) v[j] = __fadd_rn(sum[at + j], comp[at + j]);
-}
-
-__device__ __forceinline__ int view_clamp_index(float f, int n) {   // (the float first: whatever f is, the cast is defined)
-  return static_cast<int>(fminf(fmaxf(f, 0.0f), static_cast<float>(n - 1)));
-}
-
-// The sample at the continuous position (fx, fy), pixel n's centre at n.  Bilinear: columns floor(fx) and floor(fx) + 1 clamped to the frame — or
-// taken modulo the width, the rectangular lens's own wrap — rows clamped; three lerps per channel, each one subtraction and one fma, each a
-// single fp32 rounding.  Nearest: the pixel floor(f + 0.5), clamped (wrapped) alike.  Every index is inside the frame whatever (fx, fy) is.
-__device__ __forceinline__ void view_sample(const float* __restrict__ sum, const float* __restrict__ comp, int w, int h, bool wrap, bool bilinear, float fx, float fy,
-                                            float c[3]) {
-#pragma clang fp contract(off)
-  const float bx = floorf(bilinear ? fx : fx + 0.5f), by = floorf(bilinear ? fy : fy + 0.5f);
-  int x0, x1;
-  if (wrap) {
-    const int raw = static_cast<int>(fminf(fmaxf(bx, -1073741824.0f), 1073741824.0f));
-    x0 = ((raw % w) + w) % w;
-    x1 = x0 + 1 == w ? 0 : x0 + 1;
-  } else {
-    x0 = view_clamp_index(bx, w);
-    x1 = view_clamp_index(bx + 1.0f, w);
+    for (int j = 0; j < 3; j++) v[j] = __fadd_rn(sum[3u * pixel + j], comp[3u * pixel + j]);
   }
-  const int y0 = view_clamp_index(by, h), y1 = view_clamp_index(by + 1.0f, h);
-  float v00[3];
-  view_tap(sum, comp, w, x0, y0, v00);
-  if (!bilinear) {
-#pragma unroll
-    for (int j = 0; j < 3; j++) c[j] = v00[j];
-    return;
-  }
-  const float ax = fx - bx, ay = fy - by;   // (exact: a float less its own floor)
-  float v10[3], v01[3], v11[3];
-  view_tap(sum, comp, w, x1, y0, v10);
-  view_tap(sum, comp, w, x0, y1, v01);
-  view_tap(sum, comp, w, x1, y1, v11);
-#pragma unroll
-  for (int j = 0; j < 3; j++) {
-    const float top = fmaf(ax, v10[j] - v00[j], v00[j]);
-    const float bot = fmaf(ax, v11[j] - v01[j], v01[j]);
-    c[j] = fmaf(ay, bot - top, top);
-  }
-}
+  __device__ __forceinline__ void operator()(int ix, int iy, float v[3]) const { at(static_cast<uint32_t>(iy) * static_cast<uint32_t>(w) + static_cast<uint32_t>(ix), v); }
+};
 
 }  // namespace
 
@@ -155,14 +116,14 @@ __global__ void __launch_bounds__(kBlock) halo_view_filtered_kernel(const float*
     float raw[3] = {0.0f, 0.0f, 0.0f};
     if (from >= 0) {
       if (bilinear) {
-        view_sample(sum, comp, sw, sh, wrap, true, pos[0], pos[1], raw);
+        view_sample(XyzTap{sum, comp, sw}, sw, sh, wrap, true, pos[0], pos[1], raw);
       } else {   // the copy halo_view_kernel makes
 #pragma unroll
         for (int j = 0; j < 3; j++) raw[j] = __fadd_rn(sum[3u * static_cast<uint32_t>(from) + j], comp[3u * static_cast<uint32_t>(from) + j]);
       }
       if (DUAL_SRC && blend && hits == 2) {
         float c2[3];
-        view_sample(sum, comp, sw, sh, false, bilinear != 0, pos[2], pos[3], c2);
+        view_sample(XyzTap{sum, comp, sw}, sw, sh, false, bilinear != 0, pos[2], pos[3], c2);
 #pragma unroll
         for (int j = 0; j < 3; j++) raw[j] = fmaf(pos[4], c2[j] - raw[j], raw[j]);
       }

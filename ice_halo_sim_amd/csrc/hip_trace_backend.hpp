@@ -183,6 +183,19 @@ class HipTraceBackend {
             float* tap_out = nullptr) {
     Check(halo_consumer_view_filtered(h_, &spec, &filter, rgb_out, xyz_out, map_out, dir_out, tap_out));
   }
+  // The class composite through the view (halo_consumer_view_composite: the reference's preview in RGB mode): srgb_out 3 bytes, value_out 3 floats
+  // in byte units, map_out / tap_out the filtered view's; returns CompositeColorClasses' answer.  spec.display is ignored; the source render has
+  // the lanes' size.  {HALO_VIEW_NEAREST, 0} shows halo_consumer_composite's own bytes.
+  bool ViewComposite(const HaloViewSpec& spec, const HaloViewFilter& filter, const HaloComposite& composite, uint8_t* srgb_out, float* value_out = nullptr,
+                     int32_t* map_out = nullptr, float* tap_out = nullptr, float* participating_p99_y = nullptr) {
+    int32_t produced = 0;
+    Check(halo_consumer_view_composite(h_, &spec, &filter, &composite, srgb_out, value_out, map_out, tap_out, participating_p99_y, &produced));
+    return produced != 0;
+  }
+  // ... and the class lanes themselves (halo_consumer_view_lanes): lanes_out float[class_count][view height][view width], raw
+  void ViewLanes(const HaloViewSpec& spec, const HaloViewFilter& filter, float* lanes_out, int32_t* map_out = nullptr, float* tap_out = nullptr) {
+    Check(halo_consumer_view_lanes(h_, &spec, &filter, lanes_out, map_out, tap_out));
+  }
   // The reference GUI's Adaptive Brightness anchor (gui/gui_ev_auto.hpp ComputeP99Y + ComputeEvAuto) on the device consumer: expose a
   // snapshot with display.intensity_factor * exp2(result.ev_auto); result.produced == 0 is the GUI's "auto: no data"
   HaloAutoEv AutoEv(int downsample = 8, float target_white = 135.f) {

@@ -634,7 +634,7 @@ typedef struct HaloViewSpec {
  *   rgb_out  (3 bytes) halo_consumer_snapshot's display transform of that value: rgb_view[p] == rgb_snapshot[map[p]] byte for byte; at -1 what
  *            the snapshot gives a zero pixel.
  * A gather with no Jacobian, like the reference's shader: from an equal-area source (dual fisheye equal area is the reference's choice and the
- * recommended one) the view shows radiance; from any other source it shows the source pixels' energy as it lies.  No filtering, no class lanes.
+ * recommended one) the view shows radiance; from any other source it shows the source pixels' energy as it lies.  No filtering (halo_consumer_view_filtered); the class composite and the class lanes have calls of their own below.
  * Host pointers, any of them NULL to skip that output; runs on the backend's stream with one synchronise; reads the consumer only.
  * HALO_FATAL (handle still usable) before any fold / consume, inside a session, with every output NULL, with a source render whose size is not
  * the consumer's, with has_source = 0 on a handle that has had no session, with an empty view or an unknown lens; HALO_UNAVAILABLE for a view of
@@ -666,7 +666,7 @@ typedef struct HaloViewFilter {
  *            and a disc's rim fades into it as the reference's does.  Zeros at -1.
  *   rgb_out  (3 bytes) the snapshot's display transform of xyz_out: it runs on the filtered value, as the shader's does.
  * filter = nearest, blend = 0 gives the view call's bytes.  blend = 1 on a source without an overlap band changes nothing.  No area filter for
- * minified views, no Jacobian, no class lanes.  Refusals are the view call's (every output NULL counts tap_out), plus HALO_FATAL — the handle
+ * minified views, no Jacobian.  Refusals are the view call's (every output NULL counts tap_out), plus HALO_FATAL — the handle
  * stays usable — for a NULL filter, an unknown filter, a blend other than 0 or 1, non-zero reserved words. */
 int halo_consumer_view_filtered(halo_handle_t h, const HaloViewSpec* spec, const HaloViewFilter* filter, uint8_t* rgb_out, float* xyz_out, int32_t* map_out,
                                 float* dir_out, float* tap_out);
@@ -708,6 +708,39 @@ int halo_consumer_composite(halo_handle_t h, const HaloComposite* spec, float* l
 int halo_consumer_load_lanes(halo_handle_t h, const float* lanes, int width, int height, int class_count, double total_intensity);
 /* ParseCompositeMode (component_compositor.cpp:118-134): "dominant" / "additive" / "painter"; anything else is painter. */
 int halo_host_parse_composite_mode(const char* mode);
+
+/* --- the raypath-colour images through any lens: what the reference's preview shader shows in RGB mode — the composited sRGB bytes as its texture
+ *     (gui/preview_renderer.cpp:660-678, GL_RGB8), GL_LINEAR taps and sampleDualFisheye's cross-fade, no xyzToSrgb (:458-464) --- */
+/* halo_consumer_view_filtered's gather, of halo_consumer_composite's image instead of the consumer's.  Stage 1 composites the source render's
+ * image by halo_consumer_composite's code — active classes, participating P99, exposure scale, the composite kernel — into device memory, where
+ * it stays; stage 2 gathers the view from its bytes.  Per pixel of `spec->view`, row-major:
+ *   map_out    (int32) and
+ *   tap_out    (5 floats) are halo_consumer_view_filtered's for the same spec, bit for bit: a pixel has a source iff map_out >= 0.  They do not
+ *              depend on the composite and are written whenever the call returns HALO_OK.
+ *   value_out  (3 floats) the sample in BYTE units: a tap is the composite's sRGB byte triple as floats, float(b) — the GL texel times 255, an exact
+ *              integer, so a constant image stays that constant to the bit — and the taps, the three lerps (each one subtraction and one fma) and the
+ *              blend c = fma(t, c2 - c, c) are halo_consumer_view_filtered's.  Zeros at -1 (the shader's final_color = vec3(0)).
+ *   srgb_out   (3 bytes) uint8(floorf(value + 0.5f)), the framebuffer's round to nearest; the value lies in [0, 255].  With filter = nearest and
+ *              blend = 0: srgb_view[p] == srgb_composite[map[p]], halo_consumer_composite's byte.
+ * filter == NULL is nearest without a blend.  spec->display is ignored (the composite carries its own exposure).  The source render — spec->source,
+ * or the handle's last session's with has_source = 0 — must have the LANES' size; the consumer's image is not read and no fold is needed: the lanes
+ * exist after a colour session or halo_consumer_load_lanes, and stay as they are.  *produced and *participating_p99_y are halo_consumer_composite's:
+ * no class bit referenced — *produced = 0, neither image written; no active class — *produced = 1, both images black, P99 0; total intensity or
+ * P99 zero — *produced = 0, P99 written, srgb_out untouched, value_out zeroed.  Host pointers, any output NULL to skip it (participating_p99_y may
+ * be NULL, produced may not); runs on the backend's stream, the host waiting where the P99 select does and once at the end.
+ * HALO_FATAL (handle still usable) for a NULL spec, composite or produced, inside a session, with every output NULL, without lanes, with a source
+ * render whose size is not the lanes', with has_source = 0 on a handle that has had no session, with an empty view, an unknown lens, filter or
+ * composite mode, a blend other than 0 or 1, non-zero reserved words, a class_count other than halo_set_color's; HALO_UNAVAILABLE for a view of
+ * more than 2^25 pixels. */
+int halo_consumer_view_composite(halo_handle_t h, const HaloViewSpec* spec, const HaloViewFilter* filter, const HaloComposite* composite,
+                                 uint8_t* srgb_out, float* value_out, int32_t* map_out, float* tap_out,
+                                 float* participating_p99_y, int32_t* produced);
+/* The class lanes themselves through the view: lanes_out is float[class_count][view height][view width] for every class of halo_set_color, per
+ * class the same sample of float(lane) — the fp64 device lane narrowed per tap, as halo_readback_class_lanes narrows it — with the same taps, lerps
+ * and blend; zeros at -1.  No exposure, no composite: what a host with its own compositor, or a per-class analysis of one view, starts from.
+ * map_out, tap_out, filter, source and refusals as above; also HALO_UNAVAILABLE for class_count x view pixels of more than 2^27 floats. */
+int halo_consumer_view_lanes(halo_handle_t h, const HaloViewSpec* spec, const HaloViewFilter* filter,
+                             float* lanes_out, int32_t* map_out, float* tap_out);
 
 /* --- host-side pieces of the path, exported for parity tests (no GPU needed) ---------------- */
 /* Geometry tables the kernels consume (reference: Crystal::PopulateFromCfGeom crystal.cpp:304-347,

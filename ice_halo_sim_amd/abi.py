@@ -177,6 +177,22 @@ class HaloViewFilter(C.Structure):
     _fields_ = [("filter", C.c_int32), ("blend", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+VIEW_MAX_SUN_CIRCLES = 16
+VIEW_OVERLAY_LAYERS = {"horizon": "show_horizon", "grid": "show_grid", "circles": "show_sun_circles", "zenith": "show_zenith_nadir", "sun": "show_sun_marker"}
+
+
+class HaloViewOverlay(C.Structure):
+    """halo_consumer_view_overlay's record: the five layer switches, the grid step, the sun's travel direction, the sun circles' angles, per layer a
+    colour and an alpha in [0, 1], the ring and marker radii in view pixels, two zero words.  halo_host_view_overlay_defaults fills the reference's."""
+    _fields_ = [("show_horizon", C.c_int32), ("show_grid", C.c_int32), ("show_sun_circles", C.c_int32), ("show_zenith_nadir", C.c_int32),
+                ("show_sun_marker", C.c_int32), ("grid_step_deg", C.c_float), ("sun_dir", C.c_float * 3), ("sun_circle_count", C.c_int32),
+                ("sun_circle_deg", C.c_float * VIEW_MAX_SUN_CIRCLES),
+                ("horizon_color", C.c_float * 3), ("horizon_alpha", C.c_float), ("grid_color", C.c_float * 3), ("grid_alpha", C.c_float),
+                ("sun_circles_color", C.c_float * 3), ("sun_circles_alpha", C.c_float), ("zenith_nadir_color", C.c_float * 3), ("zenith_nadir_alpha", C.c_float),
+                ("sun_marker_color", C.c_float * 3), ("sun_marker_alpha", C.c_float), ("zenith_nadir_radius_px", C.c_float), ("sun_marker_radius_px", C.c_float),
+                ("reserved", C.c_int32 * 2)]
+
+
 COMPOSITE_DOMINANT, COMPOSITE_ADDITIVE, COMPOSITE_PAINTER = 0, 1, 2
 
 

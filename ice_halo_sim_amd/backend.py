@@ -101,6 +101,14 @@ def load_library():
         "halo_consumer_view_composite": (C.c_int, [H, C.POINTER(abi.HaloViewSpec), C.POINTER(abi.HaloViewFilter), C.POINTER(abi.HaloComposite), C.POINTER(C.c_uint8), f32p,
                                                    C.POINTER(C.c_int32), f32p, f32p, C.POINTER(C.c_int32)]),
         "halo_consumer_view_lanes": (C.c_int, [H, C.POINTER(abi.HaloViewSpec), C.POINTER(abi.HaloViewFilter), f32p, C.POINTER(C.c_int32), f32p]),
+        "halo_host_view_overlay_defaults": (C.c_int, [C.c_float, f32p, C.POINTER(abi.HaloViewOverlay)]),
+        "halo_consumer_view_overlay": (C.c_int, [H, C.POINTER(abi.HaloViewSpec), C.POINTER(abi.HaloViewFilter), C.POINTER(abi.HaloViewOverlay), C.POINTER(C.c_uint8), f32p, f32p,
+                                                 f32p, C.POINTER(C.c_int32), f32p]),
+        "halo_consumer_view_composite_overlay": (C.c_int, [H, C.POINTER(abi.HaloViewSpec), C.POINTER(abi.HaloViewFilter), C.POINTER(abi.HaloComposite),
+                                                           C.POINTER(abi.HaloViewOverlay), C.POINTER(C.c_uint8), f32p, f32p, f32p, C.POINTER(C.c_int32), f32p, f32p, f32p,
+                                                           C.POINTER(C.c_int32)]),
+        "halo_host_view_sky": (C.c_int, [f32p, f32p, f32p]),
+        "halo_host_view_overlay_pixel": (C.c_int, [C.POINTER(C.c_uint8), f32p, f32p, f32p, C.POINTER(abi.HaloViewOverlay), f32p]),
         "halo_host_prism_geometry": (C.c_int, [C.c_float, f32p, C.POINTER(abi.HaloGeomTables)]),
         "halo_host_pyramid_geometry": (C.c_int, [C.c_float] * 5 + [f32p, C.POINTER(abi.HaloGeomTables)]),
         "halo_host_shape_scalars": (C.c_int, [C.POINTER(abi.HaloCrystal), C.c_uint32, C.c_uint64, C.c_int, f32p]),
@@ -136,6 +144,7 @@ EXPORTED_SYMBOLS = [
     "halo_consumer_stats", "halo_host_percentile_rank", "halo_host_binned_sum",
     "halo_consumer_view", "halo_host_view_direction", "halo_consumer_view_filtered", "halo_host_view_source_pos",
     "halo_consumer_view_composite", "halo_consumer_view_lanes",
+    "halo_host_view_overlay_defaults", "halo_consumer_view_overlay", "halo_consumer_view_composite_overlay", "halo_host_view_sky", "halo_host_view_overlay_pixel",
     "halo_set_shard", "halo_host_shard_slice", "halo_export_fixed", "halo_import_fixed",
 ]
 
@@ -579,6 +588,108 @@ class HipTraceBackend:
         f = abi.HaloViewFilter(abi.VIEW_FILTERS[filter], 1 if blend else 0)
         self._check(self._L.halo_consumer_view_lanes(self._h, C.byref(spec), C.byref(f), ptr("lanes", C.c_float), ptr("map", C.c_int32), ptr("tap", C.c_float)))
         return out
+
+    def ViewOverlay(self, view, overlay, source=None, intensity_factor=1.0, ray_color=(-1.0, -1.0, -1.0), background=(0.0, 0.0, 0.0), filter="nearest", blend=False,
+                    want=("rgb",)):
+        """View's image with the auxiliary lines on it (halo_consumer_view_overlay): `overlay` is an abi.HaloViewOverlay (view_overlay makes one) —
+        horizon, altitude / azimuth grid, circles around the sun, zenith and nadir rings, a sun marker, drawn on the device from the direction of each
+        view pixel.  The other arguments are View's.  want: any of "rgb" (uint8[H,W,3]), "value" (float32[H,W,3]: the colour after the last layer in
+        byte units, rgb = floor(clamp(value) + 0.5)), "sky" (float32[H,W,6]: alt, az, dist and their pixel footprints, degrees), "marks" (float32[3,3]:
+        x, y, present of zenith, nadir, sun in view pixels), "map" and "dir" (View's).  Returns a dict of the arrays asked for."""
+        unknown = set(want) - {"rgb", "value", "sky", "marks", "map", "dir"}
+        if unknown:
+            raise ValueError("ViewOverlay: unknown output %r" % sorted(unknown))
+        if filter not in abi.VIEW_FILTERS:
+            raise ValueError("ViewOverlay: unknown filter %r (nearest | bilinear)" % (filter,))
+        spec = abi.HaloViewSpec()
+        spec.view = view
+        spec.has_source = 0 if source is None else 1
+        if source is not None:
+            spec.source = source
+        spec.display = abi.HaloDisplay(float(intensity_factor), (C.c_float * 3)(*ray_color), (C.c_float * 3)(*background))
+        h, w = max(int(view.height), 0), max(int(view.width), 0)
+        big = w * h > 1 << 25   # (refused by the library: nothing of that size is allocated here)
+        shapes = {"rgb": ((h, w, 3), np.uint8), "value": ((h, w, 3), np.float32), "sky": ((h, w, 6), np.float32), "map": ((h, w), np.int32),
+                  "dir": ((h, w, 3), np.float32)}
+        out = {k: np.zeros((3, 3) if k == "marks" else (0,) if big else shapes[k][0], np.float32 if k == "marks" else shapes[k][1]) for k in want}
+
+        def ptr(k, t):
+            return out[k].ctypes.data_as(C.POINTER(t)) if k in out else None
+        f = abi.HaloViewFilter(abi.VIEW_FILTERS[filter], 1 if blend else 0)
+        self._check(self._L.halo_consumer_view_overlay(self._h, C.byref(spec), C.byref(f), C.byref(overlay), ptr("rgb", C.c_uint8), ptr("value", C.c_float),
+                                                       ptr("sky", C.c_float), ptr("marks", C.c_float), ptr("map", C.c_int32), ptr("dir", C.c_float)))
+        return out
+
+    def ViewCompositeOverlay(self, view, overlay, classes, mode="painter", display_exposure_scale=1.0, intensity_factor=1.0, source=None, filter="nearest", blend=False,
+                             want=("srgb",)):
+        """ViewComposite's image with ViewOverlay's lines on it (halo_consumer_view_composite_overlay).  want: any of "srgb", "value" (the colour
+        after the last layer), "sky", "marks", "map", "tap", "dir"; "produced" and "p99" as ViewComposite gives them: with produced False "srgb" is
+        None and nothing is drawn."""
+        spec, h, w = self._lane_view_spec("ViewCompositeOverlay", view, source, filter, want, ("srgb", "value", "sky", "marks", "map", "tap", "dir"))
+        comp = abi.composite(classes, mode, display_exposure_scale, intensity_factor)
+        big = w * h > 1 << 25   # (refused by the library: nothing of that size is allocated here)
+        shapes = {"srgb": ((h, w, 3), np.uint8), "value": ((h, w, 3), np.float32), "sky": ((h, w, 6), np.float32), "map": ((h, w), np.int32),
+                  "tap": ((h, w, 5), np.float32), "dir": ((h, w, 3), np.float32)}
+        out = {k: np.zeros((3, 3) if k == "marks" else (0,) if big else shapes[k][0], np.float32 if k == "marks" else shapes[k][1]) for k in want}
+
+        def ptr(k, t):
+            return out[k].ctypes.data_as(C.POINTER(t)) if k in out else None
+        f = abi.HaloViewFilter(abi.VIEW_FILTERS[filter], 1 if blend else 0)
+        p99, produced = C.c_float(0.0), C.c_int32(0)
+        self._check(self._L.halo_consumer_view_composite_overlay(self._h, C.byref(spec), C.byref(f), C.byref(comp), C.byref(overlay), ptr("srgb", C.c_uint8),
+                                                                 ptr("value", C.c_float), ptr("sky", C.c_float), ptr("marks", C.c_float), ptr("map", C.c_int32),
+                                                                 ptr("tap", C.c_float), ptr("dir", C.c_float), C.byref(p99), C.byref(produced)))
+        if not produced.value and "srgb" in out:
+            out["srgb"] = None
+        out["produced"], out["p99"] = bool(produced.value), p99.value
+        return out
+
+
+def view_overlay(fov, sun_alt_az=None, layers=(), circles=None, grid_step=None):
+    """An abi.HaloViewOverlay with the reference's defaults (halo_host_view_overlay_defaults; no device needed) for a view of `fov` degrees and the
+    sun at sun_alt_az = (altitude, azimuth) degrees (None: the zenith).  layers: names of abi.VIEW_OVERLAY_LAYERS to switch on (horizon, grid,
+    circles, zenith, sun); circles: the angular distances from the sun (default 22, 46); grid_step: degrees (default: by the field of view)."""
+    o = abi.HaloViewOverlay()
+    sun = None if sun_alt_az is None else (C.c_float * 2)(float(sun_alt_az[0]), float(sun_alt_az[1]))
+    size = load_library().halo_host_view_overlay_defaults(float(fov), sun, C.byref(o))
+    if size != C.sizeof(abi.HaloViewOverlay):
+        raise BackendError("HaloViewOverlay is %d bytes in the library, %d here" % (size, C.sizeof(abi.HaloViewOverlay)))
+    for name in layers:
+        if name not in abi.VIEW_OVERLAY_LAYERS:
+            raise ValueError("view_overlay: unknown layer %r (%s)" % (name, " | ".join(abi.VIEW_OVERLAY_LAYERS)))
+        setattr(o, abi.VIEW_OVERLAY_LAYERS[name], 1)
+    if circles is not None:
+        circles = [float(v) for v in circles]
+        if len(circles) > abi.VIEW_MAX_SUN_CIRCLES:
+            raise ValueError("view_overlay: at most %d sun circles" % abi.VIEW_MAX_SUN_CIRCLES)
+        o.sun_circle_count = len(circles)
+        for i in range(abi.VIEW_MAX_SUN_CIRCLES):
+            o.sun_circle_deg[i] = circles[i] if i < len(circles) else 0.0
+    if grid_step is not None:
+        o.grid_step_deg = float(grid_step)
+    return o
+
+
+def host_view_sky(direction, sun_dir):
+    """halo_host_view_sky: float32[3] = altitude, azimuth, angular distance from the sun (degrees) of the travel direction `direction`, by the
+    overlay's own code on the host (no device needed)."""
+    d, s = np.ascontiguousarray(direction, np.float32), np.ascontiguousarray(sun_dir, np.float32)
+    sky = np.zeros(3, np.float32)
+    f32p = C.POINTER(C.c_float)
+    load_library().halo_host_view_sky(d.ctypes.data_as(f32p), s.ctypes.data_as(f32p), sky.ctypes.data_as(f32p))
+    return sky
+
+
+def host_view_overlay_pixel(base_rgb, sky6, pixel_xy, marks, overlay):
+    """halo_host_view_overlay_pixel: float32[3], the colour in byte units after the last layer of one pixel that has a direction (no device needed)."""
+    b = np.ascontiguousarray(base_rgb, np.uint8)
+    s, xy, m = (np.ascontiguousarray(v, np.float32).reshape(-1) for v in (sky6, pixel_xy, marks))
+    v = np.zeros(3, np.float32)
+    f32p = C.POINTER(C.c_float)
+    if not load_library().halo_host_view_overlay_pixel(b.ctypes.data_as(C.POINTER(C.c_uint8)), s.ctypes.data_as(f32p), xy.ctypes.data_as(f32p), m.ctypes.data_as(f32p),
+                                                       C.byref(overlay), v.ctypes.data_as(f32p)):
+        raise ValueError("host_view_overlay_pixel: refused (a circle count outside 0 .. 16)")
+    return v
 
 
 def host_view_direction(view, px, py):

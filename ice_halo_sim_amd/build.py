@@ -15,10 +15,10 @@ if TAG == "strict":
     os.environ["HALO_DEFS"] = (os.environ.get("HALO_DEFS", "") + " -DHALO_STRICT=1 -DHALO_FRESNEL=1").strip()
     os.environ["HALO_FP_CONTRACT"] = "off"
 LIB = os.path.join(HERE, "libhalo_hip_%s.so" % TAG if TAG else "libhalo_hip.so")
-SOURCES = ["halo_trace_m0.hip", "halo_trace_m1.hip", "halo_trace_m2.hip", "halo_trace_m3.hip", "halo_trace_m4.hip", "halo_trace_fx0.hip", "halo_trace_fx1.hip", "halo_trace_fxl0.hip", "halo_trace_fxl1.hip", "halo_trace_tl0.hip", "halo_kernels.hip", "halo_autoev.hip", "halo_stats.hip", "halo_view.hip", "halo_view_composite.hip", "halo_shapegen.hip", "halo_backend.cpp",
+SOURCES = ["halo_trace_m0.hip", "halo_trace_m1.hip", "halo_trace_m2.hip", "halo_trace_m3.hip", "halo_trace_m4.hip", "halo_trace_fx0.hip", "halo_trace_fx1.hip", "halo_trace_fxl0.hip", "halo_trace_fxl1.hip", "halo_trace_tl0.hip", "halo_kernels.hip", "halo_autoev.hip", "halo_stats.hip", "halo_view.hip", "halo_view_composite.hip", "halo_view_overlay.hip", "halo_shapegen.hip", "halo_backend.cpp",
            "halo_consumer.cpp", "halo_host_abi.cpp", "halo_host.cpp"]
 NO_CONTRACT = {"halo_shapegen.hip", "halo_stats.hip"}   # geometry / the percentile rank rule shared with the host: same rounding on both sides
-HEADERS = ["halo_device.h", "halo_launch.h", "halo_select.h", "halo_radix.h", "halo_trace.inl", "halo_geom.h", "halo_view.h", "halo_view_sample.h", "halo_display.h", "halo_host.hpp", "halo_state.h", "halo_options.h", "halo_order.h", "cie_tables.inc", os.path.join("..", "..", "include", "halo_trace.h")]
+HEADERS = ["halo_device.h", "halo_launch.h", "halo_select.h", "halo_radix.h", "halo_trace.inl", "halo_geom.h", "halo_view.h", "halo_view_sample.h", "halo_overlay.h", "halo_display.h", "halo_host.hpp", "halo_state.h", "halo_options.h", "halo_order.h", "cie_tables.inc", os.path.join("..", "..", "include", "halo_trace.h")]
 
 
 def hipcc():

@@ -145,6 +145,25 @@ def exposure_factor(be, rid, factor, args):
     return factor * 2.0 ** a["ev_auto"]
 
 
+def view_overlay(args, job, view):
+    """--view-overlay: the HaloViewOverlay for `view`, or None.  The sun is the configuration's."""
+    if not args.view_overlay:
+        return None
+    layers = [v.strip() for v in args.view_overlay.split(",") if v.strip()]
+    unknown = [v for v in layers if v not in abi.VIEW_OVERLAY_LAYERS]
+    if unknown:
+        raise config.ConfigError("--view-overlay: unknown layer %r (horizon, grid, circles, zenith, sun)" % unknown[0])
+    try:
+        circles = [float(v) for v in args.view_circles.split(",")] if args.view_circles else None
+        step = None if args.view_grid_step == "auto" else float(args.view_grid_step)
+    except ValueError:
+        raise config.ConfigError("--view-circles wants DEG,DEG,... and --view-grid-step auto or DEG")
+    if circles is not None and len(circles) > abi.VIEW_MAX_SUN_CIRCLES:
+        raise config.ConfigError("--view-circles: at most %d" % abi.VIEW_MAX_SUN_CIRCLES)
+    from .backend import view_overlay as make
+    return make(view.fov, (job.scene.sun_altitude, job.scene.sun_azimuth), layers, circles, step)
+
+
 def view_render(args, source):
     """--out-view: the HaloRender to look through.  What is not given keeps the traced render's value (size, view direction, visible range,
     overlap) or the lens's usual field of view; the lens shift is none."""
@@ -254,6 +273,12 @@ def main(argv=None):
     ap.add_argument("--out-lanes", default=None, help="raypath_color configs: write the per-class Y lanes (classes, H, W) as .npy")
     ap.add_argument("--out-composite", default=None, help="raypath_color configs: write the class composite (the config's mode: dominant | additive | "
                     "painter; component_compositor.cpp) as binary PPM, composited on the device")
+    ap.add_argument("--view-overlay", default=None, metavar="LAYERS",
+                    help="draw auxiliary lines over --out-view and --out-view-composite, on the device: a comma-separated list of horizon, grid (altitude / "
+                    "azimuth), circles (of constant angular distance from the sun), zenith (zenith and nadir rings) and sun (a marker); the sun is the "
+                    "configuration's")
+    ap.add_argument("--view-circles", default=None, metavar="DEG,DEG", help="angular distances of --view-overlay circles from the sun (default 22,46; at most 16)")
+    ap.add_argument("--view-grid-step", default="auto", metavar="auto|DEG", help="spacing of the --view-overlay grid in degrees (auto: by the view's field of view)")
     ap.add_argument("--out-view-composite", default=None, metavar="FILE.ppm",
                     help="raypath_color configs: write the class composite seen through another lens as binary PPM — --out-composite's image gathered "
                     "on the device the way --out-view gathers the traced one (the --view-* arguments, --view-filter and --view-blend apply; "
@@ -361,7 +386,12 @@ def main(argv=None):
         np.save(args.out_xyz, xyz)
     if args.out_view:
         try:
-            write_ppm(args.out_view, be.View(view_render(args, res["render"]), res["render"], filter=args.view_filter, blend=args.view_blend, **display)["rgb"])
+            view = view_render(args, res["render"])
+            overlay = view_overlay(args, job, view)
+            if overlay is None:
+                write_ppm(args.out_view, be.View(view, res["render"], filter=args.view_filter, blend=args.view_blend, **display)["rgb"])
+            else:
+                write_ppm(args.out_view, be.ViewOverlay(view, overlay, res["render"], filter=args.view_filter, blend=args.view_blend, **display)["rgb"])
         except config.ConfigError as e:
             print("config error: %s" % e, file=sys.stderr)
             be.close()
@@ -374,8 +404,14 @@ def main(argv=None):
             print("no composite: the participating classes hold no energy (P99 %.3g)" % p99, file=sys.stderr)
     if args.out_view_composite and job.color_classes:   # ... and so does its view
         try:
-            out = be.ViewComposite(view_render(args, res["render"]), job.color_meta, job.color_mode, 2.0 ** args.display_ev, meta.get("intensity_factor", 1.0),
-                                   source=res["render"], filter=args.view_filter, blend=args.view_blend)
+            view = view_render(args, res["render"])
+            overlay = view_overlay(args, job, view)
+            if overlay is None:
+                out = be.ViewComposite(view, job.color_meta, job.color_mode, 2.0 ** args.display_ev, meta.get("intensity_factor", 1.0),
+                                       source=res["render"], filter=args.view_filter, blend=args.view_blend)
+            else:
+                out = be.ViewCompositeOverlay(view, overlay, job.color_meta, job.color_mode, 2.0 ** args.display_ev, meta.get("intensity_factor", 1.0),
+                                              source=res["render"], filter=args.view_filter, blend=args.view_blend)
         except config.ConfigError as e:
             print("config error: %s" % e, file=sys.stderr)
             be.close()

@@ -1,6 +1,6 @@
 // halo_consumer.cpp — the consumer stages of the C ABI (RenderConsumer, server/render.hpp, on the device): the Neumaier running image and its
 // total landed intensity (reset, fold, consume), and what is made of them — snapshot, auto exposure, image statistics, the view through another
-// lens — and of the class lanes: load, composite, composite and lanes through another lens, read-back.  Their state is HaloBackend::cons (halo_state.h Consumer); the lanes themselves are
+// lens, with or without the auxiliary lines — and of the class lanes: load, composite, composite and lanes through another lens, read-back.  Their state is HaloBackend::cons (halo_state.h Consumer); the lanes themselves are
 // written by trace sessions and stay with the session state.  Host C++ only; built without FMA contraction like every host unit: the float
 // expressions below are the reference's, operand for operand.
 #include <hip/hip_runtime.h>
@@ -41,16 +41,24 @@ int start_image(HaloBackend* b, int w, int h) {
   return HALO_OK;
 }
 
-// halo_consumer_view and halo_consumer_view_filtered (`filter` != nullptr: its kernel and its fifth output): the argument checks, the launch, the
-// copy-back.  `who` names the call in the messages.
-int view_call(HaloBackend* b, const char* who, const HaloViewSpec* spec, const HaloViewFilter* filter, uint8_t* rgb_out, float* xyz_out, int32_t* map_out, float* dir_out,
-              float* tap_out) {
+// The view calls in two steps, so that a pass can run between them on the gather's device buffers (halo_consumer_view_overlay).
+// view_launch: halo_consumer_view's and halo_consumer_view_filtered's (`filter` != nullptr: its kernel and its fifth output) argument checks and
+// launch; `want` says which of the five device buffers the kernel fills, `any_output` whether the caller takes anything at all.  `who` names the
+// call in the messages.
+struct ViewWant {
+  bool rgb, xyz, map, dir, tap;
+};
+struct ViewPlan {
+  size_t npix = 0, n = 0;   // view pixels, and three per pixel
+  float scale = 0.0f;       // the exposure scale (0: PostSnapshot's early-out, the bytes are zeros whatever the kernel wrote)
+};
+int view_launch(HaloBackend* b, const char* who, const HaloViewSpec* spec, const HaloViewFilter* filter, const ViewWant& want, bool any_output, ViewPlan* plan) {
   if (!b) return HALO_FATAL;
   const std::string name(who);
   if (!spec) return fail(b, HALO_FATAL, name + ": spec is NULL");
   if (!b->cons.sum.ptr) return fail(b, HALO_FATAL, name + " before consumer_fold");
   if (b->in_session) return fail(b, HALO_FATAL, name + " inside a session");
-  if (!rgb_out && !xyz_out && !map_out && !dir_out && !tap_out) return fail(b, HALO_FATAL, name + ": every output is NULL");
+  if (!any_output) return fail(b, HALO_FATAL, name + ": every output is NULL");
   const HaloRender& view = spec->view;
   if (view.width <= 0 || view.height <= 0) return fail(b, HALO_FATAL, name + ": empty view");
   if (static_cast<uint64_t>(view.width) * static_cast<uint64_t>(view.height) > (1ull << 25))
@@ -64,31 +72,72 @@ int view_call(HaloBackend* b, const char* who, const HaloViewSpec* spec, const H
   const uint32_t cons_pix = static_cast<uint32_t>(b->cons.w) * static_cast<uint32_t>(b->cons.h);
   const size_t npix = static_cast<size_t>(view.width) * static_cast<size_t>(view.height), n = npix * 3;
   const float scale = exposure_scale(b, spec->display.intensity_factor, cons_pix);   // over the CONSUMER's pixels, as halo_consumer_snapshot: a view pixel is its source pixel's byte
-  if (rgb_out) HIPCHK(b, b->cons.view_rgb.reserve(n));
-  if (xyz_out) HIPCHK(b, b->cons.view_xyz.reserve(n));
-  if (dir_out) HIPCHK(b, b->cons.view_dir.reserve(n));
-  if (map_out) HIPCHK(b, b->cons.view_map.reserve(npix));
-  if (tap_out) HIPCHK(b, b->cons.view_tap.reserve(npix * 5));
-  uint8_t* rgb_dev = rgb_out ? b->cons.view_rgb.ptr : nullptr;
-  float* xyz_dev = xyz_out ? b->cons.view_xyz.ptr : nullptr;
-  int32_t* map_dev = map_out ? b->cons.view_map.ptr : nullptr;
-  float* dir_dev = dir_out ? b->cons.view_dir.ptr : nullptr;
+  plan->npix = npix;
+  plan->n = n;
+  plan->scale = scale;
+  if (want.rgb) HIPCHK(b, b->cons.view_rgb.reserve(n));
+  if (want.xyz) HIPCHK(b, b->cons.view_xyz.reserve(n));
+  if (want.dir) HIPCHK(b, b->cons.view_dir.reserve(n));
+  if (want.map) HIPCHK(b, b->cons.view_map.reserve(npix));
+  if (want.tap) HIPCHK(b, b->cons.view_tap.reserve(npix * 5));
+  uint8_t* rgb_dev = want.rgb ? b->cons.view_rgb.ptr : nullptr;
+  float* xyz_dev = want.xyz ? b->cons.view_xyz.ptr : nullptr;
+  int32_t* map_dev = want.map ? b->cons.view_map.ptr : nullptr;
+  float* dir_dev = want.dir ? b->cons.view_dir.ptr : nullptr;
   hipError_t e;
   if (filter)
     e = launch_view_filtered(b->cons.sum.ptr, b->cons.comp.ptr, host::BuildProj(view), host::BuildProj(source), scale, spec->display.ray_color, spec->display.background,
-                             filter->filter == HALO_VIEW_BILINEAR, filter->blend != 0, rgb_dev, xyz_dev, map_dev, dir_dev, tap_out ? b->cons.view_tap.ptr : nullptr,
+                             filter->filter == HALO_VIEW_BILINEAR, filter->blend != 0, rgb_dev, xyz_dev, map_dev, dir_dev, want.tap ? b->cons.view_tap.ptr : nullptr,
                              b->cu_count * 8, main_q(b));
   else
     e = launch_view(b->cons.sum.ptr, b->cons.comp.ptr, host::BuildProj(view), host::BuildProj(source), scale, spec->display.ray_color, spec->display.background, rgb_dev,
                     xyz_dev, map_dev, dir_dev, b->cu_count * 8, main_q(b));
   if (e != hipSuccess) return hip_fail(b, e, filter ? "halo_view_filtered_kernel launch" : "halo_view_kernel launch");
+  return HALO_OK;
+}
+// view_copy_back: the device buffers of a launched view into the caller's (any may be null), one synchronise, and the early-out's zero bytes.
+int view_copy_back(HaloBackend* b, const ViewPlan& plan, uint8_t* rgb_out, float* xyz_out, int32_t* map_out, float* dir_out, float* tap_out) {
+  const size_t npix = plan.npix, n = plan.n;
   if (rgb_out) HIPCHK(b, hipMemcpyAsync(rgb_out, b->cons.view_rgb.ptr, n, hipMemcpyDeviceToHost, main_q(b)));
   if (xyz_out) HIPCHK(b, hipMemcpyAsync(xyz_out, b->cons.view_xyz.ptr, n * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
   if (map_out) HIPCHK(b, hipMemcpyAsync(map_out, b->cons.view_map.ptr, npix * sizeof(int32_t), hipMemcpyDeviceToHost, main_q(b)));
   if (dir_out) HIPCHK(b, hipMemcpyAsync(dir_out, b->cons.view_dir.ptr, n * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
   if (tap_out) HIPCHK(b, hipMemcpyAsync(tap_out, b->cons.view_tap.ptr, npix * 5 * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
   HIPCHK(b, hipStreamSynchronize(main_q(b)));
-  if (rgb_out && scale == 0.0f) std::memset(rgb_out, 0, n);   // PostSnapshot's early-out, as halo_consumer_snapshot has it
+  if (rgb_out && plan.scale == 0.0f) std::memset(rgb_out, 0, n);   // PostSnapshot's early-out, as halo_consumer_snapshot has it
+  return HALO_OK;
+}
+int view_call(HaloBackend* b, const char* who, const HaloViewSpec* spec, const HaloViewFilter* filter, uint8_t* rgb_out, float* xyz_out, int32_t* map_out, float* dir_out,
+              float* tap_out) {
+  ViewPlan plan;
+  const ViewWant want{rgb_out != nullptr, xyz_out != nullptr, map_out != nullptr, dir_out != nullptr, tap_out != nullptr};
+  if (int rc = view_launch(b, who, spec, filter, want, rgb_out || xyz_out || map_out || dir_out || tap_out, &plan)) return rc;
+  return view_copy_back(b, plan, rgb_out, xyz_out, map_out, dir_out, tap_out);
+}
+
+// What halo_consumer_view_filtered refuses in a filter, for every call that takes one (nullptr: nothing).
+const char* filter_refusal(const HaloViewFilter* filter) {
+  if (filter->filter != HALO_VIEW_NEAREST && filter->filter != HALO_VIEW_BILINEAR) return ": unknown filter";
+  if (filter->blend != 0 && filter->blend != 1) return ": blend must be 0 or 1";
+  if (filter->reserved[0] != 0 || filter->reserved[1] != 0) return ": reserved words must be zero";
+  return nullptr;
+}
+
+// The overlay pass behind a gather (halo_view_overlay.hip), for both overlay calls: the marks, the launch over the gather's view_dir and — null: the
+// sky coordinates alone — its view_rgb, and the copies of what the pass alone makes (not synchronised: the caller's last copy-back waits).
+int overlay_pass(HaloBackend* b, const HaloRender& view, const HaloViewOverlay& overlay, bool draw, float* value_out, float* sky_out, float* marks_out) {
+  const size_t npix = static_cast<size_t>(view.width) * static_cast<size_t>(view.height);
+  float marks[9];
+  host::ViewOverlayMarks(view, overlay.sun_dir, marks);
+  if (marks_out) std::memcpy(marks_out, marks, sizeof(marks));
+  if (!draw && !sky_out) return HALO_OK;
+  if (draw && value_out) HIPCHK(b, b->cons.view_val.reserve(npix * 3));
+  if (sky_out) HIPCHK(b, b->cons.view_sky.reserve(npix * 6));
+  hipError_t e = launch_view_overlay(b->cons.view_dir.ptr, overlay, marks, view.width, view.height, draw ? b->cons.view_rgb.ptr : nullptr,
+                                     draw && value_out ? b->cons.view_val.ptr : nullptr, sky_out ? b->cons.view_sky.ptr : nullptr, b->cu_count * 8, main_q(b));
+  if (e != hipSuccess) return hip_fail(b, e, "halo_view_overlay_kernel launch");
+  if (draw && value_out) HIPCHK(b, hipMemcpyAsync(value_out, b->cons.view_val.ptr, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
+  if (sky_out) HIPCHK(b, hipMemcpyAsync(sky_out, b->cons.view_sky.ptr, npix * 6 * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
   return HALO_OK;
 }
 
@@ -220,6 +269,81 @@ int lane_view_checks(HaloBackend* b, const std::string& name, const HaloViewSpec
   if (view.lens_type < HALO_LENS_LINEAR || view.lens_type > HALO_LENS_GLOBE || src.lens_type < HALO_LENS_LINEAR || src.lens_type > HALO_LENS_GLOBE)
     return fail(b, HALO_FATAL, name + ": unknown lens type");
   *source = &src;
+  return HALO_OK;
+}
+
+// halo_consumer_view_composite (`overlay` == nullptr: sky_out, marks_out and dir_out are null too) and halo_consumer_view_composite_overlay: stage 1,
+// the gather and — with an overlay — the view's directions and the overlay pass over the gathered bytes; value_out is then the pass's.
+int view_composite_call(HaloBackend* b, const std::string& name, const HaloViewSpec* spec, const HaloViewFilter* filter, const HaloComposite* composite,
+                        const HaloViewOverlay* overlay, uint8_t* srgb_out, float* value_out, float* sky_out, float* marks_out, int32_t* map_out, float* tap_out, float* dir_out,
+                        float* participating_p99_y, int32_t* produced) {
+  if (!produced) return fail(b, HALO_FATAL, name + ": produced is NULL");
+  *produced = 0;
+  const HaloRender* source = nullptr;
+  if (int rc = lane_view_checks(b, name, spec, filter, srgb_out || value_out || sky_out || marks_out || map_out || tap_out || dir_out, &source)) return rc;
+  if (!composite) return fail(b, HALO_FATAL, name + ": composite is NULL");
+  if (composite->mode < HALO_COMPOSITE_DOMINANT || composite->mode > HALO_COMPOSITE_PAINTER) return fail(b, HALO_FATAL, name + ": unknown mode");
+  if (composite->class_count != static_cast<int>(b->color_classes.size())) return fail(b, HALO_FATAL, name + ": class_count differs from halo_set_color's");
+  HIPCHK(b, hipSetDevice(b->device));
+  if (int rc = join_aux(b)) return rc;   // (kernels of queued sessions may still be adding to the lanes on the trace / auxiliary streams)
+  CompositePlan plan;
+  if (int rc = composite_prepare(b, name.c_str(), composite, &plan)) return rc;
+  const HaloRender& view = spec->view;
+  const size_t npix = static_cast<size_t>(view.width) * static_cast<size_t>(view.height), n = npix * 3;
+  const bool ready = plan.state == kCompositeReady;
+  const uint8_t* src_dev = nullptr;
+  if (ready && (srgb_out || value_out)) {
+    HIPCHK(b, b->cons.view_comp_src.reserve(static_cast<size_t>(plan.npix) * 3u));
+    hipError_t e = launch_composite(b->lanes.ptr, plan.npix, plan.cd, nullptr, b->cons.view_comp_src.ptr, b->cu_count * 8, main_q(b));
+    if (e != hipSuccess) return hip_fail(b, e, "halo_composite_kernel launch");
+    src_dev = b->cons.view_comp_src.ptr;
+  }
+  // with an overlay the gather always writes its bytes (the pass draws on them) and never its value: value_out is the colour after the last layer
+  const bool gather_rgb = src_dev && (srgb_out || (overlay && value_out)), gather_value = src_dev && value_out && !overlay;
+  bool pending = false;
+  if (src_dev || map_out || tap_out) {
+    if (gather_rgb) HIPCHK(b, b->cons.view_rgb.reserve(n));
+    if (gather_value) HIPCHK(b, b->cons.view_xyz.reserve(n));
+    if (map_out) HIPCHK(b, b->cons.view_map.reserve(npix));
+    if (tap_out) HIPCHK(b, b->cons.view_tap.reserve(npix * 5));
+    hipError_t e = launch_view_composite(src_dev, host::BuildProj(view), host::BuildProj(*source), filter && filter->filter == HALO_VIEW_BILINEAR, filter && filter->blend != 0,
+                                         gather_rgb ? b->cons.view_rgb.ptr : nullptr, gather_value ? b->cons.view_xyz.ptr : nullptr,
+                                         map_out ? b->cons.view_map.ptr : nullptr, tap_out ? b->cons.view_tap.ptr : nullptr, b->cu_count * 8, main_q(b));
+    if (e != hipSuccess) return hip_fail(b, e, "halo_view_composite_kernel launch");
+    pending = true;
+  }
+  if (overlay) {
+    if (gather_rgb || sky_out || dir_out) {
+      HIPCHK(b, b->cons.view_dir.reserve(n));
+      hipError_t e = launch_view_dir(host::BuildProj(view), b->cons.view_dir.ptr, b->cu_count * 8, main_q(b));
+      if (e != hipSuccess) return hip_fail(b, e, "halo_view_dir_kernel launch");
+      if (dir_out) HIPCHK(b, hipMemcpyAsync(dir_out, b->cons.view_dir.ptr, n * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
+      pending = true;
+    }
+    if (int rc = overlay_pass(b, view, *overlay, gather_rgb, value_out, sky_out, marks_out)) return rc;
+  }
+  if (pending) {
+    if (gather_rgb && srgb_out) HIPCHK(b, hipMemcpyAsync(srgb_out, b->cons.view_rgb.ptr, n, hipMemcpyDeviceToHost, main_q(b)));
+    if (gather_value) HIPCHK(b, hipMemcpyAsync(value_out, b->cons.view_xyz.ptr, n * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
+    if (map_out) HIPCHK(b, hipMemcpyAsync(map_out, b->cons.view_map.ptr, npix * sizeof(int32_t), hipMemcpyDeviceToHost, main_q(b)));
+    if (tap_out) HIPCHK(b, hipMemcpyAsync(tap_out, b->cons.view_tap.ptr, npix * 5 * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
+    HIPCHK(b, hipStreamSynchronize(main_q(b)));
+  }
+  // the cases that stop before a composite, as halo_consumer_composite has them
+  if (plan.state == kCompositeNothing) return HALO_OK;   // neither image is written
+  if (plan.state == kCompositeBlack) {
+    if (srgb_out) std::memset(srgb_out, 0, n);
+    if (value_out) std::memset(value_out, 0, n * sizeof(float));
+    if (participating_p99_y) *participating_p99_y = 0.0f;
+    *produced = 1;
+    return HALO_OK;
+  }
+  if (participating_p99_y) *participating_p99_y = plan.p99;
+  if (plan.state == kCompositeNoScale) {   // the bytes stay untouched; the value image is the zeros the reference assigns its linear buffer
+    if (value_out) std::memset(value_out, 0, n * sizeof(float));
+    return HALO_OK;
+  }
+  *produced = 1;
   return HALO_OK;
 }
 
@@ -494,59 +618,37 @@ int halo_consumer_composite(halo_handle_t b, const HaloComposite* spec, float* l
 int halo_consumer_view_composite(halo_handle_t b, const HaloViewSpec* spec, const HaloViewFilter* filter, const HaloComposite* composite, uint8_t* srgb_out,
                                  float* value_out, int32_t* map_out, float* tap_out, float* participating_p99_y, int32_t* produced) {
   if (!b) return HALO_FATAL;
-  const std::string name("consumer_view_composite");
-  if (!produced) return fail(b, HALO_FATAL, name + ": produced is NULL");
-  *produced = 0;
-  const HaloRender* source = nullptr;
-  if (int rc = lane_view_checks(b, name, spec, filter, srgb_out || value_out || map_out || tap_out, &source)) return rc;
-  if (!composite) return fail(b, HALO_FATAL, name + ": composite is NULL");
-  if (composite->mode < HALO_COMPOSITE_DOMINANT || composite->mode > HALO_COMPOSITE_PAINTER) return fail(b, HALO_FATAL, name + ": unknown mode");
-  if (composite->class_count != static_cast<int>(b->color_classes.size())) return fail(b, HALO_FATAL, name + ": class_count differs from halo_set_color's");
-  HIPCHK(b, hipSetDevice(b->device));
-  if (int rc = join_aux(b)) return rc;   // (kernels of queued sessions may still be adding to the lanes on the trace / auxiliary streams)
-  CompositePlan plan;
-  if (int rc = composite_prepare(b, name.c_str(), composite, &plan)) return rc;
-  const HaloRender& view = spec->view;
-  const size_t npix = static_cast<size_t>(view.width) * static_cast<size_t>(view.height), n = npix * 3;
-  const bool ready = plan.state == kCompositeReady;
-  const uint8_t* src_dev = nullptr;
-  if (ready && (srgb_out || value_out)) {
-    HIPCHK(b, b->cons.view_comp_src.reserve(static_cast<size_t>(plan.npix) * 3u));
-    hipError_t e = launch_composite(b->lanes.ptr, plan.npix, plan.cd, nullptr, b->cons.view_comp_src.ptr, b->cu_count * 8, main_q(b));
-    if (e != hipSuccess) return hip_fail(b, e, "halo_composite_kernel launch");
-    src_dev = b->cons.view_comp_src.ptr;
-  }
-  if (src_dev || map_out || tap_out) {
-    if (src_dev && srgb_out) HIPCHK(b, b->cons.view_rgb.reserve(n));
-    if (src_dev && value_out) HIPCHK(b, b->cons.view_xyz.reserve(n));
-    if (map_out) HIPCHK(b, b->cons.view_map.reserve(npix));
-    if (tap_out) HIPCHK(b, b->cons.view_tap.reserve(npix * 5));
-    hipError_t e = launch_view_composite(src_dev, host::BuildProj(view), host::BuildProj(*source), filter && filter->filter == HALO_VIEW_BILINEAR, filter && filter->blend != 0,
-                                         src_dev && srgb_out ? b->cons.view_rgb.ptr : nullptr, src_dev && value_out ? b->cons.view_xyz.ptr : nullptr,
-                                         map_out ? b->cons.view_map.ptr : nullptr, tap_out ? b->cons.view_tap.ptr : nullptr, b->cu_count * 8, main_q(b));
-    if (e != hipSuccess) return hip_fail(b, e, "halo_view_composite_kernel launch");
-    if (src_dev && srgb_out) HIPCHK(b, hipMemcpyAsync(srgb_out, b->cons.view_rgb.ptr, n, hipMemcpyDeviceToHost, main_q(b)));
-    if (src_dev && value_out) HIPCHK(b, hipMemcpyAsync(value_out, b->cons.view_xyz.ptr, n * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
-    if (map_out) HIPCHK(b, hipMemcpyAsync(map_out, b->cons.view_map.ptr, npix * sizeof(int32_t), hipMemcpyDeviceToHost, main_q(b)));
-    if (tap_out) HIPCHK(b, hipMemcpyAsync(tap_out, b->cons.view_tap.ptr, npix * 5 * sizeof(float), hipMemcpyDeviceToHost, main_q(b)));
-    HIPCHK(b, hipStreamSynchronize(main_q(b)));
-  }
-  // the cases that stop before a composite, as halo_consumer_composite has them
-  if (plan.state == kCompositeNothing) return HALO_OK;   // neither image is written
-  if (plan.state == kCompositeBlack) {
-    if (srgb_out) std::memset(srgb_out, 0, n);
-    if (value_out) std::memset(value_out, 0, n * sizeof(float));
-    if (participating_p99_y) *participating_p99_y = 0.0f;
-    *produced = 1;
-    return HALO_OK;
-  }
-  if (participating_p99_y) *participating_p99_y = plan.p99;
-  if (plan.state == kCompositeNoScale) {   // the bytes stay untouched; the value image is the zeros the reference assigns its linear buffer
-    if (value_out) std::memset(value_out, 0, n * sizeof(float));
-    return HALO_OK;
-  }
-  *produced = 1;
-  return HALO_OK;
+  return view_composite_call(b, "consumer_view_composite", spec, filter, composite, nullptr, srgb_out, value_out, nullptr, nullptr, map_out, tap_out, nullptr,
+                             participating_p99_y, produced);
+}
+
+// ---- the auxiliary lines over a view (halo_view_overlay.hip, halo_overlay.h) ---------------------------------------------------------------
+int halo_consumer_view_overlay(halo_handle_t b, const HaloViewSpec* spec, const HaloViewFilter* filter, const HaloViewOverlay* overlay, uint8_t* rgb_out, float* value_out,
+                               float* sky_out, float* marks_out, int32_t* map_out, float* dir_out) {
+  if (!b) return HALO_FATAL;
+  const std::string name("consumer_view_overlay");
+  if (filter)
+    if (const char* why = filter_refusal(filter)) return fail(b, HALO_FATAL, name + why);
+  if (!overlay) return fail(b, HALO_FATAL, name + ": overlay is NULL");
+  if (const char* why = host::ViewOverlayRefusal(*overlay)) return fail(b, HALO_FATAL, name + ": " + why);
+  const bool draw = rgb_out || value_out;
+  ViewPlan plan;
+  const ViewWant want{draw, false, map_out != nullptr, draw || sky_out || dir_out, false};
+  if (int rc = view_launch(b, name.c_str(), spec, filter, want, rgb_out || value_out || sky_out || marks_out || map_out || dir_out, &plan)) return rc;
+  if (draw && plan.scale == 0.0f) HIPCHK(b, hipMemsetAsync(b->cons.view_rgb.ptr, 0, plan.n, main_q(b)));   // PostSnapshot's early-out: the lines lie on zero bytes
+  if (int rc = overlay_pass(b, spec->view, *overlay, draw, value_out, sky_out, marks_out)) return rc;
+  if (rgb_out) HIPCHK(b, hipMemcpyAsync(rgb_out, b->cons.view_rgb.ptr, plan.n, hipMemcpyDeviceToHost, main_q(b)));
+  return view_copy_back(b, plan, nullptr, nullptr, map_out, dir_out, nullptr);
+}
+
+int halo_consumer_view_composite_overlay(halo_handle_t b, const HaloViewSpec* spec, const HaloViewFilter* filter, const HaloComposite* composite,
+                                         const HaloViewOverlay* overlay, uint8_t* srgb_out, float* value_out, float* sky_out, float* marks_out, int32_t* map_out,
+                                         float* tap_out, float* dir_out, float* participating_p99_y, int32_t* produced) {
+  if (!b) return HALO_FATAL;
+  const std::string name("consumer_view_composite_overlay");
+  if (!overlay) return fail(b, HALO_FATAL, name + ": overlay is NULL");
+  if (const char* why = host::ViewOverlayRefusal(*overlay)) return fail(b, HALO_FATAL, name + ": " + why);
+  return view_composite_call(b, name, spec, filter, composite, overlay, srgb_out, value_out, sky_out, marks_out, map_out, tap_out, dir_out, participating_p99_y, produced);
 }
 
 int halo_consumer_view_lanes(halo_handle_t b, const HaloViewSpec* spec, const HaloViewFilter* filter, float* lanes_out, int32_t* map_out, float* tap_out) {

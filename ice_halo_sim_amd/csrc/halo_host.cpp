@@ -11,6 +11,7 @@
 
 #include "cie_tables.inc"
 #include "halo_geom.h"
+#include "halo_overlay.h"
 #include "halo_view.h"
 
 namespace halo {
@@ -968,6 +969,74 @@ int ViewSourcePos(const HaloRender& source, const float dir[3], float pos[5]) {
   float pre[4];
   view_proj_pre(p, pre);
   return view_source_pos(p, pre, dir[0], dir[1], dir[2], pos);
+}
+
+// ---- the auxiliary lines over a view (halo_consumer_view_overlay): halo_overlay.h on the host ---------------------------------------------
+void ViewOverlayDefaults(float fov, const float sun_alt_az_deg[2], HaloViewOverlay* out) {
+  HaloViewOverlay o{};
+  // the grid step by field of view: coarser lines for wider views
+  o.grid_step_deg = fov >= 120.0f ? 30.0f : fov >= 60.0f ? 20.0f : fov >= 30.0f ? 10.0f : fov >= 15.0f ? 5.0f : fov >= 6.0f ? 2.0f : fov >= 2.0f ? 1.0f : 0.5f;
+  const float alt = (sun_alt_az_deg ? sun_alt_az_deg[0] : 90.0f) * kDegToRad, az = (sun_alt_az_deg ? sun_alt_az_deg[1] : 0.0f) * kDegToRad;
+  o.sun_dir[0] = -(std::cos(alt) * std::cos(az));
+  o.sun_dir[1] = -(std::cos(alt) * std::sin(az));
+  o.sun_dir[2] = -std::sin(alt);
+  if (!sun_alt_az_deg) o.sun_dir[0] = o.sun_dir[1] = 0.0f, o.sun_dir[2] = -1.0f;
+  o.sun_circle_count = 2;
+  o.sun_circle_deg[0] = 22.0f;
+  o.sun_circle_deg[1] = 46.0f;
+  const float red[3] = {0.8f, 0.2f, 0.2f}, white[3] = {1.0f, 1.0f, 1.0f}, sun[3] = {1.0f, 0.9f, 0.3f};
+  for (int j = 0; j < 3; j++) {
+    o.horizon_color[j] = o.zenith_nadir_color[j] = red[j];
+    o.grid_color[j] = white[j];
+    o.sun_circles_color[j] = o.sun_marker_color[j] = sun[j];
+  }
+  o.horizon_alpha = o.zenith_nadir_alpha = 0.6f;
+  o.grid_alpha = 0.3f;
+  o.sun_circles_alpha = 0.5f;
+  o.sun_marker_alpha = 0.75f;
+  o.zenith_nadir_radius_px = 8.0f;
+  o.sun_marker_radius_px = 5.0f;
+  *out = o;
+}
+
+const char* ViewOverlayRefusal(const HaloViewOverlay& o) {
+  auto unit = [](float v) { return v >= 0.0f && v <= 1.0f; };   // (false for a NaN)
+  const float* colours[5] = {o.horizon_color, o.grid_color, o.sun_circles_color, o.zenith_nadir_color, o.sun_marker_color};
+  const float alphas[5] = {o.horizon_alpha, o.grid_alpha, o.sun_circles_alpha, o.zenith_nadir_alpha, o.sun_marker_alpha};
+  for (int k = 0; k < 5; k++) {
+    for (int j = 0; j < 3; j++)
+      if (!unit(colours[k][j])) return "a colour outside [0, 1]";
+    if (!unit(alphas[k])) return "an alpha outside [0, 1]";
+  }
+  if (o.show_grid && !(o.grid_step_deg > 0.0f)) return "grid_step_deg must be positive with the grid on";
+  if (o.sun_circle_count < 0 || o.sun_circle_count > HALO_VIEW_MAX_SUN_CIRCLES) return "sun_circle_count must lie in 0 .. 16";
+  for (int i = 0; i < o.sun_circle_count; i++)
+    if (!(o.sun_circle_deg[i] > 0.0f && o.sun_circle_deg[i] <= 180.0f)) return "a sun circle angle outside (0, 180]";
+  if (!(o.zenith_nadir_radius_px >= 0.0f) || !(o.sun_marker_radius_px >= 0.0f)) return "a negative radius";
+  if (o.show_sun_circles || o.show_sun_marker) {
+    const double n = std::sqrt(static_cast<double>(o.sun_dir[0]) * o.sun_dir[0] + static_cast<double>(o.sun_dir[1]) * o.sun_dir[1] + static_cast<double>(o.sun_dir[2]) * o.sun_dir[2]);
+    if (!(std::fabs(n - 1.0) <= 1e-3)) return "sun_dir is no unit vector";
+  }
+  if (o.reserved[0] != 0 || o.reserved[1] != 0) return "reserved words must be zero";
+  return nullptr;
+}
+
+void ViewOverlayMarks(const HaloRender& view, const float sun_dir[3], float marks[9]) {
+  const float dirs[3][3] = {{0.0f, 0.0f, -1.0f}, {0.0f, 0.0f, 1.0f}, {sun_dir[0], sun_dir[1], sun_dir[2]}};
+  for (int m = 0; m < 3; m++) {
+    float pos[5];
+    const int hits = ViewSourcePos(view, dirs[m], pos);
+    marks[3 * m] = hits > 0 ? pos[0] : 0.0f;
+    marks[3 * m + 1] = hits > 0 ? pos[1] : 0.0f;
+    marks[3 * m + 2] = hits > 0 ? 1.0f : 0.0f;
+  }
+}
+
+void ViewSky(const float dir[3], const float sun_dir[3], float sky[3]) { overlay_sky(dir, sun_dir, sky); }
+
+void ViewOverlayPixel(const uint8_t base_rgb[3], const float sky[6], const float pixel_xy[2], const float marks[9], const HaloViewOverlay& o, float value[3]) {
+  const float base[3] = {static_cast<float>(base_rgb[0]), static_cast<float>(base_rgb[1]), static_cast<float>(base_rgb[2])};
+  overlay_pixel(base, sky, pixel_xy[0], pixel_xy[1], marks, o, value);
 }
 
 }  // namespace host

@@ -86,6 +86,14 @@ bool ViewDirection(const HaloRender& view, int px, int py, float dir[3]);
 // ... and of halo_consumer_view_filtered: where the exit direction `dir` lands under `source`, continuous — halo_view.h view_source_pos on
 // BuildProj(source): {fx0, fy0, fx1, fy1, t}, the hit count returned (0 and zeros: culled, or an unknown lens).
 int ViewSourcePos(const HaloRender& source, const float dir[3], float pos[5]);
+// ... and of halo_consumer_view_overlay (halo_overlay.h): the reference's default record for a view of `fov` degrees and a sun at (alt, az) degrees;
+// what the calls refuse in a record (nullptr: nothing; else the message's tail); the three marks {x, y, present} of zenith, nadir and sun under
+// `view`, ViewSourcePos's primary hits; {alt, az, dist} of a direction; the value of one pixel that has a direction.
+void ViewOverlayDefaults(float fov, const float sun_alt_az_deg[2], HaloViewOverlay* out);
+const char* ViewOverlayRefusal(const HaloViewOverlay& o);
+void ViewOverlayMarks(const HaloRender& view, const float sun_dir[3], float marks[9]);
+void ViewSky(const float dir[3], const float sun_dir[3], float sky[3]);
+void ViewOverlayPixel(const uint8_t base_rgb[3], const float sky[6], const float pixel_xy[2], const float marks[9], const HaloViewOverlay& o, float value[3]);
 
 }  // namespace host
 

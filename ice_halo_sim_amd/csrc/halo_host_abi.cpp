@@ -77,6 +77,25 @@ int halo_host_view_source_pos(const HaloRender* source, const float dir[3], floa
   if (!source || !dir || !pos) return 0;
   return host::ViewSourcePos(*source, dir, pos);
 }
+int halo_host_view_overlay_defaults(float view_fov_deg, const float sun_alt_az_deg[2], HaloViewOverlay* out) {
+  if (!out) return 0;
+  host::ViewOverlayDefaults(view_fov_deg, sun_alt_az_deg, out);
+  return static_cast<int>(sizeof(HaloViewOverlay));
+}
+int halo_host_view_sky(const float dir[3], const float sun_dir[3], float sky3[3]) {
+  if (sky3) sky3[0] = sky3[1] = sky3[2] = 0.0f;
+  if (!dir || !sun_dir || !sky3) return 0;
+  host::ViewSky(dir, sun_dir, sky3);
+  return 1;
+}
+int halo_host_view_overlay_pixel(const uint8_t base_rgb[3], const float sky6[6], const float pixel_xy[2], const float marks9[9], const HaloViewOverlay* overlay,
+                                 float value3[3]) {
+  if (value3) value3[0] = value3[1] = value3[2] = 0.0f;
+  if (!base_rgb || !sky6 || !pixel_xy || !marks9 || !overlay || !value3) return 0;
+  if (overlay->sun_circle_count < 0 || overlay->sun_circle_count > HALO_VIEW_MAX_SUN_CIRCLES) return 0;   // (the one field that bounds a loop over the record)
+  host::ViewOverlayPixel(base_rgb, sky6, pixel_xy, marks9, *overlay, value3);
+  return 1;
+}
 
 // ---- display-side composite of the class lanes (server/component_compositor.cpp) -------------------------
 int halo_host_parse_composite_mode(const char* mode) {   // ParseCompositeMode, component_compositor.cpp:118-134

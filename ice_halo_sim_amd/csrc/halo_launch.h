@@ -126,6 +126,12 @@ hipError_t launch_view_composite(const uint8_t* srgb_src, const ProjDev& view, c
                                  int32_t* map_out, float* tap_out, int blocks, hipStream_t stream);
 hipError_t launch_view_lanes(const double* lanes, uint32_t class_count, const ProjDev& view, const ProjDev& source, bool bilinear, bool blend, float* lanes_out,
                              int32_t* map_out, float* tap_out, int blocks, hipStream_t stream);
+// halo_view_overlay.hip — the auxiliary lines over a gathered view (halo_overlay.h): `dir` and `rgb` are the gather's device buffers of a
+// view_w x view_h view, rgb is rewritten in place (null: the sky coordinates alone); value_out (3 floats) and sky_out (6 floats per pixel) may be
+// null.  marks: {x, y, present} of zenith, nadir and sun in view pixels.  launch_view_dir writes launch_view's dir_out alone.
+hipError_t launch_view_overlay(const float* dir, const HaloViewOverlay& overlay, const float marks[9], int view_w, int view_h, uint8_t* rgb, float* value_out, float* sky_out,
+                               int blocks, hipStream_t stream);
+hipError_t launch_view_dir(const ProjDev& view, float* dir_out, int blocks, hipStream_t stream);
 hipError_t launch_cont_reorder(const float* in, uint32_t in_stride, uint32_t region, const uint32_t* cnt, uint32_t max_fill, const uint32_t* mask, uint32_t n_roots,
                                uint32_t* tile_sum, uint32_t* base, float* out, uint32_t out_stride, uint32_t n_cont, uint32_t planes, uint32_t* err, hipStream_t stream);
 

@@ -97,6 +97,7 @@ struct Consumer {
   // halo_consumer_view_composite: the source-sized composite its gather reads (never copied back); halo_consumer_view_lanes: the class planes of the view
   DevBuf<uint8_t> view_comp_src;
   DevBuf<float> view_lanes;
+  DevBuf<float> view_sky, view_val;   // halo_consumer_view_overlay: the sky coordinates and the value after the last layer
   int w = 0, h = 0;
   double total_intensity = 0.0;
 };

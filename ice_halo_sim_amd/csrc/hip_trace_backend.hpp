@@ -196,6 +196,22 @@ class HipTraceBackend {
   void ViewLanes(const HaloViewSpec& spec, const HaloViewFilter& filter, float* lanes_out, int32_t* map_out = nullptr, float* tap_out = nullptr) {
     Check(halo_consumer_view_lanes(h_, &spec, &filter, lanes_out, map_out, tap_out));
   }
+  // The filtered view with the auxiliary lines on it (halo_consumer_view_overlay: horizon, grid, sun circles, zenith / nadir rings, sun marker —
+  // halo_host_view_overlay_defaults fills the reference's record): rgb_out 3 bytes, value_out 3 floats in byte units, sky_out 6 floats per pixel,
+  // marks_out 9 floats, map_out / dir_out the view's
+  void ViewOverlay(const HaloViewSpec& spec, const HaloViewFilter& filter, const HaloViewOverlay& overlay, uint8_t* rgb_out, float* value_out = nullptr,
+                   float* sky_out = nullptr, float* marks_out = nullptr, int32_t* map_out = nullptr, float* dir_out = nullptr) {
+    Check(halo_consumer_view_overlay(h_, &spec, &filter, &overlay, rgb_out, value_out, sky_out, marks_out, map_out, dir_out));
+  }
+  // ... and the class composite's view with them (halo_consumer_view_composite_overlay); returns CompositeColorClasses' answer: false, nothing drawn
+  bool ViewCompositeOverlay(const HaloViewSpec& spec, const HaloViewFilter& filter, const HaloComposite& composite, const HaloViewOverlay& overlay, uint8_t* srgb_out,
+                            float* value_out = nullptr, float* sky_out = nullptr, float* marks_out = nullptr, int32_t* map_out = nullptr, float* tap_out = nullptr,
+                            float* dir_out = nullptr, float* participating_p99_y = nullptr) {
+    int32_t produced = 0;
+    Check(halo_consumer_view_composite_overlay(h_, &spec, &filter, &composite, &overlay, srgb_out, value_out, sky_out, marks_out, map_out, tap_out, dir_out,
+                                               participating_p99_y, &produced));
+    return produced != 0;
+  }
   // The reference GUI's Adaptive Brightness anchor (gui/gui_ev_auto.hpp ComputeP99Y + ComputeEvAuto) on the device consumer: expose a
   // snapshot with display.intensity_factor * exp2(result.ev_auto); result.produced == 0 is the GUI's "auto: no data"
   HaloAutoEv AutoEv(int downsample = 8, float target_white = 135.f) {

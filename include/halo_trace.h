@@ -742,6 +742,69 @@ int halo_consumer_view_composite(halo_handle_t h, const HaloViewSpec* spec, cons
 int halo_consumer_view_lanes(halo_handle_t h, const HaloViewSpec* spec, const HaloViewFilter* filter,
                              float* lanes_out, int32_t* map_out, float* tap_out);
 
+/* --- the auxiliary lines over a view: what the reference's preview draws over its image (gui/preview_renderer.cpp overlayAuxLines) — the horizon,
+ *     an altitude / azimuth grid, circles of constant angular distance from the sun, zenith and nadir rings, a sun marker — per view pixel from the
+ *     direction the gather has already computed.  No text labels, no background image. --- */
+#define HALO_VIEW_MAX_SUN_CIRCLES 16
+typedef struct HaloViewOverlay {
+  int32_t show_horizon, show_grid, show_sun_circles, show_zenith_nadir, show_sun_marker; /* the five layers, each 0 | non-zero */
+  float grid_step_deg;                               /* the grid's spacing in altitude and azimuth, > 0 where the grid is on */
+  float sun_dir[3];                                  /* the sun's TRAVEL direction (sky position -sun_dir), a unit vector */
+  int32_t sun_circle_count;                          /* 0 .. HALO_VIEW_MAX_SUN_CIRCLES */
+  float sun_circle_deg[HALO_VIEW_MAX_SUN_CIRCLES];   /* angular distances from the sun in (0, 180] */
+  float horizon_color[3], horizon_alpha;             /* every colour channel and every alpha in [0, 1] */
+  float grid_color[3], grid_alpha;
+  float sun_circles_color[3], sun_circles_alpha;
+  float zenith_nadir_color[3], zenith_nadir_alpha;
+  float sun_marker_color[3], sun_marker_alpha;
+  float zenith_nadir_radius_px;                      /* the rings' radius in view pixels, >= 0 */
+  float sun_marker_radius_px;                        /* the disc's radius in view pixels, >= 0 */
+  int32_t reserved[2];                               /* zero */
+} HaloViewOverlay;
+/* The reference's defaults (gui/preview_renderer.hpp OverlayDecoration) into *out: every switch off; circles at 22 and 46 degrees; horizon
+ * (0.8, 0.2, 0.2) at 0.6; grid white at 0.3; circles (1, 0.9, 0.3) at 0.5; rings as the horizon, radius 8; marker (1, 0.9, 0.3) at 0.75, radius 5;
+ * the grid step by the view's field of view: 30 / 20 / 10 / 5 / 2 / 1 / 0.5 degrees for fov >= 120 / 60 / 30 / 15 / 6 / 2 / below;
+ * sun_dir = (-cos alt cos az, -cos alt sin az, -sin alt) of the sun's altitude and azimuth in degrees (NULL: altitude 90, (0, 0, -1)).
+ * Returns sizeof(HaloViewOverlay) (0 for a NULL out), which a binding checks against its own mirror of the struct.  No GPU needed. */
+int halo_host_view_overlay_defaults(float view_fov_deg, const float sun_alt_az_deg[2], HaloViewOverlay* out);
+/* halo_consumer_view_filtered's image with the lines on it (filter == NULL: nearest without a blend).  dir_out and map_out are that call's, bit for
+ * bit.  Per view pixel, with w = dir_out, s = overlay->sun_dir and D = 57.29578f, every operation one fp32 rounding:
+ *   sky_out    (6 floats) {alt, az, dist, fw_alt, fw_az, fw_dist} in degrees: alt = atan2f(-wz, sqrtf(wx wx + wy wy)) D, az = atan2f(-wy, -wx) D,
+ *              dist = atan2f(|w x s|, w . s) D, and the pixel footprints fw(q) = |q(x ^ 1, y) - q| + |q(x, y ^ 1) - q| — a partner outside the view or
+ *              without a direction is replaced by the pixel's other neighbour on that axis (x - 1 for even x, x + 1 for odd x), a term with neither
+ *              is 0, the azimuth difference is wrapped once into [-180, 180] — clamped to [1e-4, 2] (fw_az: [1e-4, 5]).  Zeros without a direction.
+ *   value_out  (3 floats) the colour after the last layer, in byte units: c = float(byte) of the filtered view, then per layer
+ *              c = fma(colour * 255, k, c * (1 - k)) — grid, sun circles in list order, horizon, zenith ring, nadir ring, sun marker — with
+ *              smoothstep(e0, e1, x) = t t (3 - 2 t), t = clamp((x - e0) / (e1 - e0), 0, 1), cover(d, fw) = 1 - smoothstep(0, 1.5 fw, d),
+ *              mod(x, g) = x - g floorf(x / g), h = step / 2 and
+ *                grid     k = max(cover(|mod(|alt| + h, step) - h|, fw_alt), cover(|mod(az + 180 + h, step) - h|, fw_az) where |alt| < 85) grid_alpha
+ *                circles  k = cover(|dist - angle_i|, fw_dist) sun_circles_alpha
+ *                horizon  k = cover(|alt|, fw_alt) horizon_alpha
+ *                rings    k = (1 - smoothstep(0, 1.5, |r - radius|)) alpha, r the distance from the pixel's centre to the mark, in pixels
+ *                marker   k = (1 - smoothstep(radius - 1.5, radius + 1.5, r)) alpha.
+ *              A pixel without a direction keeps float(byte).
+ *   rgb_out    (3 bytes) uint8(floorf(clamp(value, 0, 255) + 0.5f)).  With every switch off, or every alpha 0, the filtered view's bytes.
+ *   marks_out  (9 floats, not per pixel) {x, y, present} of the zenith (0, 0, -1), the nadir (0, 0, 1) and the sun: halo_host_view_source_pos's
+ *              primary hit of that direction under spec->view (pixel n's centre at n); present = 0 and zeros where the projection culls it.
+ * The lines are drawn wherever the view has a direction, whether or not the source covers it (map_out = -1).  Host pointers, any output NULL to skip
+ * it.  Refusals are halo_consumer_view_filtered's (every output NULL counts all six per-pixel and marks_out), plus HALO_FATAL — the handle stays
+ * usable — for a NULL overlay, a colour or alpha outside [0, 1], grid_step_deg <= 0 with the grid on, a circle count outside 0 .. 16, a circle
+ * angle outside (0, 180], a negative radius, a sun_dir more than 1e-3 from unit length while circles or marker are on, non-zero reserved words. */
+int halo_consumer_view_overlay(halo_handle_t h, const HaloViewSpec* spec, const HaloViewFilter* filter, const HaloViewOverlay* overlay, uint8_t* rgb_out,
+                               float* value_out, float* sky_out, float* marks_out, int32_t* map_out, float* dir_out);
+/* The same pass over halo_consumer_view_composite's srgb: srgb_out, value_out (the colour after the last layer), sky_out, marks_out as above, map_out
+ * / tap_out / participating_p99_y / produced that call's, dir_out the view call's.  Where that call writes no composite or a constant one
+ * (*produced = 0; no active class) nothing is drawn: the images are that call's.  Refusals: that call's and the overlay's above. */
+int halo_consumer_view_composite_overlay(halo_handle_t h, const HaloViewSpec* spec, const HaloViewFilter* filter, const HaloComposite* composite,
+                                         const HaloViewOverlay* overlay, uint8_t* srgb_out, float* value_out, float* sky_out, float* marks_out,
+                                         int32_t* map_out, float* tap_out, float* dir_out, float* participating_p99_y, int32_t* produced);
+/* sky_out[0:3] of one direction, and value_out of one pixel that has a direction — base_rgb its 3 bytes, sky6 its sky_out, pixel_xy its integer
+ * coordinates as floats, marks9 the call's marks_out — by the same code on the host.  They return 1, or 0 (outputs zeroed) for a NULL argument or a circle count outside 0 .. 16.
+ * The record is taken as it is: the refusals above are the calls'.  No GPU needed. */
+int halo_host_view_sky(const float dir[3], const float sun_dir[3], float sky3[3]);
+int halo_host_view_overlay_pixel(const uint8_t base_rgb[3], const float sky6[6], const float pixel_xy[2], const float marks9[9], const HaloViewOverlay* overlay,
+                                 float value3[3]);
+
 /* --- host-side pieces of the path, exported for parity tests (no GPU needed) ---------------- */
 /* Geometry tables the kernels consume (reference: Crystal::PopulateFromCfGeom crystal.cpp:304-347,
  * detail::BuildEntrySubTris simulator.cpp:90-129). */
@@ -862,6 +925,7 @@ HALO_STATIC_ASSERT(sizeof(HaloStatsSpec) == 16 + 8 * HALO_STATS_MAX_PERCENTILES,
 HALO_STATIC_ASSERT(sizeof(HaloImageStats) == 56 + 32 * HALO_STATS_MAX_PERCENTILES, "HaloImageStats");
 HALO_STATIC_ASSERT(sizeof(HaloViewSpec) == 44 + 4 + 44 + 28, "HaloViewSpec");
 HALO_STATIC_ASSERT(sizeof(HaloViewFilter) == 16, "HaloViewFilter");
+HALO_STATIC_ASSERT(sizeof(HaloViewOverlay) == 20 + 4 + 12 + 4 + 4 * HALO_VIEW_MAX_SUN_CIRCLES + 5 * 16 + 8 + 8, "HaloViewOverlay");
 HALO_STATIC_ASSERT(sizeof(HaloCompositeClass) == 24, "HaloCompositeClass");
 HALO_STATIC_ASSERT(sizeof(HaloComposite) == 16 + HALO_COLOR_MAX_CLASSES * 24, "HaloComposite");
 HALO_STATIC_ASSERT(sizeof(HaloGeomTables) == 4 + HALO_MAX_FACES * 20 + 4 + HALO_MAX_TRIS * (36 + 12 + 4 + 4), "HaloGeomTables");
